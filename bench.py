@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- training frames/s of the ML-GGD DNN trainer hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run measures the headline and nothing else: set-up, clock ramp and --warmup steps, ONE timed window of exactly
+--steps steps, the line.  `--full` adds everything else this script measures or checks (the `roofline` post-pass,
+`dp_breakdown`, `loss_vs_oracle` and its oracle yardsticks, `cpu_baseline`, the `ml_ggd` leg, the `dp_arms`, the
+1-rank `dp_rehearsal_1rank`) and times the headline over 9 windows by default.  `--dump-outputs DIR` writes, after the
+timed steps, what the timed path leaves its caller -- the trained weights `w<l>` and biases `b<l>` (and, with the ML-GGD
+loss, the `scalefactor`) -- as DIR/<name>.npy in float32; the inputs are seeded, so two runs with the same arguments
+train on the same data, and two builds can be compared array for array.
 
 N > 1 needs no launcher: when WORLD_SIZE is not set, this process starts N child ranks itself -- BEFORE it imports
 torch or touches a GPU -- (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment), relays rank
@@ -17,7 +25,8 @@ section 6; `--dp-mode allreduce` / MLGGD_DP_MODE=allreduce selects BASELINE.json
 gradients, which is also measured as `dp_arms.allreduce` in the same invocation).  torch.distributed is used over
 GLOO only -- rendezvous, barriers, max over ranks; the only RCCL communicator is the engine's own.
 
-Timing: `ms_per_step` is the MEDIAN over `--windows` (default 9) back-to-back windows of exactly --steps steps each;
+Timing: `ms_per_step` is the MEDIAN over `--windows` (default 1; 9 with --full) back-to-back windows of exactly --steps
+steps each;
 a window is [barrier + device sync] t0 [K steps] [device sync] t1 on every rank, its time the MAX over ranks of
 t1 - t0 (no collective and no event inside a window).  `window_ms_min/max` give the spread.
 
@@ -30,7 +39,7 @@ dispatch's own begin/end timestamps, comparable with rocprofv3's average); `ml_g
 kernel class): device time of the rank's own kernels per step against the step's wall time -- the difference is the
 exposed part of the exchange.
 
-Time budget (`--budget-s`, default 300 s from process start): the headline always runs; every further leg (dp_breakdown,
+Time budget (`--budget-s`, default 300 s from process start; --full): the headline always runs; every further leg (dp_breakdown,
 N > 1 `loss_vs_oracle`, `dp_arms.*` -- all-reduce first, it is the exchange BASELINE.json names --, `ml_ggd`, the 1-rank
 rehearsal, the CPU baseline and its parity legs) is started only if its estimated cost still fits, else it is listed
 under `skipped` (rank 0 decides, the decision is broadcast).  The headline is copied to stderr the moment it exists;
@@ -74,12 +83,41 @@ def flop_per_frame(ls):
     return 2 * P + 2 * P + 2 * (P - ls[0] * ls[1])  # fwd + dW + dX (no dX for layer 1)
 
 
+DUMP_MAX_BYTES = 60 * 10 ** 6  # array data of --dump-outputs; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(eng, ml, d):
+    """--dump-outputs: what a caller of the training path receives after the last timed step, as float32 .npy files.
+    Above DUMP_MAX_BYTES every array is replaced by the same fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    ws, bs = eng.returnWeights()
+    arrs = {"w%d" % l: w for l, w in enumerate(ws)}
+    arrs.update({"b%d" % l: b for l, b in enumerate(bs)})
+    if ml:
+        arrs["scalefactor"] = eng.scalefactor()
+    total = sum(np.asarray(a).size * 4 for a in arrs.values())
+    frac = min(1.0, DUMP_MAX_BYTES / total)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrs.items():
+        a = np.asarray(a, np.float32)
+        if frac < 1.0:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, max(1, int(a.size * frac)), replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {"dir": d, "arrays": sorted(arrs), "dtype": "float32", "sampled": frac < 1.0}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
-    ap.add_argument("--windows", type=int, default=9, help="timed windows of --steps steps each; the median is reported")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each; the median is reported (default 1; 9 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline (module docstring); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the weights, biases (and ML-GGD scale factor) the timed steps left as DIR/<name>.npy")
     ap.add_argument("--loss", choices=["mmse", "ml"], default="mmse",
                     help="mmse = BASELINE.json configs[1] (MLflag=0, beta=2); ml = configs[2] (MLflag=1, beta=1.2)")
     ap.add_argument("--bunch", type=int, default=128)
@@ -109,7 +147,12 @@ def parse_args(argv=None):
                     help="TESTS ONLY (tests/test_bench_launcher.py): run the rank code over tests/bench_stub.py, a do-nothing "
                          "stand-in for the package, so the multi-rank control flow is exercised on a machine without GPUs; "
                          "the line it prints is marked and means nothing")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 9 if args.full else 1
+    if not args.full:  # the headline only: every optional leg is off
+        args.no_dp_arms = args.no_cpu_baseline = args.no_kernel_timing = args.no_ml = args.no_dp_rehearsal = True
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -460,6 +503,10 @@ def rank_main(args):
     mode = eng.dp_mode()
     head = measure(eng, "headline", args.ramp)
     cost["measure"] = time.time() - t_leg
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before any post-pass trains further: the state the timed steps left
+        wd.enter("dump outputs", 300)
+        dumped = dump_outputs(eng, ml, args.dump_outputs)
 
     roofline = None
     if not args.no_kernel_timing:
@@ -556,6 +603,8 @@ def rank_main(args):
                        ("external launcher" if world > 1 else "direct"),
         "budget_s": args.budget_s,
     })
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     state["headline_done"] = True
     if rank == 0:  # an early copy for whoever watches stderr: a run cut short after this point is not an empty run
         sys.stderr.write("bench.py headline after %.0f s (early copy; the line on stdout follows at the end): %s\n"
@@ -635,7 +684,7 @@ def rank_main(args):
 
     est_parity = cost["measure"] + 10 + 0.25 * world * min(20, nb)  # the oracle: ~0.2 s per 1,024-frame step
     # (the stub engine of the tests has no oracle-grade numbers to offer; MLGGD_BENCH_STUB_PARITY=1 runs the leg's control flow anyway)
-    want_parity = dp and (not args.no_cpu_baseline or os.environ.get("MLGGD_BENCH_STUB_PARITY") == "1")
+    want_parity = dp and args.full and (not args.no_cpu_baseline or os.environ.get("MLGGD_BENCH_STUB_PARITY") == "1")
     if want_parity and fits("loss_vs_oracle", est_parity):
         out["loss_vs_oracle"] = dp_parity(ml, beta, args.dp_mode, "loss_vs_oracle")
 

@@ -10,6 +10,41 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "speech-enhancement-based-on-a-maximum-likelihood-criterion_amd", "host")
 _lib = None
+SAMPLE = os.path.join(ROOT, "tests", "golden", "tools_pfile.npz")
+SAMPLE_NORM = os.path.join(ROOT, "tests", "golden", "tools_pfile_train_noisy.norm")
+
+
+def sample_pfiles(dest):
+    """The original project's 10-sentence sample (its tools_pfile/: train_noisy.pfile, train_clean.pfile and
+    train_noisy.norm), rebuilt in the directory dest, which is returned.  The norm file is stored whole; of each pfile
+    tests/golden/tools_pfile.npz keeps the original bytes of the 32 KB header, the sentence table and the rows
+    `keep_rows` (the first rows and those around the first CV frame, 1491).  Every other row is the original's
+    sentence / frame numbers with 257 features drawn, seeded, from N(mean, 1 / inv_std) of the norm file: the file's
+    layout, sentence lengths and the rows a test compares with known values are the original's."""
+    import shutil
+    D, NCOL, HDR = 257, 259, 32768
+    os.makedirs(dest, exist_ok=True)
+    shutil.copyfile(SAMPLE_NORM, os.path.join(dest, "train_noisy.norm"))
+    vals = np.array([float(x) for x in open(SAMPLE_NORM).read().split() if x != "vec"], np.float64)
+    mean, inv = vals[1:1 + D], vals[2 + D:2 + 2 * D]
+    z = np.load(SAMPLE)
+    keep = z["keep_rows"]
+    for seed, tag in enumerate(("noisy", "clean")):
+        table = np.frombuffer(z[tag + "_tail"].tobytes(), ">i4")
+        n = int(table[-1])
+        sent = np.repeat(np.arange(len(table) - 1), np.diff(table))
+        frame = np.arange(n) - table[sent]
+        feats = mean + np.random.default_rng(seed).standard_normal((n, D)) / inv
+        rows = np.empty((n, NCOL), ">f4")
+        rows[:, 2:] = feats
+        ids = rows.view(">i4")
+        ids[:, 0], ids[:, 1] = sent, frame
+        rows = rows.view(np.uint8).reshape(n, NCOL * 4)
+        rows[keep] = z[tag + "_rows"]
+        assert len(z[tag + "_header"]) == HDR
+        with open(os.path.join(dest, "train_%s.pfile" % tag), "wb") as f:
+            f.write(z[tag + "_header"].tobytes() + rows.tobytes() + z[tag + "_tail"].tobytes())
+    return str(dest)
 
 
 def lib():

@@ -134,9 +134,10 @@ def test_reference_main_builds_and_links_against_the_bp_gpu_shim(pkg, tmp_path):
     subprocess.check_call([os.path.join(host, "gen_rand_net"), "5", *map(str, ls), str(tmp_path), str(tmp_path / "init.wts"),
                            "1", "2", "5"], stdout=subprocess.DEVNULL)
     argv = json.load(open(os.path.join(ROOT, "tests", "golden", "finetune_argv.json")))["argv"][0]
+    sample = hostlib.sample_pfiles(tmp_path / "tools_pfile")    # the reference's sample data, from tests/golden/
     sub = {"initwts_file": tmp_path / "init.wts", "outwts_file": tmp_path / "mlp.1.wts", "log_file": tmp_path / "mlp.1.log",
-           "norm_file": "/root/reference/tools_pfile/train_noisy.norm", "fea_file": "/root/reference/tools_pfile/train_noisy.pfile",
-           "targ_file": "/root/reference/tools_pfile/train_clean.pfile"}
+           "norm_file": os.path.join(sample, "train_noisy.norm"), "fea_file": os.path.join(sample, "train_noisy.pfile"),
+           "targ_file": os.path.join(sample, "train_clean.pfile")}
     argv = ["%s=%s" % (a.split("=", 1)[0], sub.get(a.split("=", 1)[0], a.split("=", 1)[1])) for a in argv]
     r = subprocess.run([str(exe)] + argv, capture_output=True, text=True, timeout=300)
     import torch

@@ -89,7 +89,7 @@ def test_the_rank_code_runs_end_to_end_on_a_stub_engine(form):
     """The world > 1 branches of bench.py (communicator hand-off over gloo, windows with max over ranks, ml_ggd leg, the
     three exchange arms, dp_breakdown, teardown) first run for real on the driver's multi-GPU node; here they run over
     tests/bench_stub.py so that a slip in that control flow shows on the CPU.  The numbers mean nothing."""
-    cmd = [BENCH, "--gpus", "2", "--steps", "4", "--warmup", "2", "--windows", "3", "--stub-engine"]
+    cmd = [BENCH, "--gpus", "2", "--steps", "4", "--warmup", "2", "--windows", "3", "--full", "--stub-engine"]
     if form == "torchrun":
         s = socket.socket()
         s.bind(("127.0.0.1", 0))
@@ -130,7 +130,7 @@ def test_the_rank_code_runs_end_to_end_on_a_stub_engine(form):
 def test_stub_engine_arm_the_shape_rules_out_is_reported_not_fatal():
     # 2 x 96 frames: the factor exchange is unusable, the default is the all-reduce, the other two arms say why not
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "2", "--bunch", "96",
-                        "--no-ml", "--stub-engine"], capture_output=True, text=True, timeout=600, env=_env())
+                        "--no-ml", "--full", "--stub-engine"], capture_output=True, text=True, timeout=600, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["config"]["dp_mode"] == "allreduce" and d["dp_arms"]["allreduce"]["same_as"] == "headline"
@@ -144,7 +144,7 @@ def test_stub_engine_two_ranks_take_the_parity_leg():
     rank-major rows while the other ranks wait in a barrier.  The stub's numbers mean nothing; the control flow (and the
     REAL oracle at bunchsize 256 on the rows of both ranks) is what runs here."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--windows", "2", "--no-dp-arms",
-                        "--hidden", "64", "--nhid", "1", "--stub-engine"], capture_output=True, text=True, timeout=600,
+                        "--hidden", "64", "--nhid", "1", "--full", "--stub-engine"], capture_output=True, text=True, timeout=600,
                        env=_env(MLGGD_BENCH_STUB_PARITY="1"))
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -159,7 +159,7 @@ def test_budget_skips_optional_legs_and_says_so():
     """--budget-s: the headline always runs; a leg whose estimated cost no longer fits is not started and is listed
     under `skipped` (rank 0 decides, the decision is broadcast so that no rank enters a collective alone)."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "4", "--warmup", "2", "--windows", "3", "--budget-s", "1",
-                        "--stub-engine"], capture_output=True, text=True, timeout=600, env=_env())
+                        "--full", "--stub-engine"], capture_output=True, text=True, timeout=600, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert d["value"] > 0 and d["roofline"] is not None and "incomplete" not in d
@@ -205,3 +205,45 @@ def test_watchdog_after_the_headline_delivers_the_line_but_fails_the_run():
     assert r.returncode == 4, (r.returncode, r.stderr[-2000:])
     d = _json_line(r.stdout)
     assert d["value"] > 0 and d["incomplete"].startswith("watchdog: stuck in phase 'test hang after the headline'")
+
+
+def _plain_stub_run(tmp_path, name, *extra):
+    d = tmp_path / name
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "6", "--warmup", "2", "--stub-engine",
+                        "--dump-outputs", str(d)] + list(extra), capture_output=True, text=True, timeout=600, env=_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    return _json_line(r.stdout), d
+
+
+def test_plain_run_is_the_headline_only_and_dumps_what_it_trained(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times ONE window of exactly K steps and runs no other leg; with
+    --dump-outputs it writes the weights and biases the timed path leaves its caller, the same files on every run."""
+    runs = [_plain_stub_run(tmp_path, "out%d" % i, "--hidden", "64", "--nhid", "2") for i in range(2)]
+    for d, out in runs:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["timing"]["windows"] == 1 and len(d["timing"]["window_ms"]) == 1
+        assert abs(d["ms_per_step"] * 6 - d["timing"]["window_ms"][0]) <= 1e-3
+        assert d["roofline"] is None and d["skipped"] == [] and "incomplete" not in d
+        for leg in ("dp_breakdown", "cpu_baseline", "loss_vs_oracle", "ml_ggd", "dp_arms", "dp_rehearsal_1rank"):
+            assert leg not in d, leg
+        assert d["dump_outputs"]["sampled"] is False
+        assert sorted(os.listdir(out)) == ["b0.npy", "b1.npy", "b2.npy", "w0.npy", "w1.npy", "w2.npy"]
+    import numpy as np
+    ls = [257 * 11, 64, 64, 257]
+    for i in range(3):
+        w, b = np.load(runs[0][1] / ("w%d.npy" % i)), np.load(runs[0][1] / ("b%d.npy" % i))
+        assert w.dtype == np.float32 and w.shape == (ls[i], ls[i + 1]) and b.shape == (ls[i + 1],)
+        for n in ("w%d.npy" % i, "b%d.npy" % i):
+            assert np.array_equal(np.load(runs[0][1] / n), np.load(runs[1][1] / n))
+
+
+def test_dump_of_a_large_net_is_a_fixed_sample_under_64_mb(tmp_path):
+    import numpy as np
+    runs = [_plain_stub_run(tmp_path, "out%d" % i, "--hidden", "4096", "--loss", "ml") for i in range(2)]
+    for d, out in runs:
+        assert d["dump_outputs"]["sampled"] is True and "scalefactor" in d["dump_outputs"]["arrays"]
+        assert sum(os.path.getsize(out / n) for n in os.listdir(out)) <= 64 * 10 ** 6
+    for n in os.listdir(runs[0][1]):
+        a = np.load(runs[0][1] / n)
+        assert a.dtype == np.float32 and np.array_equal(a, np.load(runs[1][1] / n))

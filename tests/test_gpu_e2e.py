@@ -617,7 +617,7 @@ def test_bench_rehearses_the_data_parallel_path_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-dp", "--steps", "5", "--warmup", "2",
-                        "--windows", "3"], capture_output=True, text=True, timeout=900)
+                        "--windows", "3", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = r.stdout.splitlines()
     assert len(lines) == 1, r.stdout
@@ -642,3 +642,37 @@ def test_bench_rehearses_the_data_parallel_path_on_one_gpu():
         assert leg["cv_sqerr_rel"] < 1e-4 and leg["cv_abserr_rel"] < 1e-4 and leg["weights_relmax"] < 2e-5
     assert d["ml_ggd"]["loss_vs_oracle"]["cv_loglik_rel"] < 1e-4
     assert d["loss_vs_oracle"]["hip_equals_mfma_order_twin_bitwise"] is True   # MMSE through the factor exchange: the twin's bits
+
+
+def test_bench_plain_run_dumps_what_the_timed_steps_trained(pkg, synth, tmp_path):
+    """`bench.py --dump-outputs DIR` (plain run: clock ramp, warm-up, one window of --steps steps): the arrays it writes
+    are, bit for bit, the weights, biases and scale factor of an engine driven through the same steps on the same seeded
+    data in this process."""
+    import json
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--ramp", "8",
+                        "--loss", "ml", "--hidden", "256", "--nhid", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.splitlines()
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 5 and d["timing"]["windows"] == 1 and d["roofline"] is None and d["value"] > 0
+    B, nb = 128, 5
+    ls = synth.baseline_layersizes(hidden=256, nhid=2)
+    ws, bs = synth.make_weights(ls)
+    inp, targ = synth.make_frames(nb * B, 257, 11, seed=synth.DEFAULT_SEED + 1)
+    eng = pkg.BPGpu(synth.DEFAULT_SEED, 0, ls, B, 0.1, 0.9, 1e-5, ws, bs, 1.2, 1)
+    eng.load_chunk(inp, targ)
+    for m in (5, 3, 2, 5):                      # ramp 8 (5 + 3 resident bunches), warm-up 2, the timed window of 5
+        assert eng.train_resident(0, m * B) == m
+    w, b = eng.returnWeights()
+    alpha = eng.scalefactor()
+    eng.close()
+    assert sorted(os.listdir(out)) == sorted(["w%d.npy" % l for l in range(3)] + ["b%d.npy" % l for l in range(3)] +
+                                             ["scalefactor.npy"])
+    for l in range(3):
+        assert np.array_equal(np.load(out / ("w%d.npy" % l)), w[l]) and np.array_equal(np.load(out / ("b%d.npy" % l)), b[l])
+    assert np.array_equal(np.load(out / "scalefactor.npy"), alpha)

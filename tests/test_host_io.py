@@ -1,6 +1,6 @@
 """CPU: the C++ host code (CLI, norm, .wts, pfile reader, chunk planner, chunk reader,
-lrand48 shuffles) against independent restatements, synthetic pfiles, and -- in the build
-container only -- the reference's own sample pfiles/norm file (SURVEY.md 4 / 8c KATs)."""
+lrand48 shuffles) against independent restatements, synthetic pfiles, and the reference's
+own sample pfiles/norm file, stored under tests/golden/tools_pfile/ (SURVEY.md 4 / 8c KATs)."""
 import json
 import os
 import re
@@ -15,9 +15,12 @@ import pytest
 import finetune_recorder
 import hostlib
 
-REF = "/root/reference/tools_pfile"
-have_ref = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "train_noisy.pfile")),
-                              reason="reference sample files only exist in the build container")
+
+
+@pytest.fixture(scope="module")
+def ref_pfiles(tmp_path_factory):
+    """The reference's sample pfiles and norm file, unpacked from tests/golden/tools_pfile/."""
+    return hostlib.sample_pfiles(tmp_path_factory.mktemp("tools_pfile"))
 
 
 @pytest.fixture(scope="module")
@@ -182,8 +185,7 @@ def test_wts_container_kat(corpus, tmp_path):
     assert ws[0].std() > 0.3 * np.abs(ws[0]).max()
 
 
-@have_ref
-def test_reference_sample_pfiles(tmp_path):
+def test_reference_sample_pfiles(tmp_path, ref_pfiles):
     """The reference's own 10-sentence sample (tools_pfile/): reader + planner KATs, SURVEY.md 4."""
     ls = [257 * 7, 8, 257]
     rng = np.random.default_rng(0)
@@ -197,8 +199,8 @@ def test_reference_sample_pfiles(tmp_path):
                           [np.zeros(lsz[i + 1], np.float32) for i in range(2)])
         return hostlib.HostIO(layersizes=",".join(map(str, lsz)), bunchsize=128, fea_dim=257, fea_context=ctx,
                               traincache=cache, init_randem_seed=27870775, targ_offset=(ctx - 1) // 2,
-                              initwts_file=tmp_path / "i.wts", norm_file=REF + "/train_noisy.norm",
-                              fea_file=REF + "/train_noisy.pfile", targ_file=REF + "/train_clean.pfile",
+                              initwts_file=tmp_path / "i.wts", norm_file=ref_pfiles + "/train_noisy.norm",
+                              fea_file=ref_pfiles + "/train_noisy.pfile", targ_file=ref_pfiles + "/train_clean.pfile",
                               outwts_file=tmp_path / "o.wts", log_file=tmp_path / "l.txt")
 
     io = io_for(7, 102400)
@@ -213,14 +215,14 @@ def test_reference_sample_pfiles(tmp_path):
     # feature of the file is 13.5513
     inp, tg = io.read_chunk(0, 257 * 7, 257, 102400, cv=True)
     assert inp.shape == (382, 1799)
-    with open(REF + "/train_noisy.pfile", "rb") as f:
+    with open(ref_pfiles + "/train_noisy.pfile", "rb") as f:
         f.seek(32768 + 8)
         first = struct.unpack(">3f", f.read(12))
         assert [round(x, 4) for x in first] == [13.5513, 15.4622, 15.6788]
         f.seek(32768 + 1491 * 259 * 4 + 8)
         row = np.frombuffer(f.read(257 * 4), ">f4").astype(np.float32)
     assert np.array_equal(inp[0, :257], ((row - mean) * inv).astype(np.float32))
-    with open(REF + "/train_clean.pfile", "rb") as f:
+    with open(ref_pfiles + "/train_clean.pfile", "rb") as f:
         f.seek(32768 + 8)
         assert [round(x, 4) for x in struct.unpack(">2f", f.read(8))] == [10.8714, 9.1289]
         f.seek(32768 + (1491 + 3) * 259 * 4 + 8)
@@ -295,27 +297,32 @@ def test_rendezvous_never_accepts_a_stale_id_file(tmp_path):
         hostlib.rendezvous(path, 2, 1, None, timeout=0.2)
 
 
-@pytest.mark.skipif(not finetune_recorder.available(), reason="reference tree / perl not present")
-def test_reference_finetune_pl_argv_through_the_parser(tmp_path):
+def test_reference_finetune_pl_argv_through_the_parser(tmp_path, ref_pfiles):
     """the reference's epoch driver `finetune.pl` must run unmodified against the new binary
-    except `$exe`.  The script itself is run here by perl (in-container only; nothing of it is committed or shipped:
-    a temporary copy gets its `$exe` line pointed at a recorder, tests/finetune_recorder.py), and every argv its three
-    system() call sites emit (finetune.pl:50-76 epoch 1, :89-115 epochs 2-10, :127-153 epochs 11-50) goes through
-    Interface::Initial; each key must land where the reference's parser puts it (Interface.cc:150-315): strings
-    verbatim, ints by atoi, floats by atof -> float; `numlayers=` is not a key of that parser (the count comes from
-    layersizes=).  The recorded lists are also what tests/golden/finetune_argv.json holds (the GPU test
-    tests/test_gpu_finetune.py drives BPtrain_Sigmoid with them): the fixture must equal today's recording."""
+    except `$exe`.  Every argv its three system() call sites emit (finetune.pl:50-76 epoch 1, :89-115 epochs 2-10,
+    :127-153 epochs 11-50) -- recorded by running the script under perl against a recorder (tests/finetune_recorder.py
+    writes tests/golden/finetune_argv.json; the GPU test tests/test_gpu_finetune.py drives BPtrain_Sigmoid with the same
+    lists) -- goes through Interface::Initial in the directory tree the script runs in, with the reference's sample
+    pfiles (tests/golden/tools_pfile/) where its relative paths point; each key must land where the reference's parser
+    puts it (Interface.cc:150-315): strings verbatim, ints by atoi, floats by atof -> float; `numlayers=` is not a key
+    of that parser (the count comes from layersizes=)."""
     ls = finetune_recorder.LAYERS
     hostlib.lib()
-
-    def make_init(path):   # the init file finetune.pl:47 names is not shipped by the reference: gen_rand_net makes it (SURVEY 8f3)
-        subprocess.check_call([os.path.join(hostlib.HOST, "gen_rand_net"), "5", *map(str, ls), os.path.dirname(path), path,
-                               "1", "2", "5"], stdout=subprocess.DEVNULL)
-
-    argvs, tc = finetune_recorder.record(tmp_path, make_init)
+    argvs = json.load(open(finetune_recorder.FIXTURE))["argv"]
     assert len(argvs) == 50  # one process per epoch
     assert all(len(a) == 25 and a[1] == "numlayers=5" for a in argvs)
-    assert json.load(open(finetune_recorder.FIXTURE))["argv"] == argvs
+    # the tree finetune.pl runs in: Train_code_ML_GGD/{pretraining_weights,MLGGD1} next to tools_pfile/
+    top = tmp_path / "ref"
+    tc = str(top / "Train_code_ML_GGD")
+    os.makedirs(os.path.join(tc, "pretraining_weights"))
+    os.makedirs(os.path.join(tc, "MLGGD1"))
+    os.symlink(ref_pfiles, str(top / "tools_pfile"))
+    init = os.path.join(tc, "pretraining_weights", finetune_recorder.INIT_WTS)
+    # the init file finetune.pl:47 names is not shipped by the reference: gen_rand_net makes it (SURVEY 8f3)
+    subprocess.check_call([os.path.join(hostlib.HOST, "gen_rand_net"), "5", *map(str, ls), os.path.dirname(init), init,
+                           "1", "2", "5"], stdout=subprocess.DEVNULL)
+    for epoch in range(1, 50):  # each epoch resumes from the previous one's output: stand in for it with the init file
+        os.symlink(init, os.path.join(tc, "MLGGD1", "mlp.%d.wts" % epoch))
 
     seed, lrate = 27870775, 0.1
     for epoch in (1, 2, 10, 11, 12, 50):

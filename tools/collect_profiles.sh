@@ -9,7 +9,7 @@ Q="--no-cpu-baseline --no-kernel-timing --no-ml --no-dp-rehearsal --budget-s 200
 C5="--hidden 4096 --nhid 6 --bunch 512 --loss ml"
 case "$1" in
 a)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --no-cpu-baseline --no-dp-rehearsal --budget-s 2000 > $O/bench_under_rocprof.json 2>$O/trace.err &&
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-dp-rehearsal --budget-s 2000 > $O/bench_under_rocprof.json 2>$O/trace.err &&
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 40 --warmup 10 $Q > /dev/null 2>$O/f.err &&
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 40 --warmup 10 $Q > /dev/null 2>$O/w.err &&
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU --output-format csv -d $O/sq1 -- python3 $R/bench.py --steps 20 --warmup 5 $Q > /dev/null 2>$O/s1.err &&
@@ -22,14 +22,14 @@ rm -rf $O/trace $O/pmc_fetch $O/pmc_write $O/sq1 $O/sq2
 ;;
 b)
 cd $R
-python bench.py > $O/bench_n1.json 2> $O/bench_n1.err
+python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err
 python tools/stamps.py > $O/phase_stamps.txt 2>&1
 python tools/dwp_phases.py >> $O/phase_stamps.txt 2>&1
 python tools/dp_sim.py > $O/dp_sim.txt 2>&1
-python bench.py --loss ml --no-cpu-baseline --no-dp-rehearsal > $O/bench_ml.json 2>/dev/null
-python bench.py $C5 --no-cpu-baseline --no-dp-rehearsal --steps 100 --warmup 10 > $O/bench_cfg5.json 2>/dev/null
-python bench.py --bunch 256 --no-cpu-baseline --no-ml --no-dp-rehearsal > $O/bench_b256.json 2>/dev/null
-python bench.py --bunch 512 --no-cpu-baseline --no-ml --no-dp-rehearsal > $O/bench_b512.json 2>/dev/null
+python bench.py --full --loss ml --no-cpu-baseline --no-dp-rehearsal > $O/bench_ml.json 2>/dev/null
+python bench.py --full $C5 --no-cpu-baseline --no-dp-rehearsal --steps 100 --warmup 10 > $O/bench_cfg5.json 2>/dev/null
+python bench.py --full --bunch 256 --no-cpu-baseline --no-ml --no-dp-rehearsal > $O/bench_b256.json 2>/dev/null
+python bench.py --full --bunch 512 --no-cpu-baseline --no-ml --no-dp-rehearsal > $O/bench_b512.json 2>/dev/null
 ;;
 c)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace5 -- python3 $R/bench.py $C5 --steps 40 --warmup 10 --windows 3 $Q > /dev/null 2>$O/t5.err &&

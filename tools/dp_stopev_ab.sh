@@ -8,7 +8,7 @@ for ml in 0 1; do
     for f in 0 1; do
       [ $m = shard ] && [ $f = 1 ] && continue
       extra=""; [ $ml = 1 ] && extra="--loss ml"
-      MLGGD_DP_STOPEV=$ml MLGGD_DP_FINE=$f python3 $R/bench.py --rehearse-dp --dp-mode $m --steps 20 --warmup 5 --no-ml --no-dp-arms --no-kernel-timing 2>/dev/null | line "STOPEV=$ml $m DP_FINE=$f"
+      MLGGD_DP_STOPEV=$ml MLGGD_DP_FINE=$f python3 $R/bench.py --rehearse-dp --dp-mode $m --steps 20 --warmup 5 --windows 9 --no-ml --no-dp-arms --no-kernel-timing 2>/dev/null | line "STOPEV=$ml $m DP_FINE=$f"
     done
   done
 done
