@@ -195,6 +195,16 @@ int mlggd_dp_mode(mlggd_handle h, int *mode);
  * [r*bunchsize,(r+1)*bunchsize) of them.  mode: 0 = factor all-gather + replicated update, 1 = factor
  * all-gather + sharded update, 2 = gradient all-reduce, 3 = sharded update with the activations by all-to-all. */
 int mlggd_debug_fake_world(mlggd_handle h, int world_size, int mode);
+/* Test hook: per-rank read-back of a training step.  mlggd_debug_keep_ranks(h, 1) (after mlggd_debug_fake_world, or
+ * before it, and before training) makes every step copy what emulated ranks 0..world-2 computed -- device-to-device
+ * copies on the engine's stream, taken where each rank produced it; nothing else of the step changes.  Off (the
+ * default): no allocation and no extra launch.  mlggd_debug_rank_tensor then returns rank `rank`'s tensor of the
+ * last step, row-major and un-padded: "x" [bunchsize][units(0)] = the input rows the step's kernels consumed (after
+ * input dropout); "y" (layer 1..numlayers-2), "dedx" (layer 1..numlayers-1) [bunchsize][units(layer)]; "out"
+ * [bunchsize][units(numlayers-1)].  The rank whose step ran last (the last emulated rank; a communicator's own rank;
+ * rank 0 on one device) reads the current buffers and needs no snapshot. */
+int mlggd_debug_keep_ranks(mlggd_handle h, int on);
+int mlggd_debug_rank_tensor(mlggd_handle h, const char *name, int layer, int rank, float *dst, size_t count);
 /* Test hook: number of launch plans (tile-record tables) the persistent dW kernel has cached; constant after the
  * first steps of a run (2 on one GPU, a few in the data-parallel modes). */
 int mlggd_debug_plan_count(mlggd_handle h, int *plans);

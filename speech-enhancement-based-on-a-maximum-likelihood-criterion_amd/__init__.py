@@ -49,6 +49,7 @@ EXPORTS = [
     "mlggd_load_frames", "mlggd_train_frames", "mlggd_train_frames_async", "mlggd_cv_all_frames", "mlggd_forward_frames",
     "mlggd_alloc_pinned", "mlggd_alloc_pinned_on", "mlggd_free_pinned", "mlggd_set_cv_device_reduce",
     "mlggd_comm_info", "mlggd_debug_plan_count", "mlggd_debug_math", "mlggd_debug_out_slabs", "mlggd_debug_gemm_plan",
+    "mlggd_debug_keep_ranks", "mlggd_debug_rank_tensor",
 ]
 
 _lib = None
@@ -108,6 +109,8 @@ def load():
     L.mlggd_dw_launches_per_step.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.mlggd_dp_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.mlggd_debug_fake_world.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.mlggd_debug_keep_ranks.argtypes = [C.c_void_p, C.c_int]
+    L.mlggd_debug_rank_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _fp, C.c_size_t]
     L.mlggd_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mlggd_debug_plan_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.mlggd_debug_out_slabs.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
@@ -447,6 +450,22 @@ class BPGpu:
         """Emulate world_size ranks on this GPU: every step consumes world_size*bunchsize rows, rank r owns
         rows [r*bunchsize,(r+1)*bunchsize) of them (test hook, mlggd_debug_fake_world)."""
         _check(load().mlggd_debug_fake_world(self._h, int(world_size), 3 if a2a else 2 if allreduce else 1 if sharded else 0))
+
+    def keep_ranks(self, on=True):
+        """From the next step on, keep what every emulated rank computed (test hook, mlggd_debug_keep_ranks)."""
+        _check(load().mlggd_debug_keep_ranks(self._h, 1 if on else 0))
+
+    def rank_tensor(self, name, layer=0, rank=0):
+        """Rank `rank`'s "x" (input rows after input dropout), "y", "dedx" or "out" of the last step, [bunchsize][units]
+        (test hook, mlggd_debug_rank_tensor)."""
+        units = {"x": self.K0, "out": self.D}.get(name)
+        if units is None:
+            if name not in ("y", "dedx"):
+                raise KeyError(name)
+            units = self.layersizes[layer]
+        a = np.empty((self.bunchsize, units), np.float32)
+        _check(load().mlggd_debug_rank_tensor(self._h, name.encode(), int(layer), int(rank), _p(a), a.size))
+        return a
 
     def stamp_select(self, kernel_class, layer):
         _check(load().mlggd_debug_stamp_select(self._h, kernel_class.encode(), int(layer)))

@@ -242,6 +242,10 @@ struct mlggd_engine {
     bool ev_W_pending[MLGGD_MAXLAYER] = {false};
     bool fake_world = false;  // test hook: `world` ranks emulated one after the other on this GPU, no communicator
     float *Yall[MLGGD_MAXLAYER] = {0}, *dEdXall[MLGGD_MAXLAYER] = {0};
+    // test hook (mlggd_debug_keep_ranks): what emulated ranks 0..world-2 computed in the last step, copied where they
+    // produced it (fake_world_prepass) -- the staged input rows, Y_l, dEdX_l and the output, in the engine's layouts
+    bool keep_ranks = false;
+    std::vector<float *> snap_x, snap_out, snap_y[MLGGD_MAXLAYER], snap_dedx[MLGGD_MAXLAYER];
     hipEvent_t ev_ready = nullptr, ev_gathered = nullptr;
     // fine-grained factor exchange (few ranks: cheap collectives, few links): every factor is sent as soon as it
     // exists, and ev_layer[l] marks the moment both factors of layer l have arrived
@@ -1230,6 +1234,46 @@ static int launch_accum(float *dst, const float *a, const float *b, size_t n, hi
 // colsum_tot, their factors in slot r of Yall / dEdXall (gather modes), or their gradients summed into
 // Gpre / gbpre (all-reduce mode).  The last rank then takes the real data-parallel path of run_step with
 // device copies / adds in place of the RCCL calls.
+// floats of Y_l (l = 0: the staged input rows) as the producers write it: [Bp][lsp[l]], or -- all-to-all form -- owner-
+// blocked, world blocks of [Bp][block width of layer l+1]
+static size_t y_count(const mlggd_engine *e, int l) {
+    return e->dp_a2a ? (size_t)e->world * e->Bp * e->shard_rows[l + 1] * 64 : (size_t)e->Bp * e->lsp[l];
+}
+static int keep_alloc(mlggd_engine *e) {
+    if (!e->keep_ranks || !e->fake_world || !e->snap_x.empty()) return MLGGD_OK;
+    for (int r = 0; r + 1 < e->world; r++) {
+        float *p = nullptr;
+        CHK(dev_alloc(e, &p, y_count(e, 0)));
+        e->snap_x.push_back(p);
+        CHK(dev_alloc(e, &p, (size_t)e->Dp * e->Bp));
+        e->snap_out.push_back(p);
+        for (int l = 1; l < e->L; l++) {
+            if (l < e->L - 1) {
+                CHK(dev_alloc(e, &p, y_count(e, l)));
+                e->snap_y[l].push_back(p);
+            }
+            CHK(dev_alloc(e, &p, (size_t)e->Bp * e->lsp[l]));
+            e->snap_dedx[l].push_back(p);
+        }
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+// emulated rank r's step is complete up to dW: its factors and output, device to device on the engine's stream
+static int keep_snapshot(mlggd_engine *e, int r, const float *in_rows) {
+    auto cp = [&](float *dst, const float *src, size_t count) -> int {
+        HIPCHK(hipMemcpyAsync(dst, src, count * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+        return MLGGD_OK;
+    };
+    CHK(cp(e->snap_x[r], in_rows, y_count(e, 0)));
+    CHK(cp(e->snap_out[r], e->outT, (size_t)e->Dp * e->Bp));
+    for (int l = 1; l < e->L; l++) {
+        if (l < e->L - 1) CHK(cp(e->snap_y[l][r], e->Y[l], y_count(e, l)));
+        CHK(cp(e->snap_dedx[l][r], e->dEdX[l], (size_t)e->Bp * e->lsp[l]));
+    }
+    return MLGGD_OK;
+}
+
 static int fake_world_prepass(mlggd_engine *e, int sample0, float nf, float inv_n) {
     const int L = e->L, B = e->B, Bp = e->Bp, W = e->world;
     StageArgs none;
@@ -1246,6 +1290,7 @@ static int fake_world_prepass(mlggd_engine *e, int sample0, float nf, float inv_
         const float *in_rows = bunch_rows(e, bn);
         CHK(run_loss(e, bn, nf, inv_n, CS_GIVEN, false, none, 0));
         for (int l = L - 1; l >= 2; l--) CHK(run_dx(e, l));
+        if (e->keep_ranks) CHK(keep_snapshot(e, r, in_rows));
         if (e->dp_mode >= 1) {
             auto put = [&](const float *src, float *dst, size_t count) -> int {
                 HIPCHK(hipMemcpyAsync(dst + (size_t)r * count, src, count * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
@@ -2191,6 +2236,28 @@ int mlggd_forward_frames(mlggd_handle e, int n_frames, int fea_context, const fl
     return MLGGD_OK;
 }
 
+// row-major [B][N] on the host from a device activation buffer: [Bp][Np], or owner-blocked [world][Bp][yb] (yb > 0:
+// the all-to-all form's Y_l and staged rows)
+static int rows_to_host(mlggd_engine *e, const float *src, int N, int Np, int yb, float *dst) {
+    const int B = e->B, Bp = e->Bp;
+    std::vector<float> t(yb ? (size_t)e->world * Bp * yb : (size_t)Bp * Np);
+    HIPCHK(hipMemcpyAsync(t.data(), src, t.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int b = 0; b < B; b++)
+        for (int n = 0; n < N; n++)
+            dst[(size_t)b * N + n] = yb ? t[(size_t)(n / yb) * Bp * yb + (size_t)b * yb + n % yb] : t[(size_t)b * Np + n];
+    return MLGGD_OK;
+}
+// [B][D] on the host from outT [Dp][Bp]
+static int out_to_host(mlggd_engine *e, const float *outT, float *dst) {
+    std::vector<float> t((size_t)e->Dp * e->Bp);
+    HIPCHK(hipMemcpyAsync(t.data(), outT, t.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    for (int b = 0; b < e->B; b++)
+        for (int d = 0; d < e->D; d++) dst[(size_t)b * e->D + d] = t[(size_t)d * e->Bp + b];
+    return MLGGD_OK;
+}
+
 int mlggd_debug_tensor(mlggd_handle e, const char *name, int layer, float *dst, size_t count) {
     if (!e || !name || !dst) return fail(MLGGD_ERR_ARG, "NULL argument");
     HIPCHK(hipSetDevice(e->device));
@@ -2205,12 +2272,7 @@ int mlggd_debug_tensor(mlggd_handle e, const char *name, int layer, float *dst, 
     }
     if (nm == "out") {  // outT [Dp][Bp] -> [B][D]
         CHK(need((size_t)B * e->D));
-        std::vector<float> t((size_t)e->Dp * Bp);
-        HIPCHK(hipMemcpyAsync(t.data(), e->outT, t.size() * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        for (int b = 0; b < B; b++)
-            for (int d = 0; d < e->D; d++) dst[(size_t)b * e->D + d] = t[(size_t)d * Bp + b];
-        return MLGGD_OK;
+        return out_to_host(e, e->outT, dst);
     }
     if (layer < 1 || layer >= L) return fail(MLGGD_ERR_ARG, "layer %d not in 1..%d", layer, L - 1);
     const int N = e->ls[layer], Np = e->lsp[layer], K = e->ls[layer - 1];
@@ -2220,21 +2282,12 @@ int mlggd_debug_tensor(mlggd_handle e, const char *name, int layer, float *dst, 
                            : (nm == "yt") ? e->Yt[layer] : e->dEdXt[layer];
         if (!src) return fail(MLGGD_ERR_ARG, "%s not kept for layer %d", name, layer);
         CHK(need((size_t)B * N));
+        if (!tr) return rows_to_host(e, src, N, Np, (nm == "y" && e->dp_a2a && layer < L - 1) ? e->shard_rows[layer + 1] * 64 : 0, dst);
         std::vector<float> t((size_t)Np * Bp);
         HIPCHK(hipMemcpyAsync(t.data(), src, t.size() * 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
-        const int yb = (nm == "y" && e->dp_a2a && layer < L - 1) ? e->shard_rows[layer + 1] * 64 : 0;
-        if (yb) {  // owner-blocked layout (all-to-all form): [block][Bp][yb]
-            std::vector<float> tb((size_t)e->world * Bp * yb);
-            HIPCHK(hipMemcpyAsync(tb.data(), src, tb.size() * 4, hipMemcpyDeviceToHost, e->stream));
-            HIPCHK(hipStreamSynchronize(e->stream));
-            for (int b = 0; b < B; b++)
-                for (int n = 0; n < N; n++) dst[(size_t)b * N + n] = tb[(size_t)(n / yb) * Bp * yb + (size_t)b * yb + n % yb];
-            return MLGGD_OK;
-        }
         for (int b = 0; b < B; b++)
-            for (int n = 0; n < N; n++)
-                dst[(size_t)b * N + n] = tr ? t[(size_t)n * Bp + b] : t[(size_t)b * Np + n];
+            for (int n = 0; n < N; n++) dst[(size_t)b * N + n] = t[(size_t)n * Bp + b];
         return MLGGD_OK;
     }
     if (nm == "weights" || nm == "delta_w" || nm == "grad_w") {
@@ -2253,6 +2306,44 @@ int mlggd_debug_tensor(mlggd_handle e, const char *name, int layer, float *dst, 
                               hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         return MLGGD_OK;
+    }
+    return fail(MLGGD_ERR_ARG, "unknown tensor name '%s'", name);
+}
+
+int mlggd_debug_keep_ranks(mlggd_handle e, int on) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    HIPCHK(hipSetDevice(e->device));
+    e->keep_ranks = on != 0;
+    return keep_alloc(e);
+}
+
+int mlggd_debug_rank_tensor(mlggd_handle e, const char *name, int layer, int rank, float *dst, size_t count) {
+    if (!e || !name || !dst) return fail(MLGGD_ERR_ARG, "NULL argument");
+    HIPCHK(hipSetDevice(e->device));
+    const int L = e->L, B = e->B;
+    const std::string nm(name);
+    if (rank < 0 || rank >= e->world) return fail(MLGGD_ERR_ARG, "rank %d not in 0..%d", rank, e->world - 1);
+    // the rank whose step ran last in this process reads the live buffers; an emulated earlier rank its snapshot
+    const bool live = rank == (e->fake_world ? e->world - 1 : e->rank);
+    if (!live && (!e->fake_world || (size_t)rank >= e->snap_x.size()))
+        return fail(MLGGD_ERR_STATE, "rank %d: only emulated ranks are kept (mlggd_debug_keep_ranks before training)", rank);
+    auto need = [&](size_t n) -> int {
+        return count < n ? fail(MLGGD_ERR_ARG, "dst holds %zu floats, %s needs %zu", count, name, n) : MLGGD_OK;
+    };
+    if (nm == "out") {
+        CHK(need((size_t)B * e->D));
+        return out_to_host(e, live ? e->outT : e->snap_out[rank], dst);
+    }
+    if (nm == "x") {
+        CHK(need((size_t)B * e->ls[0]));
+        return rows_to_host(e, live ? e->in_bunch : e->snap_x[rank], e->ls[0], e->lsp[0], e->dp_a2a ? e->shard_rows[1] * 64 : 0, dst);
+    }
+    if (nm == "y" || nm == "dedx") {
+        const bool y = nm == "y";
+        if (layer < 1 || layer >= (y ? L - 1 : L)) return fail(MLGGD_ERR_ARG, "%s: layer %d not in 1..%d", name, layer, y ? L - 2 : L - 1);
+        CHK(need((size_t)B * e->ls[layer]));
+        const float *src = y ? (live ? e->Y[layer] : e->snap_y[layer][rank]) : (live ? e->dEdX[layer] : e->snap_dedx[layer][rank]);
+        return rows_to_host(e, src, e->ls[layer], e->lsp[layer], (y && e->dp_a2a) ? e->shard_rows[layer + 1] * 64 : 0, dst);
     }
     return fail(MLGGD_ERR_ARG, "unknown tensor name '%s'", name);
 }
@@ -2419,12 +2510,14 @@ int mlggd_debug_fake_world(mlggd_handle e, int world_size, int mode) {
         CHK(allreduce_alloc(e));
         for (int l = 1; l < e->L; l++) CHK(dev_alloc(e, &e->Gpre[l], (size_t)e->lsp[l - 1] * e->lsp[l]));
         CHK(dev_alloc(e, &e->gbpre, e->gb_all_count));
+        CHK(keep_alloc(e));
         HIPCHK(hipStreamSynchronize(e->stream));
         return MLGGD_OK;
     }
     if (mode == 3) CHK(shard_alloc(e));
     CHK(gather_alloc(e));
     if (mode == 1) CHK(shard_alloc(e));
+    CHK(keep_alloc(e));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }

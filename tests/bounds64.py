@@ -30,6 +30,29 @@ used here, where every sum of relative error coefficients stays below 1e-2):
 * weight apply: W' = fl32(W + D') exactly (one IEEE add).
 * CV sums: see `expect_cv`.
 
+Data-parallel steps (one process per rank, or ranks emulated on one device): rows are independent up to the loss, so
+the ranks' rows stacked in rank order -- world x B rows of x, y, out and dedx, each rank's read back where it produced
+them -- form one step of n = world B rows, and `check_step` applies unchanged.  What the ranks do differently is only
+the ORDER of the sums over frames, which the any-order bounds above already cover:
+* dW / G on the all-reduce path: each rank's fp32 chain over its B frames, then world - 1 adds of the partial sums
+  (Gpre + G, k_accum, or the collective's own order).  Along any path of that tree an element's product meets at most
+  (B - 1) + (world - 1) <= n - 1 roundings, so |fl - exact| <= gamma_{n-1} sum |y||d| <= the gamma_B-of-n term of
+  `expect_dw` / `expect_grad`.  The gather modes form the sum over all n frames in one chain: the same bound.
+* a division by n taken per rank before the sum (G_r / n, then the adds) adds one rounding per term: gamma_n, which the
+  bound of `expect_dw` (gamma_n for the GEMM, 6u of slack for the update) contains.
+* the ML column sums met in rank order (k_colsum per rank, then k_accum, or the all-reduce): a sum of n non-negative
+  terms in some order, gamma_{n-1} <= gamma_n of `loss_rel` -- evaluated at n = world B rows, which `expect_loss`
+  does when it is given the stacked output.  The 1/n of the gradient and of alpha is the global n on every rank.
+* the update (k_apply_update: fl(G / n), the same four operations as the fused epilogue) is the 6u slack of `expect_dw`.
+So a data-parallel step needs no new bound; `expect_grad` adds the summed gradient G itself (before k_apply_update).
+
+Dropout (training, one device): y = mask * sigma(z), no rescale, the same mask on the row-major and the transposed copy
+of each layer; `expect_dropout_layer` expects exactly 0 where a unit was dropped and the sigmoid bound elsewhere.  The
+mask is read off the engine's own y (y == 0 where the bound does not allow 0); `mask_stats` then holds it to binomial
+limits (rate, per unit, per frame, overlap between masks), so that a mask read off wrongly -- or drawn wrongly -- shows.
+CV under dropout (`cv_dropout_weights`): bunch j runs on fl32(W_j keep) with W_{j+1} = fl32(fl32(W_j keep) fl32(1/keep))
+exactly (k_scale before and after each GEMM); the outputs go to `expect_forward_chain`, the weights compare exactly.
+
 Tight statistic: err minus the non-GEMM part of the bound, divided by u times the GEMM's sum of |a||b| (scaled as the
 element is), maximised over the tensor and asserted <= 4 sqrt(K + S).  A correct fp32 dot product of K terms sits at
 a few units of this (the rounding errors of a chain do not all point one way); an order-preserving loss of precision
@@ -374,6 +397,7 @@ class Step:
     ml: int
     slabs: int = 1
     alpha: np.ndarray = None
+    dropout: bool = False     # hidden layers masked (training with dropoutflag): `expect_dropout_layer`
 
 
 def check_step(s, layers=None):
@@ -384,7 +408,9 @@ def check_step(s, layers=None):
     yin = lambda l: s.x if l == 1 else s.y[l - 1]
     reps = []
     for l in sorted(layers):
-        if l < L - 1:
+        if l < L - 1 and s.dropout:
+            reps.append(compare("fwd %d" % l, s.y[l], expect_dropout_layer(yin(l), s.W[l - 1], s.b[l - 1], s.y[l])[0]))
+        elif l < L - 1:
             reps.append(compare("fwd %d" % l, s.y[l], expect_sigmoid_layer(yin(l), s.W[l - 1], s.b[l - 1])))
         else:
             reps.append(compare("out (S=%d)" % s.slabs, s.out, expect_linear(yin(l), s.W[l - 1], s.b[l - 1], s.slabs)))
@@ -401,3 +427,100 @@ def check_step(s, layers=None):
         reps.append(compare_exact("apply W %d" % l, s.W_new[l - 1], apply_exact(s.W[l - 1], s.dW_new[l - 1])))
         reps.append(compare_exact("apply b %d" % l, s.b_new[l - 1], apply_exact(s.b[l - 1], s.db_new[l - 1])))
     return reps
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# data parallel
+def expect_grad(y_prev, d):
+    """G_l = Y^T dEdX over the whole minibatch, what the all-reduce path holds before k_apply_update (dEdX carries the
+    1/n already): any order of the n products (per-rank chains, then the adds): gamma_n sum |y||d|; the products may
+    underflow, n TINY / 2 more"""
+    y, d = _d(y_prev), _d(d)
+    n = y.shape[0]
+    GS = np.abs(y).T @ np.abs(d)
+    slack = n * TINY / 2.0
+    return Expect(y.T @ d, gamma(n) * GS + slack, slack, U * GS, 4.0 * math.sqrt(n))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dropout
+def expect_dropout_layer(x, W, b, y):
+    """hidden layer under dropout: y = mask * sigma(x W + b), no rescale.  The mask is read off the engine's own `y`: a
+    unit is dropped where y == 0 and the sigmoid bound does not allow 0.  Returns (Expect, dropped, known): exactly 0
+    with a zero bound where dropped, the sigmoid bound elsewhere; `known` marks where the mask is determined (False
+    where sigma may round to 0 anyway: there a dropped and a kept unit look alike).  Where the mask is unknown and
+    y == 0, the unit may have been dropped: its error |0 - sigma(z)| is then no rounding error, so it joins the slack
+    (the tight statistic measures the GEMM's rounding only); the hard bound already allows it (bound >= sigma(z))."""
+    e = expect_sigmoid_layer(x, W, b)
+    allow0 = e.ref - e.bound * SECOND_ORDER <= 0.0
+    y0 = np.asarray(y) == 0
+    drop = y0 & ~allow0
+    z = lambda a: np.where(drop, 0.0, np.broadcast_to(a, drop.shape))
+    slack = np.where(y0 & allow0, np.maximum(e.slack, e.ref), e.slack)
+    return Expect(z(e.ref), z(e.bound), z(slack), z(e.den), e.limit), drop, ~allow0
+
+
+def input_mask(x_raw, x_seen):
+    """the input layer's mask from the raw rows and the rows the kernels consumed: every element is either untouched
+    or exactly 0.  Returns (Report of elements that are neither, dropped, known)"""
+    x_raw, x_seen = np.asarray(x_raw, np.float32), np.asarray(x_seen, np.float32)
+    same = x_seen.view(np.uint32) == x_raw.view(np.uint32)
+    drop = (x_seen == 0) & (x_raw != 0)
+    bad = ~same & ~drop
+    where = [tuple(int(i) for i in ix) for ix in np.argwhere(bad)[:5]]
+    return Report("x = raw or 0", int(bad.sum()), int(bad.size), float(np.inf if bad.any() else 0.0), 0.0, 0.0,
+                  where), drop, x_raw != 0
+
+
+def _zreport(name, z, size):
+    """a binomial statistic as a Report: hard = |z| / 6 (6 sigma), one violation when it exceeds 1"""
+    h = abs(float(z)) / 6.0
+    return Report(name, int(not h <= 1.0), size, h, 0.0, 0.0)
+
+
+def _dispersion(c, n, p):
+    """chi-square of counts c out of n (per unit or per frame) against Binomial(n, p), as a z-score: each standardised
+    square has mean 1 and variance 2 + (1 - 6pq) / (npq)"""
+    keep = n > 0
+    c, n = c[keep].astype(np.float64), n[keep].astype(np.float64)
+    q = 1.0 - p
+    chi = ((c - n * p) ** 2 / (n * p * q)).sum()
+    var = (2.0 + (1.0 - 6.0 * p * q) / (n * p * q)).sum()
+    return (chi - keep.sum()) / math.sqrt(var)
+
+
+def mask_stats(name, drop, known, p):
+    """a dropout mask [frames][units] (True = dropped) against independent Bernoulli(p) draws, on the elements where
+    it is known: the rate, the dispersion of the counts per unit and per frame (a hash of only the frame or only the
+    unit makes them all-or-nothing)"""
+    drop, known = np.asarray(drop, bool) & known, np.asarray(known, bool)
+    n = int(known.sum())
+    k = int(drop.sum())
+    reps = [_zreport("%s rate %.4f" % (name, k / max(n, 1)), (k - n * p) / math.sqrt(n * p * (1.0 - p)), n)]
+    reps.append(_zreport("%s per unit" % name, _dispersion(drop.sum(0), known.sum(0), p), n))
+    reps.append(_zreport("%s per frame" % name, _dispersion(drop.sum(1), known.sum(1), p), n))
+    return reps
+
+
+def mask_overlap(name, d1, k1, d2, k2, p1, p2):
+    """two masks that should be independent (consecutive steps, two layers, two seeds) on their common [frames][units]
+    corner: the fraction dropped in both is p1 p2"""
+    r, c = min(d1.shape[0], d2.shape[0]), min(d1.shape[1], d2.shape[1])
+    known = k1[:r, :c] & k2[:r, :c]
+    both = int((d1[:r, :c] & d2[:r, :c] & known).sum())
+    n, pp = int(known.sum()), p1 * p2
+    return _zreport("%s overlap %.4f" % (name, both / max(n, 1)), (both - n * pp) / math.sqrt(n * pp * (1.0 - pp)), n)
+
+
+def cv_dropout_weights(W, keeps, bunches):
+    """forward() under dropout scales W_l by keep_l before its GEMM and by fl32(1/keep_l) after it (k_scale; the
+    reference's kernWeightMultiP, BP_GPU.cu:484-501).  Returns ([the weights bunch j's GEMMs read, j < bunches], the
+    weights left behind), exactly in fp32"""
+    F = np.float32
+    cur = [np.asarray(w, F).copy() for w in W]
+    used = []
+    for _ in range(bunches):
+        sc = [(w * F(k)).astype(F) for w, k in zip(cur, keeps)]
+        used.append(sc)
+        cur = [(s * (F(1) / F(k))).astype(F) for s, k in zip(sc, keeps)]
+    return used, cur

@@ -315,3 +315,262 @@ def test_forward_chain_bound_and_ragged_rows(mut):
         assert r.ok, r.line()
     else:
         assert r.count > 0 and all(i >= 2 * B for i, _ in r.where), r.line()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. data-parallel steps: a rank-split fp32 implementation (per-rank chains, statistics and partial sums met in rank
+# order), checked as ONE step of the ranks' rows stacked in rank order -- the form tests/test_gpu_dp_vs_float64.py uses
+def fp32_dp_step(x, t, W, b, dW, db, hp, beta, ml, world, mut=None):
+    lr, mom, wc = (F(v) for v in hp)
+    beta = F(beta)
+    L = len(W) + 1
+    n = x.shape[0]
+    B = n // world
+    rows = [slice(r * B, (r + 1) * B) for r in range(world)]
+    ys, outs, es = [], [], []
+    for sl in rows:
+        y = {0: np.asarray(x[sl], F)}
+        for l in range(1, L - 1):
+            y[l] = sigmoid32((mm_np32(y[l - 1], W[l - 1]) + b[l - 1]).astype(F))
+        out = (mm_np32(y[L - 2], W[L - 2]) + b[L - 2]).astype(F)
+        ys.append(y)
+        outs.append(out)
+        es.append((out - np.asarray(t[sl], F)).astype(F))
+    inv_n = F(1) / F(n)
+    alpha = None
+    if ml == 1:                                     # k_colsum per rank, k_accum in rank order
+        parts = [(np.abs(e) ** beta).astype(F).sum(axis=0, dtype=F) for e in es]
+        s = parts[-1] if mut == "ml_last_rank" else parts[0]
+        for p in ([] if mut == "ml_last_rank" else parts[1:]):
+            s = (s + p).astype(F)
+        alpha = (((s / F(n)).astype(F) * beta).astype(F) ** (F(1) / beta)).astype(F)
+        q = (alpha ** beta).astype(F)
+    ds = []
+    for y, e in zip(ys, es):
+        with np.errstate(divide="ignore"):
+            P = np.where(e == 0, F(0), np.abs(e) ** (beta - F(1))).astype(F)
+        g = ((np.sign(e) * P * beta).astype(F) / q).astype(F) if ml == 1 else (beta * np.sign(e) * P).astype(F)
+        d = {L - 1: (g * inv_n).astype(F)}
+        for l in range(L - 2, 0, -1):
+            d[l] = (mm_np32(d[l + 1], W[l].T) * (y[l] * (F(1) - y[l])).astype(F)).astype(F)
+        ds.append(d)
+    nf = F(B) if mut == "local_n" else F(n)
+    dW_new, db_new, W_new, b_new = [], [], [], []
+    for l in range(1, L):
+        fy = [y[l - 1].copy() for y in ys]
+        fd = [d[l].copy() for d in ds]
+        if mut == "seam":                           # rank r's first frame replaced by rank r-1's last in the factors
+            for r in range(world - 1, 0, -1):
+                fy[r][0], fd[r][0] = fy[r - 1][-1], fd[r - 1][-1]
+        G = [mm_np32(a.T, c) for a, c in zip(fy, fd)]
+        order = list(range(world))
+        if mut == "rank_twice":
+            order.append(0)
+        elif mut == "rank_missing":
+            order.remove(1)
+        Gs = G[order[0]]
+        for r in order[1:]:
+            Gs = (Gs + G[r]).astype(F)
+        gb = [c.sum(axis=0, dtype=F) for c in fd]
+        gbs = gb[-1] if mut == "bias_last_rank" else gb[0]
+        for v in ([] if mut == "bias_last_rank" else gb[1:]):
+            gbs = (gbs + v).astype(F)
+        upd = lambda Wo, Do: ((mom * Do - lr * ((Gs / nf).astype(F) + (wc * Wo).astype(F))).astype(F))
+        D = upd(W[l - 1], dW[l - 1])
+        Wn = (W[l - 1] + D).astype(F)
+        if l == 1 and mut in ("tile_row_stale", "tile_row_twice"):   # the 64-row shard tile row 1 of layer 1
+            tr = slice(64, 128)
+            if mut == "tile_row_stale":
+                D[tr], Wn[tr] = dW[0][tr], W[0][tr]
+            else:
+                D2 = upd(Wn, D)
+                D[tr], Wn[tr] = D2[tr], (Wn + D2).astype(F)[tr]
+        dW_new.append(D)
+        W_new.append(Wn)
+        Db = (mom * db[l - 1] - lr * (gbs / nf).astype(F)).astype(F)
+        db_new.append(Db)
+        b_new.append((b[l - 1] + Db).astype(F))
+    stack = lambda k: np.vstack([y[k] for y in ys])
+    st = b6.Step(np.asarray(x, F), np.asarray(t, F), list(W), list(b), list(dW), list(db),
+                 {l: stack(l) for l in range(1, L - 1)}, np.vstack(outs),
+                 {l: np.vstack([d[l] for d in ds]) for l in range(1, L)}, dW_new, db_new, W_new, b_new,
+                 float(lr), float(mom), float(wc), float(beta), ml, 1, alpha)
+    st.grad = [(np.vstack([y[l - 1] for y in ys]), Gs) for l in [L - 1]]   # layer L-1's factors and summed G
+    return st
+
+
+def dp_two_steps(ls, B, world, hp, beta, ml, seed=1, mut=None):
+    W, b = b6.make_net(ls, seed)
+    n = world * B
+    x, t = b6.make_data(ls, 2 * n, seed + 1, 8, W[0], B)
+    s1 = fp32_dp_step(x[:n], t[:n], W, b, [np.zeros_like(w) for w in W], [np.zeros_like(v) for v in b], hp, beta,
+                      ml, world)
+    return fp32_dp_step(x[n:], t[n:], s1.W_new, s1.b_new, s1.dW_new, s1.db_new, hp, beta, ml, world, mut)
+
+
+@pytest.mark.parametrize("world,B", [(2, 50), (3, 50), (8, 20)])
+@pytest.mark.parametrize("ml,beta,hp", [(1, 1.2, (0.3, 0.5, 1e-2)), (1, 0.9, (0.1, 0.9, 1e-5)), (0, 2.0, (0.1, 0.9, 1e-5))])
+def test_rank_split_implementation_passes_every_bound(world, B, ml, beta, hp):
+    s = dp_two_steps([300, 250, 97, 33], B, world, hp, beta, ml, seed=5 + world)
+    reps = b6.check_step(s)
+    y, G = s.grad[0]
+    reps.append(b6.compare("grad %d" % (len(s.W)), G, b6.expect_grad(y, s.dedx[len(s.W)])))
+    print("rank split world %d B %d: worst hard %.4f tight %.2f" % (
+        world, B, max(r.hard for r in reps), max(r.tight / r.limit for r in reps if r.limit > 0)))
+    assert_clean(reps)
+
+
+DP_KILLS = [
+    ("local_n", "dw 1"), ("local_n", "db 2"),
+    ("ml_last_rank", "alpha"), ("ml_last_rank", "loss ML beta 1.2"),
+    ("rank_twice", "dw 1"), ("rank_missing", "dw 2"),
+    ("seam", "dw 1"),
+    ("tile_row_stale", "apply W 1"), ("tile_row_stale", "dw 1"), ("tile_row_twice", "dw 1"),
+    ("bias_last_rank", "db 1"),
+]
+
+
+@pytest.mark.parametrize("mut,report", DP_KILLS)
+def test_data_parallel_slip_is_killed(mut, report):
+    s = dp_two_steps([300, 250, 97, 33], 50, 3, (0.3, 0.5, 1e-2), 1.2, 1, seed=8, mut=mut)
+    r = {r.name: r for r in b6.check_step(s)}[report]
+    print("%-16s -> %s" % (mut, r.line()))
+    assert r.count > 0, r.line()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. dropout: the training step with masks, CV's weight round trips, the mask statistics
+def fp32_dropout_step(x, t, W, b, dW, db, hp, beta, p_in, p_hid, rng, mut=None):
+    """one training step under dropout (MMSE, beta as given): a mask per layer, the row-major copy (reported, dW's
+    operand) and the transposed copy (the next forward's and dX's operand).  Returns (Step, {layer: mask})."""
+    lr, mom, wc = (F(v) for v in hp)
+    beta = F(beta)
+    L = len(W) + 1
+    n = x.shape[0]
+
+    def draw(shape, p):
+        if mut == "unit_hash":
+            return np.broadcast_to(rng.random(shape[1]) < p, shape).copy()
+        return rng.random(shape) < p
+
+    masks = {0: draw(x.shape, p_in)}
+    xr = np.where(masks[0], F(0), x).astype(F)            # row-major input (in_bunch)
+    yt = {0: xr}
+    if mut == "input_row_missing":
+        xr = np.asarray(x, F)
+    yr = {0: xr}
+    for l in range(1, L - 1):
+        z = (mm_np32(yt[l - 1], W[l - 1]) + b[l - 1]).astype(F)
+        s = sigmoid32(z)
+        masks[l] = draw(s.shape, p_hid)
+        yt[l] = np.where(masks[l], F(0), s).astype(F)
+        if mut == "inverted":
+            yt[l] = (yt[l] * (F(1) / F(1 - p_hid))).astype(F)
+        yr[l] = s if (mut == "mask_T_only" and l == 1) else yt[l]
+    out = (mm_np32(yt[L - 2], W[L - 2]) + b[L - 2]).astype(F)
+    e = (out - np.asarray(t, F)).astype(F)
+    P = (np.abs(e) ** (beta - F(1))).astype(F)
+    d = {L - 1: ((beta * np.sign(e) * P).astype(F) * (F(1) / F(n))).astype(F)}
+    for l in range(L - 2, 0, -1):
+        d[l] = (mm_np32(d[l + 1], W[l].T) * (yt[l] * (F(1) - yt[l])).astype(F)).astype(F)
+    dW_new, db_new, W_new, b_new = [], [], [], []
+    for l in range(1, L):
+        D = (mom * dW[l - 1] - lr * ((mm_np32(yr[l - 1].T, d[l]) / F(n)).astype(F) + (wc * W[l - 1]).astype(F))).astype(F)
+        Db = (mom * db[l - 1] - lr * (d[l].sum(axis=0, dtype=F) / F(n)).astype(F)).astype(F)
+        dW_new.append(D)
+        db_new.append(Db)
+        W_new.append((W[l - 1] + D).astype(F))
+        b_new.append((b[l - 1] + Db).astype(F))
+    st = b6.Step(yr[0], np.asarray(t, F), list(W), list(b), list(dW), list(db), {l: yr[l] for l in range(1, L - 1)},
+                 out, d, dW_new, db_new, W_new, b_new, float(lr), float(mom), float(wc), float(beta), 0, 1, None,
+                 dropout=True)
+    return st, masks
+
+
+def dropout_checks(st, x_raw, p_in, p_hid):
+    """what the GPU test asserts of one dropout step: every operation, the input rows raw-or-0, the mask statistics"""
+    L = len(st.W) + 1
+    reps = b6.check_step(st)
+    rep, drop0, known0 = b6.input_mask(x_raw, st.x)
+    reps.append(rep)
+    reps += b6.mask_stats("mask 0", drop0, known0, p_in)
+    masks = {0: (drop0, known0)}
+    for l in range(1, L - 1):
+        _, dr, kn = b6.expect_dropout_layer(st.x if l == 1 else st.y[l - 1], st.W[l - 1], st.b[l - 1], st.y[l])
+        masks[l] = (dr, kn)
+        reps += b6.mask_stats("mask %d" % l, dr, kn, p_hid)
+    if L > 3:
+        reps.append(b6.mask_overlap("masks 1 x 2", *masks[1], *masks[2], p_hid, p_hid))
+    return reps, masks
+
+
+DROP_LS, DROP_P = [300, 250, 97, 33], (0.2, 0.3)
+
+
+def dropout_run(mut=None, seed=31):
+    rng = np.random.default_rng(seed)
+    W, b = b6.make_net(DROP_LS, seed)
+    x, t = b6.make_data(DROP_LS, 2 * 96, seed + 1, 8, W[0], 96)    # saturating rows: y == 0 without a mask too
+    s1, _ = fp32_dropout_step(x[:96], t[:96], W, b, [np.zeros_like(w) for w in W], [np.zeros_like(v) for v in b],
+                              (0.3, 0.5, 1e-2), 2.0, *DROP_P, rng)
+    s2, _ = fp32_dropout_step(x[96:], t[96:], s1.W_new, s1.b_new, s1.dW_new, s1.db_new, (0.3, 0.5, 1e-2), 2.0, *DROP_P,
+                              rng, mut)
+    r1, m1 = dropout_checks(s1, x[:96], *DROP_P)
+    r2, m2 = dropout_checks(s2, x[96:], *DROP_P)
+    r2.append(b6.mask_overlap("mask 1 steps 1 x 2", *m1[1], *m2[1], DROP_P[1], DROP_P[1]))
+    return r1, r2
+
+
+def test_dropout_step_passes_every_bound_and_statistic():
+    r1, r2 = dropout_run()
+    for r in r1 + r2:
+        print(r.line())
+    assert_clean(r1 + r2)
+
+
+DROP_KILLS = [("inverted", "fwd 1"), ("mask_T_only", "fwd 2"), ("input_row_missing", "fwd 1"),
+              ("input_row_missing", "mask 0 rate"), ("unit_hash", "mask 1 per unit")]
+
+
+@pytest.mark.parametrize("mut,report", DROP_KILLS)
+def test_dropout_slip_is_killed(mut, report):
+    _, r2 = dropout_run(mut)
+    hit = [r for r in r2 if r.name.startswith(report)]
+    assert hit, [r.name for r in r2]
+    print("%-18s -> %s" % (mut, hit[0].line()))
+    assert hit[0].count > 0, hit[0].line()
+
+
+def test_mask_statistics_see_a_repeated_or_reseeded_mask():
+    """masks of two steps (or two seeds) that coincide fail the overlap test; independent ones pass it"""
+    rng = np.random.default_rng(3)
+    a, b = rng.random((128, 200)) < 0.25, rng.random((128, 200)) < 0.25
+    k = np.ones_like(a)
+    assert b6.mask_overlap("indep", a, k, b, k, 0.25, 0.25).ok
+    assert not b6.mask_overlap("same", a, k, a, k, 0.25, 0.25).ok
+
+
+@pytest.mark.parametrize("mut", [None, "div_keep"])
+def test_cv_dropout_weight_round_trips(mut):
+    """forward() under dropout leaves fl32(fl32(W keep) fl32(1/keep)) per bunch; dividing by keep instead rounds
+    differently and the exact compare sees it"""
+    ls, B, keeps = [300, 250, 33], 64, (F(1) - F(0.2), F(1) - F(0.3))
+    W, b = b6.make_net(ls, 41)
+    x, _ = b6.make_data(ls, 3 * B + 17, 42)
+    used, left = b6.cv_dropout_weights(W, keeps, 4)
+    cur, outs = [w.copy() for w in W], []
+    for j in range(4):
+        sc = [(w * k).astype(F) for w, k in zip(cur, keeps)]
+        y = x[j * B:(j + 1) * B]
+        y = sigmoid32((mm_np32(y, sc[0]) + b[0]).astype(F))
+        outs.append((mm_np32(y, sc[1]) + b[1]).astype(F))
+        cur = [((s / k) if mut == "div_keep" else (s * (F(1) / k))).astype(F) for s, k in zip(sc, keeps)]
+    reps = [b6.compare_exact("W %d after CV" % (l + 1), cur[l], left[l]) for l in range(2)]
+    for j in range(4):
+        reps.append(b6.compare("bunch %d" % j, outs[j], b6.expect_forward_chain(x[j * B:(j + 1) * B], used[j], b)))
+    for r in reps:
+        print(mut, r.line())
+    if mut is None:
+        assert_clean(reps)
+    else:
+        assert any(r.count > 0 for r in reps[:2])
