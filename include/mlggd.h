@@ -122,6 +122,27 @@ int mlggd_alloc_pinned(size_t bytes, void **out);
 int mlggd_alloc_pinned_on(int device, size_t bytes, void **out);
 int mlggd_free_pinned(void *p);
 
+/* ---- spectral front end / back end: the original project's Wav2LPS_be and LPS2Wav_be (Wav2LogSpec_be.c,
+ * LogSpec2Wav.c with OLA_KIND 1) and its decoder decode.m, on the device.  fs_khz in {8, 11, 16}: frame L / hop S /
+ * FFT N = 256/128/256, 256/110/256, 512/256/512; D = N/2 + 1 bins.  A wave of n int16 samples gives
+ * F = (n - (L - S)) / S frames (0 if n < L; trailing samples dropped); a synthesised wave has F*S + L - S samples.
+ *
+ * mlggd_wave_to_lps: lps [F][D] = log |FFT(frame * Hamming)|^2 (floored at -50).  Stateless, any device; lps NULL =
+ * query F only.
+ * mlggd_lps_to_wave: the noisy wave's phase with the magnitude sqrt(exp(lps)), inverse FFT, window, overlap-add
+ * / sum w^2; out = trunc toward zero, saturated to int16; out_f32 (optional) = the value before the cast.  n_frames
+ * must be the F of n_samples.
+ * mlggd_enhance_wave: the whole of decode.m on the engine's stream: noisy -> LPS -> (lps - mean) * inv_std ->
+ * edge-replicated windows of fea_context frames -> forward pass -> y / inv_std + mean -> synthesis against the same
+ * noisy wave.  Needs fea_context * D == layersizes[0] and layersizes[L-1] == D; n_samples >= L.  Inputs longer than
+ * the chunk capacity (max_cache_frames) run in chunks whose frame streams overlap by fea_context - 1 frames: the
+ * result does not depend on the chunking.  *n_out (optional) receives F*S + L - S. */
+int mlggd_wave_to_lps(int device, int fs_khz, int n_samples, const int16_t *wave, int *n_frames, float *lps);
+int mlggd_lps_to_wave(int device, int fs_khz, int n_samples, const int16_t *noisy, int n_frames, const float *lps,
+                      int16_t *out, float *out_f32);
+int mlggd_enhance_wave(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                       int n_samples, const int16_t *noisy, int16_t *out, float *out_f32, int *n_out);
+
 /* ---- state: BP_GPU::returnWeights (BP_GPU.cu:514-525) and dev.scalefactor (:287) ---- */
 int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias);
 int mlggd_set_weights(mlggd_handle h, const float *const *weights, const float *const *bias);

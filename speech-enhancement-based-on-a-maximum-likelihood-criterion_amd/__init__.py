@@ -50,6 +50,7 @@ EXPORTS = [
     "mlggd_alloc_pinned", "mlggd_alloc_pinned_on", "mlggd_free_pinned", "mlggd_set_cv_device_reduce",
     "mlggd_comm_info", "mlggd_debug_plan_count", "mlggd_debug_math", "mlggd_debug_out_slabs", "mlggd_debug_gemm_plan",
     "mlggd_debug_keep_ranks", "mlggd_debug_rank_tensor",
+    "mlggd_wave_to_lps", "mlggd_lps_to_wave", "mlggd_enhance_wave",
 ]
 
 _lib = None
@@ -57,7 +58,7 @@ _lib = None
 
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -126,6 +127,10 @@ def load():
     L.mlggd_forward_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, C.c_int, _ip, _fp]
     L.mlggd_alloc_pinned.argtypes = [C.c_size_t, C.POINTER(C.c_void_p)]
     L.mlggd_free_pinned.argtypes = [C.c_void_p]
+    _sp = C.POINTER(C.c_int16)
+    L.mlggd_wave_to_lps.argtypes = [C.c_int, C.c_int, C.c_int, _sp, C.POINTER(C.c_int), _fp]
+    L.mlggd_lps_to_wave.argtypes = [C.c_int, C.c_int, C.c_int, _sp, C.c_int, _fp, _sp, _fp]
+    L.mlggd_enhance_wave.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _sp, _fp, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -162,6 +167,49 @@ def device_count():
 
 def gamma(x):
     return float(load().mlggd_gamma(float(x)))
+
+
+# frame length L, hop S and FFT length N of the spectral front end per sampling rate in kHz (Wav2LogSpec_be.c)
+SPECTRAL_PARAMS = {8: (256, 128, 256), 11: (256, 110, 256), 16: (512, 256, 512)}
+
+
+def _wave(a):
+    a = np.asarray(a)
+    if a.ndim != 1 or a.dtype != np.int16:
+        raise ValueError("a wave is a 1-D int16 array")
+    return np.ascontiguousarray(a)
+
+
+def _sp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int16))
+
+
+def wave_to_lps(wave, fs_khz=16, device=0):
+    """Log-power spectra [F][N/2+1] float32 of an int16 wave (the original project's Wav2LPS_be)."""
+    wave = _wave(wave)
+    F = C.c_int(0)
+    _check(load().mlggd_wave_to_lps(int(device), int(fs_khz), wave.size, _sp(wave), C.byref(F), None))
+    L, S, N = SPECTRAL_PARAMS[int(fs_khz)]
+    lps = np.empty((F.value, N // 2 + 1), np.float32)
+    if F.value:
+        _check(load().mlggd_wave_to_lps(int(device), int(fs_khz), wave.size, _sp(wave), C.byref(F), _p(lps)))
+    return lps
+
+
+def lps_to_wave(noisy, lps, fs_khz=16, device=0, return_float=False):
+    """int16 wave of F*S + L - S samples from LPS rows and the noisy wave's phase (the original project's LPS2Wav_be);
+    return_float: (int16 wave, float32 wave before the cast)."""
+    noisy = _wave(noisy)
+    lps = _f32(lps)
+    if lps.ndim != 2:
+        raise ValueError("lps must be [n_frames][N/2+1]")
+    L, S, N = SPECTRAL_PARAMS[int(fs_khz)]
+    n_out = lps.shape[0] * S + L - S
+    out = np.empty(n_out, np.int16)
+    outf = np.empty(n_out, np.float32) if return_float else None
+    _check(load().mlggd_lps_to_wave(int(device), int(fs_khz), noisy.size, _sp(noisy), lps.shape[0], _p(lps), _sp(out),
+                                    _p(outf) if return_float else None))
+    return (out, outf) if return_float else out
 
 
 def comm_unique_id():
@@ -293,6 +341,20 @@ class BPGpu:
 
     def sync(self):
         _check(load().mlggd_sync(self._h))
+
+    # -- Test_code/decode.m on the device: noisy wave -> LPS -> normalise -> context -> forward -> de-normalise -> wave
+    def enhance_wave(self, noisy, mean, inv_std, fea_context=7, fs_khz=16, return_float=False):
+        noisy = _wave(noisy)
+        L, S, N = SPECTRAL_PARAMS[int(fs_khz)]
+        mean = _f32(mean, (N // 2 + 1,))
+        inv = _f32(inv_std, (N // 2 + 1,))
+        F = max(0, (noisy.size - (L - S)) // S)
+        out = np.empty(F * S + L - S, np.int16)
+        outf = np.empty(out.size, np.float32) if return_float else None
+        n = C.c_int(0)
+        _check(load().mlggd_enhance_wave(self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), noisy.size,
+                                         _sp(noisy), _sp(out), _p(outf) if return_float else None, C.byref(n)))
+        return (out, outf) if return_float else out
 
     def last_train_ms(self):
         ms, steps = C.c_float(0), C.c_int(0)

@@ -15,11 +15,13 @@
 #include <string.h>
 
 #include <functional>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/mlggd.h"
 #include "kernels.hip.h"
+#include "spectral.hip.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -2748,6 +2750,289 @@ int mlggd_kernel_work(mlggd_handle e, const char *kernel_class, int layer, doubl
     if (flops) *flops = f;
     if (bytes) *bytes = by;
     return MLGGD_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ spectral front end / back end (spectral.hip.h)
+// Wav2LPS_be / LPS2Wav_be / decode.m of the original project.  The window and twiddle tables are computed in double,
+// rounded to float and uploaded once per (device, rate).
+namespace {
+
+struct SpecPlan {
+    SpecDims d;
+    float *win = nullptr;    // [L], mirrored half table
+    float2 *tw = nullptr;    // [M/2] exp(-2 pi i j / M)
+    float2 *tws = nullptr;   // [D]   exp(-2 pi i k / N)
+};
+constexpr int SPEC_MAX_DEVICES = 64;
+std::mutex g_spec_mu;
+SpecPlan g_spec[SPEC_MAX_DEVICES][3];
+
+int spec_dims(int fs_khz, SpecDims *d, int *slot) {
+    int L, S, N;
+    switch (fs_khz) {  // Wav2LogSpec_be.c / LogSpec2Wav.c #defines
+        case 8: L = 256, S = 128, N = 256, *slot = 0; break;
+        case 11: L = 256, S = 110, N = 256, *slot = 1; break;
+        case 16: L = 512, S = 256, N = 512, *slot = 2; break;
+        default: return fail(MLGGD_ERR_ARG, "fs_khz %d: must be 8, 11 or 16", fs_khz);
+    }
+    d->L = L, d->S = S, d->N = N, d->M = N / 2, d->D = N / 2 + 1;
+    d->logM = 0;
+    while ((1 << d->logM) < d->M) d->logM++;
+    return MLGGD_OK;
+}
+
+// twiddle in double, an exact 0 where the value is 0 (the DC / Nyquist outputs stay real)
+float2 twiddle(int k, int n) {
+    const double a = -2.0 * M_PI * k / n;
+    double c = cos(a), s = sin(a);
+    if (4 * k == n || 4 * k == 3 * n) c = 0.0;
+    if (2 * k == n || k == 0) s = 0.0;
+    return make_float2((float)c, (float)s);
+}
+
+// the plan of (current device, rate); the caller has selected the device
+int spec_plan(int device, int fs_khz, const SpecPlan **out) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (device < 0 || device >= SPEC_MAX_DEVICES) return fail(MLGGD_ERR_ARG, "device %d out of range", device);
+    std::lock_guard<std::mutex> lock(g_spec_mu);
+    SpecPlan &p = g_spec[device][slot];
+    if (!p.win) {
+        std::vector<float> win(d.L);
+        for (int i = 0; i < d.L / 2; i++) win[i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (d.L - 1)));  // FEfunc.c
+        for (int i = d.L / 2; i < d.L; i++) win[i] = win[d.L - 1 - i];
+        std::vector<float2> tw(d.M / 2), tws(d.D);
+        for (int j = 0; j < d.M / 2; j++) tw[j] = twiddle(j, d.M);
+        for (int k = 0; k < d.D; k++) tws[k] = twiddle(k, d.N);
+        float *w = nullptr;
+        float2 *a = nullptr, *b = nullptr;
+        HIPCHK(hipMalloc((void **)&w, win.size() * sizeof(float)));
+        HIPCHK(hipMalloc((void **)&a, tw.size() * sizeof(float2)));
+        HIPCHK(hipMalloc((void **)&b, tws.size() * sizeof(float2)));
+        HIPCHK(hipMemcpy(w, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(a, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b, tws.data(), tws.size() * sizeof(float2), hipMemcpyHostToDevice));
+        p.d = d, p.win = w, p.tw = a, p.tws = b;
+    }
+    *out = &p;
+    return MLGGD_OK;
+}
+
+int spec_frames(const SpecDims &d, int n_samples) { return n_samples < d.L ? 0 : (n_samples - (d.L - d.S)) / d.S; }
+
+// device buffers of one call, freed on every return path
+struct DevBufs {
+    std::vector<void *> p;
+    ~DevBufs() {
+        for (void *q : p) hipFree(q);
+    }
+    template <typename T>
+    int alloc(T **out, size_t count) {
+        void *q = nullptr;
+        HIPCHK(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
+        p.push_back(q);
+        *out = (T *)q;
+        return MLGGD_OK;
+    }
+};
+
+unsigned spec_grid(int frames) { return (unsigned)((frames + SPEC_FRAMES - 1) / SPEC_FRAMES); }
+
+int launch_analysis(const SpecPlan *p, const int16_t *wave, int F, float *lps, float2 *X, hipStream_t st) {
+    if (F == 0) return MLGGD_OK;
+    hipLaunchKernelGGL(k_lps_analysis, dim3(spec_grid(F)), dim3(64 * SPEC_FRAMES), 0, st, wave, F, p->d, p->win, p->tw,
+                       p->tws, (float)exp(-50.0), lps, X);
+    return launch_check("k_lps_analysis");
+}
+
+int launch_synthesis(const SpecPlan *p, const float *src, const float *mean, const float *inv, const float2 *X, int t0,
+                     int nf, float *blk, hipStream_t st) {
+    if (nf == 0) return MLGGD_OK;
+    hipLaunchKernelGGL(k_lps_synthesis, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, X, t0, nf,
+                       p->d, p->win, p->tw, p->tws, (float)exp(-50.0), blk);
+    return launch_check("k_lps_synthesis");
+}
+
+int launch_ola(const SpecPlan *p, const float *blk, int F, float *out_f, int16_t *out_i, hipStream_t st) {
+    const int n_out = F * p->d.S + p->d.L - p->d.S;
+    hipLaunchKernelGGL(k_ola, dim3((n_out + 255) / 256), dim3(256), 0, st, blk, F, p->d, p->win, out_f, out_i, n_out);
+    return launch_check("k_ola");
+}
+
+// out (int16) and out_f32 (optional) of n_out samples from the time blocks of F frames
+int ola_to_host(const SpecPlan *p, const float *blk, int F, int16_t *out, float *out_f32, hipStream_t st) {
+    const size_t n_out = (size_t)F * p->d.S + p->d.L - p->d.S;
+    DevBufs b;
+    float *of = nullptr;
+    int16_t *oi = nullptr;
+    CHK(b.alloc(&oi, n_out));
+    if (out_f32) CHK(b.alloc(&of, n_out));
+    CHK(launch_ola(p, blk, F, of, oi, st));
+    if (out) HIPCHK(hipMemcpyAsync(out, oi, n_out * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+    if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, of, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MLGGD_OK;
+}
+
+// the frame stream of output frames [a, a + n) written by k_lps_stream into the engine's idle raw buffer set, which
+// then becomes the current one: the device-side counterpart of mlggd_load_frames (first_frame[i] = i, no targets)
+int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, int ctx, const float *mean,
+                       const float *inv) {
+    if (!e->copy_stream) {
+        CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));
+        for (auto &r : e->raw) HIPCHK(hipEventCreateWithFlags(&r.last_use, hipEventDisableTiming));
+    }
+    const int fdim = e->K0 / ctx, rows = n + ctx - 1;
+    mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
+    HIPCHK(hipEventSynchronize(r.last_use));
+    const size_t need = (size_t)rows + ctx + 8;
+    if (need > r.raw_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (r.feat) hipFree(r.feat);
+        if (r.targ) hipFree(r.targ);
+        r.feat = r.targ = nullptr;
+        r.raw_cap = 0;
+        HIPCHK(hipMalloc((void **)&r.feat, need * fdim * sizeof(float)));
+        HIPCHK(hipMalloc((void **)&r.targ, need * e->D * sizeof(float)));
+        HIPCHK(hipMemsetAsync(r.feat, 0, need * fdim * sizeof(float), e->stream));
+        HIPCHK(hipMemsetAsync(r.targ, 0, need * e->D * sizeof(float), e->stream));
+        r.raw_cap = need;
+    }
+    const size_t need_s = (size_t)n + e->Bp + 32;
+    if (need_s > r.first_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (r.first) hipFree(r.first);
+        r.first = nullptr;
+        r.first_cap = 0;
+        HIPCHK(hipMalloc((void **)&r.first, need_s * sizeof(int)));
+        HIPCHK(hipMemsetAsync(r.first, 0, need_s * sizeof(int), e->stream));
+        r.first_cap = need_s;
+    }
+    const size_t work = std::max((size_t)rows * fdim, (size_t)n);
+    hipLaunchKernelGGL(k_lps_stream, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, lps, F, fdim, a,
+                       rows, (ctx - 1) / 2, mean, inv, r.feat, r.first, n);
+    CHK(launch_check("k_lps_stream"));
+    e->raw_cur ^= 1;
+    e->raw_feat = r.feat;
+    e->raw_targ = r.targ;
+    e->first_frame = r.first;
+    e->raw_cap = r.raw_cap;
+    e->first_cap = r.first_cap;
+    e->chunk_frames = n;
+    e->raw_frames = rows;
+    e->indexed = true;
+    e->fdim = fdim;
+    e->toff = 0;
+    return MLGGD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mlggd_wave_to_lps(int device, int fs_khz, int n_samples, const int16_t *wave, int *n_frames, float *lps) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (n_samples < 0) return fail(MLGGD_ERR_ARG, "n_samples %d < 0", n_samples);
+    if (!n_frames) return fail(MLGGD_ERR_ARG, "n_frames is NULL");
+    const int F = spec_frames(d, n_samples);
+    *n_frames = F;
+    if (!lps || F == 0) return MLGGD_OK;
+    if (!wave) return fail(MLGGD_ERR_ARG, "wave is NULL");
+    HIPCHK(hipSetDevice(device));
+    const SpecPlan *p;
+    CHK(spec_plan(device, fs_khz, &p));
+    DevBufs b;
+    int16_t *dw = nullptr;
+    float *dl = nullptr;
+    const size_t used = (size_t)F * d.S + d.L - d.S;  // the samples the frames cover
+    CHK(b.alloc(&dw, used));
+    CHK(b.alloc(&dl, (size_t)F * d.D));
+    HIPCHK(hipMemcpy(dw, wave, used * sizeof(int16_t), hipMemcpyHostToDevice));
+    CHK(launch_analysis(p, dw, F, dl, nullptr, nullptr));
+    HIPCHK(hipMemcpy(lps, dl, (size_t)F * d.D * sizeof(float), hipMemcpyDeviceToHost));
+    return MLGGD_OK;
+}
+
+int mlggd_lps_to_wave(int device, int fs_khz, int n_samples, const int16_t *noisy, int n_frames, const float *lps,
+                      int16_t *out, float *out_f32) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (n_samples < d.L) return fail(MLGGD_ERR_ARG, "n_samples %d is shorter than one frame (%d)", n_samples, d.L);
+    const int F = spec_frames(d, n_samples);
+    if (n_frames != F)
+        return fail(MLGGD_ERR_ARG, "n_frames %d: the %d noisy samples give %d frames", n_frames, n_samples, F);
+    if (!noisy || !lps || !out) return fail(MLGGD_ERR_ARG, "noisy/lps/out is NULL");
+    HIPCHK(hipSetDevice(device));
+    const SpecPlan *p;
+    CHK(spec_plan(device, fs_khz, &p));
+    DevBufs b;
+    int16_t *dw = nullptr;
+    float *dl = nullptr, *blk = nullptr;
+    float2 *X = nullptr;
+    const size_t used = (size_t)F * d.S + d.L - d.S;
+    CHK(b.alloc(&dw, used));
+    CHK(b.alloc(&dl, (size_t)F * d.D));
+    CHK(b.alloc(&X, (size_t)F * d.D));
+    CHK(b.alloc(&blk, (size_t)F * d.L));
+    HIPCHK(hipMemcpy(dw, noisy, used * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dl, lps, (size_t)F * d.D * sizeof(float), hipMemcpyHostToDevice));
+    CHK(launch_analysis(p, dw, F, nullptr, X, nullptr));
+    CHK(launch_synthesis(p, dl, nullptr, nullptr, X, 0, F, blk, nullptr));
+    return ola_to_host(p, blk, F, out, out_f32, nullptr);
+}
+
+int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                       int n_samples, const int16_t *noisy, int16_t *out, float *out_f32, int *n_out) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (fea_context < 1 || fea_context % 2 == 0) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", fea_context);
+    if ((long long)fea_context * d.D != e->K0)
+        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
+    if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
+    if (e->world > 1 || e->fake_world)
+        return fail(MLGGD_ERR_STATE, "mlggd_enhance_wave runs on a single-device engine");
+    if (n_samples < d.L) return fail(MLGGD_ERR_ARG, "n_samples %d is shorter than one frame (%d)", n_samples, d.L);
+    if (!noisy || !norm_mean || !norm_inv_std || !out) return fail(MLGGD_ERR_ARG, "noisy/norm/out is NULL");
+    const int F = spec_frames(d, n_samples);
+    const size_t used = (size_t)F * d.S + d.L - d.S;
+    if (n_out) *n_out = (int)used;
+    HIPCHK(hipSetDevice(e->device));
+    const SpecPlan *p;
+    CHK(spec_plan(e->device, fs_khz, &p));
+    hipStream_t st = e->stream;
+    DevBufs b;
+    int16_t *dw = nullptr;
+    float *dl = nullptr, *blk = nullptr, *mean = nullptr, *inv = nullptr;
+    float2 *X = nullptr;
+    CHK(b.alloc(&dw, used));
+    CHK(b.alloc(&dl, (size_t)F * d.D));
+    CHK(b.alloc(&X, (size_t)F * d.D));
+    CHK(b.alloc(&blk, (size_t)F * d.L));
+    CHK(b.alloc(&mean, d.D));
+    CHK(b.alloc(&inv, d.D));
+    HIPCHK(hipMemcpyAsync(dw, noisy, used * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(mean, norm_mean, d.D * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(inv, norm_inv_std, d.D * sizeof(float), hipMemcpyHostToDevice, st));
+    CHK(launch_analysis(p, dw, F, dl, X, st));  // the noisy wave is transformed once
+    // chunks of at most the chunk capacity; each one's stream carries (ctx - 1) / 2 context frames on either side,
+    // so consecutive streams overlap by ctx - 1 frames and every output frame sees the same input rows
+    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    for (int a = 0; a < F; a += cap) {
+        const int n = std::min(cap, F - a);
+        CHK(load_frames_device(e, dl, F, a, n, fea_context, mean, inv));
+        CHK(forward_resident(e, n));
+        CHK(launch_synthesis(p, e->chunk_out, mean, inv, X, a, n, blk, st));
+        HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
+    }
+    return ola_to_host(p, blk, F, out, out_f32, st);
 }
 
 }  // extern "C"

@@ -1,0 +1,192 @@
+// spectral.hip.h -- the spectral front end and back end of the original project's Wav2LPS_be / LPS2Wav_be
+// (Wav2LogSpec_be.c, LogSpec2Wav.c with OLA_KIND 1, FEfunc.c) on the device.  Included by engine.hip.
+//
+//   k_lps_analysis   int16 frames -> window -> real N-point FFT in LDS -> log power rows (and the complex spectrum X)
+//   k_lps_stream     LPS rows -> (lps - mean) * inv_std, edge-replicated context stream for the forward pass
+//   k_lps_synthesis  LPS rows, or the forward pass's outputs de-normalised, + X -> noisy phase, inverse FFT, window
+//   k_ola            overlap-add of the windowed time blocks, / sum w^2, float and saturated int16 output
+//
+// FFT form: the real N-point spectrum is an M = N/2-point complex FFT of z_m = x_2m + i x_2m+1
+// (radix-2 decimation in time: bit-reversed load, log2(M) butterfly stages in LDS) followed by the real split step
+// X_k = (Z_k + conj Z_{M-k}) / 2 - i W_N^k (Z_k - conj Z_{M-k}) / 2.  The inverse runs the same steps backwards
+// (the conjugate trick: IDFT(Z) = conj(DFT(conj Z)) / M).  One wavefront per frame, SPEC_FRAMES frames per
+// workgroup.  Twiddles and the window come from tables computed on the host in double and rounded to float; the log
+// and exp are evaluated in double as the original does.  Every output element is a fixed sequence of IEEE fp32
+// operations (-ffp-contract=off), so results are deterministic and independent of launch geometry and chunking.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define SPEC_FRAMES 4     // frames (= wavefronts) per workgroup
+#define SPEC_MAXM 256     // largest complex FFT (N = 512)
+#define SPEC_FLOOR (-50.0f)
+
+// LDS index with one float of padding every 32: the power-of-two strides of the butterflies do not all land on
+// one bank (cdna_hip_programming.md Guideline 4)
+__device__ __forceinline__ int spec_pad(int i) { return i + (i >> 5); }
+#define SPEC_ROW (SPEC_MAXM + SPEC_MAXM / 32)
+
+struct SpecDims {
+    int L, S, N, M, logM, D;  // frame length, hop, FFT length, N/2, log2(M), N/2 + 1
+};
+
+// forward complex FFT of the M points in (re, im) of one wavefront's LDS row, data already in bit-reversed order
+__device__ __forceinline__ void spec_fft_rows(float *re, float *im, const float2 *__restrict__ tw, int M, int logM,
+                                              int lane) {
+    for (int s = 0; s < logM; s++) {
+        const int h = 1 << s, tstep = M >> (s + 1);
+        for (int b = lane; b < M / 2; b += 64) {
+            const int j = b & (h - 1);
+            const int i0 = ((b >> s) << (s + 1)) + j, i1 = i0 + h;
+            const float2 w = tw[j * tstep];
+            const float ar = re[spec_pad(i0)], ai = im[spec_pad(i0)];
+            const float br = re[spec_pad(i1)], bi = im[spec_pad(i1)];
+            const float cr = br * w.x - bi * w.y, ci = br * w.y + bi * w.x;
+            re[spec_pad(i0)] = ar + cr;
+            im[spec_pad(i0)] = ai + ci;
+            re[spec_pad(i1)] = ar - cr;
+            im[spec_pad(i1)] = ai - ci;
+        }
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ int spec_bitrev(int m, int logM) { return (int)(__brev((unsigned)m) >> (32 - logM)); }
+
+// grid: ceil(F / SPEC_FRAMES) workgroups of 64 * SPEC_FRAMES threads.  win [L] (full, mirrored), tw [M/2] =
+// exp(-2 pi i j / M), tws [D] = exp(-2 pi i k / N).  lps [F][D] and X [F][D] are each optional (nullptr).
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_analysis(const int16_t *__restrict__ wave, int F, SpecDims d,
+                                                                   const float *__restrict__ win,
+                                                                   const float2 *__restrict__ tw,
+                                                                   const float2 *__restrict__ tws, float floor_p,
+                                                                   float *__restrict__ lps, float2 *__restrict__ X) {
+    __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * SPEC_FRAMES + wv;
+    const bool live = t < F;  // a dead wave still takes part in the barriers
+    float *re = s_re[wv], *im = s_im[wv];
+    const int16_t *x = wave + (size_t)(live ? t : 0) * d.S;  // frame t: samples [t S, t S + L), inside the wave
+    for (int m = lane; m < d.M; m += 64) {
+        const int n0 = 2 * m, n1 = 2 * m + 1;
+        const float v0 = (live && n0 < d.L) ? (float)x[n0] * win[n0] : 0.0f;  // zero padding to N
+        const float v1 = (live && n1 < d.L) ? (float)x[n1] * win[n1] : 0.0f;
+        const int r = spec_pad(spec_bitrev(m, d.logM));
+        re[r] = v0;
+        im[r] = v1;
+    }
+    __syncthreads();
+    spec_fft_rows(re, im, tw, d.M, d.logM, lane);
+    if (!live) return;
+    for (int k = lane; k < d.D; k += 64) {
+        const int ka = (k == d.M) ? 0 : k, kb = (k == 0) ? 0 : d.M - k;  // Z_{k mod M}, Z_{(M-k) mod M}
+        const float zr = re[spec_pad(ka)], zi = im[spec_pad(ka)];
+        const float cr = re[spec_pad(kb)], ci = -im[spec_pad(kb)];   // conj Z_{M-k}
+        const float er = (zr + cr) * 0.5f, ei = (zi + ci) * 0.5f;
+        const float orr = (zr - cr) * 0.5f, oi = (zi - ci) * 0.5f;
+        const float2 w = tws[k];
+        const float pr = w.x * orr - w.y * oi, pi = w.x * oi + w.y * orr;  // W^k O
+        const float xr = er + pi, xi = ei - pr;                             // E - i W^k O
+        if (X) X[(size_t)t * d.D + k] = make_float2(xr, xi);
+        if (lps) {
+            const float P = xr * xr + xi * xi;
+            lps[(size_t)t * d.D + k] = (P < floor_p) ? SPEC_FLOOR : (float)log((double)P);
+        }
+    }
+}
+
+// The forward pass's input for output frames [a, a + n) of an F-frame utterance: n + 2 half rows, row j = frame
+// clamp(a - half + j, 0, F - 1) normalised as (lps - mean) * inv_std (two IEEE operations); and first[i] = i.
+__global__ void k_lps_stream(const float *__restrict__ lps, int F, int D, int a, int rows, int half,
+                             const float *__restrict__ mean, const float *__restrict__ inv, float *__restrict__ stream,
+                             int *__restrict__ first, int n_first) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < (size_t)n_first) first[i] = (int)i;
+    if (i >= (size_t)rows * D) return;
+    const int j = (int)(i / D), k = (int)(i % D);
+    int src = a - half + j;
+    src = src < 0 ? 0 : (src >= F ? F - 1 : src);
+    const float c = lps[(size_t)src * D + k] - mean[k];
+    stream[i] = c * inv[k];
+}
+
+// Frames [t0, t0 + nf): target LPS row r = src[(t - t0) * D + k] (de-normalised first when mean != nullptr: y / inv +
+// mean, two IEEE operations), noisy spectrum X [t][k] -> windowed time block blk [t][L].
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float *__restrict__ src, const float *__restrict__ mean,
+                                                                    const float *__restrict__ inv, const float2 *__restrict__ X,
+                                                                    int t0, int nf, SpecDims d, const float *__restrict__ win,
+                                                                    const float2 *__restrict__ tw,
+                                                                    const float2 *__restrict__ tws, float floor_exp,
+                                                                    float *__restrict__ blk) {
+    __shared__ float s_yr[SPEC_FRAMES][SPEC_MAXM + 1], s_yi[SPEC_FRAMES][SPEC_MAXM + 1];
+    __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * SPEC_FRAMES + wv;
+    const bool live = r < nf;
+    const size_t t = (size_t)t0 + (live ? r : 0);
+    float *yr = s_yr[wv], *yi = s_yi[wv], *re = s_re[wv], *im = s_im[wv];
+    // magnitude substitution, LogSpec2Wav.c:481-494, 683-696
+    for (int k = lane; k < d.D; k += 64) {
+        float v = live ? src[(size_t)(live ? r : 0) * d.D + k] : 0.0f;
+        if (mean) {
+            const float q = v / inv[k];
+            v = q + mean[k];
+        }
+        const float ph = (v < SPEC_FLOOR) ? floor_exp : (float)exp((double)v);
+        const float mag = sqrtf(ph);
+        const float2 x = live ? X[t * d.D + k] : make_float2(0.0f, 0.0f);
+        const float A = sqrtf(x.x * x.x + x.y * x.y);
+        float or_ = mag, oi = 0.0f;  // |X| = 0 (digital silence): phase 0
+        if (A > 0.0f) {
+            const float g = mag / A;
+            or_ = x.x * g;
+            oi = x.y * g;
+        }
+        yr[k] = or_;
+        yi[k] = oi;
+    }
+    __syncthreads();
+    // inverse split: Z_k = A_k + i B_k, A_k = (Y_k + conj Y_{M-k}) / 2, B_k = conj(W_N^k) (Y_k - conj Y_{M-k}) / 2,
+    // loaded conjugated and bit-reversed for the forward butterflies
+    for (int k = lane; k < d.M; k += 64) {
+        const float ar = yr[k], ai = yi[k], cr = yr[d.M - k], ci = -yi[d.M - k];
+        const float er = (ar + cr) * 0.5f, ei = (ai + ci) * 0.5f;
+        const float dr = (ar - cr) * 0.5f, di = (ai - ci) * 0.5f;
+        const float2 w = tws[k];
+        const float br = w.x * dr + w.y * di, bi = w.x * di - w.y * dr;  // conj(W) (dr + i di)
+        const float zr = er - bi, zi = ei + br;                            // A + i B
+        const int p = spec_pad(spec_bitrev(k, d.logM));
+        re[p] = zr;
+        im[p] = -zi;
+    }
+    __syncthreads();
+    spec_fft_rows(re, im, tw, d.M, d.logM, lane);
+    if (!live) return;
+    const float scale = 1.0f / (float)d.M;  // a power of two: exact
+    for (int n = lane; n < d.L; n += 64) {
+        const int m = n >> 1;
+        const float v = (n & 1) ? -im[spec_pad(m)] * scale : re[spec_pad(m)] * scale;  // rifft divides by N
+        blk[t * d.L + n] = v * win[n];                                                  // OLA_KIND 1: window again
+    }
+}
+
+// One thread per output sample i of F S + L - S: the frames that cover it, in frame order, then / sum w^2 (formed in
+// the same order, LogSpec2Wav.c:799-826).  int16 out = trunc toward zero, saturated.
+__global__ void k_ola(const float *__restrict__ blk, int F, SpecDims d, const float *__restrict__ win,
+                      float *__restrict__ out_f, int16_t *__restrict__ out_i, int n_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_out) return;
+    int lo = i - d.L + 1;
+    lo = lo <= 0 ? 0 : (lo + d.S - 1) / d.S;
+    int hi = i / d.S;
+    if (hi > F - 1) hi = F - 1;
+    float acc = 0.0f, cnt = 0.0f;
+    for (int t = lo; t <= hi; t++) {
+        const int j = i - t * d.S;
+        acc += blk[(size_t)t * d.L + j];
+        cnt += win[j] * win[j];
+    }
+    const float v = acc / cnt;
+    if (out_f) out_f[i] = v;
+    const float c = truncf(v);
+    out_i[i] = (int16_t)(c >= 32767.0f ? 32767 : (c <= -32768.0f ? -32768 : (int)c));
+}

@@ -15,67 +15,19 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <sstream>
 #include <string>
 #include <vector>
 
-#include "../../include/mlggd.h"
-
-namespace {
+#include "tool_io.h"
 
 [[noreturn]] void die(const std::string &m) {
     fprintf(stderr, "enhance_lps: %s\n", m.c_str());
     exit(1);
 }
-uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-uint16_t bswap16(uint16_t v) { return (uint16_t)((v >> 8) | (v << 8)); }
 
-struct Htk {
-    int nframes = 0, samp_period = 0, samp_size = 0, parm_kind = 0;
-    std::vector<float> data;  // [nframes][samp_size/4]
-};
-
-Htk read_htk(const std::string &path) {  // readHTK_new.m, 'be'
-    FILE *fp = fopen(path.c_str(), "rb");
-    if (!fp) die("cannot open " + path);
-    uint32_t h[2];
-    uint16_t s[2];
-    if (fread(h, 4, 2, fp) != 2 || fread(s, 2, 2, fp) != 2) die("short HTK header in " + path);
-    Htk f;
-    f.nframes = (int)bswap32(h[0]);
-    f.samp_period = (int)bswap32(h[1]);
-    f.samp_size = bswap16(s[0]);
-    f.parm_kind = bswap16(s[1]);
-    const size_t n = (size_t)f.nframes * (f.samp_size / 4);
-    std::vector<uint32_t> raw(n);
-    if (f.nframes <= 0 || f.samp_size % 4 || fread(raw.data(), 4, n, fp) != n) die("bad HTK body in " + path);
-    fclose(fp);
-    f.data.resize(n);
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t v = bswap32(raw[i]);
-        memcpy(&f.data[i], &v, 4);
-    }
-    return f;
-}
-
-void write_htk(const std::string &path, const float *data, int nframes, int dim) {  // writeHTK_new.m
-    FILE *fp = fopen(path.c_str(), "wb");
-    if (!fp) die("cannot open " + path + " for writing");
-    const uint32_t h[2] = {bswap32((uint32_t)nframes), bswap32(160000u)};
-    const uint16_t s[2] = {bswap16((uint16_t)(dim * 4)), bswap16(9)};
-    fwrite(h, 4, 2, fp);
-    fwrite(s, 2, 2, fp);
-    std::vector<uint32_t> raw((size_t)nframes * dim);
-    for (size_t i = 0; i < raw.size(); i++) {
-        uint32_t v;
-        memcpy(&v, &data[i], 4);
-        raw[i] = bswap32(v);
-    }
-    fwrite(raw.data(), 4, raw.size(), fp);
-    fclose(fp);
-}
-
-}  // namespace
+using tool_io::Htk;
+using tool_io::read_htk;
+using tool_io::write_htk;
 
 int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp;
@@ -99,58 +51,18 @@ int main(int argc, char **argv) {
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
 
     // ---- model: the trainer's .wts container (Interface.cc:484-516)
-    std::vector<std::vector<float>> W(1), Bv(1);
-    std::vector<int> ls;
-    {
-        FILE *fp = fopen(wts.c_str(), "rb");
-        if (!fp) die("cannot open " + wts);
-        int32_t stat[5];
-        char name[256];
-        while (fread(stat, 4, 5, fp) == 5) {
-            if (stat[4] < 1 || stat[4] > 255 || fread(name, 1, stat[4], fp) != (size_t)stat[4]) die("bad matrix header in " + wts);
-            std::vector<float> m((size_t)stat[1] * stat[2]);
-            if (fread(m.data(), 4, m.size(), fp) != m.size()) die("truncated matrix in " + wts);
-            if (stat[1] != 1) {  // weights: mrows = out, ncols = in
-                if (ls.empty()) ls.push_back(stat[2]);
-                if (ls.back() != stat[2]) die("layer sizes in " + wts + " do not chain");
-                ls.push_back(stat[1]);
-                W.push_back(m);
-            } else {
-                Bv.push_back(m);
-            }
-        }
-        fclose(fp);
-        if (W.size() < 2 || W.size() != Bv.size() || (int)W.size() > MLGGD_MAXLAYER) die("unexpected matrix list in " + wts);
-    }
+    const tool_io::Model model = tool_io::read_wts(wts);
+    const std::vector<int> &ls = model.ls;
     const int L = (int)ls.size(), D = ls[L - 1];
     if (ls[0] % ctx) die("layersizes[0] is not a multiple of fea_context");
     const int dim = ls[0] / ctx;
 
     // ---- norm file (Interface.cc:373-399 layout: "vec N", N means, "vec N", N inverse std-devs)
-    std::vector<float> mean(dim), inv(dim);
-    {
-        std::ifstream f(norm_file);
-        if (!f) die("cannot open " + norm_file);
-        std::string line;
-        std::getline(f, line);
-        for (int j = 0; j < dim; j++) { std::getline(f, line); mean[j] = (float)atof(line.c_str()); }
-        std::getline(f, line);
-        for (int j = 0; j < dim; j++) { std::getline(f, line); inv[j] = (float)atof(line.c_str()); }
-    }
+    std::vector<float> mean, inv;
+    tool_io::read_norm(norm_file, dim, mean, inv);
     if (D % dim) die("output dimension is not a multiple of the feature dimension");
 
-    mlggd_config cfg;
-    memset(&cfg, 0, sizeof(cfg));
-    cfg.struct_size = sizeof(cfg);
-    cfg.device = gpu;
-    cfg.numlayers = L;
-    for (int i = 0; i < L; i++) cfg.layersizes[i] = ls[i];
-    cfg.bunchsize = bunch;
-    cfg.shapefactor = 2.0f;
-    std::vector<const float *> wp(L, nullptr), bp(L, nullptr);
-    for (int l = 1; l < L; l++) { wp[l] = W[l].data(); bp[l] = Bv[l].data(); }
-    mlggd_handle h = nullptr;
-    if (mlggd_create(&cfg, wp.data(), bp.data(), &h) != MLGGD_OK) die(std::string("mlggd_create: ") + mlggd_last_error());
+    mlggd_handle h = tool_io::create_engine(model, gpu, bunch);
 
     std::vector<std::pair<std::string, std::string>> jobs;
     if (!scp.empty()) {
