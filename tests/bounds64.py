@@ -201,12 +201,14 @@ def expect_sigmoid_layer(x, W, b):
     return _sigmoid_expect(x @ W + b, gamma(K + 2) * scale, scale, K)
 
 
-def expect_forward_chain(x, Ws, bs, slabs=1):
+def expect_forward_chain(x, Ws, bs, slabs=1, x_err=0.0):
     """out of a whole forward pass (forward(), CV): the layers chain, so each input's error bound is propagated:
     E_z = E_y |W| + gamma_{K+2} ((|y| + E_y) |W| + |b|),  E_y = sigma'(z) E_z + E_z^2/10 + 4 u y + 4 TINY (+ y where
-    exp may overflow).  The tight statistic is measured against the first-order GEMM part of the final bound."""
+    exp may overflow).  The tight statistic is measured against the first-order GEMM part of the final bound.
+    x_err: a bound on the error of the fp32 input itself against the float64 `x` (scalar or per element; the input
+    enters as E_y of layer 0), e.g. the roundings of the normalisation in front of the network (spec64.decode64)."""
     y = _d(x)
-    Ey = np.zeros_like(y)
+    Ey = np.zeros_like(y) + _d(x_err)
     L = len(Ws)
     for i, (W, b) in enumerate(zip(Ws, bs)):
         W, b = _d(W), _d(b)

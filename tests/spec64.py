@@ -42,6 +42,7 @@ import numpy as np
 
 U = 2.0 ** -24
 C_FFT = 7.0
+C_NORM = 9.0   # the normwise bound of the whole error spectrum (synthesis_bound)
 FLOOR_P = float(np.float32(np.exp(-50.0)))  # (float) exp(-50.0), the analysis floor
 PARAMS = {8: (256, 128, 256), 11: (256, 110, 256), 16: (512, 256, 512)}  # fs_khz -> frame L, hop S, FFT N
 
@@ -83,6 +84,13 @@ def fft_bound(norm_xw, fs_khz):
     """The per-bin amplitude bound of an fp32 FFT of one frame, for every frame (module docstring)."""
     N = params(fs_khz)[2]
     return C_FFT * np.log2(N) * U * np.sqrt(N) * np.asarray(norm_xw, np.float64)
+
+
+def fft_norm_bound(norm_xw, fs_khz):
+    """The weighted 2-norm bound sqrt(sum_k w_k |dX_k|^2) of an fp32 FFT's whole error spectrum, for every frame
+    (derived in synthesis_bound)"""
+    N = params(fs_khz)[2]
+    return C_NORM * np.log2(N) * U * np.sqrt(N) * np.asarray(norm_xw, np.float64)
 
 
 def analysis64(wave, fs_khz=16):
@@ -163,6 +171,295 @@ def ola_norm(F, fs_khz):
     for t in range(F):
         cnt[t * S:t * S + L] += w * w
     return cnt
+
+
+def synthesis_bound(noisy, lps, fs_khz=16, lps_eps=0.0):
+    """Per-sample bound on |fp32 synthesis - synthesis64| for LPS rows `lps` given exactly, plus `lps_eps` of error in
+    the log domain (a scalar or a per-element [F][N/2+1] array: the chain's bound of `decode64`).
+
+    Derivation, per frame t and bin k (Y = the modified spectrum of `synthesis64`, mag = sqrt(exp(lps))):
+    * noisy phase: X^ / |X^| is within 2 |dX_k| / |X_k| of X / |X| (dX = X^ - X, the analysis error), and within 2
+      (the diameter of the unit circle) outright, which is what is taken where |X| <= E_t: the bin may have cancelled.
+      The analysis error is bounded normwise as well (`fft_norm_bound`): the weighted 2-norm
+      sqrt(sum_k w_k |dX_k|^2) of the error spectrum (w_k as below: the norm of the conjugate-symmetric N-point
+      extension) is at most C_NORM log2(N) u sqrt(N) ||x_t||_2, C_NORM = 9.  Derivation: Higham's theorem bounds the
+      complex stages normwise, ||dZ||_2 <= (log2(M) eta + u) sqrt(M) ||x_t||_2 (the rounding of x * w included; ||Z||_2
+      = sqrt(M) ||x_t||_2).  The exact split step maps Z onto the N-point spectrum with norm ratio sqrt(2) (N ||x||^2
+      against M ||x||^2), which gives (log2(M) eta + u) sqrt(N) ||x_t||.  Its own roundings per bin: E and O one
+      rounding each (u |E|, u |O|), W^k O a complex product with a rounded twiddle (sqrt(2) gamma_2 + u, < 4.9 u, plus
+      O's u), the final sum u (|E| + |P|): below 8 u (|E| + |O|) <= 8 u (|Z_k| + |Z_{M-k}|).  Weighted over the bins,
+      sum_k w_k (|Z_k| + |Z_{M-k}|)^2 <= 2 sum_k w_k (|Z_k|^2 + |Z_{M-k}|^2) <= 8 ||Z||^2, so these add
+      2 * 8 u sqrt(N) ||x_t||.  In all (log2(N) - 1) 6.66 u + 17 u per sqrt(N) ||x_t||: 70.3 u < 9 * 9 u at N = 512,
+      63.6 u < 9 * 8 u at N = 256.  So by Cauchy-Schwarz the phase error reaches a time sample with at most
+      2 sqrt(sum_k w_k (mag_k / |X_k|)^2) E_norm / N, summed over the bins with |X| > E_t (any threshold is sound
+      there; below it the cap 2 is taken): a factor ~sqrt(N) below the per-bin E_t summed bin by bin;
+    * magnitude: exp in double rounded to float, sqrtf, |X^| (two products, a sum, sqrtf), mag / A, X * g: fewer than
+      10 roundings, 10 u relative;
+    * an lps error eps moves mag by a factor exp(+-eps / 2): expm1(eps / 2) relative, counted twice for the
+      second-order term and the float rounding of the chain's output;
+    so |dY_k| <= mag (10 u + 2 expm1(eps / 2)) besides the phase term.  The inverse real split and the M-point inverse FFT are the
+    forward form run backwards (the conjugate trick): a per-sample error of at most sum_k w_k |dY_k| / N (w_k = 2 for the
+    bins that appear twice in the real spectrum, 1 for DC and Nyquist) from the input, and C_FFT log2(N) u ||Y||_2 /
+    sqrt(N) from the arithmetic (the forward bound of the module docstring, scaled by the exact 1 / M and the split's
+    1 / 2), with ||Y|| taken at mag (1 + ph) to cover the perturbed phase.  The window multiply adds u |raw|.  The
+    overlap-add sums at most ceil(L / S) = 3 terms (2 at 8 and 16 kHz) in frame order, divides by sum w^2 formed the
+    same way (3 roundings more) and the division rounds once: 6 u of the sum of |terms|.  1.01 covers the second-order
+    products.  A slip below these margins -- one ulp in one twiddle, the floor compare `<` against `<=` at exactly
+    -50 (which changes exp(-50) by nothing: the floor IS exp(-50)) -- is below what the bound can resolve."""
+    L, S, N = params(fs_khz)
+    X, nrm = spectrum64(noisy, fs_khz)
+    E = fft_bound(nrm, fs_khz)[:, None]
+    lps = np.asarray(lps, np.float64)
+    mag = np.sqrt(np.where(lps < -50, np.exp(-50.0), np.exp(lps)))
+    A = np.abs(X)
+    far = A > E
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ph = np.where(far, np.minimum(2.0, 2.0 * E / np.where(A > 0, A, 1.0)), 2.0)
+        q = np.where(far, mag / np.where(far, A, 1.0), 0.0)
+    dY = mag * (np.where(far, 0.0, 2.0) + 10 * U + 2 * np.expm1(np.asarray(lps_eps, np.float64) / 2.0))
+    wts = np.full(dY.shape[1], 2.0)
+    wts[0] = wts[-1] = 1.0
+    Ymax = mag * (1 + ph)
+    e_phase = 2.0 * np.sqrt((q * q * wts).sum(axis=1)) * fft_norm_bound(nrm, fs_khz) / N
+    e = (dY * wts).sum(axis=1) / N + e_phase + \
+        C_FFT * np.log2(N) * U * np.sqrt((Ymax ** 2 * wts).sum(axis=1)) / np.sqrt(N)
+    _, raw = synthesis64(noisy, lps, fs_khz, return_frames=True)
+    w = window(L).astype(np.float64)
+    F = X.shape[0]
+    acc, mag_acc = np.zeros(F * S + L - S), np.zeros(F * S + L - S)
+    for t in range(F):
+        acc[t * S:t * S + L] += w * (e[t] + U * np.abs(raw[t]).max())
+        mag_acc[t * S:t * S + L] += np.abs(raw[t] * w) + w * e[t]
+    cnt = ola_norm(F, fs_khz)
+    return 1.01 * (acc / cnt + 6 * U * mag_acc / cnt)
+
+
+def synthesis_ratio(out_f, noisy, lps, fs_khz=16, lps_eps=0.0):
+    """worst |out_f - synthesis64| / synthesis_bound over the samples (<= 1 passes; NaN / inf count as inf)"""
+    want = synthesis64(noisy, lps, fs_khz)
+    with np.errstate(invalid="ignore", over="ignore"):
+        err = np.abs(np.asarray(out_f, np.float64) - want)
+    err = np.where(np.isfinite(err), err, np.inf)
+    return float((err / synthesis_bound(noisy, lps, fs_khz, lps_eps)).max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# float32 restatements of the kernels (spectral.hip.h): every step the IEEE fp32 operation the kernel performs, in the
+# same order, vectorised across frames.  They serve as the "correct fp32 twin" that the bounds must pass and as the
+# body into which the mutation tests plant one-line slips.
+F32 = np.float32
+
+
+def twiddle32(k, n):
+    """exp(-2 pi i k / n) in double, exact zeros where the value is 0, rounded to float (engine.hip twiddle())"""
+    k = np.asarray(k)
+    a = -2.0 * np.pi * k / n
+    c, s = np.cos(a), np.sin(a)
+    c = np.where((4 * k == n) | (4 * k == 3 * n), 0.0, c)
+    s = np.where((2 * k == n) | (k == 0), 0.0, s)
+    return c.astype(F32), s.astype(F32)
+
+
+def bitrev(m, logM):
+    m = np.asarray(m)
+    r = np.zeros_like(m)
+    for b in range(logM):
+        r |= ((m >> b) & 1) << (logM - 1 - b)
+    return r
+
+
+def round_bits(a, bits):
+    """round float32 values to `bits` explicit mantissa bits, to nearest even (bf16: 7, a 10-bit mantissa: 10)"""
+    u = np.asarray(a, F32).view(np.uint32).astype(np.uint64)
+    drop = 23 - bits
+    half = (1 << (drop - 1)) - 1
+    u = (u + half + ((u >> drop) & 1)) & ~np.uint64((1 << drop) - 1)
+    return u.astype(np.uint32).view(F32)
+
+
+def fft32(re, im, M, tw, bf16_stage=None):
+    """spec_fft_rows: radix-2 DIT butterflies in place on [F][M] rows already in bit-reversed order; twiddle pair tw;
+    bf16_stage: that stage's operands rounded to bf16 (a mutation)"""
+    logM = int(np.log2(M))
+    b = np.arange(M // 2)
+    for s in range(logM):
+        h, tstep = 1 << s, M >> (s + 1)
+        j = b & (h - 1)
+        i0 = ((b >> s) << (s + 1)) + j
+        i1 = i0 + h
+        wx, wy = tw[0][j * tstep], tw[1][j * tstep]
+        ar, ai, br, bi = re[:, i0], im[:, i0], re[:, i1], im[:, i1]
+        if s == bf16_stage:
+            ar, ai, br, bi = (round_bits(v, 7) for v in (ar, ai, br, bi))
+        cr = br * wx - bi * wy
+        ci = br * wy + bi * wx
+        re[:, i0], im[:, i0] = ar + cr, ai + ci
+        re[:, i1], im[:, i1] = ar - cr, ai - ci
+    return re, im
+
+
+def analysis32(wave, fs_khz=16):
+    """k_lps_analysis in float32: (lps [F][D] float32, X real and imaginary parts [F][D] float32)"""
+    L, S, N = params(fs_khz)
+    M, D = N // 2, N // 2 + 1
+    logM = int(np.log2(M))
+    x = np.zeros((n_frames(len(wave), fs_khz), N), F32)
+    x[:, :L] = frames(wave, fs_khz).astype(F32) * window(L)
+    re, im = np.empty((x.shape[0], M), F32), np.empty((x.shape[0], M), F32)
+    r = bitrev(np.arange(M), logM)
+    re[:, r], im[:, r] = x[:, 0::2], x[:, 1::2]
+    fft32(re, im, M, twiddle32(np.arange(M // 2), M))
+    k = np.arange(D)
+    ka, kb = np.where(k == M, 0, k), np.where(k == 0, 0, M - k)
+    zr, zi, cr, ci = re[:, ka], im[:, ka], re[:, kb], -im[:, kb]
+    h = F32(0.5)
+    er, ei, orr, oi = (zr + cr) * h, (zi + ci) * h, (zr - cr) * h, (zi - ci) * h
+    wx, wy = twiddle32(k, N)
+    pr, pi = wx * orr - wy * oi, wx * oi + wy * orr
+    xr, xi = er + pi, ei - pr
+    P = xr * xr + xi * xi
+    with np.errstate(divide="ignore"):
+        lps = np.where(P < F32(FLOOR_P), F32(-50.0), np.log(P.astype(np.float64)).astype(F32)).astype(F32)
+    return lps, xr, xi
+
+
+SYNTH_MUTATIONS = ["window_n_plus_1", "ola_norm_missing_frame", "block_one_sample_late", "split_W_not_conj",
+                   "nyquist_dropped", "no_final_conj", "phase_of_next_frame", "bf16_butterfly_stage",
+                   "twiddle_10bit"]
+
+
+def synthesis32(noisy, lps, fs_khz=16, mean=None, inv=None, mut=None):
+    """k_lps_synthesis + k_ola in float32: (int16 wave, float32 wave before the cast).  With mean / inv the rows are
+    de-normalised first (fl(fl(y / inv) + mean)), as in enhance_wave.  `mut` plants one of SYNTH_MUTATIONS."""
+    L, S, N = params(fs_khz)
+    M, D = N // 2, N // 2 + 1
+    logM = int(np.log2(M))
+    _, xr, xi = analysis32(noisy, fs_khz)
+    Fn = xr.shape[0]
+    if mut == "phase_of_next_frame":
+        nxt = np.minimum(np.arange(Fn) + 1, Fn - 1)
+        xr, xi = xr[nxt], xi[nxt]
+    v = np.asarray(lps, F32)
+    if v.shape != (Fn, D):
+        raise ValueError("lps must be [%d][%d]" % (Fn, D))
+    if mean is not None:
+        v = v / np.asarray(inv, F32) + np.asarray(mean, F32)
+    # magnitude substitution: exp in double rounded to float, floor below -50, phase 0 where |X| = 0
+    ph = np.where(v < F32(-50.0), F32(np.exp(-50.0)), np.exp(v.astype(np.float64)).astype(F32)).astype(F32)
+    mag = np.sqrt(ph)
+    A = np.sqrt(xr * xr + xi * xi)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = mag / np.where(A > 0, A, F32(1.0))
+    yr = np.where(A > 0, xr * g, mag).astype(F32)
+    yi = np.where(A > 0, xi * g, F32(0.0)).astype(F32)
+    if mut == "nyquist_dropped":
+        yr[:, M] = yi[:, M] = 0
+    # inverse split, loaded conjugated and bit-reversed
+    k = np.arange(M)
+    ar, ai, cr, ci = yr[:, k], yi[:, k], yr[:, M - k], -yi[:, M - k]
+    h = F32(0.5)
+    er, ei, dr, di = (ar + cr) * h, (ai + ci) * h, (ar - cr) * h, (ai - ci) * h
+    wx, wy = twiddle32(k, N)
+    if mut == "split_W_not_conj":
+        br, bi = wx * dr - wy * di, wx * di + wy * dr
+    else:
+        br, bi = wx * dr + wy * di, wx * di - wy * dr
+    zr, zi = er - bi, ei + br
+    re, im = np.empty((Fn, M), F32), np.empty((Fn, M), F32)
+    p = bitrev(k, logM)
+    re[:, p], im[:, p] = zr, -zi
+    tw = twiddle32(np.arange(M // 2), M)
+    if mut == "twiddle_10bit":
+        tw = (round_bits(tw[0], 10), round_bits(tw[1], 10))
+    fft32(re, im, M, tw, bf16_stage=1 if mut == "bf16_butterfly_stage" else None)
+    scale = F32(1.0 / M)
+    n = np.arange(L)
+    odd = (n & 1) == 1
+    sgn = F32(1.0) if mut == "no_final_conj" else F32(-1.0)
+    raw = np.where(odd, (sgn * im[:, n >> 1]) * scale, re[:, n >> 1] * scale).astype(F32)
+    win = window(L)
+    wn = win[np.minimum(n + 1, L - 1)] if mut == "window_n_plus_1" else win
+    blk = (raw * wn).astype(F32)
+    # overlap-add in frame order, / sum w^2 formed in the same order
+    n_out = Fn * S + L - S
+    acc, cnt = np.zeros(n_out, F32), np.zeros(n_out, F32)
+    w2 = (win * win).astype(F32)
+    last = np.minimum(np.arange(n_out) // S, Fn - 1)           # the last frame that covers each sample (k_ola's hi)
+    first = np.maximum(0, (np.arange(n_out) - L + 1 + S - 1) // S)
+    for t in range(Fn):
+        sl = slice(t * S, t * S + L)
+        if mut == "block_one_sample_late" and t == Fn // 2:
+            acc[t * S + 1:t * S + L] = acc[t * S + 1:t * S + L] + blk[t, :L - 1]
+        else:
+            acc[sl] = acc[sl] + blk[t]
+        if mut == "ola_norm_missing_frame":                  # hi off by one in the normaliser where 2+ frames cover
+            keep = (t < last[sl]) | (first[sl] == last[sl])
+            cnt[sl] = np.where(keep, cnt[sl] + w2, cnt[sl])
+        else:
+            cnt[sl] = cnt[sl] + w2
+    out_f = (acc / cnt).astype(F32)
+    c = np.trunc(out_f)
+    return np.clip(c, -32768, 32767).astype(np.int16), out_f
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# decode.m downstream of the analysis: edge-replicated context, normalisation, the network, de-normalisation
+def context_index(F, ctx, mut=None):
+    """[F][ctx] frame index of the edge-replicated context window; mut "shift" / "wrap" plant a slip"""
+    half = (ctx - 1) // 2
+    idx = np.arange(F)[:, None] + np.arange(-half, half + 1)[None, :]
+    if mut == "shift":
+        idx = idx + 1
+    if mut == "wrap":
+        return idx % F
+    return np.clip(idx, 0, F - 1)
+
+
+def decode64(lps, mean, inv, ctx, Ws, bs, slabs=1):
+    """float64 decode.m target LPS [F][D] from the engine's own fp32 analysis rows `lps` (exact input: the analysis is
+    bounded on its own), and a per-element bound lps_eps on any correct fp32 evaluation of the same chain:
+    * x = fl(fl(lps - mean) * inv): two roundings, |dx| <= (2 u + u^2) |x|, which enter the network as x_err;
+    * the forward chain: bounds64.expect_forward_chain, propagated through the layers;
+    * out = fl(fl(y / inv) + mean) of the network's y = z + dz: |dz| / |inv| propagated, one rounding of the quotient
+      and one of the sum.
+    Returns (target LPS float64, lps_eps) -- the inputs of synthesis_bound."""
+    import bounds64
+    lps = np.asarray(lps, np.float64)
+    mean, inv = np.asarray(mean, np.float64), np.asarray(inv, np.float64)
+    F, D = lps.shape
+    x = (lps - mean) * inv
+    idx = context_index(F, ctx)
+    a = x[idx].reshape(F, ctx * D)
+    ex = bounds64.expect_forward_chain(a, Ws, bs, slabs=slabs, x_err=(2.0 * U + U * U) * np.abs(a))
+    z, Ez = ex.ref, ex.bound * bounds64.SECOND_ORDER
+    ainv = np.abs(inv)
+    q = z / inv
+    Eq = Ez / ainv + U * (np.abs(q) + Ez / ainv)
+    want = q + mean
+    eps = Eq + U * (np.abs(want) + Eq)
+    return want, eps * bounds64.SECOND_ORDER
+
+
+def decode32(lps, mean, inv, ctx, Ws, bs, mut=None):
+    """the same chain in float32 (numpy's float32 matmul, the engine's sigmoid formula); mut: "raw" (the network's
+    output, not de-normalised: the input of synthesis32(mean=, inv=)), "denorm_order"
+    (y * inv + mean), "shift" (context one frame late), "wrap" (edges wrap around instead of clamping)"""
+    lps = np.asarray(lps, F32)
+    mean, inv = np.asarray(mean, F32), np.asarray(inv, F32)
+    F, D = lps.shape
+    x = ((lps - mean) * inv).astype(F32)
+    y = x[context_index(F, ctx, mut if mut in ("shift", "wrap") else None)].reshape(F, ctx * D)
+    for i, (W, b) in enumerate(zip(Ws, bs)):
+        z = (np.matmul(y, np.asarray(W, F32)).astype(F32) + np.asarray(b, F32)).astype(F32)
+        if i < len(Ws) - 1:
+            with np.errstate(over="ignore"):
+                z = (F32(1) / (F32(1) + np.exp(-z))).astype(F32)
+        y = z
+    if mut == "raw":
+        return y
+    if mut == "denorm_order":
+        return (y * inv + mean).astype(F32)
+    return (y / inv + mean).astype(F32)
 
 
 def quality64(clean, noisy, lps, fs_khz=16):

@@ -317,6 +317,51 @@ def test_forward_chain_bound_and_ragged_rows(mut):
         assert r.count > 0 and all(i >= 2 * B for i, _ in r.where), r.line()
 
 
+
+def test_forward_chain_bound_with_an_input_error():
+    """x_err: an fp32 forward from inputs scaled up by 5 to 10 % (a correlated input error) stays within the bound propagated from that
+    input error, and leaves it when the error is not declared; the default (and x_err = 0) gives the bits of the loop as it was
+    before x_err (a frozen copy)"""
+    ls, B = [531, 1024, 96, 257], 64
+    W, b = b6.make_net(ls, 23)
+    x, _ = b6.make_data(ls, 2 * B + 5, 24)
+    x64 = x.astype(np.float64)
+    rel = 0.1
+    r = np.random.default_rng(25).uniform(0.5, 1.0, x.shape)
+    xp = (x64 * (1.0 + rel * r)).astype(F)                       # within rel |x| (1 + u) of x64
+    out = fp32_forward(xp, W, b, B)
+    ex = b6.expect_forward_chain(x64, W, b, x_err=rel * (1.0 + 2 * b6.U) * np.abs(x64))
+    rep = b6.compare("forward chain, x_err", out, ex)
+    print(rep.line())
+    assert rep.ok, rep.line()
+    plain = b6.compare("forward chain, no x_err", out, b6.expect_forward_chain(x64, W, b))
+    print(plain.line())
+    assert plain.count > 0
+    for slabs in (1, 4):
+        frozen = frozen_forward_chain(x, W, b, slabs)
+        for e in (b6.expect_forward_chain(x, W, b, slabs=slabs), b6.expect_forward_chain(x, W, b, slabs, x_err=0.0)):
+            assert np.array_equal(e.bound, frozen.bound) and np.array_equal(e.ref, frozen.ref)
+
+
+def frozen_forward_chain(x, Ws, bs, slabs=1):
+    """bounds64.expect_forward_chain as it was before x_err, frozen: the default must give these bits"""
+    y = b6._d(x)
+    Ey = np.zeros_like(y)
+    L = len(Ws)
+    for i, (Wl, bl) in enumerate(zip(Ws, bs)):
+        Wl, bl = b6._d(Wl), b6._d(bl)
+        K = Wl.shape[0]
+        aW = np.abs(Wl)
+        prop = Ey @ aW
+        last = i == L - 1
+        scale = (np.abs(y) + Ey) @ aW + np.abs(bl)
+        z = y @ Wl + bl
+        Ez = prop + b6.gamma(K + (slabs if last else 0) + 2) * scale
+        if last:
+            return b6.Expect(z, Ez)
+        e = b6._sigmoid_expect(z, Ez, scale, K)
+        y, Ey = e.ref, e.bound
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 3. data-parallel steps: a rank-split fp32 implementation (per-rank chains, statistics and partial sums met in rank
 # order), checked as ONE step of the ranks' rows stacked in rank order -- the form tests/test_gpu_dp_vs_float64.py uses
