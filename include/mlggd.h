@@ -142,6 +142,22 @@ int mlggd_lps_to_wave(int device, int fs_khz, int n_samples, const int16_t *nois
                       int16_t *out, float *out_f32);
 int mlggd_enhance_wave(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
                        int n_samples, const int16_t *noisy, int16_t *out, float *out_f32, int *n_out);
+/* mlggd_enhance_waves: mlggd_enhance_wave over a list of utterances in one pass.  Utterance u is
+ * noisy[offsets[u] .. offsets[u+1]) (offsets non-decreasing, every utterance at least one frame long: otherwise
+ * MLGGD_ERR_ARG naming the utterance) and has F_u frames by the rule above; the frames of all utterances form one
+ * packed stream, so every forward bunch but the last is full, while the analysis, the context replication and the
+ * overlap-add keep to each utterance's own edges.  Utterance u's F_u*S + L - S output samples start at out[out_off[u]]
+ * (out_f32, optional, alike); lps_out (optional) [sum F][D] receives the de-normalised network output y / inv_std +
+ * mean, utterance u's rows from frame_off[u].  Every bit of out / out_f32 equals mlggd_enhance_wave on the utterance
+ * alone, whatever its neighbours, its position, the batch or max_cache_frames (chunks run over the packed frames).
+ * The device buffers belong to the engine and only grow: after the first calls a call allocates nothing, uploads the
+ * packed wave, downloads each requested output once and synchronises once.  n_utts == 0 does nothing.
+ * mlggd_enhance_waves_layout: frame_off / out_off [n_utts+1] (each optional) of such a batch; host only. */
+int mlggd_enhance_waves_layout(int fs_khz, int n_utts, const int64_t *offsets /* [n_utts+1] */,
+                               int32_t *frame_off /* [n_utts+1] */, int64_t *out_off /* [n_utts+1] */);
+int mlggd_enhance_waves(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                        int n_utts, const int16_t *noisy, const int64_t *offsets /* [n_utts+1] */, int16_t *out,
+                        float *out_f32 /* optional */, float *lps_out /* optional */);
 
 /* ---- state: BP_GPU::returnWeights (BP_GPU.cu:514-525) and dev.scalefactor (:287) ---- */
 int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias);

@@ -51,6 +51,7 @@ EXPORTS = [
     "mlggd_comm_info", "mlggd_debug_plan_count", "mlggd_debug_math", "mlggd_debug_out_slabs", "mlggd_debug_gemm_plan",
     "mlggd_debug_keep_ranks", "mlggd_debug_rank_tensor",
     "mlggd_wave_to_lps", "mlggd_lps_to_wave", "mlggd_enhance_wave",
+    "mlggd_enhance_waves_layout", "mlggd_enhance_waves",
 ]
 
 _lib = None
@@ -131,6 +132,9 @@ def load():
     L.mlggd_wave_to_lps.argtypes = [C.c_int, C.c_int, C.c_int, _sp, C.POINTER(C.c_int), _fp]
     L.mlggd_lps_to_wave.argtypes = [C.c_int, C.c_int, C.c_int, _sp, C.c_int, _fp, _sp, _fp]
     L.mlggd_enhance_wave.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _sp, _fp, C.POINTER(C.c_int)]
+    _lp = C.POINTER(C.c_int64)
+    L.mlggd_enhance_waves_layout.argtypes = [C.c_int, C.c_int, _lp, C.POINTER(C.c_int32), _lp]
+    L.mlggd_enhance_waves.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _lp, _sp, _fp, _fp]
     _lib = L
     return L
 
@@ -210,6 +214,27 @@ def lps_to_wave(noisy, lps, fs_khz=16, device=0, return_float=False):
     _check(load().mlggd_lps_to_wave(int(device), int(fs_khz), noisy.size, _sp(noisy), lps.shape[0], _p(lps), _sp(out),
                                     _p(outf) if return_float else None))
     return (out, outf) if return_float else out
+
+
+def _offsets(lengths):
+    off = np.zeros(len(lengths) + 1, np.int64)
+    np.cumsum(np.asarray(lengths, np.int64), out=off[1:])
+    return off
+
+
+def enhance_waves_layout(lengths, fs_khz=16):
+    """(frames, frame_off, out_off) of a packed batch of utterances of `lengths` samples (BPGpu.enhance_waves):
+    frames [n] per utterance, frame_off [n+1] int32 into the packed frames, out_off [n+1] int64 into the packed
+    output.  A host call: needs no device."""
+    off = _offsets(lengths)
+    n = off.size - 1
+    frame_off = np.zeros(n + 1, np.int32)
+    out_off = np.zeros(n + 1, np.int64)
+    _lp = C.POINTER(C.c_int64)
+    _check(load().mlggd_enhance_waves_layout(int(fs_khz), n, off.ctypes.data_as(_lp),
+                                             frame_off.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             out_off.ctypes.data_as(_lp)))
+    return np.diff(frame_off), frame_off, out_off
 
 
 def comm_unique_id():
@@ -355,6 +380,35 @@ class BPGpu:
         _check(load().mlggd_enhance_wave(self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), noisy.size,
                                          _sp(noisy), _sp(out), _p(outf) if return_float else None, C.byref(n)))
         return (out, outf) if return_float else out
+
+    def enhance_waves(self, waves, mean, inv_std, fs_khz=16, fea_context=None, return_f32=False, return_lps=False):
+        """enhance_wave over a list of int16 waves in one pass over the device (mlggd_enhance_waves): a list of int16
+        arrays, each bit-equal to enhance_wave on that wave alone; with return_f32 / return_lps a tuple of lists, the
+        float32 waves before the cast and the de-normalised network outputs [F_u][D] added in that order.
+        fea_context None: layersizes[0] / bins."""
+        waves = [_wave(w) for w in waves]
+        L, S, N = SPECTRAL_PARAMS[int(fs_khz)]
+        D = N // 2 + 1
+        mean = _f32(mean, (D,))
+        inv = _f32(inv_std, (D,))
+        if fea_context is None:
+            fea_context = self.K0 // D
+        frames, frame_off, out_off = enhance_waves_layout([w.size for w in waves], fs_khz)
+        n = len(waves)
+        packed = np.concatenate(waves) if n else np.zeros(0, np.int16)
+        off = _offsets([w.size for w in waves])
+        out = np.empty(int(out_off[-1]), np.int16)
+        outf = np.empty(out.size, np.float32) if return_f32 else None
+        lps = np.empty((int(frame_off[-1]), D), np.float32) if return_lps else None
+        _check(load().mlggd_enhance_waves(self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), n, _sp(packed),
+                                          off.ctypes.data_as(C.POINTER(C.c_int64)), _sp(out),
+                                          _p(outf) if return_f32 else None, _p(lps) if return_lps else None))
+        res = [[out[out_off[u]:out_off[u + 1]] for u in range(n)]]
+        if return_f32:
+            res.append([outf[out_off[u]:out_off[u + 1]] for u in range(n)])
+        if return_lps:
+            res.append([lps[frame_off[u]:frame_off[u + 1]] for u in range(n)])
+        return res[0] if len(res) == 1 else tuple(res)
 
     def last_train_ms(self):
         ms, steps = C.c_float(0), C.c_int(0)

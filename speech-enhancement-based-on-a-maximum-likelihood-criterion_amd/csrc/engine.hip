@@ -213,6 +213,20 @@ struct mlggd_engine {
     } raw[2];
     int raw_cur = 0;
     hipStream_t copy_stream = nullptr;
+    // mlggd_enhance_waves: device workspace that only grows (freed in mlggd_destroy) and the host copies of the
+    // tables and norm vectors it holds, so a call in the steady state allocates nothing and uploads the wave alone
+    struct WsBuf {
+        void *p = nullptr;
+        size_t cap = 0;  // bytes
+    };
+    struct WavesWs {
+        WsBuf wave, lps, X, blk, out_i, out_f, lps_den, norm, frame_off, out_off, wave_off, utt_of;
+        std::vector<int32_t> h_frame_off, h_utt_of;
+        std::vector<long long> h_out_off, h_wave_off;
+        std::vector<float> h_norm;  // [2 D]: mean, inv_std as uploaded last
+        int lookup_table = 0;       // utterance of a frame: 0 = binary search over frame_off (default), 1 = per-frame
+                                    // table (MLGGD_WAVES_LOOKUP=table, for A/B runs)
+    } ww;
     bool indexed = false;
     int fdim = 0, toff = 0, raw_frames = 0;
     unsigned step_counter = 0;
@@ -1633,6 +1647,7 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     e->D = e->ls[e->L - 1];
     e->Dp = e->lsp[e->L - 1];
     if (const char *v = getenv("MLGGD_FWD_NW")) e->fwd_nw = atoi(v);
+    if (const char *v = getenv("MLGGD_WAVES_LOOKUP")) e->ww.lookup_table = !strcmp(v, "table");
     if (const char *v = getenv("MLGGD_DX_NW")) e->dx_nw = atoi(v);
     if (const char *v = getenv("MLGGD_FWD_PIPE")) e->fwd_pipe = atoi(v);
     if (const char *v = getenv("MLGGD_DX_PIPE")) e->dx_pipe = atoi(v);
@@ -1732,6 +1747,10 @@ int mlggd_destroy(mlggd_handle e) {
         if (r.last_use) hipEventDestroy(r.last_use);
     }
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
+    for (mlggd_engine::WsBuf *b : {&e->ww.wave, &e->ww.lps, &e->ww.X, &e->ww.blk, &e->ww.out_i, &e->ww.out_f,
+                                   &e->ww.lps_den, &e->ww.norm, &e->ww.frame_off, &e->ww.out_off, &e->ww.wave_off,
+                                   &e->ww.utt_of})
+        if (b->p) hipFree(b->p);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
     for (int l = 0; l < MLGGD_MAXLAYER; l++) {
         if (e->ev_grad[l]) hipEventDestroy(e->ev_grad[l]);
@@ -2849,10 +2868,10 @@ int launch_analysis(const SpecPlan *p, const int16_t *wave, int F, float *lps, f
 }
 
 int launch_synthesis(const SpecPlan *p, const float *src, const float *mean, const float *inv, const float2 *X, int t0,
-                     int nf, float *blk, hipStream_t st) {
+                     int nf, float *blk, hipStream_t st, float *lps_den = nullptr) {
     if (nf == 0) return MLGGD_OK;
     hipLaunchKernelGGL(k_lps_synthesis, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, X, t0, nf,
-                       p->d, p->win, p->tw, p->tws, (float)exp(-50.0), blk);
+                       p->d, p->win, p->tw, p->tws, (float)exp(-50.0), blk, lps_den);
     return launch_check("k_lps_synthesis");
 }
 
@@ -2877,15 +2896,14 @@ int ola_to_host(const SpecPlan *p, const float *blk, int F, int16_t *out, float 
     return MLGGD_OK;
 }
 
-// the frame stream of output frames [a, a + n) written by k_lps_stream into the engine's idle raw buffer set, which
-// then becomes the current one: the device-side counterpart of mlggd_load_frames (first_frame[i] = i, no targets)
-int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, int ctx, const float *mean,
-                       const float *inv) {
+// the engine's idle raw buffer set, grown to `rows` stream rows and n samples, for a frame stream written on the
+// device; raw_set_commit then makes it the current one: the device-side counterpart of mlggd_load_frames (no targets)
+int raw_set_acquire(mlggd_engine *e, int rows, int n, int ctx, mlggd_engine::RawSet **out) {
     if (!e->copy_stream) {
         CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));
         for (auto &r : e->raw) HIPCHK(hipEventCreateWithFlags(&r.last_use, hipEventDisableTiming));
     }
-    const int fdim = e->K0 / ctx, rows = n + ctx - 1;
+    const int fdim = e->K0 / ctx;
     mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
     HIPCHK(hipEventSynchronize(r.last_use));
     const size_t need = (size_t)rows + ctx + 8;
@@ -2911,10 +2929,11 @@ int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, i
         HIPCHK(hipMemsetAsync(r.first, 0, need_s * sizeof(int), e->stream));
         r.first_cap = need_s;
     }
-    const size_t work = std::max((size_t)rows * fdim, (size_t)n);
-    hipLaunchKernelGGL(k_lps_stream, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, lps, F, fdim, a,
-                       rows, (ctx - 1) / 2, mean, inv, r.feat, r.first, n);
-    CHK(launch_check("k_lps_stream"));
+    *out = &r;
+    return MLGGD_OK;
+}
+
+void raw_set_commit(mlggd_engine *e, mlggd_engine::RawSet &r, int rows, int n, int ctx) {
     e->raw_cur ^= 1;
     e->raw_feat = r.feat;
     e->raw_targ = r.targ;
@@ -2924,8 +2943,66 @@ int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, i
     e->chunk_frames = n;
     e->raw_frames = rows;
     e->indexed = true;
-    e->fdim = fdim;
+    e->fdim = e->K0 / ctx;
     e->toff = 0;
+}
+
+// the frame stream of output frames [a, a + n) of an F-frame utterance, written by k_lps_stream (first_frame[i] = i)
+int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, int ctx, const float *mean,
+                       const float *inv) {
+    const int fdim = e->K0 / ctx, rows = n + ctx - 1;
+    mlggd_engine::RawSet *r;
+    CHK(raw_set_acquire(e, rows, n, ctx, &r));
+    const size_t work = std::max((size_t)rows * fdim, (size_t)n);
+    hipLaunchKernelGGL(k_lps_stream, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, lps, F, fdim, a,
+                       rows, (ctx - 1) / 2, mean, inv, r->feat, r->first, n);
+    CHK(launch_check("k_lps_stream"));
+    raw_set_commit(e, *r, rows, n, ctx);
+    return MLGGD_OK;
+}
+
+// frames, frame offsets and output offsets of a packed batch (mlggd_enhance_waves_layout); frame_off / out_off may
+// be NULL
+int waves_layout(const SpecDims &d, int n_utts, const int64_t *offsets, int32_t *frame_off, int64_t *out_off) {
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (frame_off) frame_off[0] = 0;
+    if (out_off) out_off[0] = 0;
+    if (n_utts == 0) return MLGGD_OK;
+    if (!offsets) return fail(MLGGD_ERR_ARG, "offsets is NULL");
+    long long fsum = 0, osum = 0;
+    for (int u = 0; u < n_utts; u++) {
+        if (offsets[u + 1] < offsets[u])
+            return fail(MLGGD_ERR_ARG, "offsets decrease at utterance %d (%lld after %lld)", u, (long long)offsets[u + 1],
+                        (long long)offsets[u]);
+        const long long len = (long long)offsets[u + 1] - (long long)offsets[u];
+        if (len < d.L)
+            return fail(MLGGD_ERR_ARG, "utterance %d: %lld samples is shorter than one frame (%d)", u, len, d.L);
+        const long long F = (len - (d.L - d.S)) / d.S;
+        fsum += F;
+        osum += F * d.S + d.L - d.S;
+        if (fsum > INT32_MAX)
+            return fail(MLGGD_ERR_ARG, "the batch has more than %d frames (reached at utterance %d)", INT32_MAX, u);
+        if (frame_off) frame_off[u + 1] = (int32_t)fsum;
+        if (out_off) out_off[u + 1] = osum;
+    }
+    return MLGGD_OK;
+}
+
+// a workspace buffer of at least `bytes` (plus an eighth of headroom when it has to grow, so that batches of slightly
+// different sizes settle after the first few); the old contents are dropped
+template <typename T>
+int ws_grow(mlggd_engine *e, mlggd_engine::WsBuf &b, size_t count, T **out) {
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    if (bytes > b.cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (b.p) hipFree(b.p);
+        b.p = nullptr;
+        b.cap = 0;
+        const size_t want = bytes + bytes / 8 + 256;
+        HIPCHK(hipMalloc(&b.p, want));
+        b.cap = want;
+    }
+    *out = (T *)b.p;
     return MLGGD_OK;
 }
 
@@ -3033,6 +3110,123 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
         HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
     }
     return ola_to_host(p, blk, F, out, out_f32, st);
+}
+
+int mlggd_enhance_waves_layout(int fs_khz, int n_utts, const int64_t *offsets, int32_t *frame_off, int64_t *out_off) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    return waves_layout(d, n_utts, offsets, frame_off, out_off);
+}
+
+int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                        int n_utts, const int16_t *noisy, const int64_t *offsets, int16_t *out, float *out_f32,
+                        float *lps_out) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (fea_context < 1 || fea_context % 2 == 0) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", fea_context);
+    if ((long long)fea_context * d.D != e->K0)
+        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
+    if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
+    if (e->world > 1 || e->fake_world)
+        return fail(MLGGD_ERR_STATE, "mlggd_enhance_waves runs on a single-device engine");
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (n_utts == 0) return MLGGD_OK;
+    if (!noisy || !offsets || !norm_mean || !norm_inv_std || !out)
+        return fail(MLGGD_ERR_ARG, "noisy/offsets/norm/out is NULL");
+    mlggd_engine::WavesWs &w = e->ww;
+    w.h_frame_off.resize((size_t)n_utts + 1);
+    w.h_out_off.resize((size_t)n_utts + 1);
+    w.h_wave_off.resize((size_t)n_utts + 1);
+    {
+        std::vector<int64_t> oo((size_t)n_utts + 1);
+        CHK(waves_layout(d, n_utts, offsets, w.h_frame_off.data(), oo.data()));
+        for (int u = 0; u <= n_utts; u++) {
+            w.h_out_off[u] = oo[u];
+            w.h_wave_off[u] = (long long)offsets[u] - (long long)offsets[0];
+        }
+    }
+    const int FT = w.h_frame_off[n_utts];  // every utterance has a frame: FT >= n_utts
+    const size_t n_wave = (size_t)w.h_wave_off[n_utts], n_out = (size_t)w.h_out_off[n_utts];
+    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    // the stream rows of a chunk: its frames + (ctx - 1) per utterance it touches, in int
+    if ((long long)std::min(cap, FT) + (long long)std::min(n_utts, cap) * (fea_context - 1) > INT32_MAX / 2)
+        return fail(MLGGD_ERR_ARG, "a chunk of %d frames over %d utterances is too large", std::min(cap, FT), n_utts);
+    HIPCHK(hipSetDevice(e->device));
+    const SpecPlan *p;
+    CHK(spec_plan(e->device, fs_khz, &p));
+    hipStream_t st = e->stream;
+    int16_t *dw = nullptr, *oi = nullptr;
+    float *dl = nullptr, *blk = nullptr, *of = nullptr, *den = nullptr, *norm = nullptr;
+    float2 *X = nullptr;
+    int *d_foff = nullptr, *d_utt = nullptr;
+    long long *d_ooff = nullptr, *d_woff = nullptr;
+    CHK(ws_grow(e, w.wave, n_wave, &dw));
+    CHK(ws_grow(e, w.lps, (size_t)FT * d.D, &dl));
+    CHK(ws_grow(e, w.X, (size_t)FT * d.D, &X));
+    CHK(ws_grow(e, w.blk, (size_t)FT * d.L, &blk));
+    CHK(ws_grow(e, w.out_i, n_out, &oi));
+    if (out_f32) CHK(ws_grow(e, w.out_f, n_out, &of));
+    if (lps_out) CHK(ws_grow(e, w.lps_den, (size_t)FT * d.D, &den));
+    CHK(ws_grow(e, w.frame_off, (size_t)n_utts + 1, &d_foff));
+    CHK(ws_grow(e, w.out_off, (size_t)n_utts + 1, &d_ooff));
+    CHK(ws_grow(e, w.wave_off, (size_t)n_utts + 1, &d_woff));
+    {   // the norm vectors stay on the device until the caller passes other values
+        const size_t had = w.norm.cap;
+        CHK(ws_grow(e, w.norm, (size_t)2 * d.D, &norm));
+        std::vector<float> nv((size_t)2 * d.D);
+        memcpy(nv.data(), norm_mean, d.D * sizeof(float));
+        memcpy(nv.data() + d.D, norm_inv_std, d.D * sizeof(float));
+        if (w.norm.cap != had || nv.size() != w.h_norm.size() ||
+            memcmp(nv.data(), w.h_norm.data(), nv.size() * sizeof(float)) != 0) {
+            HIPCHK(hipStreamSynchronize(st));  // no copy out of the old h_norm is in flight
+            w.h_norm.swap(nv);
+            HIPCHK(hipMemcpyAsync(norm, w.h_norm.data(), w.h_norm.size() * sizeof(float), hipMemcpyHostToDevice, st));
+        }
+    }
+    const float *mean = norm, *inv = norm + d.D;
+    HIPCHK(hipMemcpyAsync(dw, noisy + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_foff, w.h_frame_off.data(), ((size_t)n_utts + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ooff, w.h_out_off.data(), ((size_t)n_utts + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_woff, w.h_wave_off.data(), ((size_t)n_utts + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    if (w.lookup_table) {
+        w.h_utt_of.resize(FT);
+        for (int u = 0; u < n_utts; u++)
+            std::fill(w.h_utt_of.begin() + w.h_frame_off[u], w.h_utt_of.begin() + w.h_frame_off[u + 1], u);
+        CHK(ws_grow(e, w.utt_of, (size_t)FT, &d_utt));
+        HIPCHK(hipMemcpyAsync(d_utt, w.h_utt_of.data(), (size_t)FT * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, dw, d_woff, d_foff, d_utt,
+                       n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0), dl, X);
+    CHK(launch_check("k_lps_analysis_seg"));
+    // chunks over the packed frame index: a chunk's stream carries the context rows of every utterance it touches, so
+    // an output frame sees the same input rows wherever the boundaries fall; bunches run across utterances
+    for (int a = 0, u0 = 0; a < FT; a += cap) {
+        const int n = std::min(cap, FT - a);
+        while (w.h_frame_off[u0 + 1] <= a) u0++;
+        int u1 = u0;
+        while (w.h_frame_off[u1 + 1] < a + n) u1++;
+        const int rows = n + (u1 - u0 + 1) * (fea_context - 1);
+        mlggd_engine::RawSet *r;
+        CHK(raw_set_acquire(e, rows, n, fea_context, &r));
+        hipLaunchKernelGGL(k_lps_stream_seg, dim3((unsigned)rows), dim3(256), 0, st, dl, d_foff, d_utt, n_utts, d.D, a, n,
+                           u0, u1, fea_context, mean, inv, r->feat, r->first);
+        CHK(launch_check("k_lps_stream_seg"));
+        raw_set_commit(e, *r, rows, n, fea_context);
+        CHK(forward_resident(e, n));
+        CHK(launch_synthesis(p, e->chunk_out, mean, inv, X, a, n, blk, st, den));
+        HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
+    }
+    hipLaunchKernelGGL(k_ola_seg, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, blk, d_foff, d_ooff, n_utts,
+                       p->d, p->win, of, oi, (long long)n_out);
+    CHK(launch_check("k_ola_seg"));
+    HIPCHK(hipMemcpyAsync(out, oi, n_out * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+    if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, of, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (lps_out) HIPCHK(hipMemcpyAsync(lps_out, den, (size_t)FT * d.D * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return MLGGD_OK;
 }
 
 }  // extern "C"

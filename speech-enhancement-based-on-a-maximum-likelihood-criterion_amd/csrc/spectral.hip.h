@@ -6,6 +6,10 @@
 //   k_lps_synthesis  LPS rows, or the forward pass's outputs de-normalised, + X -> noisy phase, inverse FFT, window
 //   k_ola            overlap-add of the windowed time blocks, / sum w^2, float and saturated int16 output
 //
+// The *_seg kernels are the same steps over a packed batch of utterances (mlggd_enhance_waves): global frame g of
+// the batch is local frame g - frame_off[u] of utterance u, and every edge (frame positions, context replication,
+// overlap-add coverage) is the utterance's own.  Per element they run the operation sequences of the kernels above.
+//
 // FFT form: the real N-point spectrum is an M = N/2-point complex FFT of z_m = x_2m + i x_2m+1
 // (radix-2 decimation in time: bit-reversed load, log2(M) butterfly stages in LDS) followed by the real split step
 // X_k = (Z_k + conj Z_{M-k}) / 2 - i W_N^k (Z_k - conj Z_{M-k}) / 2.  The inverse runs the same steps backwards
@@ -53,19 +57,13 @@ __device__ __forceinline__ void spec_fft_rows(float *re, float *im, const float2
 
 __device__ __forceinline__ int spec_bitrev(int m, int logM) { return (int)(__brev((unsigned)m) >> (32 - logM)); }
 
-// grid: ceil(F / SPEC_FRAMES) workgroups of 64 * SPEC_FRAMES threads.  win [L] (full, mirrored), tw [M/2] =
-// exp(-2 pi i j / M), tws [D] = exp(-2 pi i k / N).  lps [F][D] and X [F][D] are each optional (nullptr).
-__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_analysis(const int16_t *__restrict__ wave, int F, SpecDims d,
-                                                                   const float *__restrict__ win,
-                                                                   const float2 *__restrict__ tw,
-                                                                   const float2 *__restrict__ tws, float floor_p,
-                                                                   float *__restrict__ lps, float2 *__restrict__ X) {
-    __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int t = blockIdx.x * SPEC_FRAMES + wv;
-    const bool live = t < F;  // a dead wave still takes part in the barriers
-    float *re = s_re[wv], *im = s_im[wv];
-    const int16_t *x = wave + (size_t)(live ? t : 0) * d.S;  // frame t: samples [t S, t S + L), inside the wave
+// one wavefront: the frame of L samples at x -> row t of lps / X (each optional, nullptr).  win [L] (full, mirrored),
+// tw [M/2] = exp(-2 pi i j / M), tws [D] = exp(-2 pi i k / N).  A dead wave (!live) still takes part in the barriers.
+__device__ __forceinline__ void spec_analysis_frame(const int16_t *__restrict__ x, bool live, size_t t, const SpecDims &d,
+                                                    const float *__restrict__ win, const float2 *__restrict__ tw,
+                                                    const float2 *__restrict__ tws, float floor_p,
+                                                    float *__restrict__ lps, float2 *__restrict__ X, float *re,
+                                                    float *im, int lane) {
     for (int m = lane; m < d.M; m += 64) {
         const int n0 = 2 * m, n1 = 2 * m + 1;
         const float v0 = (live && n0 < d.L) ? (float)x[n0] * win[n0] : 0.0f;  // zero padding to N
@@ -86,12 +84,57 @@ __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_analysis(const int16_t
         const float2 w = tws[k];
         const float pr = w.x * orr - w.y * oi, pi = w.x * oi + w.y * orr;  // W^k O
         const float xr = er + pi, xi = ei - pr;                             // E - i W^k O
-        if (X) X[(size_t)t * d.D + k] = make_float2(xr, xi);
+        if (X) X[t * d.D + k] = make_float2(xr, xi);
         if (lps) {
             const float P = xr * xr + xi * xi;
-            lps[(size_t)t * d.D + k] = (P < floor_p) ? SPEC_FLOOR : (float)log((double)P);
+            lps[t * d.D + k] = (P < floor_p) ? SPEC_FLOOR : (float)log((double)P);
         }
     }
+}
+
+// grid: ceil(F / SPEC_FRAMES) workgroups of 64 * SPEC_FRAMES threads, one wavefront per frame
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_analysis(const int16_t *__restrict__ wave, int F, SpecDims d,
+                                                                   const float *__restrict__ win,
+                                                                   const float2 *__restrict__ tw,
+                                                                   const float2 *__restrict__ tws, float floor_p,
+                                                                   float *__restrict__ lps, float2 *__restrict__ X) {
+    __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * SPEC_FRAMES + wv;
+    const bool live = t < F;
+    const int16_t *x = wave + (size_t)(live ? t : 0) * d.S;  // frame t: samples [t S, t S + L), inside the wave
+    spec_analysis_frame(x, live, (size_t)(live ? t : 0), d, win, tw, tws, floor_p, lps, X, s_re[wv], s_im[wv], lane);
+}
+
+// The utterance of global frame g: the largest u with frame_off[u] <= g (every utterance has at least one frame, so
+// frame_off is strictly increasing).  utt_of, when given, is the per-frame table of the same answer.
+__device__ __forceinline__ int seg_of_frame(const int *__restrict__ frame_off, int n_utts,
+                                            const int *__restrict__ utt_of, int g) {
+    if (utt_of) return utt_of[g];
+    int lo = 0, hi = n_utts - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_off[mid] <= g) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// k_lps_analysis over a packed batch: global frame g = local frame g - frame_off[u] of utterance u, whose samples
+// start at wave + wave_off[u].  lps / X rows are indexed by g.
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_analysis_seg(
+    const int16_t *__restrict__ wave, const long long *__restrict__ wave_off, const int *__restrict__ frame_off,
+    const int *__restrict__ utt_of, int n_utts, int F, SpecDims d, const float *__restrict__ win,
+    const float2 *__restrict__ tw, const float2 *__restrict__ tws, float floor_p, float *__restrict__ lps,
+    float2 *__restrict__ X) {
+    __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int g = blockIdx.x * SPEC_FRAMES + wv;
+    const bool live = g < F;
+    const int gg = live ? g : 0;
+    const int u = seg_of_frame(frame_off, n_utts, utt_of, gg);
+    const int16_t *x = wave + wave_off[u] + (size_t)(gg - frame_off[u]) * d.S;
+    spec_analysis_frame(x, live, (size_t)gg, d, win, tw, tws, floor_p, lps, X, s_re[wv], s_im[wv], lane);
 }
 
 // The forward pass's input for output frames [a, a + n) of an F-frame utterance: n + 2 half rows, row j = frame
@@ -109,14 +152,45 @@ __global__ void k_lps_stream(const float *__restrict__ lps, int F, int D, int a,
     stream[i] = c * inv[k];
 }
 
+// The forward pass's input for the packed frames [a, a + n), which touch utterances u0..u1: utterance u contributes
+// the rows of its frames in the chunk plus ctx - 1 context rows, edge-replicated inside the utterance, so its section
+// starts at row rs(u) = max(frame_off[u], a) - a + (u - u0) (ctx - 1) and sample i (frame a + i of utterance u)
+// starts at first[i] = i + (u - u0) (ctx - 1).  One workgroup per stream row; the row's utterance is found by a
+// search every lane runs alike.
+__global__ void k_lps_stream_seg(const float *__restrict__ lps, const int *__restrict__ frame_off,
+                                 const int *__restrict__ utt_of, int n_utts, int D, int a, int n, int u0, int u1, int ctx,
+                                 const float *__restrict__ mean, const float *__restrict__ inv,
+                                 float *__restrict__ stream, int *__restrict__ first) {
+    const int r = blockIdx.x, half = (ctx - 1) / 2;
+    if (r < n && threadIdx.x == 0) first[r] = r + (seg_of_frame(frame_off, n_utts, utt_of, a + r) - u0) * (ctx - 1);
+    int lo = u0, hi = u1;  // the largest u with rs(u) <= r
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        const int fo = frame_off[mid];
+        if ((fo > a ? fo : a) - a + (mid - u0) * (ctx - 1) <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    const int u = lo, fo = frame_off[u], Fu = frame_off[u + 1] - fo;
+    const int ga = fo > a ? fo : a;
+    int t = (ga - fo) - half + (r - (ga - a + (u - u0) * (ctx - 1)));
+    t = t < 0 ? 0 : (t >= Fu ? Fu - 1 : t);
+    const float *src = lps + (size_t)(fo + t) * D;
+    float *dst = stream + (size_t)r * D;
+    for (int k = threadIdx.x; k < D; k += blockDim.x) {
+        const float c = src[k] - mean[k];
+        dst[k] = c * inv[k];
+    }
+}
+
 // Frames [t0, t0 + nf): target LPS row r = src[(t - t0) * D + k] (de-normalised first when mean != nullptr: y / inv +
-// mean, two IEEE operations), noisy spectrum X [t][k] -> windowed time block blk [t][L].
+// mean, two IEEE operations), noisy spectrum X [t][k] -> windowed time block blk [t][L].  lps_den (optional, with
+// mean): receives the de-normalised rows, [t][D].
 __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float *__restrict__ src, const float *__restrict__ mean,
                                                                     const float *__restrict__ inv, const float2 *__restrict__ X,
                                                                     int t0, int nf, SpecDims d, const float *__restrict__ win,
                                                                     const float2 *__restrict__ tw,
                                                                     const float2 *__restrict__ tws, float floor_exp,
-                                                                    float *__restrict__ blk) {
+                                                                    float *__restrict__ blk, float *__restrict__ lps_den) {
     __shared__ float s_yr[SPEC_FRAMES][SPEC_MAXM + 1], s_yi[SPEC_FRAMES][SPEC_MAXM + 1];
     __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -130,6 +204,7 @@ __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float 
         if (mean) {
             const float q = v / inv[k];
             v = q + mean[k];
+            if (lps_den && live) lps_den[t * d.D + k] = v;
         }
         const float ph = (v < SPEC_FLOOR) ? floor_exp : (float)exp((double)v);
         const float mag = sqrtf(ph);
@@ -189,4 +264,36 @@ __global__ void k_ola(const float *__restrict__ blk, int F, SpecDims d, const fl
     if (out_f) out_f[i] = v;
     const float c = truncf(v);
     out_i[i] = (int16_t)(c >= 32767.0f ? 32767 : (c <= -32768.0f ? -32768 : (int)c));
+}
+
+// k_ola over a packed batch: output sample i belongs to the utterance u with out_off[u] <= i < out_off[u + 1]; the
+// frames that cover it are clamped to that utterance's F_u frames (time blocks frame_off[u] ..), summed in frame order
+// and divided by sum w^2 formed in the same order, as k_ola does.
+__global__ void k_ola_seg(const float *__restrict__ blk, const int *__restrict__ frame_off,
+                          const long long *__restrict__ out_off, int n_utts, SpecDims d, const float *__restrict__ win,
+                          float *__restrict__ out_f, int16_t *__restrict__ out_i, long long n_out) {
+    const long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi >= n_out) return;
+    int ul = 0, uh = n_utts - 1;
+    while (ul < uh) {
+        const int mid = (ul + uh + 1) >> 1;
+        if (out_off[mid] <= gi) ul = mid;
+        else uh = mid - 1;
+    }
+    const int fo = frame_off[ul], F = frame_off[ul + 1] - fo;
+    const int i = (int)(gi - out_off[ul]);
+    int lo = i - d.L + 1;
+    lo = lo <= 0 ? 0 : (lo + d.S - 1) / d.S;
+    int hi = i / d.S;
+    if (hi > F - 1) hi = F - 1;
+    float acc = 0.0f, cnt = 0.0f;
+    for (int t = lo; t <= hi; t++) {
+        const int j = i - t * d.S;
+        acc += blk[(size_t)(fo + t) * d.L + j];
+        cnt += win[j] * win[j];
+    }
+    const float v = acc / cnt;
+    if (out_f) out_f[gi] = v;
+    const float c = truncf(v);
+    out_i[gi] = (int16_t)(c >= 32767.0f ? 32767 : (c <= -32768.0f ? -32768 : (int)c));
 }

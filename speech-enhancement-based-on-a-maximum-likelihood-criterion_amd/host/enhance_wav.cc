@@ -1,16 +1,23 @@
 // enhance_wav.cc -- the whole of the original project's decoder (Test_code/decode.m) in one process: noisy RIFF
 // WAV -> LPS -> z-normalise with the training norm file -> edge-replicated context of fea_context frames -> sigmoid
 // MLP from the trainer's .wts -> de-normalise -> overlap-add resynthesis with the noisy phase -> enhanced RIFF WAV,
-// all on the GPU by mlggd_enhance_wave.  With clean= and info=, the quality report of LPS2Wav_be against the clean
-// wave (its LPS is the de-normalised network output, formed again from the public pieces on the same engine).
+// all on the GPU.  With a clean wave and an info file, the quality report of LPS2Wav_be against the clean wave (its
+// LPS is the de-normalised network output).
 //
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
-//               [fea_context=7] [gpu_used=0] [bunchsize=512] [clean=clean.wav info=info.txt]
+//               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
 //
-// scp lists "in out" lines, like enhance_lps.
+// scp lists "in out" or "in out clean info" lines.  A list is decoded in batches of batch_s seconds of audio by
+// mlggd_enhance_waves: the utterances of a batch form one frame stream, so the forward bunches are full, and the
+// quality report takes the network's output rows from the same pass.  A batch ends early where the sample rate
+// changes.  batch_s=0: one mlggd_enhance_wave call per line.  The files and the lines on stdout are the same either
+// way.  Device memory per 16 kHz frame (256 new samples): 512 B wave + 1028 B LPS + 2056 B spectrum + 2048 B time block
+// + 512 B output + 1028 B report rows, an eighth of headroom on each, and 5 x 1028 B of frame stream and network output
+// = about 13 KB; 62.5 frames per second make 0.8 MB per second of audio, 250 MB at the default batch_s=300.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -21,9 +28,36 @@
     exit(1);
 }
 
+struct Job {
+    std::string in, out, clean, info;
+};
+
+// an utterance read and checked, waiting for its batch
+struct Item {
+    Job job;
+    std::vector<int16_t> noisy;
+    int rate = 0, fs = 0, F = 0;
+};
+
+// LPS2Wav_be's report for one utterance from its enhanced LPS rows y [F][D]
+void report(const Item &it, const float *y) {
+    int L, S, N;
+    tool_io::spectral_params(it.fs, &L, &S, &N);
+    int cr = 0;
+    const std::vector<int16_t> cw = tool_io::read_wav(it.job.clean, &cr);
+    if (cr != it.rate) die(it.job.clean + ": sample rate differs from " + it.job.in);
+    const int Fc = cw.size() < (size_t)L ? 0 : (int)((cw.size() - (L - S)) / S);
+    const int Fm = std::min(it.F, Fc);
+    if (Fm == 0) die(it.job.clean + ": shorter than one frame");
+    double segsnr = 0.0, lsd = 0.0;
+    tool_io::quality(it.fs, cw, it.noisy, y, Fm, &segsnr, &lsd);
+    tool_io::write_info(it.job.info, segsnr, lsd);
+}
+
 int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp, clean, info;
     int ctx = 7, gpu = 0, bunch = 512;
+    double batch_s = 300.0;
     for (int a = 1; a < argc; a++) {
         const std::string arg(argv[a]);
         const size_t eq = arg.find('=');
@@ -39,14 +73,16 @@ int main(int argc, char **argv) {
         else if (k == "fea_context") ctx = atoi(v.c_str());
         else if (k == "gpu_used") gpu = atoi(v.c_str());
         else if (k == "bunchsize") bunch = atoi(v.c_str());
+        else if (k == "batch_s") batch_s = atof(v.c_str());
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
         die("usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
-            "[clean=F info=F]");
+            "[batch_s=300] [clean=F info=F]");
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
     if (clean.empty() != info.empty()) die("clean= and info= go together");
-    if (!clean.empty() && !scp.empty()) die("clean= / info= need a single in= / out= pair");
+    if (!clean.empty() && !scp.empty()) die("clean= / info= need a single in= / out= pair (or four-field scp lines)");
+    if (batch_s < 0) die("batch_s must not be negative");
 
     const tool_io::Model model = tool_io::read_wts(wts);
     const int D = model.ls.back();
@@ -55,32 +91,88 @@ int main(int argc, char **argv) {
     tool_io::read_norm(norm_file, D, mean, inv);
     mlggd_handle h = tool_io::create_engine(model, gpu, bunch);
 
-    std::vector<std::pair<std::string, std::string>> jobs;
+    std::vector<Job> jobs;
     if (!scp.empty()) {
         std::ifstream f(scp);
         if (!f) die("cannot open " + scp);
-        std::string a, b;
-        while (f >> a >> b) jobs.emplace_back(a, b);
+        std::string line;
+        for (int ln = 1; std::getline(f, line); ln++) {
+            std::istringstream ss(line);
+            std::vector<std::string> w;
+            for (std::string t; ss >> t;) w.push_back(t);
+            if (w.empty()) continue;
+            if (w.size() != 2 && w.size() != 4)
+                die(scp + " line " + std::to_string(ln) + ": expected \"in out\" or \"in out clean info\"");
+            jobs.push_back(w.size() == 2 ? Job{w[0], w[1], "", ""} : Job{w[0], w[1], w[2], w[3]});
+        }
     } else {
-        jobs.emplace_back(in, out);
+        jobs.push_back(Job{in, out, clean, info});
     }
+    const bool batched = !scp.empty() && batch_s > 0;
+
+    // the batch: utterances of one rate, decoded by one mlggd_enhance_waves call when it is full or the rate changes
+    std::vector<Item> pend;
+    size_t pend_samples = 0;
+    auto flush = [&]() {
+        if (pend.empty()) return;
+        const int n = (int)pend.size(), fs = pend[0].fs;
+        std::vector<int64_t> off(n + 1, 0), out_off(n + 1, 0);
+        std::vector<int32_t> frame_off(n + 1, 0);
+        for (int u = 0; u < n; u++) off[u + 1] = off[u] + (int64_t)pend[u].noisy.size();
+        std::vector<int16_t> packed((size_t)off[n]);
+        bool want_lps = false;
+        for (int u = 0; u < n; u++) {
+            std::copy(pend[u].noisy.begin(), pend[u].noisy.end(), packed.begin() + off[u]);
+            want_lps = want_lps || !pend[u].job.clean.empty();
+        }
+        if (mlggd_enhance_waves_layout(fs, n, off.data(), frame_off.data(), out_off.data()) != MLGGD_OK)
+            die(std::string("mlggd_enhance_waves_layout: ") + mlggd_last_error());
+        std::vector<int16_t> enh((size_t)out_off[n]);
+        std::vector<float> lps(want_lps ? (size_t)frame_off[n] * D : 0);
+        if (mlggd_enhance_waves(h, fs, ctx, mean.data(), inv.data(), n, packed.data(), off.data(), enh.data(), nullptr,
+                                want_lps ? lps.data() : nullptr) != MLGGD_OK)
+            die(std::string("mlggd_enhance_waves: ") + mlggd_last_error());
+        for (int u = 0; u < n; u++) {
+            const Item &it = pend[u];
+            tool_io::write_wav(it.job.out, enh.data() + out_off[u], (size_t)(out_off[u + 1] - out_off[u]), it.rate);
+            printf("%s -> %s (%d frames)\n", it.job.in.c_str(), it.job.out.c_str(), it.F);
+            if (!it.job.clean.empty()) report(it, lps.data() + (size_t)frame_off[u] * D);
+        }
+        pend.clear();
+        pend_samples = 0;
+    };
+    // an utterance that cannot be decoded ends the run after the ones before it have been written
+    auto die_in_order = [&](const std::string &m) {
+        flush();
+        die(m);
+    };
+
     for (const auto &job : jobs) {
-        int rate = 0;
-        const std::vector<int16_t> noisy = tool_io::read_wav(job.first, &rate);
-        const int fs = tool_io::rate_khz(rate);
-        if (!fs) die(job.first + ": sample rate " + std::to_string(rate) + " Hz is not 8000, 11000 or 16000");
+        Item it;
+        it.job = job;
+        it.noisy = tool_io::read_wav(job.in, &it.rate);
+        const int rate = it.rate, fs = it.fs = tool_io::rate_khz(rate);
+        if (!fs) die_in_order(job.in + ": sample rate " + std::to_string(rate) + " Hz is not 8000, 11000 or 16000");
         int L, S, N;
         tool_io::spectral_params(fs, &L, &S, &N);
-        if (noisy.size() < (size_t)L) die(job.first + ": shorter than one frame");
-        const int F = (int)((noisy.size() - (L - S)) / S);
+        const std::vector<int16_t> &noisy = it.noisy;
+        if (noisy.size() < (size_t)L) die_in_order(job.in + ": shorter than one frame");
+        const int F = it.F = (int)((noisy.size() - (L - S)) / S);
+        if (batched) {
+            if (!pend.empty() && pend[0].rate != rate) flush();
+            pend_samples += noisy.size();
+            pend.push_back(std::move(it));
+            if ((double)pend_samples >= batch_s * rate) flush();
+            continue;
+        }
         std::vector<int16_t> enh((size_t)F * S + L - S);
         int n_out = 0;
         if (mlggd_enhance_wave(h, fs, ctx, mean.data(), inv.data(), (int)noisy.size(), noisy.data(), enh.data(), nullptr,
                                &n_out) != MLGGD_OK)
             die(std::string("mlggd_enhance_wave: ") + mlggd_last_error());
-        tool_io::write_wav(job.second, enh.data(), (size_t)n_out, rate);
-        printf("%s -> %s (%d frames)\n", job.first.c_str(), job.second.c_str(), F);
-        if (!clean.empty()) {
+        tool_io::write_wav(job.out, enh.data(), (size_t)n_out, rate);
+        printf("%s -> %s (%d frames)\n", job.in.c_str(), job.out.c_str(), F);
+        if (!job.clean.empty()) {
             // the enhanced LPS rows: the same chain through the public pieces (decode.m:31-61)
             std::vector<float> lps((size_t)F * D);
             int Fq = 0;
@@ -98,17 +190,10 @@ int main(int argc, char **argv) {
             if (mlggd_forward_frames(h, np, ctx, stream.data(), F, first.data(), y.data()) != MLGGD_OK)
                 die(std::string("mlggd_forward_frames: ") + mlggd_last_error());
             for (size_t i = 0; i < y.size(); i++) y[i] = y[i] / inv[i % D] + mean[i % D];
-            int cr = 0;
-            const std::vector<int16_t> cw = tool_io::read_wav(clean, &cr);
-            if (cr != rate) die(clean + ": sample rate differs from " + job.first);
-            const int Fc = cw.size() < (size_t)L ? 0 : (int)((cw.size() - (L - S)) / S);
-            const int Fm = std::min(F, Fc);
-            if (Fm == 0) die(clean + ": shorter than one frame");
-            double segsnr = 0.0, lsd = 0.0;
-            tool_io::quality(fs, cw, noisy, y.data(), Fm, &segsnr, &lsd);
-            tool_io::write_info(info, segsnr, lsd);
+            report(it, y.data());
         }
     }
+    flush();
     mlggd_destroy(h);
     return 0;
 }
