@@ -499,3 +499,261 @@ def synth_speech(n, fs_khz, seed=0):
 def load_fixture(path):
     z = np.load(path)
     return {k: z[k] for k in z.files}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# mlggd_enhance_waves: the index arithmetic of a packed batch of utterances.
+#
+# Twice.  waves_*_model builds every mapping utterance by utterance from what the mapping means (the frames an
+# utterance owns, the rows its section of a chunk's stream holds, the frames that cover an output sample); no search.
+# waves_*_kernel computes the same quantities the way the *_seg kernels and the engine's chunk loop do: binary
+# searches over the offset tables (or the per-frame table), rs(u), the clamps.  `slip` plants one mistake in the
+# kernel-way form; the tests show on the CPU that the inputs of each GPU test would see it, so nothing has to be
+# planted in device code.
+WAVES_DEFAULT_CAP = 200000   # MLGGD_MAXCACHEFRAME
+WAVES_SLIPS = [
+    "search_bias",            # mid = (lo + hi) >> 1 without the + 1 (a lane may then never end: reported as -1)
+    "lt_for_le",              # table[mid] < x for <= in the searches
+    "ctx_for_ctx_minus_1",    # rs(u) advances by ctx rows per utterance, not ctx - 1
+    "ga_not_clamped",         # rs(u) formed from frame_off[u], not max(frame_off[u], a), while the first local frame
+                              # stays (ga - fo); dropping the clamp from both at once cancels in t and shows nowhere
+    "fu_wrong_utterance",     # F_u, the clamp of the context and of the covering frames, from the next utterance
+    "hi_not_clamped",         # the covering frames of an output sample not clamped to F_u - 1
+    "table_plus_1",           # the per-frame table filled one frame early: an utterance's last frame says u + 1
+    "wave_off_not_rebased",   # wave_off[u] = offsets[u], though the uploaded buffer starts at offsets[0]
+]
+
+
+def waves_layout64(frames_per_utt, fs_khz, base=0):
+    """(offsets, frame_off, out_off) of utterances of exactly these frame counts packed from sample `base`"""
+    L, S, _ = params(fs_khz)
+    f = np.asarray(frames_per_utt, np.int64)
+    z = np.zeros(1, np.int64)
+    return (base + np.concatenate([z, np.cumsum(f * S + L - S)]), np.concatenate([z, np.cumsum(f)]),
+            np.concatenate([z, np.cumsum(f * S + L - S)]))
+
+
+def waves_chunks(frame_off, cap):
+    FT = int(frame_off[-1])
+    cap = cap if cap > 0 else WAVES_DEFAULT_CAP
+    return [(a, min(cap, FT - a)) for a in range(0, FT, cap)]
+
+
+def waves_analysis_model(offsets, frame_off, fs_khz):
+    """[FT]: the index into the caller's packed buffer of the first sample of every packed frame"""
+    S = params(fs_khz)[1]
+    return np.concatenate([offsets[u] + np.arange(frame_off[u + 1] - frame_off[u], dtype=np.int64) * S
+                           for u in range(len(frame_off) - 1)])
+
+
+def waves_stream_model(frame_off, ctx, cap):
+    """per chunk: (src [rows], first [n]).  Utterance u owns frames [f0, f1); of the chunk [a, a + n) it holds
+    [lo, hi), and its section of the chunk's stream is those frames with half a context on either side, clamped into
+    the utterance; the sections follow one another in utterance order; first[i] is the row where the context window
+    of frame a + i starts."""
+    fo = [int(x) for x in frame_off]
+    half = (ctx - 1) // 2
+    chunks = waves_chunks(frame_off, cap)
+    cap = chunks[0][1]                                                # the capacity, or every frame in one chunk
+    src = [[] for _ in chunks]
+    first = [np.full(n, -1, np.int64) for _, n in chunks]
+    used = [0] * len(chunks)
+    for u in range(len(fo) - 1):
+        f0, f1 = fo[u], fo[u + 1]
+        for c in range(f0 // cap, (f1 - 1) // cap + 1):
+            a, n = chunks[c]
+            lo, hi = max(f0, a), min(f1, a + n)
+            src[c].append(f0 + np.clip(np.arange(lo - f0 - half, hi - f0 + half, dtype=np.int64), 0, f1 - f0 - 1))
+            first[c][lo - a:hi - a] = used[c] + np.arange(hi - lo)
+            used[c] += hi - lo + ctx - 1
+    return [(np.concatenate(s), f) for s, f in zip(src, first)]
+
+
+def waves_ola_model(frame_off, fs_khz):
+    """(utt, lo, hi) [n_out]: the utterance of every packed output sample and the first and last packed frame whose
+    block covers it; frame t of an F-frame utterance covers its samples [t S, t S + L)"""
+    L, S, _ = params(fs_khz)
+    utt, los, his = [], [], []
+    for u in range(len(frame_off) - 1):
+        f0, F = int(frame_off[u]), int(frame_off[u + 1] - frame_off[u])
+        n = F * S + L - S
+        lo, hi = np.full(n, F, np.int64), np.full(n, -1, np.int64)
+        for t in range(F):
+            lo[t * S:t * S + L] = np.minimum(lo[t * S:t * S + L], t)
+            hi[t * S:t * S + L] = t
+        utt.append(np.full(n, u, np.int64))
+        los.append(f0 + lo)
+        his.append(f0 + hi)
+    return np.concatenate(utt), np.concatenate(los), np.concatenate(his)
+
+
+def _waves_search(table, x, lo0, hi0, slip, key=None):
+    """the kernels' search, every lane at once: the largest m in [lo0, hi0] with key(m) <= x (key(m) = table[m] when
+    not given).  A lane that has not ended after 64 rounds never would: -1."""
+    lo, hi = np.full(x.shape, lo0, np.int64), np.full(x.shape, hi0, np.int64)
+    for _ in range(64):
+        act = lo < hi
+        if not act.any():
+            return lo
+        mid = (lo + hi + (0 if slip == "search_bias" else 1)) >> 1
+        k = table[mid] if key is None else key(mid)
+        ok = (k < x) if slip == "lt_for_le" else (k <= x)
+        lo, hi = np.where(act & ok, mid, lo), np.where(act & ~ok, mid - 1, hi)
+    return np.where(lo < hi, -1, lo)
+
+
+def waves_table(frame_off, slip=None):
+    """the per-frame table of MLGGD_WAVES_LOOKUP=table"""
+    n_utts = len(frame_off) - 1
+    t = np.zeros(int(frame_off[-1]), np.int64)
+    for u in range(n_utts):
+        shift = 1 if slip == "table_plus_1" and u > 0 else 0
+        t[frame_off[u] - shift:frame_off[u + 1]] = u
+    return t
+
+
+def _waves_seg_of_frame(frame_off, g, table, slip):
+    if table is not None:
+        return table[g]
+    return _waves_search(frame_off, g, 0, len(frame_off) - 2, slip)
+
+
+def _waves_other(u, n_utts):
+    """the utterance the slip fu_wrong_utterance reads F_u from"""
+    return np.where(u + 1 < n_utts, u + 1, np.maximum(u - 1, 0))
+
+
+def waves_analysis_kernel(offsets, frame_off, fs_khz, lookup="search", slip=None):
+    S = params(fs_khz)[1]
+    offsets, frame_off = np.asarray(offsets, np.int64), np.asarray(frame_off, np.int64)
+    table = waves_table(frame_off, slip) if lookup == "table" else None
+    g = np.arange(int(frame_off[-1]), dtype=np.int64)
+    u = _waves_seg_of_frame(frame_off, g, table, slip)
+    wave_off = offsets - (0 if slip == "wave_off_not_rebased" else offsets[0])
+    start = offsets[0] + wave_off[u] + (g - frame_off[u]) * S        # the uploaded buffer starts at offsets[0]
+    return np.where(u < 0, -1, start)
+
+
+def waves_stream_kernel(frame_off, ctx, cap, lookup="search", slip=None):
+    """per chunk (src [rows], first [n]) as the engine's chunk loop and k_lps_stream_seg form them"""
+    fo = np.asarray(frame_off, np.int64)
+    n_utts, half = len(fo) - 1, (ctx - 1) // 2
+    table = waves_table(fo, slip) if lookup == "table" else None
+    c1 = ctx if slip == "ctx_for_ctx_minus_1" else ctx - 1
+    out, u0 = [], 0
+    for a, n in waves_chunks(fo, cap):
+        while fo[u0 + 1] <= a:
+            u0 += 1
+        u1 = u0
+        while fo[u1 + 1] < a + n:
+            u1 += 1
+        rows = n + (u1 - u0 + 1) * (ctx - 1)
+        seg = _waves_seg_of_frame(fo, a + np.arange(n, dtype=np.int64), table, slip)
+        first = np.where(seg < 0, -1, np.arange(n) + (seg - u0) * (ctx - 1))
+        r = np.arange(rows, dtype=np.int64)
+        clamp = (lambda f: f) if slip == "ga_not_clamped" else (lambda f: np.maximum(f, a))
+        u = _waves_search(None, r, u0, u1, slip, key=lambda m: clamp(fo[m]) - a + (m - u0) * c1)
+        uu = np.maximum(u, 0)
+        f0 = fo[uu]
+        w = _waves_other(uu, n_utts) if slip == "fu_wrong_utterance" else uu
+        Fu = fo[w + 1] - fo[w]
+        ga = np.maximum(f0, a)
+        t = (ga - f0) - half + (r - (clamp(f0) - a + (uu - u0) * c1))
+        t = np.where(t < 0, 0, np.where(t >= Fu, Fu - 1, t))
+        out.append((np.where(u < 0, -1, f0 + t), first))
+    return out
+
+
+def waves_ola_kernel(frame_off, fs_khz, slip=None):
+    """(utt, lo, hi) [n_out] as k_ola_seg forms them"""
+    L, S, _ = params(fs_khz)
+    fo = np.asarray(frame_off, np.int64)
+    n_utts = len(fo) - 1
+    out_off = np.concatenate([np.zeros(1, np.int64), np.cumsum(np.diff(fo) * S + L - S)])
+    gi = np.arange(int(out_off[-1]), dtype=np.int64)
+    u = _waves_search(out_off, gi, 0, n_utts - 1, slip)
+    uu = np.maximum(u, 0)
+    w = _waves_other(uu, n_utts) if slip == "fu_wrong_utterance" else uu
+    f0, F = fo[uu], fo[w + 1] - fo[w]
+    i = gi - out_off[uu]
+    lo = i - L + 1
+    lo = np.where(lo <= 0, 0, (lo + S - 1) // S)
+    hi = i // S
+    if slip != "hi_not_clamped":
+        hi = np.where(hi > F - 1, F - 1, hi)
+    bad = u < 0
+    return np.where(bad, -1, uu), np.where(bad, -1, f0 + lo), np.where(bad, -1, f0 + hi)
+
+
+def waves_index_model(frames_per_utt, fs_khz, ctx, cap, base=0):
+    """every mapped index of one configuration, built per utterance: a flat list of arrays"""
+    offsets, frame_off, _ = waves_layout64(frames_per_utt, fs_khz, base)
+    res = [waves_analysis_model(offsets, frame_off, fs_khz)]
+    for src, first in waves_stream_model(frame_off, ctx, cap):
+        res += [src, first]
+    return res + list(waves_ola_model(frame_off, fs_khz))
+
+
+def waves_index_kernel(frames_per_utt, fs_khz, ctx, cap, base=0, lookup="search", slip=None):
+    """the same list the kernels' way, with one planted slip"""
+    offsets, frame_off, _ = waves_layout64(frames_per_utt, fs_khz, base)
+    res = [waves_analysis_kernel(offsets, frame_off, fs_khz, lookup, slip)]
+    for src, first in waves_stream_kernel(frame_off, ctx, cap, lookup, slip):
+        res += [src, first]
+    return res + list(waves_ola_kernel(frame_off, fs_khz, slip))
+
+
+def waves_same_index(a, b):
+    return len(a) == len(b) and all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def waves_rows_per_chunk(frame_off, ctx, cap):
+    """[(n, rows, utterances touched)] of every chunk, from the per-utterance model"""
+    fo = np.asarray(frame_off, np.int64)
+    res = []
+    for (a, n), (src, _) in zip(waves_chunks(fo, cap), waves_stream_model(fo, ctx, cap)):
+        touched = int(np.count_nonzero((fo[:-1] < a + n) & (fo[1:] > a)))
+        res.append((n, len(src), touched))
+    return res
+
+
+def waves_many_frames(n_utts, seed, n_long=6):
+    """frame counts of the many-utterance batches: 1 to 4 frames (short ones the likelier), and n_long utterances of
+    200 to 400 frames spread through the batch, never first or last"""
+    rng = np.random.default_rng(seed)
+    f = rng.choice([1, 2, 3, 4], n_utts, p=[0.4, 0.3, 0.2, 0.1])
+    at = np.linspace(n_utts // 9, n_utts - n_utts // 7, n_long).astype(int)
+    f[at] = rng.integers(200, 401, n_long)
+    return [int(x) for x in f], [int(x) for x in at]
+
+
+# The batches of tests/test_gpu_enhance_waves.py: name -> fs_khz, ctx, frames per utterance, chunk capacities (0 = the
+# default), lookups, wave bases, the test that runs it and the planted slips its inputs are claimed to discriminate
+# (tests/test_enhance_waves_model.py holds each claim to the models above).
+def waves_gpu_configs():
+    many_odd, _ = waves_many_frames(2187, 1)
+    many_even, _ = waves_many_frames(2048, 2)
+    cap1 = ["search_bias", "lt_for_le", "fu_wrong_utterance", "hi_not_clamped", "table_plus_1"]   # one utterance a chunk
+    every_search = ["search_bias", "lt_for_le", "ctx_for_ctx_minus_1", "fu_wrong_utterance", "hi_not_clamped"]
+    return {
+        "table_mixed": dict(fs=16, ctx=7, frames=[1, 2, 3, 5, 17, 300], caps=[0], lookups=["table"], bases=[0],
+                            test="test_table_lookup_equals_the_search_and_the_single_call",
+                            slips=["table_plus_1", "ctx_for_ctx_minus_1", "fu_wrong_utterance", "hi_not_clamped"]),
+        "table_chunks": dict(fs=16, ctx=7, frames=[10, 20, 5, 30, 1, 14], caps=[1, 7, 33, 1000], lookups=["table"],
+                             bases=[0], test="test_table_lookup_equals_the_search_and_the_single_call",
+                             slips=["table_plus_1", "ga_not_clamped", "ctx_for_ctx_minus_1", "fu_wrong_utterance",
+                                    "hi_not_clamped"]),
+        "many_odd": dict(fs=8, ctx=11, frames=many_odd, caps=[0, 257, 1000], lookups=["search", "table"], bases=[0],
+                         test="test_thousands_of_utterances", slips=every_search + ["ga_not_clamped", "table_plus_1"]),
+        "many_even": dict(fs=8, ctx=11, frames=many_even, caps=[0, 257, 1000], lookups=["search", "table"], bases=[0],
+                          test="test_thousands_of_utterances", slips=every_search + ["ga_not_clamped", "table_plus_1"]),
+        "many_odd_cap1": dict(fs=8, ctx=11, frames=many_odd[:301], caps=[1], lookups=["search", "table"], bases=[0],
+                              test="test_thousands_of_utterances", slips=cap1),
+        "many_even_cap1": dict(fs=8, ctx=11, frames=many_even[:300], caps=[1], lookups=["search", "table"], bases=[0],
+                               test="test_thousands_of_utterances", slips=cap1),
+        "wave_base": dict(fs=16, ctx=7, frames=[3, 1, 9, 2, 40], caps=[0], lookups=["search"], bases=[1, 1000, 12345],
+                          test="test_a_wave_base_other_than_zero", slips=["wave_off_not_rebased"]),
+        "degenerate": dict(fs=16, ctx=7, frames=[12, 9, 20, 1, 15, 30, 8], caps=[0, 16], lookups=["search"],
+                           bases=[0], test="test_degenerate_utterances_as_subjects",
+                           slips=["hi_not_clamped", "fu_wrong_utterance", "ga_not_clamped"]),
+    }
