@@ -161,6 +161,9 @@ int mlggd_enhance_waves(mlggd_handle h, int fs_khz, int fea_context, const float
 
 /* ---- state: BP_GPU::returnWeights (BP_GPU.cu:514-525) and dev.scalefactor (:287) ---- */
 int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias);
+/* mlggd_set_weights replaces W and b of every layer and leaves the momentum buffers as they are; it is ordered after
+ * every step already enqueued (mlggd_train_frames_async included) and returns when the upload has completed.  A NULL
+ * layer pointer is MLGGD_ERR_ARG and changes no layer. */
 int mlggd_set_weights(mlggd_handle h, const float *const *weights, const float *const *bias);
 int mlggd_get_scalefactor(mlggd_handle h, float *alpha /* [D] */);
 int mlggd_set_scalefactor(mlggd_handle h, const float *alpha /* [D] */);
@@ -204,7 +207,7 @@ int mlggd_last_train_ms(mlggd_handle h, float *ms, int *steps);
 /* Kernel-class timing INSIDE a timed mlggd_train_resident region (bench.py's roofline
  * object): mlggd_profile_select times every launch of the named class ("transpose" "fwd"
  * "loss" "dx" "dw" "update"; layer 0 = all layers) with a pair of HIP events, up to
- * max_launches; NULL/"" switches it off.  The GEMM classes ("fwd" "dx" "dw") take the pair INTO
+ * max_launches of this call (a later call with a smaller number lowers the limit); NULL/"" switches it off.  The GEMM classes ("fwd" "dx" "dw") take the pair INTO
  * the launch (hipExtLaunchKernelGGL start/stop events = the dispatch's own begin/end timestamps,
  * what rocprofv3 --kernel-trace reports); the other classes are bracketed by events recorded on
  * the stream before and after, which adds the bracket's cost.  mlggd_profile_read syncs and returns
@@ -264,7 +267,10 @@ int mlggd_debug_math(mlggd_handle h, const char *fn, const float *x, float y, fl
 /* Diagnostic (not part of the reference surface): in-kernel phase stamps of the NEXT launch of
  * (class "fwd"|"dx"|"dw", layer): 8 int64 slots per workgroup in 100 MHz ticks
  * (s_memrealtime); slot meaning per kernel is documented at stamp() call sites in
- * csrc/kernels.hip.h.  The stamps go to a debug buffer only. */
+ * csrc/kernels.hip.h.  The stamps go to a debug buffer only.  The selection is consumed by the first launch that
+ * takes it; mlggd_debug_stamp_read then returns one row per workgroup of that launch.  Launches that carry no stamps
+ * (the output layer's forward GEMM, the 64 x 64-tile kernels k_fwd64 / k_dx64) and launches of more workgroups than the
+ * buffer has rows (8192) leave it at 0 rows.  ("dw", -1): the phase twin of the merged update kernel, 2 x grid rows. */
 int mlggd_debug_stamp_select(mlggd_handle h, const char *kernel_class, int layer);
 int mlggd_debug_stamp_read(mlggd_handle h, long long *out /* [cap_blocks][8] */, int cap_blocks, int *blocks);
 

@@ -293,7 +293,7 @@ struct mlggd_engine {
     // per-kernel-class profiling
     int prof_class = -1, prof_layer = 0, prof_stride = 1;
     std::vector<hipEvent_t> prof_ev;
-    size_t prof_used = 0;
+    size_t prof_used = 0, prof_cap = 0;  // prof_cap = 2 * max_launches of the last select (the pool itself only grows)
     hipEvent_t *prof_attach = nullptr;  // event pair waiting to be attached to the next dW launch
     bool prof_attached = false;
     // Data parallel: an event the communication stream is going to wait for can ride on the producing kernel's own
@@ -363,7 +363,7 @@ struct ProfScope {
     ProfScope(mlggd_engine *eng, int cls, int layer, hipStream_t s = nullptr)
         : e(eng), st(s ? s : eng->stream), on(false), attach(cls == KC_DW || cls == KC_FWD || cls == KC_DX) {
         if (e->prof_class == cls && (e->prof_layer == 0 || e->prof_layer == layer) &&
-            e->step_counter % (unsigned)e->prof_stride == 0 && e->prof_used + 2 <= e->prof_ev.size()) {
+            e->step_counter % (unsigned)e->prof_stride == 0 && e->prof_used + 2 <= e->prof_cap) {
             on = true;
             if (attach) {
                 e->prof_attach = &e->prof_ev[e->prof_used];  // consumed by the launch itself
@@ -1196,7 +1196,6 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
 static int run_dx(mlggd_engine *e, int l) {
     const int Kp = e->lsp[l - 1], b_tiles = e->Bp / 32;
     ProfScope ps(e, KC_DX, l);
-    long long *st = stamps_for(e, KC_DX, l, (Kp / 32) * b_tiles);
     DxArgs xa = dx_args(e, l);
     if (dx64_used(e, l)) {
         xa.k_tiles = Kp / 64;
@@ -1207,6 +1206,7 @@ static int run_dx(mlggd_engine *e, int l) {
         launch_timed(e, k_dx64, dim3(xa.k_tiles * xa.b_tiles), dim3(256), lds, e->stream, xa);
         return launch_check("k_dx64");
     }
+    long long *st = stamps_for(e, KC_DX, l, (Kp / 32) * b_tiles);  // k_dx64 carries no stamps: it leaves the selection alone
 #define LAUNCH_DX(NW, PIPE)                                                                                  \
     {                                                                                                        \
         const size_t lds = dx_lds_floats<NW, PIPE>() * sizeof(float);                                        \
@@ -1780,9 +1780,10 @@ int mlggd_destroy(mlggd_handle e) {
 int mlggd_set_weights(mlggd_handle e, const float *const *weights, const float *const *bias) {
     if (!e || !weights || !bias) return fail(MLGGD_ERR_ARG, "NULL argument");
     HIPCHK(hipSetDevice(e->device));
+    for (int l = 1; l < e->L; l++)  // before the first upload: a rejected call leaves every layer as it was
+        if (!weights[l] || !bias[l]) return fail(MLGGD_ERR_ARG, "weights[%d] or bias[%d] is NULL", l, l);
     CHK(wait_weight_gathers(e, 1, e->L - 1));
     for (int l = 1; l < e->L; l++) {
-        if (!weights[l] || !bias[l]) return fail(MLGGD_ERR_ARG, "weights[%d] or bias[%d] is NULL", l, l);
         CHK(upload_padded(e->W[l], e->lsp[l], weights[l], e->ls[l - 1], e->ls[l], e->stream));  // BP_GPU.cu:106
         HIPCHK(hipMemcpyAsync(e->bias[l], bias[l], (size_t)e->ls[l] * 4, hipMemcpyHostToDevice, e->stream));  // :107
     }
@@ -2621,11 +2622,13 @@ int mlggd_profile_select(mlggd_handle e, const char *kernel_class, int layer, in
     if (e->prof_class < 0) return fail(MLGGD_ERR_ARG, "unknown kernel class '%s'", kernel_class);
     e->prof_layer = layer;
     if (max_launches < 1) max_launches = 1;
+    e->prof_cap = 0;  // until the pool holds that many pairs
     while (e->prof_ev.size() < (size_t)2 * max_launches) {
         hipEvent_t ev;
         HIPCHK(hipEventCreate(&ev));
         e->prof_ev.push_back(ev);
     }
+    e->prof_cap = (size_t)2 * max_launches;
     return MLGGD_OK;
 }
 
