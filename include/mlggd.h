@@ -159,6 +159,29 @@ int mlggd_enhance_waves(mlggd_handle h, int fs_khz, int fea_context, const float
                         int n_utts, const int16_t *noisy, const int64_t *offsets /* [n_utts+1] */, int16_t *out,
                         float *out_f32 /* optional */, float *lps_out /* optional */);
 
+/* ---- the quality report of LPS2Wav_be on the device (csrc/score.hip.h): per utterance, the segmental SNR (frame
+ * values 10 log10(sum clean^2 / sum (est - clean)^2) clamped to [-20, 30], est = the de-windowed enhanced frame) and
+ * the log-spectral distortion (clean and enhanced power floored at 1e-5 of their maxima over the utterance's scored
+ * frames) of enhanced LPS rows against the clean wave, in fp32.  `clean` is packed with the same `offsets` as `noisy`.
+ * score_frames[u] (NULL: F_u) = the leading frames of utterance u that are scored, 0 <= score_frames[u] <= F_u; 0:
+ * the utterance is not scored and both outputs are 0.  A clean wave shorter than its noisy wave is scored over the
+ * frames it has: the caller pads its samples with zeros and passes that frame count.  An utterance's two numbers
+ * depend on that utterance alone: the same bits whatever its neighbours, its position, the batch, max_cache_frames
+ * and the run.  NULL pointers, decreasing offsets, an utterance shorter than one frame, a score_frames[u] out of range
+ * and a bad fs_khz are MLGGD_ERR_ARG (the message names the utterance), found before any device call.
+ * mlggd_score_waves: stateless, any device; lps [sum F][D], the rows of utterance u from frame_off[u].
+ * mlggd_enhance_waves_scored: mlggd_enhance_waves plus the report on its de-normalised network output, from the
+ * buffers of the same pass on the engine's stream (no second analysis, no second forward pass): the packed clean wave
+ * goes up once and 2 n_utts floats come back.  out / out_f32 / lps_out are those of mlggd_enhance_waves bit for bit;
+ * the buffers only grow, as there. */
+int mlggd_score_waves(int device, int fs_khz, int n_utts, const int16_t *clean, const int16_t *noisy,
+                      const int64_t *offsets /* [n_utts+1] */, const float *lps, const int32_t *score_frames /* optional */,
+                      float *segsnr /* [n_utts] */, float *lsd /* [n_utts] */);
+int mlggd_enhance_waves_scored(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean,
+                               const float *norm_inv_std, int n_utts, const int16_t *noisy, const int16_t *clean,
+                               const int64_t *offsets, const int32_t *score_frames /* optional */, int16_t *out,
+                               float *out_f32 /* optional */, float *lps_out /* optional */, float *segsnr, float *lsd);
+
 /* ---- state: BP_GPU::returnWeights (BP_GPU.cu:514-525) and dev.scalefactor (:287) ---- */
 int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias);
 /* mlggd_set_weights replaces W and b of every layer and leaves the momentum buffers as they are; it is ordered after

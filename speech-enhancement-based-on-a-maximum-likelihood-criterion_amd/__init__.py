@@ -52,6 +52,7 @@ EXPORTS = [
     "mlggd_debug_keep_ranks", "mlggd_debug_rank_tensor",
     "mlggd_wave_to_lps", "mlggd_lps_to_wave", "mlggd_enhance_wave",
     "mlggd_enhance_waves_layout", "mlggd_enhance_waves",
+    "mlggd_score_waves", "mlggd_enhance_waves_scored",
 ]
 
 _lib = None
@@ -59,7 +60,7 @@ _lib = None
 
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -135,6 +136,9 @@ def load():
     _lp = C.POINTER(C.c_int64)
     L.mlggd_enhance_waves_layout.argtypes = [C.c_int, C.c_int, _lp, C.POINTER(C.c_int32), _lp]
     L.mlggd_enhance_waves.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _lp, _sp, _fp, _fp]
+    L.mlggd_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, _sp, _sp, _lp, _fp, _ip, _fp, _fp]
+    L.mlggd_enhance_waves_scored.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _sp, _lp, _ip, _sp,
+                                             _fp, _fp, _fp, _fp]
     _lib = L
     return L
 
@@ -235,6 +239,55 @@ def enhance_waves_layout(lengths, fs_khz=16):
                                              frame_off.ctypes.data_as(C.POINTER(C.c_int32)),
                                              out_off.ctypes.data_as(_lp)))
     return np.diff(frame_off), frame_off, out_off
+
+
+def _score_frames(score_frames, n):
+    if score_frames is None:
+        return None
+    sf = np.ascontiguousarray(score_frames, dtype=np.int32)
+    if sf.shape != (n,):
+        raise ValueError("score_frames must hold one count per utterance")
+    return sf
+
+
+def _clean_like(cleans, noisys):
+    """the clean waves packed with the noisy waves' offsets: each one cut or zero-padded to its noisy wave's length"""
+    if len(cleans) != len(noisys):
+        raise ValueError("one clean wave per noisy wave")
+    packed = np.zeros(sum(w.size for w in noisys), np.int16)
+    at = 0
+    for c, w in zip(cleans, noisys):
+        c = _wave(c)
+        m = min(c.size, w.size)
+        packed[at:at + m] = c[:m]
+        at += w.size
+    return packed
+
+
+def score_waves(cleans, noisys, lps_list, fs_khz=16, device=0, score_frames=None):
+    """(segsnr [n], lsd [n]) float32: the quality report of the original project's LPS2Wav_be for a list of utterances
+    in one pass over the device (mlggd_score_waves) -- enhanced LPS rows lps_list[u] [F_u][N/2+1] of the noisy wave
+    noisys[u] against the clean wave cleans[u].  score_frames[u] (None: all F_u) = the leading frames that are scored;
+    0: the utterance is not scored and both numbers are 0.  A clean wave shorter than its noisy wave is zero-padded:
+    pass its own frame count in score_frames."""
+    noisys = [_wave(w) for w in noisys]
+    n = len(noisys)
+    _, frame_off, _ = enhance_waves_layout([w.size for w in noisys], fs_khz)
+    D = SPECTRAL_PARAMS[int(fs_khz)][2] // 2 + 1
+    if len(lps_list) != n:
+        raise ValueError("one LPS matrix per noisy wave")
+    rows = [_f32(l, (int(frame_off[u + 1] - frame_off[u]), D)) for u, l in enumerate(lps_list)]
+    lps = np.concatenate(rows) if n else np.zeros((0, D), np.float32)
+    clean = _clean_like(cleans, noisys)
+    packed = np.concatenate(noisys) if n else np.zeros(0, np.int16)
+    off = _offsets([w.size for w in noisys])
+    sf = _score_frames(score_frames, n)
+    segsnr, lsd = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    _check(load().mlggd_score_waves(int(device), int(fs_khz), n, _sp(clean), _sp(packed),
+                                    off.ctypes.data_as(C.POINTER(C.c_int64)), _p(lps),
+                                    sf.ctypes.data_as(C.POINTER(C.c_int32)) if sf is not None else None,
+                                    _p(segsnr), _p(lsd)))
+    return segsnr, lsd
 
 
 def comm_unique_id():
@@ -381,11 +434,15 @@ class BPGpu:
                                          _sp(noisy), _sp(out), _p(outf) if return_float else None, C.byref(n)))
         return (out, outf) if return_float else out
 
-    def enhance_waves(self, waves, mean, inv_std, fs_khz=16, fea_context=None, return_f32=False, return_lps=False):
+    def enhance_waves(self, waves, mean, inv_std, fs_khz=16, fea_context=None, return_f32=False, return_lps=False,
+                      cleans=None, score_frames=None):
         """enhance_wave over a list of int16 waves in one pass over the device (mlggd_enhance_waves): a list of int16
         arrays, each bit-equal to enhance_wave on that wave alone; with return_f32 / return_lps a tuple of lists, the
         float32 waves before the cast and the de-normalised network outputs [F_u][D] added in that order.
-        fea_context None: layersizes[0] / bins."""
+        fea_context None: layersizes[0] / bins.  With cleans (one clean wave per utterance, cut or zero-padded to the
+        noisy wave's length) the quality report of the same pass (mlggd_enhance_waves_scored) is added at the end of
+        the tuple: segsnr [n] and lsd [n] float32, over the leading score_frames[u] frames of each utterance (None:
+        all; 0: not scored, both 0)."""
         waves = [_wave(w) for w in waves]
         L, S, N = SPECTRAL_PARAMS[int(fs_khz)]
         D = N // 2 + 1
@@ -400,14 +457,26 @@ class BPGpu:
         out = np.empty(int(out_off[-1]), np.int16)
         outf = np.empty(out.size, np.float32) if return_f32 else None
         lps = np.empty((int(frame_off[-1]), D), np.float32) if return_lps else None
-        _check(load().mlggd_enhance_waves(self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), n, _sp(packed),
-                                          off.ctypes.data_as(C.POINTER(C.c_int64)), _sp(out),
-                                          _p(outf) if return_f32 else None, _p(lps) if return_lps else None))
+        if cleans is None:
+            _check(load().mlggd_enhance_waves(self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), n, _sp(packed),
+                                              off.ctypes.data_as(C.POINTER(C.c_int64)), _sp(out),
+                                              _p(outf) if return_f32 else None, _p(lps) if return_lps else None))
+        else:
+            clean = _clean_like(cleans, waves)
+            sf = _score_frames(score_frames, n)
+            segsnr, lsd = np.zeros(n, np.float32), np.zeros(n, np.float32)
+            _check(load().mlggd_enhance_waves_scored(
+                self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), n, _sp(packed), _sp(clean),
+                off.ctypes.data_as(C.POINTER(C.c_int64)),
+                sf.ctypes.data_as(C.POINTER(C.c_int32)) if sf is not None else None, _sp(out),
+                _p(outf) if return_f32 else None, _p(lps) if return_lps else None, _p(segsnr), _p(lsd)))
         res = [[out[out_off[u]:out_off[u + 1]] for u in range(n)]]
         if return_f32:
             res.append([outf[out_off[u]:out_off[u + 1]] for u in range(n)])
         if return_lps:
             res.append([lps[frame_off[u]:frame_off[u + 1]] for u in range(n)])
+        if cleans is not None:
+            res += [segsnr, lsd]
         return res[0] if len(res) == 1 else tuple(res)
 
     def last_train_ms(self):

@@ -22,6 +22,7 @@
 #include "../../include/mlggd.h"
 #include "kernels.hip.h"
 #include "spectral.hip.h"
+#include "score.hip.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -221,9 +222,11 @@ struct mlggd_engine {
     };
     struct WavesWs {
         WsBuf wave, lps, X, blk, out_i, out_f, lps_den, norm, frame_off, out_off, wave_off, utt_of;
+        WsBuf clean, Xc, fstat, sframes, scores;  // mlggd_enhance_waves_scored (score.hip.h)
         std::vector<int32_t> h_frame_off, h_utt_of;
         std::vector<long long> h_out_off, h_wave_off;
         std::vector<float> h_norm;  // [2 D]: mean, inv_std as uploaded last
+        std::vector<float> h_scores;  // [2 n_utts]: segsnr, lsd as downloaded
         int lookup_table = 0;       // utterance of a frame: 0 = binary search over frame_off (default), 1 = per-frame
                                     // table (MLGGD_WAVES_LOOKUP=table, for A/B runs)
     } ww;
@@ -1749,7 +1752,7 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
     for (mlggd_engine::WsBuf *b : {&e->ww.wave, &e->ww.lps, &e->ww.X, &e->ww.blk, &e->ww.out_i, &e->ww.out_f,
                                    &e->ww.lps_den, &e->ww.norm, &e->ww.frame_off, &e->ww.out_off, &e->ww.wave_off,
-                                   &e->ww.utt_of})
+                                   &e->ww.utt_of, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores})
         if (b->p) hipFree(b->p);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
     for (int l = 0; l < MLGGD_MAXLAYER; l++) {
@@ -3009,6 +3012,34 @@ int ws_grow(mlggd_engine *e, mlggd_engine::WsBuf &b, size_t count, T **out) {
     return MLGGD_OK;
 }
 
+// score_frames[u] (NULL: every frame) against the frames of the layout
+int check_score_frames(int n_utts, const int32_t *frame_off, const int32_t *score_frames) {
+    if (!score_frames) return MLGGD_OK;
+    for (int u = 0; u < n_utts; u++) {
+        const int Fu = frame_off[u + 1] - frame_off[u];
+        if (score_frames[u] < 0 || score_frames[u] > Fu)
+            return fail(MLGGD_ERR_ARG, "utterance %d: score_frames %d is outside 0..%d, its frames", u,
+                        (int)score_frames[u], Fu);
+    }
+    return MLGGD_OK;
+}
+
+// the quality report (score.hip.h) of FT packed frames: clean wave, LPS rows and noisy spectrum X on the device ->
+// scores [2 n_utts] = segsnr, lsd.  Xc [FT][D] and fstat [3 FT] are scratch; sframes / utt_of may be NULL.
+int launch_score(const SpecPlan *p, const int16_t *clean, const long long *wave_off, const int *frame_off,
+                 const int *utt_of, const int *sframes, int n_utts, int FT, const float *lps, const float2 *X,
+                 float2 *Xc, float *fstat, float *scores, hipStream_t st) {
+    float *snr = fstat, *maxc = fstat + FT, *maxd = fstat + (size_t)2 * FT;
+    hipLaunchKernelGGL(k_score_frames, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, clean, wave_off, frame_off,
+                       utt_of, sframes, n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0), (float)exp(-50.0),
+                       lps, X, Xc, snr, maxc, maxd);
+    CHK(launch_check("k_score_frames"));
+    hipLaunchKernelGGL(k_score_utt, dim3((unsigned)n_utts), dim3(64 * SCORE_UTT_WAVES), 0, st, frame_off, sframes,
+                       p->d.D, (float)exp(-50.0), lps, (const float2 *)Xc, (const float *)snr, (const float *)maxc,
+                       (const float *)maxd, scores, scores + n_utts);
+    return launch_check("k_score_utt");
+}
+
 }  // namespace
 
 extern "C" {
@@ -3122,9 +3153,12 @@ int mlggd_enhance_waves_layout(int fs_khz, int n_utts, const int64_t *offsets, i
     return waves_layout(d, n_utts, offsets, frame_off, out_off);
 }
 
-int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
-                        int n_utts, const int16_t *noisy, const int64_t *offsets, int16_t *out, float *out_f32,
-                        float *lps_out) {
+// mlggd_enhance_waves, and with clean != NULL mlggd_enhance_waves_scored (`who` names the entry point): the report is
+// formed after the last chunk from the buffers of the pass (X, the de-normalised rows) and changes none of them
+static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fea_context, const float *norm_mean,
+                             const float *norm_inv_std, int n_utts, const int16_t *noisy, const int16_t *clean,
+                             const int64_t *offsets, const int32_t *score_frames, int16_t *out, float *out_f32,
+                             float *lps_out, float *segsnr, float *lsd) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     SpecDims d;
     int slot;
@@ -3134,7 +3168,7 @@ int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float
         return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
     if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
     if (e->world > 1 || e->fake_world)
-        return fail(MLGGD_ERR_STATE, "mlggd_enhance_waves runs on a single-device engine");
+        return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (n_utts == 0) return MLGGD_OK;
     if (!noisy || !offsets || !norm_mean || !norm_inv_std || !out)
@@ -3151,6 +3185,7 @@ int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float
             w.h_wave_off[u] = (long long)offsets[u] - (long long)offsets[0];
         }
     }
+    if (clean) CHK(check_score_frames(n_utts, w.h_frame_off.data(), score_frames));
     const int FT = w.h_frame_off[n_utts];  // every utterance has a frame: FT >= n_utts
     const size_t n_wave = (size_t)w.h_wave_off[n_utts], n_out = (size_t)w.h_out_off[n_utts];
     const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
@@ -3172,7 +3207,18 @@ int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float
     CHK(ws_grow(e, w.blk, (size_t)FT * d.L, &blk));
     CHK(ws_grow(e, w.out_i, n_out, &oi));
     if (out_f32) CHK(ws_grow(e, w.out_f, n_out, &of));
-    if (lps_out) CHK(ws_grow(e, w.lps_den, (size_t)FT * d.D, &den));
+    if (lps_out || clean) CHK(ws_grow(e, w.lps_den, (size_t)FT * d.D, &den));
+    int16_t *d_clean = nullptr;
+    float2 *Xc = nullptr;
+    float *fstat = nullptr, *scores = nullptr;
+    int *d_sf = nullptr;
+    if (clean) {
+        CHK(ws_grow(e, w.clean, n_wave, &d_clean));
+        CHK(ws_grow(e, w.Xc, (size_t)FT * d.D, &Xc));
+        CHK(ws_grow(e, w.fstat, (size_t)3 * FT, &fstat));
+        CHK(ws_grow(e, w.scores, (size_t)2 * n_utts, &scores));
+        if (score_frames) CHK(ws_grow(e, w.sframes, (size_t)n_utts, &d_sf));
+    }
     CHK(ws_grow(e, w.frame_off, (size_t)n_utts + 1, &d_foff));
     CHK(ws_grow(e, w.out_off, (size_t)n_utts + 1, &d_ooff));
     CHK(ws_grow(e, w.wave_off, (size_t)n_utts + 1, &d_woff));
@@ -3228,7 +3274,90 @@ int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float
     HIPCHK(hipMemcpyAsync(out, oi, n_out * sizeof(int16_t), hipMemcpyDeviceToHost, st));
     if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, of, n_out * sizeof(float), hipMemcpyDeviceToHost, st));
     if (lps_out) HIPCHK(hipMemcpyAsync(lps_out, den, (size_t)FT * d.D * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (clean) {  // the clean wave goes up once; 2 n_utts floats come back
+        HIPCHK(hipMemcpyAsync(d_clean, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice, st));
+        if (score_frames)
+            HIPCHK(hipMemcpyAsync(d_sf, score_frames, (size_t)n_utts * sizeof(int), hipMemcpyHostToDevice, st));
+        CHK(launch_score(p, d_clean, d_woff, d_foff, d_utt, d_sf, n_utts, FT, den, X, Xc, fstat, scores, st));
+        w.h_scores.resize((size_t)2 * n_utts);
+        HIPCHK(hipMemcpyAsync(w.h_scores.data(), scores, (size_t)2 * n_utts * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
+    if (clean) {
+        memcpy(segsnr, w.h_scores.data(), (size_t)n_utts * sizeof(float));
+        memcpy(lsd, w.h_scores.data() + n_utts, (size_t)n_utts * sizeof(float));
+    }
+    return MLGGD_OK;
+}
+
+int mlggd_enhance_waves(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                        int n_utts, const int16_t *noisy, const int64_t *offsets, int16_t *out, float *out_f32,
+                        float *lps_out) {
+    return enhance_waves_run(e, "mlggd_enhance_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, noisy,
+                             nullptr, offsets, nullptr, out, out_f32, lps_out, nullptr, nullptr);
+}
+
+int mlggd_enhance_waves_scored(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean,
+                               const float *norm_inv_std, int n_utts, const int16_t *noisy, const int16_t *clean,
+                               const int64_t *offsets, const int32_t *score_frames, int16_t *out, float *out_f32,
+                               float *lps_out, float *segsnr, float *lsd) {
+    if (e && n_utts > 0 && (!clean || !segsnr || !lsd)) return fail(MLGGD_ERR_ARG, "clean/segsnr/lsd is NULL");
+    return enhance_waves_run(e, "mlggd_enhance_waves_scored", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts,
+                             noisy, clean, offsets, score_frames, out, out_f32, lps_out, segsnr, lsd);
+}
+
+int mlggd_score_waves(int device, int fs_khz, int n_utts, const int16_t *clean, const int16_t *noisy,
+                      const int64_t *offsets, const float *lps, const int32_t *score_frames, float *segsnr, float *lsd) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (n_utts == 0) return MLGGD_OK;
+    if (!clean || !noisy || !offsets || !lps || !segsnr || !lsd)
+        return fail(MLGGD_ERR_ARG, "clean/noisy/offsets/lps/segsnr/lsd is NULL");
+    std::vector<int32_t> frame_off((size_t)n_utts + 1);
+    std::vector<long long> wave_off((size_t)n_utts + 1);
+    CHK(waves_layout(d, n_utts, offsets, frame_off.data(), nullptr));
+    CHK(check_score_frames(n_utts, frame_off.data(), score_frames));
+    for (int u = 0; u <= n_utts; u++) wave_off[u] = (long long)offsets[u] - (long long)offsets[0];
+    const int FT = frame_off[n_utts];
+    const size_t n_wave = (size_t)wave_off[n_utts];
+    HIPCHK(hipSetDevice(device));
+    const SpecPlan *p;
+    CHK(spec_plan(device, fs_khz, &p));
+    DevBufs b;
+    int16_t *dn = nullptr, *dc = nullptr;
+    float *dl = nullptr, *fstat = nullptr, *scores = nullptr;
+    float2 *X = nullptr, *Xc = nullptr;
+    int *d_foff = nullptr, *d_sf = nullptr;
+    long long *d_woff = nullptr;
+    CHK(b.alloc(&dn, n_wave));
+    CHK(b.alloc(&dc, n_wave));
+    CHK(b.alloc(&dl, (size_t)FT * d.D));
+    CHK(b.alloc(&X, (size_t)FT * d.D));
+    CHK(b.alloc(&Xc, (size_t)FT * d.D));
+    CHK(b.alloc(&fstat, (size_t)3 * FT));
+    CHK(b.alloc(&scores, (size_t)2 * n_utts));
+    CHK(b.alloc(&d_foff, (size_t)n_utts + 1));
+    CHK(b.alloc(&d_woff, (size_t)n_utts + 1));
+    HIPCHK(hipMemcpy(dn, noisy + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dc, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dl, lps, (size_t)FT * d.D * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_foff, frame_off.data(), ((size_t)n_utts + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_woff, wave_off.data(), ((size_t)n_utts + 1) * sizeof(long long), hipMemcpyHostToDevice));
+    if (score_frames) {
+        CHK(b.alloc(&d_sf, (size_t)n_utts));
+        HIPCHK(hipMemcpy(d_sf, score_frames, (size_t)n_utts * sizeof(int), hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, nullptr, dn, d_woff, d_foff,
+                       (const int *)nullptr, n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0),
+                       (float *)nullptr, X);
+    CHK(launch_check("k_lps_analysis_seg"));
+    CHK(launch_score(p, dc, d_woff, d_foff, nullptr, d_sf, n_utts, FT, dl, X, Xc, fstat, scores, nullptr));
+    std::vector<float> h((size_t)2 * n_utts);
+    HIPCHK(hipMemcpy(h.data(), scores, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+    memcpy(segsnr, h.data(), (size_t)n_utts * sizeof(float));
+    memcpy(lsd, h.data() + n_utts, (size_t)n_utts * sizeof(float));
     return MLGGD_OK;
 }
 

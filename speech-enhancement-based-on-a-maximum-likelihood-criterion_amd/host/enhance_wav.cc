@@ -6,6 +6,7 @@
 //
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
+//               [score=host|device]
 //
 // scp lists "in out" or "in out clean info" lines.  A list is decoded in batches of batch_s seconds of audio by
 // mlggd_enhance_waves: the utterances of a batch form one frame stream, so the forward bunches are full, and the
@@ -14,6 +15,12 @@
 // way.  Device memory per 16 kHz frame (256 new samples): 512 B wave + 1028 B LPS + 2056 B spectrum + 2048 B time block
 // + 512 B output + 1028 B report rows, an eighth of headroom on each, and 5 x 1028 B of frame stream and network output
 // = about 13 KB; 62.5 frames per second make 0.8 MB per second of audio, 250 MB at the default batch_s=300.
+//
+// score=host (the default): the report is formed in double on the host, one utterance after the other.  score=device:
+// mlggd_enhance_waves_scored forms it in fp32 on the GPU from the buffers of the decoding pass (a single pair and
+// batch_s=0 lines as batches of one), over the frames the clean wave has; the clean waves are read before the pass, and
+// a list ends with one line: the number of scored utterances and their mean segmental SNR and LSD.  The enhanced waves
+// are the same bytes either way; it adds 512 B clean wave + 2056 B clean spectrum + 12 B per frame to the figures above.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -37,25 +44,38 @@ struct Item {
     Job job;
     std::vector<int16_t> noisy;
     int rate = 0, fs = 0, F = 0;
+    std::vector<int16_t> clean;  // score=device: the clean wave, and the frames it is scored over
+    int Fm = 0;
 };
 
-// LPS2Wav_be's report for one utterance from its enhanced LPS rows y [F][D]
-void report(const Item &it, const float *y) {
+// the clean wave of an utterance and the frames of min(clean, noisy); a wave that cannot be scored goes to `bad`
+template <typename Bad>
+std::vector<int16_t> read_clean(const Item &it, int *Fm, Bad bad) {
     int L, S, N;
     tool_io::spectral_params(it.fs, &L, &S, &N);
     int cr = 0;
-    const std::vector<int16_t> cw = tool_io::read_wav(it.job.clean, &cr);
-    if (cr != it.rate) die(it.job.clean + ": sample rate differs from " + it.job.in);
+    std::vector<int16_t> cw = tool_io::read_wav(it.job.clean, &cr);
+    if (cr != it.rate) bad(it.job.clean + ": sample rate differs from " + it.job.in);
     const int Fc = cw.size() < (size_t)L ? 0 : (int)((cw.size() - (L - S)) / S);
-    const int Fm = std::min(it.F, Fc);
-    if (Fm == 0) die(it.job.clean + ": shorter than one frame");
+    *Fm = std::min(it.F, Fc);
+    if (*Fm == 0) bad(it.job.clean + ": shorter than one frame");
+    return cw;
+}
+
+// LPS2Wav_be's report for one utterance from its enhanced LPS rows y [F][D]
+void report(const Item &it, const float *y) {
+    int Fm = 0;
+    const std::vector<int16_t> cw = read_clean(it, &Fm, die);
     double segsnr = 0.0, lsd = 0.0;
     tool_io::quality(it.fs, cw, it.noisy, y, Fm, &segsnr, &lsd);
     tool_io::write_info(it.job.info, segsnr, lsd);
 }
 
 int main(int argc, char **argv) {
-    std::string wts, norm_file, in, out, scp, clean, info;
+    std::string wts, norm_file, in, out, scp, clean, info, score = "host";
+    const char *usage =
+        "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
+        "[batch_s=300] [clean=F info=F] [score=host|device]";
     int ctx = 7, gpu = 0, bunch = 512;
     double batch_s = 300.0;
     for (int a = 1; a < argc; a++) {
@@ -74,11 +94,13 @@ int main(int argc, char **argv) {
         else if (k == "gpu_used") gpu = atoi(v.c_str());
         else if (k == "bunchsize") bunch = atoi(v.c_str());
         else if (k == "batch_s") batch_s = atof(v.c_str());
+        else if (k == "score") score = v;
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
-        die("usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
-            "[batch_s=300] [clean=F info=F]");
+        die(usage);
+    if (score != "host" && score != "device") die("score=" + score + ": must be host or device\n" + usage);
+    const bool on_device = score == "device";
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
     if (clean.empty() != info.empty()) die("clean= and info= go together");
     if (!clean.empty() && !scp.empty()) die("clean= / info= need a single in= / out= pair (or four-field scp lines)");
@@ -113,6 +135,8 @@ int main(int argc, char **argv) {
     // the batch: utterances of one rate, decoded by one mlggd_enhance_waves call when it is full or the rate changes
     std::vector<Item> pend;
     size_t pend_samples = 0;
+    int n_scored = 0;
+    double sum_segsnr = 0.0, sum_lsd = 0.0;
     auto flush = [&]() {
         if (pend.empty()) return;
         const int n = (int)pend.size(), fs = pend[0].fs;
@@ -125,18 +149,41 @@ int main(int argc, char **argv) {
             std::copy(pend[u].noisy.begin(), pend[u].noisy.end(), packed.begin() + off[u]);
             want_lps = want_lps || !pend[u].job.clean.empty();
         }
+        const bool scored = on_device && want_lps;
+        if (scored) want_lps = false;
         if (mlggd_enhance_waves_layout(fs, n, off.data(), frame_off.data(), out_off.data()) != MLGGD_OK)
             die(std::string("mlggd_enhance_waves_layout: ") + mlggd_last_error());
         std::vector<int16_t> enh((size_t)out_off[n]);
         std::vector<float> lps(want_lps ? (size_t)frame_off[n] * D : 0);
-        if (mlggd_enhance_waves(h, fs, ctx, mean.data(), inv.data(), n, packed.data(), off.data(), enh.data(), nullptr,
-                                want_lps ? lps.data() : nullptr) != MLGGD_OK)
+        std::vector<float> segsnr(scored ? n : 0), lsd(scored ? n : 0);
+        if (scored) {  // the clean waves in the noisy layout, zero-padded; an utterance without one scores no frame
+            std::vector<int16_t> cpacked((size_t)off[n], 0);
+            std::vector<int32_t> sframes(n, 0);
+            for (int u = 0; u < n; u++) {
+                const std::vector<int16_t> &c = pend[u].clean;
+                std::copy(c.begin(), c.begin() + std::min(c.size(), pend[u].noisy.size()), cpacked.begin() + off[u]);
+                sframes[u] = pend[u].Fm;
+            }
+            if (mlggd_enhance_waves_scored(h, fs, ctx, mean.data(), inv.data(), n, packed.data(), cpacked.data(),
+                                           off.data(), sframes.data(), enh.data(), nullptr, nullptr, segsnr.data(),
+                                           lsd.data()) != MLGGD_OK)
+                die(std::string("mlggd_enhance_waves_scored: ") + mlggd_last_error());
+        } else if (mlggd_enhance_waves(h, fs, ctx, mean.data(), inv.data(), n, packed.data(), off.data(), enh.data(),
+                                       nullptr, want_lps ? lps.data() : nullptr) != MLGGD_OK)
             die(std::string("mlggd_enhance_waves: ") + mlggd_last_error());
         for (int u = 0; u < n; u++) {
             const Item &it = pend[u];
             tool_io::write_wav(it.job.out, enh.data() + out_off[u], (size_t)(out_off[u + 1] - out_off[u]), it.rate);
             printf("%s -> %s (%d frames)\n", it.job.in.c_str(), it.job.out.c_str(), it.F);
-            if (!it.job.clean.empty()) report(it, lps.data() + (size_t)frame_off[u] * D);
+            if (it.job.clean.empty()) continue;
+            if (scored) {
+                tool_io::write_info(it.job.info, segsnr[u], lsd[u]);
+                n_scored++;
+                sum_segsnr += segsnr[u];
+                sum_lsd += lsd[u];
+            } else {
+                report(it, lps.data() + (size_t)frame_off[u] * D);
+            }
         }
         pend.clear();
         pend_samples = 0;
@@ -158,11 +205,12 @@ int main(int argc, char **argv) {
         const std::vector<int16_t> &noisy = it.noisy;
         if (noisy.size() < (size_t)L) die_in_order(job.in + ": shorter than one frame");
         const int F = it.F = (int)((noisy.size() - (L - S)) / S);
-        if (batched) {
+        if (on_device && !job.clean.empty()) it.clean = read_clean(it, &it.Fm, die_in_order);
+        if (batched || on_device) {
             if (!pend.empty() && pend[0].rate != rate) flush();
             pend_samples += noisy.size();
             pend.push_back(std::move(it));
-            if ((double)pend_samples >= batch_s * rate) flush();
+            if (!batched || (double)pend_samples >= batch_s * rate) flush();
             continue;
         }
         std::vector<int16_t> enh((size_t)F * S + L - S);
@@ -194,6 +242,13 @@ int main(int argc, char **argv) {
         }
     }
     flush();
+    if (on_device && !scp.empty()) {
+        if (n_scored)
+            printf("scored %d utterances: mean segmental SNR %f dB, mean LSD %f dB\n", n_scored, sum_segsnr / n_scored,
+                   sum_lsd / n_scored);
+        else
+            printf("scored 0 utterances\n");
+    }
     mlggd_destroy(h);
     return 0;
 }

@@ -2,8 +2,9 @@
 // LPS rows (big-endian HTK) + the noisy wave's phase -> 16-bit wave by overlap-add, on the GPU (mlggd_lps_to_wave),
 // and the quality report against the clean wave (segmental SNR, log-spectral distortion) in the original's format.
 //
-//   lps2wav clean noisy feat.htk info.txt out [-F RAW|WAV] [-fs 8|11|16] [-swap] [-q] [-gpu N]
+//   lps2wav clean noisy feat.htk info.txt out [-F RAW|WAV] [-fs 8|11|16] [-swap] [-q] [-gpu N] [score=host|device]
 //
+// score=host (the default): the report in double on the host; score=device: in fp32 on the GPU (mlggd_score_waves).
 // The argument order of LogSpec2Wav.c:233-290.  RAW (the default) writes headerless samples, WAV a RIFF file.
 #include <algorithm>
 #include <cstdio>
@@ -19,7 +20,9 @@
 }
 
 int main(int argc, char **argv) {
-    std::string kind = "RAW";
+    std::string kind = "RAW", score = "host";
+    const char *usage =
+        "usage: lps2wav clean noisy feat.htk info.txt out [-F RAW|WAV] [-fs 8|11|16] [-swap] [-gpu N] [score=host|device]";
     std::vector<std::string> files;
     int fs = 16, gpu = 0;
     bool swap = false, quiet = false;
@@ -34,10 +37,12 @@ int main(int argc, char **argv) {
         else if (arg == "-fs") fs = atoi(value().c_str());
         else if (arg == "-swap") swap = true;
         else if (arg == "-gpu") gpu = atoi(value().c_str());
+        else if (arg.compare(0, 6, "score=") == 0) score = arg.substr(6);
         else if (arg.size() > 1 && arg[0] == '-') fprintf(stderr, "WARNING:  Un-recognized flag '%s' !\n", arg.c_str());
         else files.push_back(arg);
     }
-    if (files.size() != 5) die("usage: lps2wav clean noisy feat.htk info.txt out [-F RAW|WAV] [-fs 8|11|16] [-swap] [-gpu N]");
+    if (files.size() != 5) die(usage);
+    if (score != "host" && score != "device") die("score=" + score + ": must be host or device\n" + usage);
     std::vector<int16_t> clean, noisy;
     if (kind == "RAW") {
         clean = tool_io::read_raw16(files[0], swap);
@@ -70,7 +75,15 @@ int main(int argc, char **argv) {
     if (mlggd_lps_to_wave(gpu, fs, (int)n_out, noisy.data(), F, feat.data.data(), out.data(), nullptr) != MLGGD_OK)
         die(std::string("mlggd_lps_to_wave: ") + mlggd_last_error());
     double segsnr = 0.0, lsd = 0.0;
-    tool_io::quality(fs, clean, noisy, feat.data.data(), F, &segsnr, &lsd);
+    if (score == "device") {  // one utterance of F frames: both waves hold its n_out samples
+        const int64_t off[2] = {0, (int64_t)n_out};
+        float s = 0.0f, l = 0.0f;
+        if (mlggd_score_waves(gpu, fs, 1, clean.data(), noisy.data(), off, feat.data.data(), nullptr, &s, &l) != MLGGD_OK)
+            die(std::string("mlggd_score_waves: ") + mlggd_last_error());
+        segsnr = s, lsd = l;
+    } else {
+        tool_io::quality(fs, clean, noisy, feat.data.data(), F, &segsnr, &lsd);
+    }
     tool_io::write_info(files[3], segsnr, lsd);
     if (kind == "WAV")
         tool_io::write_wav(files[4], out.data(), n_out, fs == 11 ? 11000 : fs * 1000);
