@@ -462,8 +462,17 @@ def decode32(lps, mean, inv, ctx, Ws, bs, mut=None):
     return (y / inv + mean).astype(F32)
 
 
-def quality64(clean, noisy, lps, fs_khz=16):
-    """(segmental SNR, log-spectral distortion) of LogSpec2Wav.c in float64, over min(frames of clean, of noisy)."""
+def score_floors64(pc, pd, first=None):
+    """(mc, md): the 50 dB floors of the log-spectral distortion, 1e-5 of the largest clean power pc [F][D] and of the
+    largest enhanced power pd [F][D] over the first `first` scored frames (None: over all of them, which is the
+    report; a number: the slip of a reduction that stops early)"""
+    pc, pd = np.asarray(pc, np.float64), np.asarray(pd, np.float64)
+    return float(pc[:first].max()) * 1e-5, float(pd[:first].max()) * 1e-5
+
+
+def quality64(clean, noisy, lps, fs_khz=16, floors_first=None):
+    """(segmental SNR, log-spectral distortion) of LogSpec2Wav.c in float64, over min(frames of clean, of noisy).
+    floors_first: score_floors64's `first`, a planted slip."""
     F = min(n_frames(len(clean), fs_khz), n_frames(len(noisy), fs_khz))
     L, S, _ = params(fs_khz)
     n = F * S + L - S
@@ -477,10 +486,42 @@ def quality64(clean, noisy, lps, fs_khz=16):
     Xc, _ = spectrum64(clean, fs_khz)
     pc = np.abs(Xc) ** 2
     pd = np.where(lps < -50.0, np.exp(-50.0), np.exp(lps))
-    pc = np.maximum(pc, pc.max() * 1e-5)
-    pd = np.maximum(pd, pd.max() * 1e-5)
+    mc, md = score_floors64(pc, pd, floors_first)
+    pc = np.maximum(pc, mc)
+    pd = np.maximum(pd, md)
     lsd = np.sqrt(((10.0 * np.log10(pd / pc)) ** 2).mean(axis=1))
     return float(snr.mean()), float(lsd.mean())
+
+
+# The two means of k_score_utt (score.hip.h) in float32, in the order DESIGN.md section 8 documents, with switchable
+# planted slips as in the waves_* models below.
+SCORE_WAVES = 16                 # SCORE_UTT_WAVES
+SCORE_TREE_SLIPS = [
+    "first_trip_only",           # only the frames t < 16 enter the partial sums (the frame loop never comes round again)
+    "divide_by_padded_count",    # the mean divides by ceil(n / 16) * 16, the frames the 16 wavefronts step over
+    "left_to_right",             # the 16 partials are added 0, 1, ..., 15, not by the halving tree
+]
+
+
+def score_tree_mean32(values, slip=None):
+    """float32 mean of `values` as k_score_utt forms it: partial w of 16 adds values[w], values[w + 16], ... in that
+    order from 0.0f; the partials combine as s[i] += s[i + h] for h = 8, 4, 2, 1; the result is s[0] / float(n)"""
+    v = np.asarray(values, F32).ravel()
+    n = v.size
+    s = np.zeros(SCORE_WAVES, F32)
+    for a in range(0, SCORE_WAVES if slip == "first_trip_only" else n, SCORE_WAVES):
+        row = v[a:a + SCORE_WAVES]
+        s[:row.size] = s[:row.size] + row
+    if slip == "left_to_right":
+        for i in range(1, SCORE_WAVES):
+            s[0] = s[0] + s[i]
+    else:
+        h = SCORE_WAVES // 2
+        while h > 0:
+            s[:h] = s[:h] + s[h:2 * h]
+            h >>= 1
+    count = -(-n // SCORE_WAVES) * SCORE_WAVES if slip == "divide_by_padded_count" else n
+    return F32(s[0] / F32(count))
 
 
 def synth_speech(n, fs_khz, seed=0):

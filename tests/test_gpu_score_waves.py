@@ -60,8 +60,9 @@ def batch(fs, snr_db):
 
 
 # ---- the float32 restatement
-def quality32(clean, noisy, lps, fs):
-    """(segmental SNR, LSD) of tool_io::quality / spec64.quality64 with every step in float32"""
+def quality32(clean, noisy, lps, fs, per_frame=False):
+    """(segmental SNR, LSD) of tool_io::quality / spec64.quality64 with every step in float32; per_frame: the two
+    float32 arrays [F] before the means"""
     L, S, N = spec64.params(fs)
     M, D = N // 2, N // 2 + 1
     F = min(spec64.n_frames(len(clean), fs), spec64.n_frames(len(noisy), fs))
@@ -97,6 +98,8 @@ def quality32(clean, noisy, lps, fs):
         mc, md = F32(1e-5) * pc.max(), F32(1e-5) * pd.max()
         d = F32(10.0) * np.log10(np.maximum(pd, md) / np.maximum(pc, mc))
         lsd = np.sqrt((d * d).sum(axis=1, dtype=F32) / F32(D))
+    if per_frame:
+        return snr, lsd
     return float(snr.mean(dtype=F32)), float(lsd.mean(dtype=F32))
 
 
