@@ -182,6 +182,46 @@ int mlggd_enhance_waves_scored(mlggd_handle h, int fs_khz, int fea_context, cons
                                const int64_t *offsets, const int32_t *score_frames /* optional */, int16_t *out,
                                float *out_f32 /* optional */, float *lps_out /* optional */, float *segsnr, float *lsd);
 
+/* ---- live audio: a *live group* is n_sessions independent audio sessions decoded block by block on one engine; all
+ * share fs_khz, fea_context and the norm vectors.  With half = (fea_context - 1) / 2 and F(n) the frame count above, a
+ * session that has received n samples has decoded T = max(0, F(n) - half) frames while it runs (frame t needs the rows
+ * up to t + half: no frame is decoded with a provisional right edge) and emitted T*S samples, each covered only by
+ * decoded frames and therefore final; the push that ends it decodes the remaining frames against the right edge and
+ * emits up to F*S + L - S.  A session ended with fewer than L samples in all emits nothing; that is not an error.
+ * For any way of cutting a recording into pushes (empty blocks, blocks of one sample and an `end` with no samples
+ * included) the concatenation of what a session emitted equals mlggd_enhance_wave of the whole recording in every bit
+ * of out and out_f32, whatever the other sessions do, the slot, n_sessions, bunchsize, max_cache_frames (a push whose
+ * decodable frames exceed the chunk capacity runs in chunks over the packed frames) and what the slot decoded before.
+ * Between pushes a session keeps on the device its unconsumed samples (< L), the LPS rows that are left context or not
+ * yet decoded (<= fea_context - 1), the noisy spectra of the frames not yet decoded (<= half) and the time blocks of
+ * the last ceil(L/S) - 1 decoded frames; nothing is uploaded or analysed twice.  A push in the steady state allocates
+ * nothing (buffers only grow), uploads the packed samples and one block of tables, launches a number of kernels that
+ * does not depend on n_sessions, downloads each requested output once and synchronises once.  The state is the
+ * group's own memory: other calls on the engine between two pushes (training, mlggd_enhance_waves, mlggd_set_weights)
+ * do not disturb it; after mlggd_set_weights the contract refers to the new weights.  One recording may have up to
+ * 2^31 - 1025 samples.
+ *
+ * mlggd_live_layout: host only, no device: out_off[n_sessions+1] of the push that adds add[u] samples to a session
+ * that has received had[u] so far, ending it if end[u] (end NULL: none) -- the emission rule, stated once.
+ * mlggd_live_open: needs a single-device engine (a communicator or an emulated world: MLGGD_ERR_STATE), fea_context
+ * odd and fea_context * D == layersizes[0].  mlggd_destroy while a group of the engine is open is MLGGD_ERR_STATE and
+ * leaves the engine usable: close the group first.
+ * mlggd_live_push: session u receives samples[offsets[u] .. offsets[u+1]) (may be empty); its newly final output
+ * samples go to out[out_off[u] .. out_off[u+1]) (out_f32 optional, alike); out_off is written by the call and equals
+ * mlggd_live_layout's.  end[u] != 0: the session is finished after these samples: its remaining output is emitted and
+ * the slot is empty again, ready for a new recording.  out_capacity (in samples) too small, NULL pointers and
+ * decreasing offsets (the message names the session) are MLGGD_ERR_ARG before any device call, state unchanged.
+ * mlggd_live_received: had[n_sessions], the samples each session has received since it began (host counters). */
+typedef struct mlggd_live *mlggd_live_handle;
+int mlggd_live_layout(int fs_khz, int fea_context, int n_sessions, const int64_t *had, const int64_t *add,
+                      const uint8_t *end, int64_t *out_off);
+int mlggd_live_open(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                    int n_sessions, mlggd_live_handle *out);
+int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *offsets, const uint8_t *end,
+                    int16_t *out, float *out_f32, int64_t out_capacity, int64_t *out_off);
+int mlggd_live_received(mlggd_live_handle s, int64_t *had /* [n_sessions] */);
+int mlggd_live_close(mlggd_live_handle s);
+
 /* ---- state: BP_GPU::returnWeights (BP_GPU.cu:514-525) and dev.scalefactor (:287) ---- */
 int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias);
 /* mlggd_set_weights replaces W and b of every layer and leaves the momentum buffers as they are; it is ordered after

@@ -53,6 +53,7 @@ EXPORTS = [
     "mlggd_wave_to_lps", "mlggd_lps_to_wave", "mlggd_enhance_wave",
     "mlggd_enhance_waves_layout", "mlggd_enhance_waves",
     "mlggd_score_waves", "mlggd_enhance_waves_scored",
+    "mlggd_live_layout", "mlggd_live_open", "mlggd_live_push", "mlggd_live_received", "mlggd_live_close",
 ]
 
 _lib = None
@@ -60,7 +61,8 @@ _lib = None
 
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h")]
+    srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
+                                             "live_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -139,6 +141,12 @@ def load():
     L.mlggd_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, _sp, _sp, _lp, _fp, _ip, _fp, _fp]
     L.mlggd_enhance_waves_scored.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _sp, _lp, _ip, _sp,
                                              _fp, _fp, _fp, _fp]
+    _bp = C.POINTER(C.c_uint8)
+    L.mlggd_live_layout.argtypes = [C.c_int, C.c_int, C.c_int, _lp, _lp, _bp, _lp]
+    L.mlggd_live_open.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, C.POINTER(C.c_void_p)]
+    L.mlggd_live_push.argtypes = [C.c_void_p, _sp, _lp, _bp, _sp, _fp, C.c_int64, _lp]
+    L.mlggd_live_received.argtypes = [C.c_void_p, _lp]
+    L.mlggd_live_close.argtypes = [C.c_void_p]
     _lib = L
     return L
 
@@ -241,6 +249,98 @@ def enhance_waves_layout(lengths, fs_khz=16):
     return np.diff(frame_off), frame_off, out_off
 
 
+def _end_flags(end, n):
+    if end is None:
+        return None
+    e = np.ascontiguousarray(np.asarray(end) != 0, dtype=np.uint8)
+    if e.shape != (n,):
+        raise ValueError("end must hold one flag per session")
+    return e
+
+
+def _bp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8)) if a is not None else None
+
+
+def live_layout(had, add, end=None, fs_khz=16, fea_context=7):
+    """out_off [n+1] int64 of the live push (BPGpu.live) that adds add[u] samples to a session that has received
+    had[u], ending it where end[u]: session u emits out_off[u+1] - out_off[u] samples.  A host call: needs no
+    device (mlggd_live_layout)."""
+    had = np.ascontiguousarray(had, dtype=np.int64)
+    add = np.ascontiguousarray(add, dtype=np.int64)
+    if had.ndim != 1 or had.shape != add.shape:
+        raise ValueError("had and add must hold one count per session")
+    e = _end_flags(end, had.size)
+    out_off = np.zeros(had.size + 1, np.int64)
+    _lp = C.POINTER(C.c_int64)
+    _check(load().mlggd_live_layout(int(fs_khz), int(fea_context), had.size, had.ctypes.data_as(_lp),
+                                    add.ctypes.data_as(_lp), _bp(e), out_off.ctypes.data_as(_lp)))
+    return out_off
+
+
+class LiveGroup:
+    """n_sessions audio sessions decoded block by block on one engine (BPGpu.live, mlggd_live_*): what a session
+    emits from its first sample to its end, concatenated, equals enhance_wave of the whole recording bit for bit."""
+
+    def __init__(self, eng, mean, inv_std, n_sessions, fs_khz, fea_context):
+        self._s = None
+        L, S, N = SPECTRAL_PARAMS.get(int(fs_khz), (0, 0, 0))
+        D = N // 2 + 1
+        if fea_context is None:
+            fea_context = eng.K0 // D
+        self.n_sessions, self.fs_khz, self.fea_context = int(n_sessions), int(fs_khz), int(fea_context)
+        mean = _f32(mean, (D,)) if N else _f32(mean)
+        inv = _f32(inv_std, (D,)) if N else _f32(inv_std)
+        s = C.c_void_p()
+        _check(load().mlggd_live_open(eng._h, self.fs_khz, self.fea_context, _p(mean), _p(inv), self.n_sessions,
+                                      C.byref(s)))
+        self._s = s
+        self._eng = eng
+        eng._lives.append(self)
+
+    def received(self):
+        """samples each session has received since it began, [n_sessions] int64"""
+        had = np.zeros(self.n_sessions, np.int64)
+        _check(load().mlggd_live_received(self._s, had.ctypes.data_as(C.POINTER(C.c_int64))))
+        return had
+
+    def push(self, blocks, end=None, return_f32=False):
+        """blocks: n_sessions int16 arrays (possibly empty), the next samples of every session; end[u]: session u is
+        finished after them.  Returns the list of int16 arrays that became final in this push (with return_f32 a
+        tuple of two lists, the float32 samples before the cast second)."""
+        if len(blocks) != self.n_sessions:
+            raise ValueError("one block per session")
+        blocks = [_wave(b) for b in blocks]
+        n = self.n_sessions
+        e = _end_flags(end, n)
+        off = _offsets([b.size for b in blocks])
+        total = live_layout(self.received(), np.diff(off), e, self.fs_khz, self.fea_context)[-1]
+        packed = np.concatenate(blocks) if n else np.zeros(0, np.int16)
+        out = np.empty(int(total), np.int16)
+        outf = np.empty(out.size, np.float32) if return_f32 else None
+        out_off = np.zeros(n + 1, np.int64)
+        _lp = C.POINTER(C.c_int64)
+        _check(load().mlggd_live_push(self._s, _sp(packed), off.ctypes.data_as(_lp), _bp(e), _sp(out),
+                                      _p(outf) if return_f32 else None, out.size, out_off.ctypes.data_as(_lp)))
+        res = [out[out_off[u]:out_off[u + 1]] for u in range(n)]
+        if return_f32:
+            return res, [outf[out_off[u]:out_off[u + 1]] for u in range(n)]
+        return res
+
+    def close(self):
+        if self._s:
+            load().mlggd_live_close(self._s)
+            self._s = None
+            if self in self._eng._lives:
+                self._eng._lives.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _score_frames(score_frames, n):
     if score_frames is None:
         return None
@@ -302,6 +402,7 @@ class BPGpu:
     def __init__(self, random_seed, gpu, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
                  shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0):
         self._h = None
+        self._lives = []
         self.layersizes = [int(x) for x in layersizes]
         self.numlayers = len(self.layersizes)
         if not 2 <= self.numlayers <= MAXLAYER:
@@ -337,6 +438,8 @@ class BPGpu:
     # -- lifetime
     def close(self):
         if self._h:
+            for g in list(self._lives):  # an engine with an open live group cannot be destroyed
+                g.close()
             load().mlggd_destroy(self._h)
             self._h = None
 
@@ -478,6 +581,11 @@ class BPGpu:
         if cleans is not None:
             res += [segsnr, lsd]
         return res[0] if len(res) == 1 else tuple(res)
+
+    def live(self, mean, inv_std, n_sessions, fs_khz=16, fea_context=None):
+        """A live group of n_sessions sessions on this engine (mlggd_live_open): push(blocks, end=None,
+        return_f32=False), received(), close(); BPGpu.close() closes it too.  fea_context None: layersizes[0] / bins."""
+        return LiveGroup(self, mean, inv_std, n_sessions, fs_khz, fea_context)
 
     def last_train_ms(self):
         ms, steps = C.c_float(0), C.c_int(0)

@@ -23,6 +23,8 @@
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
+#include "live.hip.h"
+#include "live_rule.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -230,6 +232,7 @@ struct mlggd_engine {
         int lookup_table = 0;       // utterance of a frame: 0 = binary search over frame_off (default), 1 = per-frame
                                     // table (MLGGD_WAVES_LOOKUP=table, for A/B runs)
     } ww;
+    int live_groups = 0;  // open live groups (mlggd_live_open): mlggd_destroy refuses while there is one
     bool indexed = false;
     int fdim = 0, toff = 0, raw_frames = 0;
     unsigned step_counter = 0;
@@ -1730,6 +1733,9 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
 
 int mlggd_destroy(mlggd_handle e) {
     if (!e) return MLGGD_OK;
+    if (e->live_groups > 0)
+        return fail(MLGGD_ERR_STATE, "%d live group(s) of this engine are open: mlggd_live_close them first",
+                    e->live_groups);
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->comm_stream) hipStreamSynchronize(e->comm_stream);
@@ -3358,6 +3364,295 @@ int mlggd_score_waves(int device, int fs_khz, int n_utts, const int16_t *clean, 
     HIPCHK(hipMemcpy(h.data(), scores, h.size() * sizeof(float), hipMemcpyDeviceToHost));
     memcpy(segsnr, h.data(), (size_t)n_utts * sizeof(float));
     memcpy(lsd, h.data() + n_utts, (size_t)n_utts * sizeof(float));
+    return MLGGD_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ live groups (live.hip.h, live_rule.h)
+// n_sessions audio sessions decoded block by block on one engine.  The sessions' state (live.hip.h) is the group's own
+// device memory, in two copies; a push borrows from the engine only what mlggd_enhance_waves borrows for the time of
+// one call -- the idle raw buffer set and chunk_out -- so training, decoding and set_weights between two pushes leave
+// the sessions as they are.
+struct mlggd_live {
+    mlggd_engine *e = nullptr;
+    int fs = 0, ctx = 0, half = 0, K = 0, NS = 0;
+    SpecDims d;
+    std::vector<long long> had;  // samples each session has received since it began
+    int cur = 0;                 // the copy of the state that is current
+    int16_t *tail[2] = {nullptr, nullptr};
+    float *lps[2] = {nullptr, nullptr}, *blk[2] = {nullptr, nullptr}, *norm = nullptr;
+    float2 *X[2] = {nullptr, nullptr};
+    // the tables of one push, one block of pinned host memory and its device twin: win_off [NS + 1], out_off [NS + 1],
+    // a_woff [NS] (long long), sess [NS], dk_off [NS + 1], dk_slot [NS], a_foff [NS + 1] (int)
+    char *h_tab = nullptr, *d_tab = nullptr;
+    size_t tab_bytes = 0;
+    mlggd_engine::WsBuf in, win, lps_new, X_new, X_dec, blk_new, out_i, out_f;  // per push; they only grow
+    std::vector<live_rule::Step> steps;
+};
+
+namespace {
+
+struct LiveTables {
+    long long *win_off, *out_off, *a_woff;
+    LiveSess *sess;
+    int *dk_off, *dk_slot, *a_foff;
+};
+
+size_t live_tables(char *base, int NS, LiveTables *t) {
+    size_t at = 0;
+    auto take = [&](size_t bytes) {
+        char *p = base + at;
+        at += (bytes + 15) / 16 * 16;
+        return p;
+    };
+    t->win_off = (long long *)take(((size_t)NS + 1) * sizeof(long long));
+    t->out_off = (long long *)take(((size_t)NS + 1) * sizeof(long long));
+    t->a_woff = (long long *)take((size_t)NS * sizeof(long long));
+    t->sess = (LiveSess *)take((size_t)NS * sizeof(LiveSess));
+    t->dk_off = (int *)take(((size_t)NS + 1) * sizeof(int));
+    t->dk_slot = (int *)take((size_t)NS * sizeof(int));
+    t->a_foff = (int *)take(((size_t)NS + 1) * sizeof(int));
+    return at;
+}
+
+void live_free(mlggd_live *s) {
+    for (int c = 0; c < 2; c++) {
+        if (s->tail[c]) hipFree(s->tail[c]);
+        if (s->lps[c]) hipFree(s->lps[c]);
+        if (s->X[c]) hipFree(s->X[c]);
+        if (s->blk[c]) hipFree(s->blk[c]);
+    }
+    if (s->norm) hipFree(s->norm);
+    if (s->d_tab) hipFree(s->d_tab);
+    if (s->h_tab) hipHostFree(s->h_tab);
+    for (mlggd_engine::WsBuf *b : {&s->in, &s->win, &s->lps_new, &s->X_new, &s->X_dec, &s->blk_new, &s->out_i, &s->out_f})
+        if (b->p) hipFree(b->p);
+    delete s;
+}
+
+int live_alloc(mlggd_live *s, const float *norm_mean, const float *norm_inv_std) {
+    mlggd_engine *e = s->e;
+    const SpecDims &d = s->d;
+    const size_t NS = (size_t)s->NS;
+    const size_t n_lps = std::max<size_t>(1, NS * (s->ctx - 1) * d.D), n_X = std::max<size_t>(1, NS * s->half * d.D);
+    const size_t n_blk = NS * s->K * d.L, n_tail = NS * d.L;
+    for (int c = 0; c < 2; c++) {
+        HIPCHK(hipMalloc((void **)&s->tail[c], n_tail * sizeof(int16_t)));
+        HIPCHK(hipMalloc((void **)&s->lps[c], n_lps * sizeof(float)));
+        HIPCHK(hipMalloc((void **)&s->X[c], n_X * sizeof(float2)));
+        HIPCHK(hipMalloc((void **)&s->blk[c], n_blk * sizeof(float)));
+        HIPCHK(hipMemsetAsync(s->tail[c], 0, n_tail * sizeof(int16_t), e->stream));
+        HIPCHK(hipMemsetAsync(s->lps[c], 0, n_lps * sizeof(float), e->stream));
+        HIPCHK(hipMemsetAsync(s->X[c], 0, n_X * sizeof(float2), e->stream));
+        HIPCHK(hipMemsetAsync(s->blk[c], 0, n_blk * sizeof(float), e->stream));
+    }
+    HIPCHK(hipMalloc((void **)&s->norm, (size_t)2 * d.D * sizeof(float)));
+    HIPCHK(hipMemcpyAsync(s->norm, norm_mean, d.D * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(s->norm + d.D, norm_inv_std, d.D * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    LiveTables t;
+    s->tab_bytes = live_tables(nullptr, s->NS, &t);
+    HIPCHK(hipHostMalloc((void **)&s->h_tab, s->tab_bytes, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void **)&s->d_tab, s->tab_bytes));
+    memset(s->h_tab, 0, s->tab_bytes);
+    HIPCHK(hipStreamSynchronize(e->stream));  // the norm vectors are the caller's
+    return MLGGD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mlggd_live_layout(int fs_khz, int fea_context, int n_sessions, const int64_t *had, const int64_t *add,
+                      const uint8_t *end, int64_t *out_off) {
+    char msg[256];
+    if (live_rule::layout(fs_khz, fea_context, n_sessions, had, add, end, out_off, msg, sizeof msg))
+        return fail(MLGGD_ERR_ARG, "%s", msg);
+    return MLGGD_OK;
+}
+
+int mlggd_live_open(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                    int n_sessions, mlggd_live_handle *out) {
+    if (!e || !out) return fail(MLGGD_ERR_ARG, "NULL handle / out");
+    *out = nullptr;
+    char msg[256];
+    int L, S, slot;
+    if (live_rule::check_group(fs_khz, fea_context, n_sessions, &L, &S, msg, sizeof msg))
+        return fail(MLGGD_ERR_ARG, "%s", msg);
+    SpecDims d;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if ((long long)fea_context * d.D != e->K0)
+        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
+    if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
+    if (e->comm || e->world > 1 || e->fake_world)
+        return fail(MLGGD_ERR_STATE, "mlggd_live_open runs on a single-device engine");
+    if (!norm_mean || !norm_inv_std) return fail(MLGGD_ERR_ARG, "norm_mean/norm_inv_std is NULL");
+    if ((long long)n_sessions * (d.L + (long long)fea_context * d.D) > INT32_MAX / 2)
+        return fail(MLGGD_ERR_ARG, "n_sessions %d is too large", n_sessions);
+    HIPCHK(hipSetDevice(e->device));
+    const SpecPlan *p;
+    CHK(spec_plan(e->device, fs_khz, &p));
+    mlggd_live *s = new mlggd_live;
+    s->e = e, s->fs = fs_khz, s->ctx = fea_context, s->half = (fea_context - 1) / 2, s->NS = n_sessions, s->d = d;
+    s->K = (d.L + d.S - 1) / d.S - 1;
+    s->had.assign((size_t)n_sessions, 0);
+    s->steps.resize((size_t)n_sessions);
+    const int rc = live_alloc(s, norm_mean, norm_inv_std);
+    if (rc != MLGGD_OK) {
+        live_free(s);
+        return rc;
+    }
+    e->live_groups++;
+    *out = s;
+    return MLGGD_OK;
+}
+
+int mlggd_live_received(mlggd_live_handle s, int64_t *had) {
+    if (!s || !had) return fail(MLGGD_ERR_ARG, "NULL handle / had");
+    for (int u = 0; u < s->NS; u++) had[u] = s->had[u];
+    return MLGGD_OK;
+}
+
+int mlggd_live_close(mlggd_live_handle s) {
+    if (!s) return MLGGD_OK;
+    mlggd_engine *e = s->e;
+    hipSetDevice(e->device);
+    hipStreamSynchronize(e->stream);
+    e->live_groups--;
+    live_free(s);
+    return MLGGD_OK;
+}
+
+int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *offsets, const uint8_t *end,
+                    int16_t *out, float *out_f32, int64_t out_capacity, int64_t *out_off) {
+    if (!s) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!offsets || !out_off) return fail(MLGGD_ERR_ARG, "offsets/out_off is NULL");
+    mlggd_engine *e = s->e;
+    const SpecDims &d = s->d;
+    const int NS = s->NS, ctx = s->ctx, half = s->half, K = s->K;
+    // ---- the plan of the push, from the host's counters alone
+    long long n_win = 0, n_emit = 0, NF = 0, ND = 0;
+    for (int u = 0; u < NS; u++) {
+        if (offsets[u + 1] < offsets[u])
+            return fail(MLGGD_ERR_ARG, "offsets decrease at session %d (%lld after %lld)", u, (long long)offsets[u + 1],
+                        (long long)offsets[u]);
+        const long long add = (long long)offsets[u + 1] - (long long)offsets[u];
+        if (add > live_rule::kMaxSamples - s->had[u])
+            return fail(MLGGD_ERR_ARG, "session %d: %lld + %lld samples exceed the %lld one recording may have: end it", u,
+                        s->had[u], add, (long long)live_rule::kMaxSamples);
+        const live_rule::Step &st = s->steps[u] = live_rule::step(d.L, d.S, half, s->had[u], add, end && end[u]);
+        n_win += st.p0 + add;
+        n_emit += st.emit;
+        NF += st.A1 - st.A0;
+        ND += st.T1 - st.T0;
+    }
+    const long long n_in = (long long)offsets[NS] - (long long)offsets[0];
+    if (n_in > 0 && !samples) return fail(MLGGD_ERR_ARG, "samples is NULL");
+    if (n_emit > 0 && !out) return fail(MLGGD_ERR_ARG, "out is NULL");
+    if (n_emit > out_capacity)
+        return fail(MLGGD_ERR_ARG, "out_capacity %lld: the push emits %lld samples", (long long)out_capacity, n_emit);
+    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    if (NF > INT32_MAX / 2 || ND > INT32_MAX / 2 ||
+        std::min<long long>(cap, ND) + (long long)std::min(NS, cap) * (ctx - 1) > INT32_MAX / 2)
+        return fail(MLGGD_ERR_ARG, "a push of %lld new frames over %d sessions is too large", std::max(NF, ND), NS);
+    LiveTables h, dv;
+    live_tables(s->h_tab, NS, &h);
+    live_tables(s->d_tab, NS, &dv);
+    int n_act = 0, n_dk = 0;
+    h.win_off[0] = h.out_off[0] = 0;
+    h.dk_off[0] = h.a_foff[0] = 0;
+    out_off[0] = 0;
+    for (int u = 0, nf_at = 0, dec_at = 0; u < NS; u++) {
+        const live_rule::Step &st = s->steps[u];
+        const long long add = (long long)offsets[u + 1] - (long long)offsets[u];
+        const int nf = (int)(st.A1 - st.A0), nd = (int)(st.T1 - st.T0);
+        LiveSess &q = h.sess[u];
+        q.in_off = (long long)offsets[u] - (long long)offsets[0];
+        q.p = (int)st.p0, q.a = (int)add, q.cut = nf * d.S;
+        q.T0 = (int)st.T0, q.A0 = (int)st.A0, q.T1 = (int)st.T1, q.A1 = (int)st.A1;
+        q.keep = (end && end[u]) ? 0 : 1;
+        q.nf_off = nf_at, q.dec_off = dec_at;
+        if (nf > 0) {  // the analysis batch: the sessions with new frames, their windows and frame offsets
+            h.a_woff[n_act] = h.win_off[u];
+            h.a_foff[++n_act] = nf_at + nf;
+        }
+        if (nd > 0) {
+            h.dk_slot[n_dk] = u;
+            h.dk_off[++n_dk] = dec_at + nd;
+        }
+        nf_at += nf, dec_at += nd;
+        h.win_off[u + 1] = h.win_off[u] + st.p0 + add;
+        h.out_off[u + 1] = h.out_off[u] + st.emit;
+        out_off[u + 1] = h.out_off[u + 1];
+    }
+    // ---- the device
+    HIPCHK(hipSetDevice(e->device));
+    const SpecPlan *p;
+    CHK(spec_plan(e->device, s->fs, &p));
+    hipStream_t st = e->stream;
+    int16_t *d_in = nullptr, *d_win = nullptr, *oi = nullptr;
+    float *lps_new = nullptr, *blk_new = nullptr, *of = nullptr;
+    float2 *X_new = nullptr, *X_dec = nullptr;
+    CHK(ws_grow(e, s->in, (size_t)n_in, &d_in));
+    CHK(ws_grow(e, s->win, (size_t)n_win, &d_win));
+    CHK(ws_grow(e, s->lps_new, (size_t)NF * d.D, &lps_new));
+    CHK(ws_grow(e, s->X_new, (size_t)NF * d.D, &X_new));
+    CHK(ws_grow(e, s->X_dec, (size_t)ND * d.D, &X_dec));
+    CHK(ws_grow(e, s->blk_new, (size_t)ND * d.L, &blk_new));
+    CHK(ws_grow(e, s->out_i, (size_t)n_emit, &oi));
+    if (out_f32) CHK(ws_grow(e, s->out_f, (size_t)n_emit, &of));
+    const int c0 = s->cur, c1 = s->cur ^ 1;
+    const float *mean = s->norm, *inv = s->norm + d.D;
+    if (n_in > 0)
+        HIPCHK(hipMemcpyAsync(d_in, samples + offsets[0], (size_t)n_in * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_tab, s->h_tab, s->tab_bytes, hipMemcpyHostToDevice, st));
+    if (n_win > 0) {
+        hipLaunchKernelGGL(k_live_window, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, d_in, s->tail[c0],
+                           s->tail[c1], dv.sess, dv.win_off, NS, d.L, d_win, n_win);
+        CHK(launch_check("k_live_window"));
+    }
+    if (NF > 0) {
+        hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid((int)NF)), dim3(64 * SPEC_FRAMES), 0, st, d_win, dv.a_woff,
+                           dv.a_foff, (const int *)nullptr, n_act, (int)NF, p->d, p->win, p->tw, p->tws, (float)exp(-50.0),
+                           lps_new, X_new);
+        CHK(launch_check("k_lps_analysis_seg"));
+    }
+    if (ND > 0) {
+        hipLaunchKernelGGL(k_live_gather_x, dim3((unsigned)ND), dim3(256), 0, st, s->X[c0], X_new, dv.sess, dv.dk_off,
+                           dv.dk_slot, n_dk, d.D, half, X_dec);
+        CHK(launch_check("k_live_gather_x"));
+    }
+    // chunks over the packed decoded frames, as in mlggd_enhance_waves
+    for (int a = 0, k0 = 0; a < (int)ND; a += cap) {
+        const int n = std::min(cap, (int)ND - a);
+        while (h.dk_off[k0 + 1] <= a) k0++;
+        int k1 = k0;
+        while (h.dk_off[k1 + 1] < a + n) k1++;
+        const int rows = n + (k1 - k0 + 1) * (ctx - 1);
+        mlggd_engine::RawSet *r;
+        CHK(raw_set_acquire(e, rows, n, ctx, &r));
+        hipLaunchKernelGGL(k_live_stream, dim3((unsigned)rows), dim3(256), 0, st, s->lps[c0], lps_new, dv.sess, dv.dk_off,
+                           dv.dk_slot, n_dk, d.D, a, n, k0, k1, ctx, mean, inv, r->feat, r->first);
+        CHK(launch_check("k_live_stream"));
+        raw_set_commit(e, *r, rows, n, ctx);
+        CHK(forward_resident(e, n));
+        CHK(launch_synthesis(p, e->chunk_out, mean, inv, X_dec, a, n, blk_new, st));
+        HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
+    }
+    if (n_emit > 0) {
+        hipLaunchKernelGGL(k_live_ola, dim3((unsigned)((n_emit + 255) / 256)), dim3(256), 0, st, s->blk[c0], blk_new,
+                           dv.sess, dv.out_off, NS, K, p->d, p->win, of, oi, n_emit);
+        CHK(launch_check("k_live_ola"));
+        HIPCHK(hipMemcpyAsync(out, oi, (size_t)n_emit * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+        if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, of, (size_t)n_emit * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
+    hipLaunchKernelGGL(k_live_carry, dim3((unsigned)(NS * (ctx - 1 + half + K))), dim3(256), 0, st, dv.sess, ctx, K, d.D,
+                       d.L, s->lps[c0], lps_new, s->lps[c1], s->X[c0], X_new, s->X[c1], s->blk[c0], blk_new, s->blk[c1]);
+    CHK(launch_check("k_live_carry"));
+    HIPCHK(hipStreamSynchronize(st));
+    s->cur = c1;
+    for (int u = 0; u < NS; u++)
+        s->had[u] = (end && end[u]) ? 0 : s->had[u] + ((long long)offsets[u + 1] - (long long)offsets[u]);
     return MLGGD_OK;
 }
 

@@ -6,7 +6,7 @@
 //
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
-//               [score=host|device]
+//               [score=host|device] [live=BLOCK [sessions=64]]
 //
 // scp lists "in out" or "in out clean info" lines.  A list is decoded in batches of batch_s seconds of audio by
 // mlggd_enhance_waves: the utterances of a batch form one frame stream, so the forward bunches are full, and the
@@ -21,6 +21,11 @@
 // batch_s=0 lines as batches of one), over the frames the clean wave has; the clean waves are read before the pass, and
 // a list ends with one line: the number of scored utterances and their mean segmental SNR and LSD.  The enhanced waves
 // are the same bytes either way; it adds 512 B clean wave + 2056 B clean spectrum + 12 B per frame to the figures above.
+// live=BLOCK (scp lists of "in out" lines): the utterances are decoded as concurrent live sessions of one group
+// (mlggd_live_*): every push feeds BLOCK samples to each of up to `sessions` utterances, an utterance is ended with its
+// last block, and its slot is refilled from the list.  The group is reopened where the sample rate changes.  The files
+// are byte-identical to the default mode's; the lines on stdout come in the order the utterances finish.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -75,8 +80,9 @@ int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp, clean, info, score = "host";
     const char *usage =
         "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
-        "[batch_s=300] [clean=F info=F] [score=host|device]";
-    int ctx = 7, gpu = 0, bunch = 512;
+        "[batch_s=300] [clean=F info=F] [score=host|device] [live=BLOCK [sessions=64]]";
+    int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64;
+    bool live = false, score_given = false;
     double batch_s = 300.0;
     for (int a = 1; a < argc; a++) {
         const std::string arg(argv[a]);
@@ -94,7 +100,9 @@ int main(int argc, char **argv) {
         else if (k == "gpu_used") gpu = atoi(v.c_str());
         else if (k == "bunchsize") bunch = atoi(v.c_str());
         else if (k == "batch_s") batch_s = atof(v.c_str());
-        else if (k == "score") score = v;
+        else if (k == "score") score = v, score_given = true;
+        else if (k == "live") live_block = atoi(v.c_str()), live = true;
+        else if (k == "sessions") n_slots = atoi(v.c_str());
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
@@ -105,6 +113,12 @@ int main(int argc, char **argv) {
     if (clean.empty() != info.empty()) die("clean= and info= go together");
     if (!clean.empty() && !scp.empty()) die("clean= / info= need a single in= / out= pair (or four-field scp lines)");
     if (batch_s < 0) die("batch_s must not be negative");
+    if (live) {
+        if (score_given) die("live= and score= do not go together: a live session has no quality report");
+        if (scp.empty()) die("live= needs an scp= list");
+        if (live_block < 1) die("live= must be a block of at least one sample");
+        if (n_slots < 1) die("sessions= must be at least 1");
+    }
 
     const tool_io::Model model = tool_io::read_wts(wts);
     const int D = model.ls.back();
@@ -129,6 +143,100 @@ int main(int argc, char **argv) {
         }
     } else {
         jobs.push_back(Job{in, out, clean, info});
+    }
+    if (live) {
+        // the list as concurrent live sessions: slots refilled as they free up, one group per run of one sample rate
+        struct Slot {
+            bool busy = false;
+            Item it;
+            size_t at = 0;
+            std::vector<int16_t> out;
+        };
+        size_t next = 0;
+        Item held;
+        bool have_held = false;
+        auto fetch = [&](Item *it) {  // the next utterance of the list, read and checked
+            if (have_held) {
+                *it = std::move(held);
+                have_held = false;
+                return true;
+            }
+            if (next >= jobs.size()) return false;
+            const Job &job = jobs[next++];
+            if (!job.clean.empty()) die(job.in + ": live= takes \"in out\" lines only");
+            *it = Item();
+            it->job = job;
+            it->noisy = tool_io::read_wav(job.in, &it->rate);
+            it->fs = tool_io::rate_khz(it->rate);
+            if (!it->fs) die(job.in + ": sample rate " + std::to_string(it->rate) + " Hz is not 8000, 11000 or 16000");
+            int L, S, N;
+            tool_io::spectral_params(it->fs, &L, &S, &N);
+            if (it->noisy.size() < (size_t)L) die(job.in + ": shorter than one frame");
+            it->F = (int)((it->noisy.size() - (L - S)) / S);
+            return true;
+        };
+        for (Item head; fetch(&head);) {  // the head of a run of one rate goes back to be fetched by the first slot
+            held = std::move(head);
+            have_held = true;
+            const int rate = held.rate, fs = held.fs;
+            mlggd_live_handle g = nullptr;
+            if (mlggd_live_open(h, fs, ctx, mean.data(), inv.data(), n_slots, &g) != MLGGD_OK)
+                die(std::string("mlggd_live_open: ") + mlggd_last_error());
+            std::vector<Slot> slots(n_slots);
+            std::vector<int64_t> off(n_slots + 1), out_off(n_slots + 1), had(n_slots), add(n_slots);
+            std::vector<uint8_t> end(n_slots);
+            std::vector<int16_t> packed, enh;
+            bool more = true;  // the list may still hold utterances of this rate
+            for (;;) {
+                int busy = 0;
+                for (Slot &sl : slots) {
+                    if (!sl.busy && more) {
+                        Item nx;
+                        if (!fetch(&nx)) {
+                            more = false;
+                        } else if (nx.rate != rate) {
+                            held = std::move(nx);
+                            have_held = true;
+                            more = false;
+                        } else {
+                            sl.busy = true, sl.it = std::move(nx), sl.at = 0;
+                            sl.out.clear();
+                        }
+                    }
+                    busy += sl.busy;
+                }
+                if (!busy) break;
+                packed.clear();
+                off[0] = 0;
+                for (int u = 0; u < n_slots; u++) {
+                    Slot &sl = slots[u];
+                    const size_t n = sl.busy ? std::min((size_t)live_block, sl.it.noisy.size() - sl.at) : 0;
+                    if (n) packed.insert(packed.end(), sl.it.noisy.begin() + sl.at, sl.it.noisy.begin() + sl.at + n);
+                    sl.at += n;
+                    add[u] = (int64_t)n;
+                    off[u + 1] = off[u] + (int64_t)n;
+                    end[u] = sl.busy && sl.at == sl.it.noisy.size();
+                }
+                if (mlggd_live_received(g, had.data()) != MLGGD_OK ||
+                    mlggd_live_layout(fs, ctx, n_slots, had.data(), add.data(), end.data(), out_off.data()) != MLGGD_OK)
+                    die(std::string("mlggd_live_layout: ") + mlggd_last_error());
+                enh.resize((size_t)out_off[n_slots] + 1);
+                if (mlggd_live_push(g, packed.data(), off.data(), end.data(), enh.data(), nullptr, out_off[n_slots],
+                                    out_off.data()) != MLGGD_OK)
+                    die(std::string("mlggd_live_push: ") + mlggd_last_error());
+                for (int u = 0; u < n_slots; u++) {
+                    Slot &sl = slots[u];
+                    sl.out.insert(sl.out.end(), enh.begin() + out_off[u], enh.begin() + out_off[u + 1]);
+                    if (!end[u]) continue;
+                    tool_io::write_wav(sl.it.job.out, sl.out.data(), sl.out.size(), sl.it.rate);
+                    printf("%s -> %s (%d frames)\n", sl.it.job.in.c_str(), sl.it.job.out.c_str(), sl.it.F);
+                    sl.busy = false;
+                }
+            }
+            mlggd_live_close(g);
+        }
+        mlggd_destroy(h);
+        return 0;
     }
     const bool batched = !scp.empty() && batch_s > 0;
 
