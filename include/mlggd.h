@@ -182,6 +182,37 @@ int mlggd_enhance_waves_scored(mlggd_handle h, int fs_khz, int fea_context, cons
                                const int64_t *offsets, const int32_t *score_frames /* optional */, int16_t *out,
                                float *out_f32 /* optional */, float *lps_out /* optional */, float *segsnr, float *lsd);
 
+/* ---- STOI on the device (csrc/stoi.hip.h, csrc/stoi_rule.h): the short-time objective intelligibility measure of
+ * Taal, Hendriks, Heusdens and Jensen (2011) of a processed int16 wave against the clean int16 wave, per utterance of
+ * a packed batch, in fp32: both waves resampled to 10 kHz (8 kHz by 5/4, "11" = 11 000 Hz by 10/11, 16 kHz by 5/8; a
+ * Kaiser-windowed sinc computed on the host in double), the frames (256 samples, hop 128) whose clean energy is more
+ * than 40 dB below the loudest removed, 15 third-octave bands of 512-point spectra, segments of 30 frames, clipping at
+ * -15 dB.  stoi_samples[u] (NULL: all) = the leading samples of utterance u that are scored, 0 <= stoi_samples[u] <=
+ * its samples.  An utterance with fewer than 30 frames left after the removal (too short, a silent clean wave,
+ * stoi_samples[u] = 0) has no value: stoi[u] = NaN and segments[u] = 0; that is not an error.  segments (optional)
+ * [n_utts] receives the number of 30-frame segments behind each value.  An utterance's value depends on that utterance
+ * alone: the same bits whatever its neighbours, its position, the batch, max_cache_frames and the run.  NULL pointers,
+ * decreasing offsets, a stoi_samples[u] out of range and a bad fs_khz are MLGGD_ERR_ARG (the message names the
+ * utterance), found before any device call.
+ * mlggd_stoi_layout: host only, no device: the 10 kHz samples and the frames of an utterance of n_samples, and the
+ * segments it has if every frame is kept (each output optional).
+ * mlggd_stoi_waves: stateless, any device; `clean` and `proc` are packed with the same `offsets`.
+ * mlggd_enhance_waves_scored_stoi: mlggd_enhance_waves_scored plus the STOI of the pass's own int16 output against
+ * the clean wave, taken from device memory on the engine's stream: no host round trip of the waves, no second decoding
+ * pass, the clean wave goes up once and 2 n_utts more words come back.  The enhanced wave of utterance u has F_u S + L
+ * - S samples: stoi_samples[u] is checked against the utterance's samples and at most the enhanced wave's are scored.
+ * out / out_f32 / lps_out / segsnr / lsd are those of mlggd_enhance_waves_scored bit for bit; the buffers only grow. */
+int mlggd_stoi_layout(int fs_khz, int64_t n_samples, int64_t *len10, int64_t *frames, int64_t *min_segments);
+int mlggd_stoi_waves(int device, int fs_khz, int n_utts, const int16_t *clean, const int16_t *proc,
+                     const int64_t *offsets /* [n_utts+1] */, const int64_t *stoi_samples /* optional */,
+                     float *stoi /* [n_utts] */, int32_t *segments /* optional [n_utts] */);
+int mlggd_enhance_waves_scored_stoi(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean,
+                                    const float *norm_inv_std, int n_utts, const int16_t *noisy, const int16_t *clean,
+                                    const int64_t *offsets, const int32_t *score_frames /* optional */, int16_t *out,
+                                    float *out_f32 /* optional */, float *lps_out /* optional */, float *segsnr,
+                                    float *lsd, const int64_t *stoi_samples /* optional */, float *stoi,
+                                    int32_t *segments /* optional */);
+
 /* ---- live audio: a *live group* is n_sessions independent audio sessions decoded block by block on one engine; all
  * share fs_khz, fea_context and the norm vectors.  With half = (fea_context - 1) / 2 and F(n) the frame count above, a
  * session that has received n samples has decoded T = max(0, F(n) - half) frames while it runs (frame t needs the rows

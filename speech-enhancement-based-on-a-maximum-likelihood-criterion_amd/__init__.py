@@ -53,6 +53,7 @@ EXPORTS = [
     "mlggd_wave_to_lps", "mlggd_lps_to_wave", "mlggd_enhance_wave",
     "mlggd_enhance_waves_layout", "mlggd_enhance_waves",
     "mlggd_score_waves", "mlggd_enhance_waves_scored",
+    "mlggd_stoi_layout", "mlggd_stoi_waves", "mlggd_enhance_waves_scored_stoi",
     "mlggd_live_layout", "mlggd_live_open", "mlggd_live_push", "mlggd_live_received", "mlggd_live_close",
 ]
 
@@ -62,7 +63,7 @@ _lib = None
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
-                                             "live_rule.h")]
+                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -141,6 +142,9 @@ def load():
     L.mlggd_score_waves.argtypes = [C.c_int, C.c_int, C.c_int, _sp, _sp, _lp, _fp, _ip, _fp, _fp]
     L.mlggd_enhance_waves_scored.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _sp, _lp, _ip, _sp,
                                              _fp, _fp, _fp, _fp]
+    L.mlggd_stoi_layout.argtypes = [C.c_int, C.c_int64, _lp, _lp, _lp]
+    L.mlggd_stoi_waves.argtypes = [C.c_int, C.c_int, C.c_int, _sp, _sp, _lp, _lp, _fp, _ip]
+    L.mlggd_enhance_waves_scored_stoi.argtypes = L.mlggd_enhance_waves_scored.argtypes + [_lp, _fp, _ip]
     _bp = C.POINTER(C.c_uint8)
     L.mlggd_live_layout.argtypes = [C.c_int, C.c_int, C.c_int, _lp, _lp, _bp, _lp]
     L.mlggd_live_open.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, C.POINTER(C.c_void_p)]
@@ -390,6 +394,44 @@ def score_waves(cleans, noisys, lps_list, fs_khz=16, device=0, score_frames=None
     return segsnr, lsd
 
 
+def stoi_layout(n_samples, fs_khz=16):
+    """(len10, frames, min_segments_if_all_kept) of an utterance of n_samples for STOI (stoi_waves): its samples at
+    10 kHz, its frames of 256 at hop 128, and the 30-frame segments it has when no frame is removed as silent.  A host
+    call: needs no device (mlggd_stoi_layout)."""
+    a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    _check(load().mlggd_stoi_layout(int(fs_khz), int(n_samples), C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def _stoi_samples(stoi_samples, n):
+    if stoi_samples is None:
+        return None
+    ss = np.ascontiguousarray(stoi_samples, dtype=np.int64)
+    if ss.shape != (n,):
+        raise ValueError("stoi_samples must hold one count per utterance")
+    return ss
+
+
+def stoi_waves(cleans, procs, fs_khz=16, device=0, stoi_samples=None, return_segments=False):
+    """STOI [n] float32 (Taal et al. 2011) of the processed int16 waves procs[u] against the clean int16 waves
+    cleans[u], in one pass over the device (mlggd_stoi_waves).  stoi_samples[u] = the leading samples that are scored
+    (None: as many as both waves have).  NaN where the utterance has no value: fewer than 30 frames after the silent
+    ones are removed.  return_segments: (stoi, segments [n] int32), the 30-frame segments behind each value."""
+    procs = [_wave(w) for w in procs]
+    n = len(procs)
+    clean = _clean_like(cleans, procs)
+    ss = _stoi_samples(stoi_samples, n)
+    if ss is None:
+        ss = np.array([min(_wave(c).size, w.size) for c, w in zip(cleans, procs)], np.int64).reshape(n)
+    packed = np.concatenate(procs) if n else np.zeros(0, np.int16)
+    off = _offsets([w.size for w in procs])
+    _lp = C.POINTER(C.c_int64)
+    stoi, seg = np.zeros(n, np.float32), np.zeros(n, np.int32)
+    _check(load().mlggd_stoi_waves(int(device), int(fs_khz), n, _sp(clean), _sp(packed), off.ctypes.data_as(_lp),
+                                   ss.ctypes.data_as(_lp), _p(stoi), seg.ctypes.data_as(C.POINTER(C.c_int32))))
+    return (stoi, seg) if return_segments else stoi
+
+
 def comm_unique_id():
     buf = (C.c_char * UNIQUE_ID_BYTES)()
     _check(load().mlggd_comm_unique_id(buf))
@@ -538,14 +580,19 @@ class BPGpu:
         return (out, outf) if return_float else out
 
     def enhance_waves(self, waves, mean, inv_std, fs_khz=16, fea_context=None, return_f32=False, return_lps=False,
-                      cleans=None, score_frames=None):
+                      cleans=None, score_frames=None, stoi=False, stoi_samples=None):
         """enhance_wave over a list of int16 waves in one pass over the device (mlggd_enhance_waves): a list of int16
         arrays, each bit-equal to enhance_wave on that wave alone; with return_f32 / return_lps a tuple of lists, the
         float32 waves before the cast and the de-normalised network outputs [F_u][D] added in that order.
         fea_context None: layersizes[0] / bins.  With cleans (one clean wave per utterance, cut or zero-padded to the
         noisy wave's length) the quality report of the same pass (mlggd_enhance_waves_scored) is added at the end of
         the tuple: segsnr [n] and lsd [n] float32, over the leading score_frames[u] frames of each utterance (None:
-        all; 0: not scored, both 0)."""
+        all; 0: not scored, both 0).  With stoi=True (needs cleans) stoi [n] float32 follows them: the STOI of the
+        pass's own int16 output against the clean wave (mlggd_enhance_waves_scored_stoi; stoi_waves on the same waves
+        bit for bit), over the leading stoi_samples[u] samples (None: as many as the clean and the noisy wave both
+        have); NaN where the utterance has no value."""
+        if stoi and cleans is None:
+            raise ValueError("stoi=True needs the clean waves")
         waves = [_wave(w) for w in waves]
         L, S, N = SPECTRAL_PARAMS[int(fs_khz)]
         D = N // 2 + 1
@@ -568,11 +615,19 @@ class BPGpu:
             clean = _clean_like(cleans, waves)
             sf = _score_frames(score_frames, n)
             segsnr, lsd = np.zeros(n, np.float32), np.zeros(n, np.float32)
-            _check(load().mlggd_enhance_waves_scored(
-                self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), n, _sp(packed), _sp(clean),
-                off.ctypes.data_as(C.POINTER(C.c_int64)),
-                sf.ctypes.data_as(C.POINTER(C.c_int32)) if sf is not None else None, _sp(out),
-                _p(outf) if return_f32 else None, _p(lps) if return_lps else None, _p(segsnr), _p(lsd)))
+            args = (self._h, int(fs_khz), int(fea_context), _p(mean), _p(inv), n, _sp(packed), _sp(clean),
+                    off.ctypes.data_as(C.POINTER(C.c_int64)),
+                    sf.ctypes.data_as(C.POINTER(C.c_int32)) if sf is not None else None, _sp(out),
+                    _p(outf) if return_f32 else None, _p(lps) if return_lps else None, _p(segsnr), _p(lsd))
+            if stoi:
+                ss = _stoi_samples(stoi_samples, n)
+                if ss is None:
+                    ss = np.array([min(_wave(c).size, w.size) for c, w in zip(cleans, waves)], np.int64).reshape(n)
+                stoi_v = np.zeros(n, np.float32)
+                _check(load().mlggd_enhance_waves_scored_stoi(*args, ss.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                              _p(stoi_v), None))
+            else:
+                _check(load().mlggd_enhance_waves_scored(*args))
         res = [[out[out_off[u]:out_off[u + 1]] for u in range(n)]]
         if return_f32:
             res.append([outf[out_off[u]:out_off[u + 1]] for u in range(n)])
@@ -580,6 +635,8 @@ class BPGpu:
             res.append([lps[frame_off[u]:frame_off[u + 1]] for u in range(n)])
         if cleans is not None:
             res += [segsnr, lsd]
+            if stoi:
+                res.append(stoi_v)
         return res[0] if len(res) == 1 else tuple(res)
 
     def live(self, mean, inv_std, n_sessions, fs_khz=16, fea_context=None):

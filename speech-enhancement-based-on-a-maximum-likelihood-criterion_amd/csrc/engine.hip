@@ -23,6 +23,8 @@
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
+#include "stoi.hip.h"
+#include "stoi_rule.h"
 #include "live.hip.h"
 #include "live_rule.h"
 
@@ -225,10 +227,13 @@ struct mlggd_engine {
     struct WavesWs {
         WsBuf wave, lps, X, blk, out_i, out_f, lps_den, norm, frame_off, out_off, wave_off, utt_of;
         WsBuf clean, Xc, fstat, sframes, scores;  // mlggd_enhance_waves_scored (score.hip.h)
+        WsBuf stoi_utt, stoi_x, stoi_f, stoi_i, stoi_res;  // mlggd_enhance_waves_scored_stoi (stoi.hip.h)
         std::vector<int32_t> h_frame_off, h_utt_of;
         std::vector<long long> h_out_off, h_wave_off;
         std::vector<float> h_norm;  // [2 D]: mean, inv_std as uploaded last
         std::vector<float> h_scores;  // [2 n_utts]: segsnr, lsd as downloaded
+        std::vector<StoiUtt> h_stoi_utt;  // [n_utts] as uploaded
+        std::vector<float> h_stoi;        // [2 n_utts]: stoi, then the segment counts (int) as downloaded
         int lookup_table = 0;       // utterance of a frame: 0 = binary search over frame_off (default), 1 = per-frame
                                     // table (MLGGD_WAVES_LOOKUP=table, for A/B runs)
     } ww;
@@ -1758,7 +1763,8 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
     for (mlggd_engine::WsBuf *b : {&e->ww.wave, &e->ww.lps, &e->ww.X, &e->ww.blk, &e->ww.out_i, &e->ww.out_f,
                                    &e->ww.lps_den, &e->ww.norm, &e->ww.frame_off, &e->ww.out_off, &e->ww.wave_off,
-                                   &e->ww.utt_of, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores})
+                                   &e->ww.utt_of, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores,
+                                   &e->ww.stoi_utt, &e->ww.stoi_x, &e->ww.stoi_f, &e->ww.stoi_i, &e->ww.stoi_res})
         if (b->p) hipFree(b->p);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
     for (int l = 0; l < MLGGD_MAXLAYER; l++) {
@@ -3046,6 +3052,126 @@ int launch_score(const SpecPlan *p, const int16_t *clean, const long long *wave_
     return launch_check("k_score_utt");
 }
 
+// ---- STOI (stoi.hip.h, stoi_rule.h).  The window and the three resampling filters are computed in double, rounded to
+// float and uploaded once per device; the FFT twiddles are the 16 kHz tables of the spectral plan (N = 512).
+struct StoiPlan {
+    float *win = nullptr;                       // [256]
+    float *h[3] = {nullptr, nullptr, nullptr};  // [2 Lh + 1] per rate slot
+};
+StoiPlan g_stoi[SPEC_MAX_DEVICES];
+
+int stoi_plan(int device, const StoiPlan **out, const SpecPlan **fft) {
+    CHK(spec_plan(device, 16, fft));  // checks the device index too
+    std::lock_guard<std::mutex> lock(g_spec_mu);
+    StoiPlan &p = g_stoi[device];
+    if (!p.win) {
+        const int rates[3] = {8, 11, 16};
+        for (int r : rates) {
+            int pp, qq, slot;
+            stoi_rule::rate(r, &pp, &qq, &slot);
+            const std::vector<float> h = stoi_rule::filter(pp, qq);
+            HIPCHK(hipMalloc((void **)&p.h[slot], h.size() * sizeof(float)));
+            HIPCHK(hipMemcpy(p.h[slot], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        const std::vector<float> w = stoi_rule::window();
+        float *dw = nullptr;
+        HIPCHK(hipMalloc((void **)&dw, w.size() * sizeof(float)));
+        HIPCHK(hipMemcpy(dw, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        p.win = dw;
+    }
+    *out = &p;
+    return MLGGD_OK;
+}
+
+// what the kernels need to know about a batch, found on the host before any device call
+struct StoiJob {
+    int p = 0, q = 0, slot = 0, FT = 0;
+    long long T10 = 0;
+};
+
+// utt[u] for clean samples from coff[u] and processed samples from poff[u]: stoi_samples[u] (NULL: all) must lie in
+// 0..len[u]; at most have[u] of them are scored (the processed wave may be shorter than the utterance)
+int stoi_job(int fs_khz, int n_utts, const long long *coff, const long long *poff, const long long *len,
+             const long long *have, const int64_t *stoi_samples, std::vector<StoiUtt> &utt, StoiJob *job) {
+    if (!stoi_rule::rate(fs_khz, &job->p, &job->q, &job->slot))
+        return fail(MLGGD_ERR_ARG, "fs_khz %d: must be 8, 11 or 16", fs_khz);
+    utt.resize((size_t)n_utts);
+    long long t10 = 0, ft = 0;
+    for (int u = 0; u < n_utts; u++) {
+        long long n = len[u];
+        if (stoi_samples) {
+            if (stoi_samples[u] < 0 || stoi_samples[u] > len[u])
+                return fail(MLGGD_ERR_ARG, "utterance %d: stoi_samples %lld is outside 0..%lld, its samples", u,
+                            (long long)stoi_samples[u], len[u]);
+            n = stoi_samples[u];
+        }
+        if (n > have[u]) n = have[u];
+        if (n > stoi_rule::kMaxSamples)
+            return fail(MLGGD_ERR_ARG, "utterance %d: %lld samples exceed the %lld one wave may have", u, n,
+                        (long long)stoi_rule::kMaxSamples);
+        StoiUtt &U = utt[u];
+        U.coff = coff[u], U.poff = poff[u], U.off10 = t10;
+        U.len = (int)n;
+        U.len10 = (int)stoi_rule::len10(n, job->p, job->q);
+        U.foff = (int)ft;
+        U.frames = (int)stoi_rule::frames(U.len10);
+        t10 += U.len10;
+        ft += U.frames;
+        if (ft > INT32_MAX / 2)
+            return fail(MLGGD_ERR_ARG, "the batch has more than %d STOI frames (reached at utterance %d)", INT32_MAX / 2, u);
+    }
+    job->T10 = t10, job->FT = (int)ft;
+    return MLGGD_OK;
+}
+
+// device buffers of one STOI pass: utt [n], x [2 T10] (clean, processed at 10 kHz), f [31 FT] (frame energies, X and Y
+// band roots), i [FT + n] (kept map, kept counts), res [2 n] (stoi; segment counts as int)
+struct StoiDev {
+    StoiUtt *utt;
+    float *x, *f;
+    int *i;
+    float *res;
+};
+
+int launch_stoi(const StoiPlan *sp, const SpecPlan *fft, const StoiJob &job, const int16_t *clean, const int16_t *proc,
+                int n_utts, const StoiDev &b, hipStream_t st) {
+    const size_t T10 = (size_t)job.T10, FT = (size_t)job.FT;
+    float *xc = b.x, *xp = b.x + T10, *en = b.f, *Xb = b.f + FT, *Yb = b.f + FT + FT * STOI_BANDS;
+    int *map = b.i, *kept = b.i + FT;
+    if (T10) {
+        hipLaunchKernelGGL(k_stoi_resample, dim3((unsigned)((T10 + 255) / 256)), dim3(256), 0, st, clean, proc,
+                           (const StoiUtt *)b.utt, n_utts, (const float *)sp->h[job.slot], job.p, job.q,
+                           stoi_rule::half_taps(job.p, job.q), (long long)job.T10, xc, xp);
+        CHK(launch_check("k_stoi_resample"));
+    }
+    if (FT) {
+        hipLaunchKernelGGL(k_stoi_energy, dim3((unsigned)((FT + 3) / 4)), dim3(256), 0, st, (const float *)xc,
+                           (const StoiUtt *)b.utt, n_utts, job.FT, (const float *)sp->win, en);
+        CHK(launch_check("k_stoi_energy"));
+    }
+    hipLaunchKernelGGL(k_stoi_select, dim3((unsigned)n_utts), dim3(64 * STOI_SELECT_WAVES), 0, st,
+                       (const StoiUtt *)b.utt, (const float *)en, map, kept);
+    CHK(launch_check("k_stoi_select"));
+    if (FT) {
+        StoiBandTable bands;
+        for (int j = 0; j < STOI_BANDS; j++) bands.lo[j] = stoi_rule::kBandLo[j], bands.hi[j] = stoi_rule::kBandHi[j];
+        hipLaunchKernelGGL(k_stoi_bands, dim3(spec_grid(job.FT)), dim3(64 * SPEC_FRAMES), 0, st, (const float *)xc,
+                           (const float *)xp, (const StoiUtt *)b.utt, n_utts, job.FT, (const float *)sp->win,
+                           (const float2 *)fft->tw, (const float2 *)fft->tws, (const int *)map, (const int *)kept, bands,
+                           Xb, Yb);
+        CHK(launch_check("k_stoi_bands"));
+    }
+    hipLaunchKernelGGL(k_stoi_utt, dim3((unsigned)n_utts), dim3(64 * SCORE_UTT_WAVES), 0, st, (const StoiUtt *)b.utt,
+                       (const int *)kept, (const float *)Xb, (const float *)Yb, (float)pow(10.0, 15.0 / 20.0), b.res,
+                       (int *)(b.res + n_utts));
+    return launch_check("k_stoi_utt");
+}
+
+void stoi_results(const float *h, int n_utts, float *stoi, int32_t *segments) {
+    memcpy(stoi, h, (size_t)n_utts * sizeof(float));
+    if (segments) memcpy(segments, h + n_utts, (size_t)n_utts * sizeof(int32_t));
+}
+
 }  // namespace
 
 extern "C" {
@@ -3164,7 +3290,8 @@ int mlggd_enhance_waves_layout(int fs_khz, int n_utts, const int64_t *offsets, i
 static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fea_context, const float *norm_mean,
                              const float *norm_inv_std, int n_utts, const int16_t *noisy, const int16_t *clean,
                              const int64_t *offsets, const int32_t *score_frames, int16_t *out, float *out_f32,
-                             float *lps_out, float *segsnr, float *lsd) {
+                             float *lps_out, float *segsnr, float *lsd, const int64_t *stoi_samples = nullptr,
+                             float *stoi = nullptr, int32_t *segments = nullptr) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     SpecDims d;
     int slot;
@@ -3192,6 +3319,16 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
         }
     }
     if (clean) CHK(check_score_frames(n_utts, w.h_frame_off.data(), score_frames));
+    StoiJob sjob;
+    if (stoi) {  // the enhanced wave of utterance u has out_off[u + 1] - out_off[u] samples: no more can be scored
+        std::vector<long long> len((size_t)n_utts), have((size_t)n_utts);
+        for (int u = 0; u < n_utts; u++) {
+            len[u] = w.h_wave_off[u + 1] - w.h_wave_off[u];
+            have[u] = w.h_out_off[u + 1] - w.h_out_off[u];
+        }
+        CHK(stoi_job(fs_khz, n_utts, w.h_wave_off.data(), w.h_out_off.data(), len.data(), have.data(), stoi_samples,
+                     w.h_stoi_utt, &sjob));
+    }
     const int FT = w.h_frame_off[n_utts];  // every utterance has a frame: FT >= n_utts
     const size_t n_wave = (size_t)w.h_wave_off[n_utts], n_out = (size_t)w.h_out_off[n_utts];
     const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
@@ -3224,6 +3361,17 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
         CHK(ws_grow(e, w.fstat, (size_t)3 * FT, &fstat));
         CHK(ws_grow(e, w.scores, (size_t)2 * n_utts, &scores));
         if (score_frames) CHK(ws_grow(e, w.sframes, (size_t)n_utts, &d_sf));
+    }
+    const StoiPlan *splan = nullptr;
+    const SpecPlan *sfft = nullptr;
+    StoiDev sdev = {};
+    if (stoi) {
+        CHK(stoi_plan(e->device, &splan, &sfft));
+        CHK(ws_grow(e, w.stoi_utt, (size_t)n_utts, &sdev.utt));
+        CHK(ws_grow(e, w.stoi_x, (size_t)2 * sjob.T10, &sdev.x));
+        CHK(ws_grow(e, w.stoi_f, (size_t)(1 + 2 * STOI_BANDS) * sjob.FT, &sdev.f));
+        CHK(ws_grow(e, w.stoi_i, (size_t)sjob.FT + n_utts, &sdev.i));
+        CHK(ws_grow(e, w.stoi_res, (size_t)2 * n_utts, &sdev.res));
     }
     CHK(ws_grow(e, w.frame_off, (size_t)n_utts + 1, &d_foff));
     CHK(ws_grow(e, w.out_off, (size_t)n_utts + 1, &d_ooff));
@@ -3288,11 +3436,18 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
         w.h_scores.resize((size_t)2 * n_utts);
         HIPCHK(hipMemcpyAsync(w.h_scores.data(), scores, (size_t)2 * n_utts * sizeof(float), hipMemcpyDeviceToHost, st));
     }
+    if (stoi) {  // the pass's own int16 output, still on the device, against the clean wave uploaded above
+        HIPCHK(hipMemcpyAsync(sdev.utt, w.h_stoi_utt.data(), (size_t)n_utts * sizeof(StoiUtt), hipMemcpyHostToDevice, st));
+        CHK(launch_stoi(splan, sfft, sjob, d_clean, oi, n_utts, sdev, st));
+        w.h_stoi.resize((size_t)2 * n_utts);
+        HIPCHK(hipMemcpyAsync(w.h_stoi.data(), sdev.res, (size_t)2 * n_utts * sizeof(float), hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(hipStreamSynchronize(st));
     if (clean) {
         memcpy(segsnr, w.h_scores.data(), (size_t)n_utts * sizeof(float));
         memcpy(lsd, w.h_scores.data() + n_utts, (size_t)n_utts * sizeof(float));
     }
+    if (stoi) stoi_results(w.h_stoi.data(), n_utts, stoi, segments);
     return MLGGD_OK;
 }
 
@@ -3364,6 +3519,76 @@ int mlggd_score_waves(int device, int fs_khz, int n_utts, const int16_t *clean, 
     HIPCHK(hipMemcpy(h.data(), scores, h.size() * sizeof(float), hipMemcpyDeviceToHost));
     memcpy(segsnr, h.data(), (size_t)n_utts * sizeof(float));
     memcpy(lsd, h.data() + n_utts, (size_t)n_utts * sizeof(float));
+    return MLGGD_OK;
+}
+
+int mlggd_enhance_waves_scored_stoi(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean,
+                                    const float *norm_inv_std, int n_utts, const int16_t *noisy, const int16_t *clean,
+                                    const int64_t *offsets, const int32_t *score_frames, int16_t *out, float *out_f32,
+                                    float *lps_out, float *segsnr, float *lsd, const int64_t *stoi_samples, float *stoi,
+                                    int32_t *segments) {
+    if (e && n_utts > 0 && (!clean || !segsnr || !lsd || !stoi))
+        return fail(MLGGD_ERR_ARG, "clean/segsnr/lsd/stoi is NULL");
+    return enhance_waves_run(e, "mlggd_enhance_waves_scored_stoi", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts,
+                             noisy, clean, offsets, score_frames, out, out_f32, lps_out, segsnr, lsd, stoi_samples, stoi,
+                             segments);
+}
+
+int mlggd_stoi_layout(int fs_khz, int64_t n_samples, int64_t *len10, int64_t *frames, int64_t *min_segments) {
+    int p, q, slot;
+    if (!stoi_rule::rate(fs_khz, &p, &q, &slot)) return fail(MLGGD_ERR_ARG, "fs_khz %d: must be 8, 11 or 16", fs_khz);
+    if (n_samples < 0 || n_samples > stoi_rule::kMaxSamples)
+        return fail(MLGGD_ERR_ARG, "n_samples %lld is outside 0..%lld", (long long)n_samples,
+                    (long long)stoi_rule::kMaxSamples);
+    const int64_t l10 = stoi_rule::len10(n_samples, p, q), F = stoi_rule::frames(l10);
+    if (len10) *len10 = l10;
+    if (frames) *frames = F;
+    if (min_segments) *min_segments = stoi_rule::segments(stoi_rule::compacted(F));
+    return MLGGD_OK;
+}
+
+int mlggd_stoi_waves(int device, int fs_khz, int n_utts, const int16_t *clean, const int16_t *proc,
+                     const int64_t *offsets, const int64_t *stoi_samples, float *stoi, int32_t *segments) {
+    int p, q, slot;
+    if (!stoi_rule::rate(fs_khz, &p, &q, &slot)) return fail(MLGGD_ERR_ARG, "fs_khz %d: must be 8, 11 or 16", fs_khz);
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (n_utts == 0) return MLGGD_OK;
+    if (!clean || !proc || !offsets || !stoi) return fail(MLGGD_ERR_ARG, "clean/proc/offsets/stoi is NULL");
+    std::vector<long long> off((size_t)n_utts), len((size_t)n_utts);
+    for (int u = 0; u < n_utts; u++) {
+        if (offsets[u + 1] < offsets[u])
+            return fail(MLGGD_ERR_ARG, "offsets decrease at utterance %d (%lld after %lld)", u, (long long)offsets[u + 1],
+                        (long long)offsets[u]);
+        off[u] = (long long)offsets[u] - (long long)offsets[0];
+        len[u] = (long long)offsets[u + 1] - (long long)offsets[u];
+    }
+    std::vector<StoiUtt> utt;
+    StoiJob job;
+    CHK(stoi_job(fs_khz, n_utts, off.data(), off.data(), len.data(), len.data(), stoi_samples, utt, &job));
+    const size_t n_wave = (size_t)((long long)offsets[n_utts] - (long long)offsets[0]);
+    HIPCHK(hipSetDevice(device));
+    const StoiPlan *sp;
+    const SpecPlan *fft;
+    CHK(stoi_plan(device, &sp, &fft));
+    DevBufs b;
+    int16_t *dc = nullptr, *dp = nullptr;
+    StoiDev sd = {};
+    CHK(b.alloc(&dc, n_wave));
+    CHK(b.alloc(&dp, n_wave));
+    CHK(b.alloc(&sd.utt, (size_t)n_utts));
+    CHK(b.alloc(&sd.x, (size_t)2 * job.T10));
+    CHK(b.alloc(&sd.f, (size_t)(1 + 2 * STOI_BANDS) * job.FT));
+    CHK(b.alloc(&sd.i, (size_t)job.FT + n_utts));
+    CHK(b.alloc(&sd.res, (size_t)2 * n_utts));
+    if (n_wave) {
+        HIPCHK(hipMemcpy(dc, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dp, proc + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(sd.utt, utt.data(), (size_t)n_utts * sizeof(StoiUtt), hipMemcpyHostToDevice));
+    CHK(launch_stoi(sp, fft, job, dc, dp, n_utts, sd, nullptr));
+    std::vector<float> h((size_t)2 * n_utts);
+    HIPCHK(hipMemcpy(h.data(), sd.res, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+    stoi_results(h.data(), n_utts, stoi, segments);
     return MLGGD_OK;
 }
 

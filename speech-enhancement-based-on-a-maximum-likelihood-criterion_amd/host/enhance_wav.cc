@@ -6,7 +6,7 @@
 //
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
-//               [score=host|device] [live=BLOCK [sessions=64]]
+//               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]]
 //
 // scp lists "in out" or "in out clean info" lines.  A list is decoded in batches of batch_s seconds of audio by
 // mlggd_enhance_waves: the utterances of a batch form one frame stream, so the forward bunches are full, and the
@@ -21,11 +21,16 @@
 // batch_s=0 lines as batches of one), over the frames the clean wave has; the clean waves are read before the pass, and
 // a list ends with one line: the number of scored utterances and their mean segmental SNR and LSD.  The enhanced waves
 // are the same bytes either way; it adds 512 B clean wave + 2056 B clean spectrum + 12 B per frame to the figures above.
+// stoi=1 (with score=device): mlggd_enhance_waves_scored_stoi also forms the STOI of every scored utterance's enhanced
+// int16 wave against its clean wave, over the samples both the clean and the noisy wave have: the utterance's line on
+// stdout ends with " stoi=V" (nan: too short or silent for a value) and the last line with the mean over the utterances
+// that have a value and their number.  Files and the other lines are the same bytes with and without it.
 // live=BLOCK (scp lists of "in out" lines): the utterances are decoded as concurrent live sessions of one group
 // (mlggd_live_*): every push feeds BLOCK samples to each of up to `sessions` utterances, an utterance is ended with its
 // last block, and its slot is refilled from the list.  The group is reopened where the sample rate changes.  The files
 // are byte-identical to the default mode's; the lines on stdout come in the order the utterances finish.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -80,9 +85,9 @@ int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp, clean, info, score = "host";
     const char *usage =
         "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
-        "[batch_s=300] [clean=F info=F] [score=host|device] [live=BLOCK [sessions=64]]";
+        "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]]";
     int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64;
-    bool live = false, score_given = false;
+    bool live = false, score_given = false, want_stoi = false;
     double batch_s = 300.0;
     for (int a = 1; a < argc; a++) {
         const std::string arg(argv[a]);
@@ -101,6 +106,7 @@ int main(int argc, char **argv) {
         else if (k == "bunchsize") bunch = atoi(v.c_str());
         else if (k == "batch_s") batch_s = atof(v.c_str());
         else if (k == "score") score = v, score_given = true;
+        else if (k == "stoi") want_stoi = atoi(v.c_str()) != 0;
         else if (k == "live") live_block = atoi(v.c_str()), live = true;
         else if (k == "sessions") n_slots = atoi(v.c_str());
         else die("unknown argument " + k);
@@ -109,6 +115,7 @@ int main(int argc, char **argv) {
         die(usage);
     if (score != "host" && score != "device") die("score=" + score + ": must be host or device\n" + usage);
     const bool on_device = score == "device";
+    if (want_stoi && !on_device) die("stoi=1 needs score=device: STOI is formed on the GPU only\n" + std::string(usage));
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
     if (clean.empty() != info.empty()) die("clean= and info= go together");
     if (!clean.empty() && !scp.empty()) die("clean= / info= need a single in= / out= pair (or four-field scp lines)");
@@ -243,8 +250,8 @@ int main(int argc, char **argv) {
     // the batch: utterances of one rate, decoded by one mlggd_enhance_waves call when it is full or the rate changes
     std::vector<Item> pend;
     size_t pend_samples = 0;
-    int n_scored = 0;
-    double sum_segsnr = 0.0, sum_lsd = 0.0;
+    int n_scored = 0, n_stoi = 0;
+    double sum_segsnr = 0.0, sum_lsd = 0.0, sum_stoi = 0.0;
     auto flush = [&]() {
         if (pend.empty()) return;
         const int n = (int)pend.size(), fs = pend[0].fs;
@@ -263,16 +270,24 @@ int main(int argc, char **argv) {
             die(std::string("mlggd_enhance_waves_layout: ") + mlggd_last_error());
         std::vector<int16_t> enh((size_t)out_off[n]);
         std::vector<float> lps(want_lps ? (size_t)frame_off[n] * D : 0);
-        std::vector<float> segsnr(scored ? n : 0), lsd(scored ? n : 0);
+        std::vector<float> segsnr(scored ? n : 0), lsd(scored ? n : 0), stoi(scored && want_stoi ? n : 0);
         if (scored) {  // the clean waves in the noisy layout, zero-padded; an utterance without one scores no frame
             std::vector<int16_t> cpacked((size_t)off[n], 0);
             std::vector<int32_t> sframes(n, 0);
+            std::vector<int64_t> ssamples(n, 0);
             for (int u = 0; u < n; u++) {
                 const std::vector<int16_t> &c = pend[u].clean;
                 std::copy(c.begin(), c.begin() + std::min(c.size(), pend[u].noisy.size()), cpacked.begin() + off[u]);
                 sframes[u] = pend[u].Fm;
+                ssamples[u] = (int64_t)std::min(c.size(), pend[u].noisy.size());
             }
-            if (mlggd_enhance_waves_scored(h, fs, ctx, mean.data(), inv.data(), n, packed.data(), cpacked.data(),
+            if (want_stoi) {
+                if (mlggd_enhance_waves_scored_stoi(h, fs, ctx, mean.data(), inv.data(), n, packed.data(),
+                                                    cpacked.data(), off.data(), sframes.data(), enh.data(), nullptr,
+                                                    nullptr, segsnr.data(), lsd.data(), ssamples.data(), stoi.data(),
+                                                    nullptr) != MLGGD_OK)
+                    die(std::string("mlggd_enhance_waves_scored_stoi: ") + mlggd_last_error());
+            } else if (mlggd_enhance_waves_scored(h, fs, ctx, mean.data(), inv.data(), n, packed.data(), cpacked.data(),
                                            off.data(), sframes.data(), enh.data(), nullptr, nullptr, segsnr.data(),
                                            lsd.data()) != MLGGD_OK)
                 die(std::string("mlggd_enhance_waves_scored: ") + mlggd_last_error());
@@ -282,7 +297,17 @@ int main(int argc, char **argv) {
         for (int u = 0; u < n; u++) {
             const Item &it = pend[u];
             tool_io::write_wav(it.job.out, enh.data() + out_off[u], (size_t)(out_off[u + 1] - out_off[u]), it.rate);
-            printf("%s -> %s (%d frames)\n", it.job.in.c_str(), it.job.out.c_str(), it.F);
+            printf("%s -> %s (%d frames)", it.job.in.c_str(), it.job.out.c_str(), it.F);
+            if (scored && want_stoi && !it.job.clean.empty()) {
+                if (std::isnan(stoi[u])) {
+                    printf(" stoi=nan");
+                } else {
+                    printf(" stoi=%f", stoi[u]);
+                    n_stoi++;
+                    sum_stoi += stoi[u];
+                }
+            }
+            printf("\n");
             if (it.job.clean.empty()) continue;
             if (scored) {
                 tool_io::write_info(it.job.info, segsnr[u], lsd[u]);
@@ -351,11 +376,15 @@ int main(int argc, char **argv) {
     }
     flush();
     if (on_device && !scp.empty()) {
-        if (n_scored)
-            printf("scored %d utterances: mean segmental SNR %f dB, mean LSD %f dB\n", n_scored, sum_segsnr / n_scored,
+        if (n_scored) {
+            printf("scored %d utterances: mean segmental SNR %f dB, mean LSD %f dB", n_scored, sum_segsnr / n_scored,
                    sum_lsd / n_scored);
-        else
+            if (want_stoi && n_stoi) printf(", mean STOI %f over %d utterances", sum_stoi / n_stoi, n_stoi);
+            else if (want_stoi) printf(", no utterance has a STOI value");
+            printf("\n");
+        } else {
             printf("scored 0 utterances\n");
+        }
     }
     mlggd_destroy(h);
     return 0;
