@@ -26,6 +26,7 @@ extern "C" {
 #define MLGGD_MAXLAYER 10          /* BP_GPU.h:6  MAXLAYER */
 #define MLGGD_MAXCACHEFRAME 200000 /* BP_GPU.h:7  MAXCACHEFRAME */
 #define MLGGD_UNIQUE_ID_BYTES 128  /* sizeof(ncclUniqueId) */
+#define MLGGD_MAX_BETAS 32         /* shapes per mlggd_error_stats call */
 
 enum {
     MLGGD_OK = 0,
@@ -116,6 +117,42 @@ int mlggd_cv_all_frames(mlggd_handle h, int n_frames, int fea_context, const flo
                         float *loglik);
 int mlggd_forward_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat, int n_samples,
                          const int32_t *first_frame, float *out);
+/* ---- the GGD error model on the device (no counterpart in the reference, which only ever holds the alpha of the
+ * last training minibatch and evaluates CrossValid2 at it, BP_GPU.cu:271-301).  The ML criterion models the error
+ * e = out - targ of every output bin d as a generalized Gaussian  beta / (2 alpha_d Gamma(1/beta)) exp(-(|e|/alpha_d)^beta);
+ * its sufficient statistics are per-bin sums over a CV pass.
+ *
+ * mlggd_error_stats / mlggd_error_stats_frames mirror mlggd_cv_all / mlggd_cv_all_frames: the chunk is loaded WITH
+ * its targets, the CV forward runs per bunch (trailing partial bunch included), and one kernel per bunch folds the
+ * bunch into sums kept on the device.  Per element x = slab sum + bias in fp32 (the bits mlggd_forward returns),
+ * e = x - t in fp32; the terms e, e*e, (e*e)*e, (e*e)*(e*e) are formed in double from that fp32 e, and for each k the
+ * fp32 value pow_or_self(|e|, betas[k]) of the trainer's own power is widened to double.  On return
+ *   sums[0..3][d] = sum e, e^2, e^3, e^4        sums[4 + k][d] = sum |e|^betas[k]        (sums is [4 + n_betas][D])
+ * OVERWRITTEN, not accumulated: the statistics are additive, a caller with several chunks adds the arrays.  The
+ * order of every addition is fixed by the sample's position in its bunch, the bunch index and bunchsize: two calls
+ * return the same bits, and the two entries return the same bits for the same rows.  (4 + n_betas) * D doubles come
+ * back, nothing of size n x D.  n_frames / n_samples == 0 returns zeros.
+ * NULL pointers, n_betas outside 1..MLGGD_MAX_BETAS, a beta <= 0 or not finite and a shape mismatch are
+ * MLGGD_ERR_ARG, found before any device call.  An engine with a communicator or an emulated world, or with
+ * dropoutflag != 0, is MLGGD_ERR_STATE; the engine stays usable. */
+int mlggd_error_stats(mlggd_handle h, int n_frames, const float *in, const float *targ,
+                      int n_betas, const float *betas, double *sums /* [4 + n_betas][D] */);
+int mlggd_error_stats_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,
+                             int n_samples, const int32_t *first_frame, int targ_offset,
+                             int n_betas, const float *betas, double *sums);
+/* mlggd_ggd_fit: host only, no device, all in double: the fit of the model to sums over n samples (added over the
+ * chunks by the caller).  mean = S1/n, var = the central second moment, kurt = m4/m2^2 - 3 (central moments from the
+ * raw sums).  For every grid shape the ML scale is alpha_d(beta)^beta = beta * P_beta,d / n -- the trainer's
+ * scalefactor expression over the whole set -- at which sum (|e|/alpha)^beta = n/beta, so the profile log-likelihood
+ * is  l_d(beta) = n [ln beta - ln 2 - lgamma(1/beta) - ln alpha_d(beta) - 1/beta]  (libm lgamma).
+ * alpha, loglik: [n_betas][D]; best[d] = the grid index with the largest l_d; loglik_shared[k] = sum_d l_d(beta_k)
+ * and best_shared its argmax -- the value for `shapefactor`, since the trainer shares one beta over all bins with an
+ * alpha per bin.  Ties go to the lower index.  A bin with sum e^2 == 0 has no fit: alpha 0, loglik and kurt NaN,
+ * best -1, left out of the shared totals (no bin with a fit: best_shared -1).  Every output pointer is optional.
+ * n <= 0, D < 1, NULL betas / sums and a bad grid are MLGGD_ERR_ARG. */
+int mlggd_ggd_fit(int D, int64_t n, int n_betas, const float *betas, const double *sums,
+                  double *mean, double *var, double *kurt, double *alpha, double *loglik, int32_t *best,
+                  double *loglik_shared, int32_t *best_shared);
 /* pinned host memory for chunk buffers (optional; faster H2D than pageable memory) */
 int mlggd_alloc_pinned(size_t bytes, void **out);
 /* the same from a thread that has not selected a device (host IO threads): pins through `device`'s context */

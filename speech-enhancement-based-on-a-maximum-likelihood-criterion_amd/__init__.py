@@ -5,6 +5,7 @@
 returnWeights) over libmlggd.so.  There is NO CPU fallback: if the HIP library is missing
 or no GPU is present, construction raises.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -55,7 +56,9 @@ EXPORTS = [
     "mlggd_score_waves", "mlggd_enhance_waves_scored",
     "mlggd_stoi_layout", "mlggd_stoi_waves", "mlggd_enhance_waves_scored_stoi",
     "mlggd_live_layout", "mlggd_live_open", "mlggd_live_push", "mlggd_live_received", "mlggd_live_close",
+    "mlggd_error_stats", "mlggd_error_stats_frames", "mlggd_ggd_fit",
 ]
+MAX_BETAS = 32
 
 _lib = None
 
@@ -63,7 +66,7 @@ _lib = None
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
-                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h")]
+                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -151,6 +154,10 @@ def load():
     L.mlggd_live_push.argtypes = [C.c_void_p, _sp, _lp, _bp, _sp, _fp, C.c_int64, _lp]
     L.mlggd_live_received.argtypes = [C.c_void_p, _lp]
     L.mlggd_live_close.argtypes = [C.c_void_p]
+    _dp = C.POINTER(C.c_double)
+    L.mlggd_error_stats.argtypes = [C.c_void_p, C.c_int, _fp, _fp, C.c_int, _fp, _dp]
+    L.mlggd_error_stats_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, C.c_int, _fp, _dp]
+    L.mlggd_ggd_fit.argtypes = [C.c_int, C.c_int64, C.c_int, _fp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip]
     _lib = L
     return L
 
@@ -432,6 +439,36 @@ def stoi_waves(cleans, procs, fs_khz=16, device=0, stoi_samples=None, return_seg
     return (stoi, seg) if return_segments else stoi
 
 
+GgdFit = collections.namedtuple("GgdFit", "mean var kurt alpha loglik best loglik_shared best_shared")
+
+
+def _betas(betas):
+    b = np.ascontiguousarray(betas, dtype=np.float32)
+    if b.ndim != 1:
+        raise ValueError("betas is a 1-D grid of shapes")
+    return b
+
+
+def ggd_fit(n, sums, betas):
+    """Fit of the GGD error model to the [4 + K][D] sums of BPGpu.error_stats over n samples (added over the chunks
+    by the caller): a GgdFit of mean, var, kurt [D], alpha, loglik [K][D] (ML scale and profile log-likelihood per
+    grid shape), best [D] (grid index per bin, -1 where the bin has no fit), loglik_shared [K] and best_shared, the
+    grid index to put into `shapefactor`.  A host call: needs no device (mlggd_ggd_fit)."""
+    b = _betas(betas)
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != 4 + b.size:
+        raise ValueError("sums must be [4 + len(betas)][D]")
+    K, D = b.size, s.shape[1]
+    _dp, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    mean, var, kurt = np.zeros(D), np.zeros(D), np.zeros(D)
+    alpha, loglik = np.zeros((K, D)), np.zeros((K, D))
+    best, shared, bs = np.zeros(D, np.int32), np.zeros(K), C.c_int32(0)
+    d = lambda a: a.ctypes.data_as(_dp)
+    _check(load().mlggd_ggd_fit(D, int(n), K, _p(b), d(s), d(mean), d(var), d(kurt), d(alpha), d(loglik),
+                                best.ctypes.data_as(_i32), d(shared), C.byref(bs)))
+    return GgdFit(mean, var, kurt, alpha, loglik, best, shared, bs.value)
+
+
 def comm_unique_id():
     buf = (C.c_char * UNIQUE_ID_BYTES)()
     _check(load().mlggd_comm_unique_id(buf))
@@ -554,6 +591,29 @@ class BPGpu:
                                           first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset), C.byref(a),
                                           C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    # -- the GGD error model: per-bin sums of e^1..4 and |e|^beta over a CV chunk, formed on the device (ggd_fit fits them)
+    def error_stats(self, inp, targ, betas):
+        """[4 + K][D] float64: sum e, e^2, e^3, e^4 and sum |e|^betas[k] per output bin over the rows of inp / targ,
+        e = forward(inp) - targ (mlggd_error_stats).  Additive over chunks."""
+        inp, targ, b = _f32(inp), _f32(targ), _betas(betas)
+        n = inp.shape[0]
+        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
+            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
+        sums = np.zeros((4 + b.size, self.D), np.float64)
+        _check(load().mlggd_error_stats(self._h, n, _p(inp), _p(targ), b.size, _p(b),
+                                        sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def error_stats_frames(self, feat, targ, first_frame, fea_context, targ_offset, betas):
+        """The same over a frame-stream chunk (mlggd_error_stats_frames): the same bits for the same rows."""
+        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
+        b = _betas(betas)
+        sums = np.zeros((4 + b.size, self.D), np.float64)
+        _check(load().mlggd_error_stats_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
+                                               first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset), b.size,
+                                               _p(b), sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
 
     def forward_frames(self, feat, first_frame, fea_context):
         feat, _, first = self._frames_args(feat, None, first_frame, fea_context)

@@ -27,6 +27,7 @@
 #include "stoi_rule.h"
 #include "live.hip.h"
 #include "live_rule.h"
+#include "errstats.hip.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -200,6 +201,7 @@ struct mlggd_engine {
     int cv_device = 0;
     double *cv_partial = nullptr;
     size_t cv_partial_cap = 0;
+    double *es_acc = nullptr;  // mlggd_error_stats: [4 + MLGGD_MAX_BETAS][D] sums of the call, allocated on first use
     size_t chunk_cap = 0, out_cap = 0;
     int chunk_frames = 0;
     // indexed chunk: raw frame streams + first frame of every sample row
@@ -1752,6 +1754,7 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->chunk_targ) hipFree(e->chunk_targ);
     if (e->chunk_out) hipFree(e->chunk_out);
     if (e->cv_partial) hipFree(e->cv_partial);
+    if (e->es_acc) hipFree(e->es_acc);
     for (auto &t : e->dwp_tables) hipFree(t.dev);
     if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
     for (auto &r : e->raw) {
@@ -2270,6 +2273,127 @@ int mlggd_forward_frames(mlggd_handle e, int n_frames, int fea_context, const fl
     CHK(forward_resident(e, n_samples));
     HIPCHK(hipMemcpyAsync(out, e->chunk_out, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+// ------------------------------------------------------------------ error model (errstats.hip.h)
+static int check_betas(int n_betas, const float *betas) {
+    if (n_betas < 1 || n_betas > MLGGD_MAX_BETAS)
+        return fail(MLGGD_ERR_ARG, "n_betas %d not in 1..%d", n_betas, MLGGD_MAX_BETAS);
+    if (!betas) return fail(MLGGD_ERR_ARG, "betas is NULL");
+    for (int k = 0; k < n_betas; k++)
+        if (!(betas[k] > 0.0f) || !std::isfinite(betas[k]))
+            return fail(MLGGD_ERR_ARG, "betas[%d] = %g: a shape must be positive and finite", k, (double)betas[k]);
+    return MLGGD_OK;
+}
+static int error_stats_state(mlggd_engine *e, const char *who) {
+    if (e->comm || e->fake_world) return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
+    if (e->cfg.dropoutflag != 0)
+        return fail(MLGGD_ERR_STATE, "%s: the error model is not available with dropoutflag = %d", who, e->cfg.dropoutflag);
+    return MLGGD_OK;
+}
+// The chunk (inputs AND targets) is resident: the CV forward per bunch, trailing partial bunch included, each
+// followed by ONE k_err_stats launch that folds the bunch into es_acc; one download and one synchronise.
+static int error_stats_resident(mlggd_engine *e, int n, int n_betas, const float *betas, double *sums) {
+    const int D = e->D, rows = 4 + n_betas;
+    if (!e->es_acc) HIPCHK(hipMalloc((void **)&e->es_acc, (size_t)(4 + MLGGD_MAX_BETAS) * D * sizeof(double)));
+    ErrStatsArgs a;
+    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
+    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = e->es_acc;
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < n_betas ? betas[k] : 1.0f;
+    for (int i = 0; i < n; i += e->B) {
+        const int fb = (e->B > n - i) ? (n - i) : e->B;
+        const Bunch bn = bunch_at(e, i);
+        CHK(run_forward(e, bn, fb, false));
+        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = i == 0;
+        hipLaunchKernelGGL(k_err_stats, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
+        CHK(launch_check("k_err_stats"));
+    }
+    HIPCHK(hipMemcpyAsync(sums, e->es_acc, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_error_stats(mlggd_handle e, int n_frames, const float *in, const float *targ, int n_betas,
+                      const float *betas, double *sums) {
+    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    CHK(check_betas(n_betas, betas));
+    CHK(check_frames(e, n_frames));
+    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
+    CHK(error_stats_state(e, "mlggd_error_stats"));
+    if (n_frames == 0) {
+        std::fill(sums, sums + (size_t)(4 + n_betas) * e->D, 0.0);
+        return MLGGD_OK;
+    }
+    CHK(mlggd_load_chunk(e, n_frames, in, targ));
+    return error_stats_resident(e, n_frames, n_betas, betas, sums);
+}
+
+int mlggd_error_stats_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                             int n_samples, const int32_t *first_frame, int targ_offset, int n_betas,
+                             const float *betas, double *sums) {
+    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    CHK(check_betas(n_betas, betas));
+    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
+    CHK(error_stats_state(e, "mlggd_error_stats_frames"));
+    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
+    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
+    if (n_samples == 0) {
+        std::fill(sums, sums + (size_t)(4 + n_betas) * e->D, 0.0);
+        return MLGGD_OK;
+    }
+    return error_stats_resident(e, n_samples, n_betas, betas, sums);
+}
+
+// Host only, no device: moments, ML scale and profile log-likelihood of the GGD error model from the sums of
+// mlggd_error_stats.  Everything in double; lgamma is libm's (the reference's polynomial Gamma, mlggd_gamma, stays
+// with the log lines it belongs to).
+int mlggd_ggd_fit(int D, int64_t n, int n_betas, const float *betas, const double *sums, double *mean, double *var,
+                  double *kurt, double *alpha, double *loglik, int32_t *best, double *loglik_shared,
+                  int32_t *best_shared) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n <= 0) return fail(MLGGD_ERR_ARG, "n %lld: the fit needs at least one sample", (long long)n);
+    CHK(check_betas(n_betas, betas));
+    if (!sums) return fail(MLGGD_ERR_ARG, "sums is NULL");
+    const double nn = (double)n, nan = std::nan("");
+    std::vector<double> shared(n_betas, 0.0);
+    for (int d = 0; d < D; d++) {
+        const double s1 = sums[d], s2 = sums[(size_t)D + d], s3 = sums[(size_t)2 * D + d], s4 = sums[(size_t)3 * D + d];
+        const bool fit = s2 != 0.0;  // every error of the bin is zero: no scale, no likelihood
+        const double mu = s1 / nn, r2 = s2 / nn, r3 = s3 / nn, r4 = s4 / nn;
+        const double m2 = r2 - mu * mu;
+        const double m4 = ((r4 - 4.0 * mu * r3) + 6.0 * (mu * mu) * r2) - 3.0 * ((mu * mu) * (mu * mu));
+        if (mean) mean[d] = mu;
+        if (var) var[d] = m2;
+        if (kurt) kurt[d] = fit ? m4 / (m2 * m2) - 3.0 : nan;
+        int arg = -1;
+        double top = 0.0;
+        for (int k = 0; k < n_betas; k++) {
+            const double b = (double)betas[k];
+            double a = 0.0, l = nan;
+            if (fit) {
+                const double lna = log(b * sums[(size_t)(4 + k) * D + d] / nn) / b;  // alpha^beta = beta P / n
+                a = exp(lna);
+                l = nn * ((((log(b) - log(2.0)) - lgamma(1.0 / b)) - lna) - 1.0 / b);
+                shared[k] += l;
+                if (arg < 0 || l > top) {
+                    arg = k;
+                    top = l;
+                }
+            }
+            if (alpha) alpha[(size_t)k * D + d] = a;
+            if (loglik) loglik[(size_t)k * D + d] = l;
+        }
+        if (best) best[d] = arg;
+    }
+    int arg = -1;
+    bool any = false;
+    for (int d = 0; d < D; d++) any = any || sums[(size_t)D + d] != 0.0;
+    if (any)
+        for (int k = 0; k < n_betas; k++)
+            if (arg < 0 || shared[k] > shared[arg]) arg = k;
+    if (loglik_shared) std::copy(shared.begin(), shared.end(), loglik_shared);
+    if (best_shared) *best_shared = arg;
     return MLGGD_OK;
 }
 

@@ -1,0 +1,91 @@
+// errstats.hip.h -- the error statistics of a CV chunk (mlggd_error_stats): per output bin d the sums over the
+// chunk's samples of  e, e^2, e^3, e^4  and of  |e|^beta_k  for a grid of K shapes, e = out - targ.  They are the
+// sufficient statistics of the GGD error model the ML criterion trains under (mlggd_ggd_fit turns them into the
+// moments, the ML scale per shape and the profile likelihood), formed beside the CV forward pass so that nothing of
+// size n x D leaves the device.  Included by engine.hip after kernels.hip.h (slab_sum, pow_or_self).
+//
+// Per element:  x = slab_sum + bias[d] in fp32 by the expression of k_cv_reduce / k_out_rowmajor (the bits
+// mlggd_forward returns);  e = x - t, one fp32 subtraction (the loss chain's kernerror);  the four moment terms in
+// DOUBLE from that fp32 e:  e, e*e, (e*e)*e, (e*e)*(e*e);  the power terms pow_or_self(fabsf(e), beta_k), the fp32
+// value of the trainer's own pow_det -- evaluated once per beta ON PURPOSE: one logarithm shared by the grid would be
+// cheaper and would leave the bits the trainer and oracle/pyoracle.pow_det agree on -- widened to double.
+//
+// The cut is that of the loss kernels: one workgroup = ES_DT = 8 bins x 32 frames, lanes along the frames (slab rows
+// read in 128-byte segments, targets in 32-byte pieces).  A half-wave owns ONE bin for the whole bunch: lane j adds
+// the rows j, j + 32, j + 64, ... of the bunch in that order into its 4 + K double accumulators, the 32 lanes are
+// combined by an xor butterfly (16, 8, 4, 2, 1: both partners form the same commutative sum), and lane 0 folds the
+// bunch's sum into acc[4 + K][D] -- written when the bunch is the call's first, added otherwise.  Bunches follow
+// each other on the engine's stream, so the order of every addition is a function of the row's position in its bunch,
+// of the bunch index and of bunchsize alone: no atomics, one launch per bunch, and device memory that does not depend
+// on the number of samples.  The accumulators are indexed by unrolled constants only (K <= 32 is tested against the
+// unrolled index, a wave-uniform branch): 36 doubles in registers, no scratch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/mlggd.h"
+
+constexpr int ES_DT = 8;  // bins per workgroup, one per half-wave
+
+struct ErrStatsArgs {
+    const float *slab;
+    int S;
+    const float *bias, *targ;
+    int B, D, Dp, Bp;
+    const int *first;
+    int toff;
+    int K;       // 1..MLGGD_MAX_BETAS
+    int fresh;   // 1: this bunch is the call's first -- acc is written, not added to
+    double *acc; // [4 + K][D]
+    float betas[MLGGD_MAX_BETAS];
+};
+
+__global__ __launch_bounds__(256) void k_err_stats(ErrStatsArgs A) {
+    const int tx = threadIdx.x & 31;
+    const int d = (int)blockIdx.x * ES_DT + (int)(threadIdx.x >> 5);  // < Dp: the grid is Dp / ES_DT
+    double m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
+    double pw[MLGGD_MAX_BETAS];
+#pragma unroll
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++) pw[k] = 0.0;
+    if (d < A.D) {
+        const float bias = A.bias[d];
+        for (int b = tx; b < A.B; b += 32) {
+            float x = slab_sum(A.slab, (size_t)d * A.Bp + b, (size_t)A.Dp * A.Bp, A.S);
+            x = x + bias;
+            const float t = A.targ[(size_t)(A.first ? A.first[b] + A.toff : b) * A.D + d];
+            const float e = x - t;
+            const double e1 = (double)e, e2 = e1 * e1;
+            m1 += e1;
+            m2 += e2;
+            m3 += e2 * e1;
+            m4 += e2 * e2;
+            const float a = fabsf(e);
+#pragma unroll
+            for (int k = 0; k < MLGGD_MAX_BETAS; k++)
+                if (k < A.K) pw[k] += (double)pow_or_self(a, A.betas[k]);
+        }
+    }
+#pragma unroll
+    for (int off = 16; off > 0; off >>= 1) {
+        m1 += __shfl_xor(m1, off, 64);
+        m2 += __shfl_xor(m2, off, 64);
+        m3 += __shfl_xor(m3, off, 64);
+        m4 += __shfl_xor(m4, off, 64);
+    }
+#pragma unroll
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++)
+        if (k < A.K) {
+#pragma unroll
+            for (int off = 16; off > 0; off >>= 1) pw[k] += __shfl_xor(pw[k], off, 64);
+        }
+    if (tx == 0 && d < A.D) {
+        double *p = A.acc + d;
+        const size_t D = (size_t)A.D;
+        p[0 * D] = A.fresh ? m1 : p[0 * D] + m1;
+        p[1 * D] = A.fresh ? m2 : p[1 * D] + m2;
+        p[2 * D] = A.fresh ? m3 : p[2 * D] + m3;
+        p[3 * D] = A.fresh ? m4 : p[3 * D] + m4;
+#pragma unroll
+        for (int k = 0; k < MLGGD_MAX_BETAS; k++)
+            if (k < A.K) p[(4 + k) * D] = A.fresh ? pw[k] : p[(4 + k) * D] + pw[k];
+    }
+}

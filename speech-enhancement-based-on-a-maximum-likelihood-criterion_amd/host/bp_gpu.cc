@@ -103,6 +103,15 @@ void BP_GPU::CrossValidAll_frames(int n_frames, int fea_context, const float *fe
                               loglik),
           "mlggd_cv_all_frames");
 }
+void BP_GPU::ErrorStats(int n, const float *in, const float *targ, int n_betas, const float *betas, double *sums) {
+    check(mlggd_error_stats(h_, n, in, targ, n_betas, betas, sums), "mlggd_error_stats");
+}
+void BP_GPU::ErrorStats_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
+                               const int *first_frame, int targ_offset, int n_betas, const float *betas, double *sums) {
+    check(mlggd_error_stats_frames(h_, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, n_betas,
+                                   betas, sums),
+          "mlggd_error_stats_frames");
+}
 void BP_GPU::returnWeights(float **weights, float **bias) {
     check(mlggd_get_weights(h_, weights, bias), "mlggd_get_weights");
 }

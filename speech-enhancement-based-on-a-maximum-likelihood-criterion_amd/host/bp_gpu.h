@@ -31,6 +31,11 @@ class BP_GPU {
     void sync();
     void CrossValidAll_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
                               const int *first_frame, int targ_offset, float *sqerr, float *abserr, float *loglik);
+    // error statistics of a CV chunk (not in the reference): sums [4 + n_betas][D] of e^1..4 and |e|^beta per output
+    // bin, overwritten; see mlggd_error_stats.  Needs a single-device engine without dropout.
+    void ErrorStats(int n_frames, const float *in, const float *targ, int n_betas, const float *betas, double *sums);
+    void ErrorStats_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
+                           const int *first_frame, int targ_offset, int n_betas, const float *betas, double *sums);
     void returnWeights(float **weights, float **bias);
     float Gamma(float x) { return mlggd_gamma(x); }
     // data parallel (not in the reference): join an RCCL communicator of `world` ranks

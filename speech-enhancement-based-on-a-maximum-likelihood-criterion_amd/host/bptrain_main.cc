@@ -11,6 +11,12 @@
 // first frame of every (shuffled) sample row and are gathered on the GPU; MLGGD_EXPANDED=1 selects
 // the reference's host-side context expansion (Interface::Readchunk) instead -- same results.
 //
+// Error model (new, opt-in): with MLGGD_ERRMODEL=FILE rank 0 makes a second pass over the CV chunks after the three CV
+// log lines, adds their error statistics (mlggd_error_stats: per-bin sums of e^1..4 and |e|^beta over the grid of
+// MLGGD_ERRMODEL_BETAS=lo:step:hi, default 0.5:0.1:2.5), fits the GGD per bin and shared (mlggd_ggd_fit) and writes
+// FILE (errmodel.h); one stdout line names the file and the shared beta -- the value for `shapefactor`.  The
+// command line, the log file and the weights do not change.
+//
 // Data parallel (new): when WORLD_SIZE > 1 (torchrun-style env: RANK,
 // LOCAL_RANK, WORLD_SIZE; MLGGD_ID_FILE names a file on a shared filesystem used to hand the
 // RCCL unique id from rank 0 to the others) every rank reads the same chunks with the same
@@ -31,6 +37,7 @@
 
 #include "bp_gpu.h"
 #include "dp_launch.h"
+#include "errmodel.h"
 #include "prefetch.h"
 #include "trainer_io.h"
 
@@ -120,6 +127,10 @@ int main(int argc, char *argv[]) {
         io->Initial(argc, argv, /*open_output=*/rank == 0);
         phase("arguments, norm, init weights", t_phase);
         WorkPara *p = io->para;
+        const char *errmodel_fn = getenv("MLGGD_ERRMODEL");
+        if (errmodel_fn && !*errmodel_fn) errmodel_fn = nullptr;
+        std::vector<float> errmodel_betas;  // a bad grid ends the run here, not after the epoch
+        if (errmodel_fn && rank == 0) errmodel_betas = mlggd_host::beta_grid(getenv("MLGGD_ERRMODEL_BETAS"));
         // ---- train (BPtrain.cc:81-102).  The chunk plan and the fetch thread only touch host state, so the
         // first chunk is read while the engine initialises HIP and uploads the weights (the reference creates
         // BP_GPU first, BPtrain.cc:77-78, and reads the first chunk afterwards).
@@ -269,6 +280,34 @@ int main(int argc, char *argv[]) {
             }
             if (io->fp_log) fflush(io->fp_log);
             phase("cross validation", t_phase);
+
+            // ---- error model of the CV set (MLGGD_ERRMODEL): a second pass, nothing of it reaches the log
+            if (errmodel_fn && (p->dropoutflag != 0 || world > 1)) {
+                printf("error model: not available %s; %s is not written\n",
+                       p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", errmodel_fn);
+            } else if (errmodel_fn) {
+                const int K = (int)errmodel_betas.size();
+                std::vector<double> total((size_t)(4 + K) * D, 0.0), part(total.size());
+                int64_t n_total = 0;
+                for (unsigned i = 0; i < io->cv_total_chunks; i++) {
+                    progress("error model");
+                    int n;
+                    if (frames) {
+                        n = io->Readchunk_frames_cv((int)i);
+                        net->ErrorStats_frames(p->chunk_frames[0], p->fea_context, p->frames_in[0], p->frames_targ[0], n,
+                                               p->first_frame[0], p->targ_offset, K, errmodel_betas.data(), part.data());
+                    } else {
+                        n = io->Readchunk_cv((int)i);
+                        net->ErrorStats(n, p->indata[0], p->targ[0], K, errmodel_betas.data(), part.data());
+                    }
+                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
+                    n_total += n;
+                }
+                if (n_total == 0) throw IoError(std::string("MLGGD_ERRMODEL: the CV set has no samples, ") + errmodel_fn + " is not written");
+                const double shared = mlggd_host::write_error_model(errmodel_fn, D, n_total, errmodel_betas, total);
+                printf("error model: %s written, %lld CV samples, shared beta %.9g\n", errmodel_fn, (long long)n_total, shared);
+                phase("error model", t_phase);
+            }
         }
         printf("all finish!\n");
         g_progress = -1000000;  // the watchdog leaves
