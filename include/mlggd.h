@@ -298,6 +298,32 @@ int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias)
 int mlggd_set_weights(mlggd_handle h, const float *const *weights, const float *const *bias);
 int mlggd_get_scalefactor(mlggd_handle h, float *alpha /* [D] */);
 int mlggd_set_scalefactor(mlggd_handle h, const float *alpha /* [D] */);
+/* One shape per output bin (no counterpart in the reference, whose shapefactor is one float).  With alpha_d in closed
+ * form the ML-GGD objective is a sum over the bins, E = sum_d [ n ln alpha_d + sum_n |e_nd|^beta_d / alpha_d^beta_d ],
+ * alpha_d^beta_d = (beta_d / n) sum_n |e_nd|^beta_d, so column d of the loss chain depends on column d's errors and on
+ * beta_d alone: with a vector set, the loss kernels of every path (fused and MLGGD_LOSS_FUSE=0, a communicator, the
+ * emulated worlds) and both CV log-likelihood paths read beta from a device array, in the expressions and the order
+ * of the scalar kernels -- a uniform vector gives the bits of the scalar engine, and the columns of one value give
+ * the bits of a scalar engine at that value.  CV: density1 = sum_d n logf(beta_d / (2 Gamma(1/beta_d))) in double,
+ * density3 with beta_d per column, density2 as before.  mlggd_error_stats* keep their own grid and are not affected.
+ * mlggd_set_shapefactors is ordered after every step already enqueued, takes effect from the next step or CV call
+ * and leaves the weights, the momentum buffers and the current scalefactor alone.  betas NULL: back to
+ * cfg.shapefactor, the launches of an engine that never had a vector.  A beta that is not positive and finite is
+ * MLGGD_ERR_ARG, found before any device call, the message names the bin; an engine with MLflag != 1 is
+ * MLGGD_ERR_STATE (a beta-norm whose exponent differs per bin has no per-bin scale).  In both cases the engine stays
+ * usable and unchanged.  mlggd_get_shapefactors returns the D values in effect: cfg.shapefactor D times without a
+ * vector. */
+int mlggd_set_shapefactors(mlggd_handle h, const float *betas /* [D], NULL: back to cfg.shapefactor */);
+int mlggd_get_shapefactors(mlggd_handle h, float *betas /* [D] */);
+/* mlggd_read_shapefactors: host only, no device.  Reads D shapes from a plain white-space separated list of exactly D
+ * numbers, or from the file MLGGD_ERRMODEL writes: '#' lines are skipped, the rows `d mean var kurt best_beta ...`
+ * must be rows 0..D-1 in order and field 5 of row d is bin d's shape.  A `nan` best_beta marks a bin without a fit:
+ * it takes the file's `# shared_beta` if that line is there and finite, else `fallback`.  A file counts as an error
+ * model when a '#' line precedes its first number or its first data line has five or more fields and starts with 0.
+ * A wrong row or number count, a row out of order, a field that is no number and a value that is not positive and
+ * finite are MLGGD_ERR_ARG with "PATH line N: ..." as the message; so are a NULL pointer, D < 1 and an unreadable
+ * file. */
+int mlggd_read_shapefactors(const char *path, int D, float fallback, float *betas /* [D] */);
 int mlggd_set_lrate(mlggd_handle h, float lrate);
 /* CV metrics: on = the three sums are formed on the device (per-tile partials in double, combined
  * on the host; no n x D copy, no host loop); off (default, or env MLGGD_CV_DEVICE=0) = outputs copied back and

@@ -57,6 +57,7 @@ EXPORTS = [
     "mlggd_stoi_layout", "mlggd_stoi_waves", "mlggd_enhance_waves_scored_stoi",
     "mlggd_live_layout", "mlggd_live_open", "mlggd_live_push", "mlggd_live_received", "mlggd_live_close",
     "mlggd_error_stats", "mlggd_error_stats_frames", "mlggd_ggd_fit",
+    "mlggd_set_shapefactors", "mlggd_get_shapefactors", "mlggd_read_shapefactors",
 ]
 MAX_BETAS = 32
 
@@ -68,6 +69,7 @@ def build(force=False):
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
+    srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -158,6 +160,9 @@ def load():
     L.mlggd_error_stats.argtypes = [C.c_void_p, C.c_int, _fp, _fp, C.c_int, _fp, _dp]
     L.mlggd_error_stats_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, C.c_int, _fp, _dp]
     L.mlggd_ggd_fit.argtypes = [C.c_int, C.c_int64, C.c_int, _fp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _dp, _ip]
+    L.mlggd_set_shapefactors.argtypes = [C.c_void_p, _fp]
+    L.mlggd_get_shapefactors.argtypes = [C.c_void_p, _fp]
+    L.mlggd_read_shapefactors.argtypes = [C.c_char_p, C.c_int, C.c_float, _fp]
     _lib = L
     return L
 
@@ -469,6 +474,15 @@ def ggd_fit(n, sums, betas):
     return GgdFit(mean, var, kurt, alpha, loglik, best, shared, bs.value)
 
 
+def read_shapefactors(path, D, fallback):
+    """[D] float32 shapes from a plain list of D numbers or from the file MLGGD_ERRMODEL writes (its best_beta column;
+    a bin without a fit takes the file's shared beta, else `fallback`).  A host call: needs no device
+    (mlggd_read_shapefactors); a malformed file raises MlggdError naming the line."""
+    b = np.empty(int(D), np.float32)
+    _check(load().mlggd_read_shapefactors(None if path is None else os.fsencode(path), int(D), float(fallback), _p(b)))
+    return b
+
+
 def comm_unique_id():
     buf = (C.c_char * UNIQUE_ID_BYTES)()
     _check(load().mlggd_comm_unique_id(buf))
@@ -759,6 +773,21 @@ class BPGpu:
     def set_scalefactor(self, alpha):
         a = _f32(alpha, (self.D,))
         _check(load().mlggd_set_scalefactor(self._h, _p(a)))
+
+    def shapefactors(self):
+        """The D shapes in effect: the vector of set_shapefactors, else `shapefactor` D times."""
+        b = np.empty(self.D, np.float32)
+        _check(load().mlggd_get_shapefactors(self._h, _p(b)))
+        return b
+
+    def set_shapefactors(self, betas):
+        """One shape per output bin from the next step or CV call on (MLflag 1 only); None: back to `shapefactor`.
+        Weights, momentum and the current scalefactor stay (mlggd_set_shapefactors)."""
+        if betas is None:
+            _check(load().mlggd_set_shapefactors(self._h, None))
+            return
+        b = _f32(betas, (self.D,))
+        _check(load().mlggd_set_shapefactors(self._h, _p(b)))
 
     def set_lrate(self, lrate):
         _check(load().mlggd_set_lrate(self._h, float(lrate)))

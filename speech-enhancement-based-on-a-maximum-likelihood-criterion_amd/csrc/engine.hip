@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/mlggd.h"
+#include "../host/errmodel.h"  // parse_shapefactors: one file format, one reader and one writer
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
@@ -195,6 +196,11 @@ struct mlggd_engine {
     float *dEdXt[MLGGD_MAXLAYER] = {0}, *dEdX[MLGGD_MAXLAYER] = {0};
     float *slab = nullptr, *outT = nullptr, *eT = nullptr, *pT = nullptr, *colsum = nullptr, *scalefactor = nullptr;
     int S_out = 1;
+    // mlggd_set_shapefactors: one shape per output bin.  betas_dev [Dp] (pads 1.0) exists from the first set on and is
+    // only read while per_bin is on; betas_host [D] is what mlggd_get_shapefactors returns and the CV sums use.
+    bool per_bin = false;
+    float *betas_dev = nullptr;
+    std::vector<float> betas_host;
     float *chunk_in = nullptr, *chunk_targ = nullptr, *chunk_out = nullptr;
     // CV metrics: 0 = outputs copied back, host fp32 accumulation in the reference's order (default: it is what
     // the log lines are compared on); 1 = sums formed on the device (k_cv_reduce), nothing of size n x D leaves it
@@ -1171,6 +1177,12 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         la.outT = e->outT; la.eT = e->eT; la.scalefactor = e->scalefactor; la.dEdXt = e->dEdXt[L - 1]; la.dEdX = e->dEdX[L - 1];
         la.first = bn.first; la.toff = e->toff;
         const size_t lds_ml = (size_t)2 * LOSS_DT * (Bp + 1) * sizeof(float);
+        if (e->per_bin) {
+            CHK(ensure_lds(e, k_loss_ml_bins, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
+            hipLaunchKernelGGL(k_loss_ml_bins, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
+                               (const float *)e->betas_dev, e->Dp / LOSS_DT, sa, n_stage);
+            return launch_check("k_loss_ml_bins");
+        }
         CHK(ensure_lds(e, k_loss_ml, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
         hipLaunchKernelGGL(k_loss_ml, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
                            e->Dp / LOSS_DT, sa, n_stage);
@@ -1181,8 +1193,14 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
     la.B = B; la.D = e->D; la.Dp = e->Dp; la.Bp = Bp; la.beta = e->cfg.shapefactor; la.want_pow = ML == 1 ? 1 : 0;
     la.outT = e->outT; la.eT = e->eT; la.pT = e->pT;
     la.b_tiles = b_tiles; la.first = bn.first; la.toff = e->toff;
-    hipLaunchKernelGGL(k_loss_err, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, n_loss, sa);
-    CHK(launch_check("k_loss_err"));
+    if (e->per_bin) {  // only ever on with ML == 1 (mlggd_set_shapefactors)
+        hipLaunchKernelGGL(k_loss_err_bins, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, (const float *)e->betas_dev,
+                           n_loss, sa);
+        CHK(launch_check("k_loss_err_bins"));
+    } else {
+        hipLaunchKernelGGL(k_loss_err, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, n_loss, sa);
+        CHK(launch_check("k_loss_err"));
+    }
     const float *colsum_in = nullptr;
     if (ML == 1 && cs == CS_GIVEN) {
         colsum_in = e->colsum_tot;
@@ -1199,6 +1217,13 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         colsum_in = e->colsum;
     }
     if (cs == CS_ACCUMULATE) return MLGGD_OK;
+    if (e->per_bin) {
+        CHK(ensure_lds(e, k_loss_grad_bins, LOSS_LDS_MAX));
+        hipLaunchKernelGGL(k_loss_grad_bins, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D,
+                           e->Dp, Bp, (const float *)e->betas_dev, nf, inv_n, e->scalefactor, e->dEdXt[L - 1],
+                           e->dEdX[L - 1], b_tiles);
+        return launch_check("k_loss_grad_bins");
+    }
     CHK(ensure_lds(e, k_loss_grad, LOSS_LDS_MAX));
     hipLaunchKernelGGL(k_loss_grad, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D, e->Dp, Bp,
                        e->cfg.shapefactor, ML, nf, inv_n, e->scalefactor, e->dEdXt[L - 1], e->dEdX[L - 1], b_tiles);
@@ -1838,6 +1863,45 @@ int mlggd_set_scalefactor(mlggd_handle e, const float *alpha) {
     return MLGGD_OK;
 }
 
+int mlggd_set_shapefactors(mlggd_handle e, const float *betas) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!betas) {  // steps already enqueued chose their kernels when they were enqueued
+        e->per_bin = false;
+        e->betas_host.clear();
+        return MLGGD_OK;
+    }
+    if (e->cfg.MLflag != 1)
+        return fail(MLGGD_ERR_STATE, "per-bin shape factors need the ML-GGD loss (MLflag 1), this engine has MLflag %d: a "
+                    "beta-norm whose exponent differs per bin has no per-bin scale", e->cfg.MLflag);
+    for (int d = 0; d < e->D; d++)
+        if (!(betas[d] > 0.0f) || !std::isfinite(betas[d]))
+            return fail(MLGGD_ERR_ARG, "betas[%d] = %g: a shape must be positive and finite", d, (double)betas[d]);
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->betas_dev) CHK(dev_alloc(e, &e->betas_dev, e->Dp));
+    std::vector<float> padded(e->Dp, 1.0f);
+    std::copy(betas, betas + e->D, padded.begin());
+    // on the engine's stream: behind every step already enqueued, which may still read the previous vector
+    HIPCHK(hipMemcpyAsync(e->betas_dev, padded.data(), (size_t)e->Dp * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->betas_host.assign(betas, betas + e->D);
+    e->per_bin = true;
+    return MLGGD_OK;
+}
+
+int mlggd_get_shapefactors(mlggd_handle e, float *betas) {
+    if (!e || !betas) return fail(MLGGD_ERR_ARG, "NULL argument");
+    for (int d = 0; d < e->D; d++) betas[d] = e->per_bin ? e->betas_host[d] : e->cfg.shapefactor;
+    return MLGGD_OK;
+}
+
+int mlggd_read_shapefactors(const char *path, int D, float fallback, float *betas) {
+    if (!path || !betas) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    std::string err;
+    if (!mlggd_host::parse_shapefactors(path, D, fallback, betas, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    return MLGGD_OK;
+}
+
 int mlggd_set_cv_device_reduce(mlggd_handle e, int on) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     e->cv_device = on ? 1 : 0;
@@ -2151,7 +2215,22 @@ static int cv_accumulate(mlggd_engine *e, int n_frames, const std::function<cons
         }
         *abserr = s / D;
     }
-    if (loglik) {
+    if (loglik && e->per_bin) {  // the same three terms with beta_d; density1 is a sum over the bins, kept in double
+        const float *betas = e->betas_host.data();
+        double d1 = 0;
+        for (int d = 0; d < D; d++) d1 += (double)n_frames * logf(betas[d] / (2 * mlggd_gamma((float)(1.0 / betas[d]))));
+        float density2 = 0, density3 = 0;
+        for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
+        density2 = density2 * n_frames;
+        for (int i = 0; i < n_frames; i++) {
+            const float *t = trow(i), *o = &out[(size_t)i * D];
+            for (int d = 0; d < D; d++) {
+                const float err = t[d] - o[d];
+                density3 += powf(fabsf(err) / scalefac[d], betas[d]);
+            }
+        }
+        *loglik = (float)d1 - density2 - density3;
+    } else if (loglik) {
         const float beta = e->cfg.shapefactor;
         float density1, density2 = 0, density3 = 0;
         density1 = n_frames * D * logf(beta / (2 * mlggd_gamma((float)(1.0 / beta))));
@@ -2194,8 +2273,13 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
         a.alpha = loglik ? e->scalefactor : nullptr;
         a.first = bn.first; a.toff = e->toff; a.b_tiles = b_tiles;
         a.partial = e->cv_partial + (size_t)k * tiles * 3;
-        hipLaunchKernelGGL(k_cv_reduce, dim3(tiles), dim3(256), 0, e->stream, a);
-        CHK(launch_check("k_cv_reduce"));
+        if (loglik && e->per_bin) {
+            hipLaunchKernelGGL(k_cv_reduce_bins, dim3(tiles), dim3(256), 0, e->stream, a, (const float *)e->betas_dev);
+            CHK(launch_check("k_cv_reduce_bins"));
+        } else {
+            hipLaunchKernelGGL(k_cv_reduce, dim3(tiles), dim3(256), 0, e->stream, a);
+            CHK(launch_check("k_cv_reduce"));
+        }
     }
     std::vector<double> part((size_t)nb * tiles * 3);
     std::vector<float> scalefac(D);
@@ -2210,7 +2294,14 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
     if (abserr) *abserr = (float)(s[1] / D);
     if (loglik) {  // density1 - density2 - density3, BP_GPU.cu:271-301
         const float beta = e->cfg.shapefactor;
-        const double density1 = (double)n_frames * D * logf(beta / (2 * mlggd_gamma((float)(1.0 / beta))));
+        double density1 = (double)n_frames * D * logf(beta / (2 * mlggd_gamma((float)(1.0 / beta))));
+        if (e->per_bin) {
+            density1 = 0;
+            for (int d = 0; d < D; d++) {
+                const float bd = e->betas_host[d];
+                density1 += (double)n_frames * logf(bd / (2 * mlggd_gamma((float)(1.0 / bd))));
+            }
+        }
         double density2 = 0;
         for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
         *loglik = (float)(density1 - density2 * n_frames - s[2]);

@@ -112,6 +112,7 @@ void BP_GPU::ErrorStats_frames(int n_frames, int fea_context, const float *feat,
                                    betas, sums),
           "mlggd_error_stats_frames");
 }
+void BP_GPU::setShapefactors(const float *betas) { check(mlggd_set_shapefactors(h_, betas), "mlggd_set_shapefactors"); }
 void BP_GPU::returnWeights(float **weights, float **bias) {
     check(mlggd_get_weights(h_, weights, bias), "mlggd_get_weights");
 }

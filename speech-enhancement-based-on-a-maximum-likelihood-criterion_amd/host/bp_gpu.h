@@ -36,6 +36,9 @@ class BP_GPU {
     void ErrorStats(int n_frames, const float *in, const float *targ, int n_betas, const float *betas, double *sums);
     void ErrorStats_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
                            const int *first_frame, int targ_offset, int n_betas, const float *betas, double *sums);
+    // one shape per output bin from the next step or CV call on (not in the reference; MLflag 1 only), nullptr: back
+    // to `shapefactor`; see mlggd_set_shapefactors
+    void setShapefactors(const float *betas);
     void returnWeights(float **weights, float **bias);
     float Gamma(float x) { return mlggd_gamma(x); }
     // data parallel (not in the reference): join an RCCL communicator of `world` ranks

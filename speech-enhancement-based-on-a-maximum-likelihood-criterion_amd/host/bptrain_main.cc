@@ -17,6 +17,12 @@
 // FILE (errmodel.h); one stdout line names the file and the shared beta -- the value for `shapefactor`.  The
 // command line, the log file and the weights do not change.
 //
+// Per-bin shapes (new, opt-in): with MLGGD_SHAPEFACTORS=FILE every rank reads one shape per output bin from FILE -- a
+// plain list of D numbers or the file MLGGD_ERRMODEL wrote in an earlier epoch (its best_beta column; a bin without a
+// fit takes the file's shared beta, else `shapefactor`) -- and sets it on the engine before the first chunk
+// (mlggd_set_shapefactors).  One stderr line names the file and the minimum, maximum and mean shape; the command line
+// and the form of the log lines do not change, the CV log likelihood is then the vector's.  Needs MLflag=1.
+//
 // Data parallel (new): when WORLD_SIZE > 1 (torchrun-style env: RANK,
 // LOCAL_RANK, WORLD_SIZE; MLGGD_ID_FILE names a file on a shared filesystem used to hand the
 // RCCL unique id from rank 0 to the others) every rank reads the same chunks with the same
@@ -131,6 +137,18 @@ int main(int argc, char *argv[]) {
         if (errmodel_fn && !*errmodel_fn) errmodel_fn = nullptr;
         std::vector<float> errmodel_betas;  // a bad grid ends the run here, not after the epoch
         if (errmodel_fn && rank == 0) errmodel_betas = mlggd_host::beta_grid(getenv("MLGGD_ERRMODEL_BETAS"));
+        const char *shapes_fn = getenv("MLGGD_SHAPEFACTORS");
+        if (shapes_fn && !*shapes_fn) shapes_fn = nullptr;
+        std::vector<float> shapes;  // a bad file or a beta-norm run ends here, before anything is trained
+        if (shapes_fn) {
+            if (p->MLflag != 1)
+                throw IoError(std::string("MLGGD_SHAPEFACTORS=") + shapes_fn + ": per-bin shape factors need MLflag=1, this run has MLflag=" +
+                              std::to_string(p->MLflag));
+            shapes.resize(p->layersizes[io->numlayers - 1]);
+            std::string why;
+            if (!mlggd_host::parse_shapefactors(shapes_fn, (int)shapes.size(), p->shapefactor, shapes.data(), &why))
+                throw IoError("MLGGD_SHAPEFACTORS: " + why);
+        }
         // ---- train (BPtrain.cc:81-102).  The chunk plan and the fetch thread only touch host state, so the
         // first chunk is read while the engine initialises HIP and uploads the weights (the reference creates
         // BP_GPU first, BPtrain.cc:77-78, and reads the first chunk afterwards).
@@ -190,6 +208,18 @@ int main(int argc, char *argv[]) {
             exchange_id(world, rank, id);
             net->joinComm(id, world, rank);  // collective: returns once every rank has joined
             if (rank == 0) mlggd_host::rendezvous_cleanup(getenv("MLGGD_ID_FILE"), world);
+        }
+        if (shapes_fn) {
+            net->setShapefactors(shapes.data());
+            float lo = shapes[0], hi = shapes[0];
+            double sum = 0;
+            for (float b : shapes) {
+                lo = b < lo ? b : lo;
+                hi = b > hi ? b : hi;
+                sum += b;
+            }
+            fprintf(stderr, "shape factors: %s, %zu bins, beta min %.9g max %.9g mean %.9g\n", shapes_fn, shapes.size(),
+                    (double)lo, (double)hi, sum / (double)shapes.size());
         }
         phase("engine (HIP init, upload)", t_phase);
         const int K0 = p->layersizes[0], D = p->layersizes[io->numlayers - 1], B = p->bunchsize;
