@@ -290,6 +290,72 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
 int mlggd_live_received(mlggd_live_handle s, int64_t *had /* [n_sessions] */);
 int mlggd_live_close(mlggd_live_handle s);
 
+/* ---- training data from waves (csrc/mix.hip.h, csrc/mix_rule.h; no counterpart in the original project, whose
+ * training set is mixed by outside tools, analysed by Wav2LPS_be, packed into pfiles and normalised by qnnorm before
+ * the trainer sees it).  Clean speech and noise are mixed at an SNR, both waves are analysed and normalised, and the
+ * result is handed to the training loop on the device: no feature row is kept anywhere.
+ *
+ * The mixing rule.  A batch is n_utts clean int16 utterances packed with offsets[n_utts+1] as in mlggd_enhance_waves
+ * (offsets[0] may be non-zero; an utterance may be empty); the noise is one packed int16 buffer of n_noise samples.
+ * Utterance u names the segment [noise_lo[u], noise_lo[u] + noise_len[u]) of it and a start noise_start[u] inside the
+ * segment: sample i is paired with noise[noise_lo[u] + (noise_start[u] + i) mod noise_len[u]], so a short segment
+ * wraps (noise_len[u] = 1 is legal).  Ec = sum clean^2 and En = sum noise^2 over exactly those pairs are exact 64-bit
+ * integers; gain[u] = sqrt((double)Ec / (double)En) * r[u], r[u] = pow(10, -snr_db[u] / 20) from the host's libm;
+ * Ec == 0, En == 0 or snr_db[u] = +inf give gain[u] = 0 and the noisy wave is the clean wave.  noisy[i] =
+ * sat16(rint(clean[i] + gain[u] * noise[.])): product and sum are two double operations, rint rounds to nearest even,
+ * sat16 clamps to [-32768, 32767] and clipped[u] counts the samples it changed.  An utterance's samples depend on that
+ * utterance alone: the same bits whatever its neighbours, its position, the batch and the run.
+ *
+ * mlggd_wave_samples: host only: all windows of fea_context frames that lie inside one utterance, in utterance and
+ * frame order, as indices into the packed frame stream (F_u frames per utterance by the rule above, none for an
+ * utterance shorter than a frame); first_frame NULL = count only.  An utterance with fewer than fea_context frames has
+ * none.  Shuffling is the caller's: permute the table.
+ * mlggd_mix_waves: stateless, any device; noisy is packed like clean; gain / clipped [n_utts] are optional.
+ * mlggd_lps_stats: stateless, any device: sums [2][D] = sum x, sum x^2 per bin in double over the LPS rows of all
+ * utterances (mlggd_wave_to_lps's rows), *n_frames their number.  OVERWRITTEN; the statistics are additive, a caller
+ * with several batches adds the arrays.  A fixed number of rows per workgroup and an ordered fold: the same input
+ * gives the same bits.  An utterance shorter than a frame contributes nothing.
+ * mlggd_norm_from_stats: host only: mean = S1/n, inv_std = 1 / sqrt(S2/n - mean^2) (the population variance) in
+ * double, rounded to float; a bin whose variance is not positive is MLGGD_ERR_ARG naming it.
+ * mlggd_load_waves: the device-side mlggd_load_frames from a wave pair (noisy and clean packed with the same offsets):
+ * feat = (lps(noisy) - mean) * inv_std, targ = (lps(clean) - mean) * inv_std -- the targets take the noisy statistics,
+ * as the trainer's loader does -- over the packed frames, without edge replication; sample i is the window of
+ * fea_context frames from first_frame[i] and its target is frame first_frame[i] + targ_offset.  Afterwards
+ * mlggd_train_resident indexes these samples; every weight equals mlggd_train_frames on the same rows built on the
+ * host, bit for bit.  Needs fea_context * D == layersizes[0] and layersizes[L-1] == D; fea_context need not be odd.
+ * mlggd_cv_all_waves: mlggd_cv_all_frames from a wave pair, the same three sums bit for bit.
+ * mlggd_set_noise: the noise bank stays on the device between calls; NULL / 0 frees it.
+ * mlggd_train_waves: mix from the bank + load + train in one pass on the engine's stream and return after the steps
+ * have completed; the noisy wave never visits the host unless noisy_out (packed like clean), gain or clipped ask.
+ * Errors, all found before any device call: NULL pointers, decreasing offsets, a bad fs_khz, a segment outside the
+ * noise, noise_len[u] < 1, a start outside its segment, an snr_db that is NaN or -inf (the message names the
+ * utterance), a window that crosses an utterance boundary or leaves the packed frames (the message names the sample),
+ * targ_offset outside [0, fea_context) and n_samples above the chunk capacity are MLGGD_ERR_ARG; mlggd_train_waves
+ * without a noise bank and any of the engine calls on an engine with a communicator or an emulated world are
+ * MLGGD_ERR_STATE, and the engine stays usable.  n_utts == 0 or n_samples == 0 does nothing and trains 0 bunches.
+ * The device buffers belong to the engine and only grow. */
+int mlggd_wave_samples(int fs_khz, int fea_context, int n_utts, const int64_t *offsets, int32_t *first_frame,
+                       int64_t *n_samples);
+int mlggd_mix_waves(int device, int n_utts, const int16_t *clean, const int64_t *offsets /* [n_utts+1] */,
+                    const int16_t *noise, int64_t n_noise, const int64_t *noise_lo, const int64_t *noise_len,
+                    const int64_t *noise_start, const double *snr_db, int16_t *noisy /* packed like clean */,
+                    double *gain /* optional */, int32_t *clipped /* optional */);
+int mlggd_lps_stats(int device, int fs_khz, int n_utts, const int16_t *wave, const int64_t *offsets,
+                    double *sums /* [2][D] */, int64_t *n_frames);
+int mlggd_norm_from_stats(int D, int64_t n, const double *sums, float *mean, float *inv_std);
+int mlggd_load_waves(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                     int n_utts, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_samples,
+                     const int32_t *first_frame, int targ_offset);
+int mlggd_cv_all_waves(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                       int n_utts, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_samples,
+                       const int32_t *first_frame, int targ_offset, float *sqerr, float *abserr, float *loglik);
+int mlggd_set_noise(mlggd_handle h, int64_t n_noise, const int16_t *noise);
+int mlggd_train_waves(mlggd_handle h, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                      int n_utts, const int16_t *clean, const int64_t *offsets, const int64_t *noise_lo,
+                      const int64_t *noise_len, const int64_t *noise_start, const double *snr_db, int n_samples,
+                      const int32_t *first_frame, int targ_offset, int16_t *noisy_out /* optional */,
+                      double *gain /* optional */, int32_t *clipped /* optional */, int *bunches_trained);
+
 /* ---- state: BP_GPU::returnWeights (BP_GPU.cu:514-525) and dev.scalefactor (:287) ---- */
 int mlggd_get_weights(mlggd_handle h, float *const *weights, float *const *bias);
 /* mlggd_set_weights replaces W and b of every layer and leaves the momentum buffers as they are; it is ordered after

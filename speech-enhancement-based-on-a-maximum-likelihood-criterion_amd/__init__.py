@@ -58,6 +58,8 @@ EXPORTS = [
     "mlggd_live_layout", "mlggd_live_open", "mlggd_live_push", "mlggd_live_received", "mlggd_live_close",
     "mlggd_error_stats", "mlggd_error_stats_frames", "mlggd_ggd_fit",
     "mlggd_set_shapefactors", "mlggd_get_shapefactors", "mlggd_read_shapefactors",
+    "mlggd_wave_samples", "mlggd_mix_waves", "mlggd_lps_stats", "mlggd_norm_from_stats",
+    "mlggd_load_waves", "mlggd_cv_all_waves", "mlggd_set_noise", "mlggd_train_waves",
 ]
 MAX_BETAS = 32
 
@@ -67,7 +69,8 @@ _lib = None
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
-                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h")]
+                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "mix.hip.h",
+                                             "mix_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     stale = not os.path.exists(LIB_PATH) or any(
@@ -163,6 +166,15 @@ def load():
     L.mlggd_set_shapefactors.argtypes = [C.c_void_p, _fp]
     L.mlggd_get_shapefactors.argtypes = [C.c_void_p, _fp]
     L.mlggd_read_shapefactors.argtypes = [C.c_char_p, C.c_int, C.c_float, _fp]
+    L.mlggd_wave_samples.argtypes = [C.c_int, C.c_int, C.c_int, _lp, _ip, _lp]
+    L.mlggd_mix_waves.argtypes = [C.c_int, C.c_int, _sp, _lp, _sp, C.c_int64, _lp, _lp, _lp, _dp, _sp, _dp, _ip]
+    L.mlggd_lps_stats.argtypes = [C.c_int, C.c_int, C.c_int, _sp, _lp, _dp, _lp]
+    L.mlggd_norm_from_stats.argtypes = [C.c_int, C.c_int64, _dp, _fp, _fp]
+    L.mlggd_load_waves.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _sp, _lp, C.c_int, _ip, C.c_int]
+    L.mlggd_cv_all_waves.argtypes = L.mlggd_load_waves.argtypes + [_fp, _fp, _fp]
+    L.mlggd_set_noise.argtypes = [C.c_void_p, C.c_int64, _sp]
+    L.mlggd_train_waves.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _lp, _lp, _lp, _lp, _dp, C.c_int,
+                                    _ip, C.c_int, _sp, _dp, _ip, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -444,6 +456,84 @@ def stoi_waves(cleans, procs, fs_khz=16, device=0, stoi_samples=None, return_seg
     return (stoi, seg) if return_segments else stoi
 
 
+def _i64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def wave_samples(lengths, fea_context, fs_khz=16):
+    """first_frame [n] int32: every window of fea_context frames that lies inside one utterance of a packed batch of
+    utterances of `lengths` samples, in utterance and frame order, as indices into the packed frame stream -- the sample
+    table of BPGpu.load_waves / train_waves.  Shuffling is the caller's: permute it.  A host call: needs no device
+    (mlggd_wave_samples)."""
+    off = _offsets(lengths)
+    n = C.c_int64(0)
+    _check(load().mlggd_wave_samples(int(fs_khz), int(fea_context), off.size - 1, _i64p(off), None, C.byref(n)))
+    first = np.zeros(n.value, np.int32)
+    _check(load().mlggd_wave_samples(int(fs_khz), int(fea_context), off.size - 1, _i64p(off),
+                                     first.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+    return first
+
+
+def _mix_args(n, n_noise, snr_db, noise_start, noise_seg):
+    """snr_db, noise_start [n] and the segments [(lo, len)] (None: the whole noise for every utterance)"""
+    snr = np.ascontiguousarray(np.broadcast_to(np.asarray(snr_db, np.float64), (n,)))
+    start = np.ascontiguousarray(np.broadcast_to(np.asarray(noise_start, np.int64), (n,)))
+    if noise_seg is None:
+        lo, ln = np.zeros(n, np.int64), np.full(n, n_noise, np.int64)
+    else:
+        seg = np.asarray(noise_seg, np.int64).reshape(-1, 2)
+        if seg.shape != (n, 2):
+            raise ValueError("noise_seg must hold one (lo, len) per utterance")
+        lo, ln = np.ascontiguousarray(seg[:, 0]), np.ascontiguousarray(seg[:, 1])
+    return snr, start, lo, ln
+
+
+def mix_waves(cleans, noise, snr_db, noise_start, noise_seg=None, device=0, return_info=False):
+    """Noisy int16 waves: cleans[u] plus `noise` scaled to snr_db[u] dB (mlggd_mix_waves; the rule is csrc/mix_rule.h).
+    Utterance u takes the noise segment noise_seg[u] = (lo, len) (None: the whole noise) from noise_start[u] inside it
+    on, wrapping at the segment's end.  return_info: (waves, gain [n] float64, clipped [n] int32)."""
+    cleans = [_wave(w) for w in cleans]
+    noise = _wave(noise)
+    n = len(cleans)
+    snr, start, lo, ln = _mix_args(n, noise.size, snr_db, noise_start, noise_seg)
+    off = _offsets([w.size for w in cleans])
+    packed = np.concatenate(cleans) if n else np.zeros(0, np.int16)
+    out = np.zeros(packed.size, np.int16)
+    gain, clipped = np.zeros(n, np.float64), np.zeros(n, np.int32)
+    _check(load().mlggd_mix_waves(int(device), n, _sp(packed), _i64p(off), _sp(noise), noise.size, _i64p(lo), _i64p(ln),
+                                  _i64p(start), snr.ctypes.data_as(C.POINTER(C.c_double)), _sp(out),
+                                  gain.ctypes.data_as(C.POINTER(C.c_double)),
+                                  clipped.ctypes.data_as(C.POINTER(C.c_int32))))
+    waves = [out[off[u]:off[u + 1]] for u in range(n)]
+    return (waves, gain, clipped) if return_info else waves
+
+
+def lps_stats(waves, fs_khz=16, device=0):
+    """(n_frames, sums [2][D] float64): per bin the sum and the sum of squares of the LPS rows of all the waves, formed
+    on the device (mlggd_lps_stats).  Additive over calls; norm_from_stats turns them into the norm vectors."""
+    waves = [_wave(w) for w in waves]
+    D = SPECTRAL_PARAMS.get(int(fs_khz), (0, 0, 512))[2] // 2 + 1
+    off = _offsets([w.size for w in waves])
+    packed = np.concatenate(waves) if waves else np.zeros(0, np.int16)
+    sums = np.zeros((2, D), np.float64)
+    n = C.c_int64(0)
+    _check(load().mlggd_lps_stats(int(device), int(fs_khz), len(waves), _sp(packed), _i64p(off),
+                                  sums.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+    return n.value, sums
+
+
+def norm_from_stats(n, sums):
+    """(mean [D], inv_std [D]) float32 from the sums of lps_stats over n frames: mean = S1/n, inv_std = 1 / sqrt(S2/n -
+    mean^2), the population variance, in double (mlggd_norm_from_stats).  A host call: needs no device."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != 2:
+        raise ValueError("sums must be [2][D]")
+    D = s.shape[1]
+    mean, inv = np.zeros(D, np.float32), np.zeros(D, np.float32)
+    _check(load().mlggd_norm_from_stats(D, int(n), s.ctypes.data_as(C.POINTER(C.c_double)), _p(mean), _p(inv)))
+    return mean, inv
+
+
 GgdFit = collections.namedtuple("GgdFit", "mean var kurt alpha loglik best loglik_shared best_shared")
 
 
@@ -496,6 +586,7 @@ class BPGpu:
                  shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0):
         self._h = None
         self._lives = []
+        self._n_noise = 0
         self.layersizes = [int(x) for x in layersizes]
         self.numlayers = len(self.layersizes)
         if not 2 <= self.numlayers <= MAXLAYER:
@@ -638,6 +729,74 @@ class BPGpu:
 
     def sync(self):
         _check(load().mlggd_sync(self._h))
+
+    # -- training data from waves: the wave pair (or the clean wave and the noise bank) is analysed, normalised and
+    # handed to the training loop on the device (mlggd_load_waves, mlggd_cv_all_waves, mlggd_train_waves)
+    def _waves_args(self, cleans, mean, inv_std, first_frame, fea_context, fs_khz):
+        cleans = [_wave(w) for w in cleans]
+        D = SPECTRAL_PARAMS.get(int(fs_khz), (0, 0, 2 * self.D - 2))[2] // 2 + 1
+        if fea_context is None:
+            fea_context = self.K0 // D
+        first = np.ascontiguousarray(first_frame, dtype=np.int32)
+        if first.ndim != 1:
+            raise ValueError("first_frame is a 1-D table of frame indices")
+        packed = np.concatenate(cleans) if cleans else np.zeros(0, np.int16)
+        return (packed, _offsets([w.size for w in cleans]), _f32(mean, (D,)), _f32(inv_std, (D,)), first,
+                int(fea_context))
+
+    def _pair_args(self, noisys, cleans, mean, inv_std, first_frame, targ_offset, fea_context, fs_khz):
+        clean, off, mean, inv, first, ctx = self._waves_args(cleans, mean, inv_std, first_frame, fea_context, fs_khz)
+        noisys = [_wave(w) for w in noisys]
+        if [w.size for w in noisys] != list(np.diff(off)):
+            raise ValueError("one noisy wave per clean wave, of the same length")
+        noisy = np.concatenate(noisys) if noisys else np.zeros(0, np.int16)
+        return (self._h, int(fs_khz), ctx, _p(mean), _p(inv), off.size - 1, _sp(noisy), _sp(clean), _i64p(off),
+                first.size, first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset))
+
+    def load_waves(self, noisys, cleans, mean, inv_std, first_frame, targ_offset, fea_context=None, fs_khz=16):
+        """load_frames from a wave pair: afterwards train_resident indexes the samples of first_frame (a table of
+        wave_samples, permuted as the caller likes).  fea_context None: layersizes[0] / bins."""
+        _check(load().mlggd_load_waves(*self._pair_args(noisys, cleans, mean, inv_std, first_frame, targ_offset,
+                                                        fea_context, fs_khz)))
+
+    def cv_all_waves(self, noisys, cleans, mean, inv_std, first_frame, targ_offset, fea_context=None, fs_khz=16):
+        """cv_all_frames from a wave pair: (sqerr, abserr, loglik), the same bits as on the rows built on the host."""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        _check(load().mlggd_cv_all_waves(*self._pair_args(noisys, cleans, mean, inv_std, first_frame, targ_offset,
+                                                          fea_context, fs_khz), C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def set_noise(self, noise):
+        """The noise bank of train_waves, kept on the device between calls; None frees it (mlggd_set_noise)."""
+        if noise is None:
+            _check(load().mlggd_set_noise(self._h, 0, None))
+            self._n_noise = 0
+            return
+        noise = _wave(noise)
+        _check(load().mlggd_set_noise(self._h, noise.size, _sp(noise)))
+        self._n_noise = noise.size
+
+    def train_waves(self, cleans, snr_db, noise_start, mean, inv_std, first_frame, targ_offset, noise_seg=None,
+                    fea_context=None, fs_khz=16, return_noisy=False):
+        """Mix cleans[u] with the noise bank at snr_db[u] (mix_waves' arguments and rule), analyse both waves, load and
+        train in one pass on the device (mlggd_train_waves).  Returns the number of bunches trained; with return_noisy
+        (bunches, noisy waves, gain, clipped) -- mix_waves' bytes."""
+        clean, off, mean, inv, first, ctx = self._waves_args(cleans, mean, inv_std, first_frame, fea_context, fs_khz)
+        n = off.size - 1
+        snr, start, lo, ln = _mix_args(n, self._n_noise, snr_db, noise_start, noise_seg)
+        out = np.zeros(clean.size, np.int16) if return_noisy else None
+        gain, clipped = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        trained = C.c_int(0)
+        _check(load().mlggd_train_waves(self._h, int(fs_khz), ctx, _p(mean), _p(inv), n, _sp(clean), _i64p(off),
+                                        _i64p(lo), _i64p(ln), _i64p(start), snr.ctypes.data_as(C.POINTER(C.c_double)),
+                                        first.size, first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset),
+                                        _sp(out) if return_noisy else None,
+                                        gain.ctypes.data_as(C.POINTER(C.c_double)) if return_noisy else None,
+                                        clipped.ctypes.data_as(C.POINTER(C.c_int32)) if return_noisy else None,
+                                        C.byref(trained)))
+        if return_noisy:
+            return trained.value, [out[off[u]:off[u + 1]] for u in range(n)], gain, clipped
+        return trained.value
 
     # -- Test_code/decode.m on the device: noisy wave -> LPS -> normalise -> context -> forward -> de-normalise -> wave
     def enhance_wave(self, noisy, mean, inv_std, fea_context=7, fs_khz=16, return_float=False):

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <functional>
 #include <mutex>
 #include <string>
@@ -29,6 +30,8 @@
 #include "live.hip.h"
 #include "live_rule.h"
 #include "errstats.hip.h"
+#include "mix.hip.h"
+#include "mix_rule.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -245,6 +248,18 @@ struct mlggd_engine {
         int lookup_table = 0;       // utterance of a frame: 0 = binary search over frame_off (default), 1 = per-frame
                                     // table (MLGGD_WAVES_LOOKUP=table, for A/B runs)
     } ww;
+    // mlggd_load_waves / mlggd_train_waves (mix.hip.h): the tables of a batch, the mixer's per-utterance words and the
+    // noise bank of mlggd_set_noise; the waves and the two LPS streams share ww.wave / ww.clean / ww.lps / ww.lps_den,
+    // which every decoding call rewrites from scratch
+    struct TrainWs {
+        WsBuf norm, frame_off, wave_off, blocks, utt, noise;
+        long long n_noise = 0;
+        std::vector<float> h_norm;
+        std::vector<int32_t> h_frame_off;
+        std::vector<long long> h_wave_off;
+        std::vector<mix_rule::Block> h_blocks;
+        std::vector<double> h_r;
+    } tw;
     int live_groups = 0;  // open live groups (mlggd_live_open): mlggd_destroy refuses while there is one
     bool indexed = false;
     int fdim = 0, toff = 0, raw_frames = 0;
@@ -1792,7 +1807,9 @@ int mlggd_destroy(mlggd_handle e) {
     for (mlggd_engine::WsBuf *b : {&e->ww.wave, &e->ww.lps, &e->ww.X, &e->ww.blk, &e->ww.out_i, &e->ww.out_f,
                                    &e->ww.lps_den, &e->ww.norm, &e->ww.frame_off, &e->ww.out_off, &e->ww.wave_off,
                                    &e->ww.utt_of, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores,
-                                   &e->ww.stoi_utt, &e->ww.stoi_x, &e->ww.stoi_f, &e->ww.stoi_i, &e->ww.stoi_res})
+                                   &e->ww.stoi_utt, &e->ww.stoi_x, &e->ww.stoi_f, &e->ww.stoi_i, &e->ww.stoi_res,
+                                   &e->tw.norm, &e->tw.frame_off, &e->tw.wave_off, &e->tw.blocks, &e->tw.utt,
+                                   &e->tw.noise})
         if (b->p) hipFree(b->p);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
     for (int l = 0; l < MLGGD_MAXLAYER; l++) {
@@ -4094,6 +4111,451 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
     for (int u = 0; u < NS; u++)
         s->had[u] = (end && end[u]) ? 0 : s->had[u] + ((long long)offsets[u + 1] - (long long)offsets[u]);
     return MLGGD_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ training data from waves (mix.hip.h, mix_rule.h)
+// The mixer, the norm statistics and the wave-pair loader: int16 waves in, the raw set of the training loop out.
+namespace {
+
+// frame_off [n_utts + 1] over ALL utterances of a batch; one shorter than a frame has none (that is no error here)
+int train_layout(const SpecDims &d, int n_utts, const int64_t *offsets, std::vector<int32_t> &frame_off) {
+    frame_off.assign((size_t)n_utts + 1, 0);
+    long long fsum = 0;
+    for (int u = 0; u < n_utts; u++) {
+        if (offsets[u + 1] < offsets[u])
+            return fail(MLGGD_ERR_ARG, "offsets decrease at utterance %d (%lld after %lld)", u, (long long)offsets[u + 1],
+                        (long long)offsets[u]);
+        const long long len = (long long)offsets[u + 1] - (long long)offsets[u];
+        fsum += len < d.L ? 0 : (len - (d.L - d.S)) / d.S;
+        if (fsum > INT32_MAX)
+            return fail(MLGGD_ERR_ARG, "the batch has more than %d frames (reached at utterance %d)", INT32_MAX, u);
+        frame_off[u + 1] = (int32_t)fsum;
+    }
+    return MLGGD_OK;
+}
+
+// every window of fea_context frames must lie inside one utterance of the layout; the message names the sample
+int check_windows(const std::vector<int32_t> &frame_off, int ctx, int n_samples, const int32_t *first_frame) {
+    const int FT = frame_off.back();
+    for (int s = 0; s < n_samples; s++) {
+        const long long f = first_frame[s];
+        if (f < 0 || f + ctx > FT)
+            return fail(MLGGD_ERR_ARG, "sample %d: window [%lld,%lld) outside the %d packed frames", s, f, f + ctx, FT);
+        // the last u with frame_off[u] <= f: utterances without frames are stepped over
+        const int u = (int)(std::upper_bound(frame_off.begin(), frame_off.end(), (int32_t)f) - frame_off.begin()) - 1;
+        if (f + ctx > frame_off[u + 1])
+            return fail(MLGGD_ERR_ARG, "sample %d: window [%lld,%lld) crosses the end of utterance %d at frame %d", s, f,
+                        f + ctx, u, (int)frame_off[u + 1]);
+    }
+    return MLGGD_OK;
+}
+
+// the tables k_lps_analysis_seg reads, over the utterances that have frames (its search needs frame_off to increase)
+void compact_tables(const std::vector<int32_t> &frame_off, const int64_t *offsets, std::vector<int32_t> &cf,
+                    std::vector<long long> &cw) {
+    cf.clear();
+    cw.clear();
+    const int n_utts = (int)frame_off.size() - 1;
+    for (int u = 0; u < n_utts; u++)
+        if (frame_off[u + 1] > frame_off[u]) {
+            cf.push_back(frame_off[u]);
+            cw.push_back((long long)offsets[u] - (long long)offsets[0]);
+        }
+    cf.push_back(frame_off[n_utts]);
+    cw.push_back((long long)offsets[n_utts] - (long long)offsets[0]);
+}
+
+// the block table of a batch: utterance u in blocks of mix_rule::kBlock samples (one without samples has none)
+void mix_blocks(int n_utts, const int64_t *offsets, const int64_t *lo, const int64_t *len, const int64_t *start,
+                std::vector<mix_rule::Block> &out) {
+    out.clear();
+    for (int u = 0; u < n_utts; u++) {
+        const long long n = (long long)offsets[u + 1] - (long long)offsets[u];
+        for (long long i0 = 0; i0 < n; i0 += mix_rule::kBlock) {
+            mix_rule::Block b;
+            b.at = (long long)offsets[u] - (long long)offsets[0] + i0;
+            b.lo = lo[u];
+            b.len = len[u];
+            b.phase = (long long)(((unsigned long long)start[u] + (unsigned long long)i0) % (unsigned long long)len[u]);
+            b.n = (int)std::min<long long>(mix_rule::kBlock, n - i0);
+            b.u = u;
+            b.first = i0 == 0;
+            b.pad = 0;
+            out.push_back(b);
+        }
+    }
+}
+
+// the mixer's words per utterance in one device buffer: E [2 n] | r [n] | gain [n] | clipped [n]
+struct MixUtt {
+    unsigned long long *E;
+    double *r, *gain;
+    int *clipped;
+    static size_t bytes(int n) { return (size_t)n * (16 + 8 + 8 + 4); }
+    MixUtt(void *p, int n) {
+        E = (unsigned long long *)p;
+        r = (double *)(E + 2 * (size_t)n);
+        gain = r + n;
+        clipped = (int *)(gain + n);
+    }
+};
+
+// both kernels over a block table on the device; the buffer of `m` is zeroed and r uploaded here
+int launch_mix(const mix_rule::Block *d_blocks, int n_blocks, const int16_t *clean, const int16_t *noise, MixUtt m,
+               int n_utts, const double *h_r, int16_t *noisy, hipStream_t st) {
+    HIPCHK(hipMemsetAsync(m.E, 0, MixUtt::bytes(n_utts), st));
+    HIPCHK(hipMemcpyAsync(m.r, h_r, (size_t)n_utts * sizeof(double), hipMemcpyHostToDevice, st));
+    if (n_blocks == 0) return MLGGD_OK;
+    hipLaunchKernelGGL(k_mix_energy, dim3((unsigned)n_blocks), dim3(MIX_THREADS), 0, st, d_blocks, clean, noise, m.E);
+    CHK(launch_check("k_mix_energy"));
+    hipLaunchKernelGGL(k_mix_apply, dim3((unsigned)n_blocks), dim3(MIX_THREADS), 0, st, d_blocks, clean, noise,
+                       (const unsigned long long *)m.E, (const double *)m.r, noisy, m.gain, m.clipped);
+    return launch_check("k_mix_apply");
+}
+
+void mix_ratios(int n_utts, const double *snr_db, std::vector<double> &r) {
+    r.resize((size_t)n_utts);
+    for (int u = 0; u < n_utts; u++) mix_rule::ratio(snr_db[u], &r[u]);  // checked before
+}
+
+// The checks of mlggd_load_waves / mlggd_cv_all_waves / mlggd_train_waves, all before any device call; frame_off
+// receives the layout over all utterances, *empty is set when there is nothing to load.
+int wave_pair_check(mlggd_engine *e, const char *who, int fs_khz, int ctx, const float *mean, const float *inv, int n_utts,
+                    const int64_t *offsets, int n_samples, const int32_t *first_frame, int targ_offset, SpecDims *d,
+                    std::vector<int32_t> &frame_off, bool *empty) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    int slot;
+    CHK(spec_dims(fs_khz, d, &slot));
+    if (ctx < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", ctx);
+    if ((long long)ctx * d->D != e->K0)
+        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", ctx, d->D, e->K0);
+    if (e->D != d->D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d->D, fs_khz);
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (targ_offset < 0 || targ_offset >= ctx)
+        return fail(MLGGD_ERR_ARG, "targ_offset %d not in [0, fea_context)", targ_offset);
+    CHK(check_frames(e, n_samples));
+    if (e->comm || e->world > 1 || e->fake_world) return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
+    *empty = n_utts == 0 || n_samples == 0;
+    if (*empty) return MLGGD_OK;
+    if (!mean || !inv || !offsets || !first_frame) return fail(MLGGD_ERR_ARG, "norm/offsets/first_frame is NULL");
+    CHK(train_layout(*d, n_utts, offsets, frame_off));
+    return check_windows(frame_off, ctx, n_samples, first_frame);
+}
+
+// noisy / clean on the device (packed alike, index 0 = the batch's first sample) -> both analysed, normalised with the
+// noisy statistics into the idle raw set, the sample table uploaded, the set made current.  Everything is enqueued on
+// the engine's stream; the caller synchronises.
+int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, const float *mean, const float *inv,
+                   const std::vector<int32_t> &frame_off, const int64_t *offsets, const int16_t *d_noisy,
+                   const int16_t *d_clean, int n_samples, const int32_t *first_frame, int targ_offset) {
+    mlggd_engine::TrainWs &t = e->tw;
+    hipStream_t st = e->stream;
+    const SpecPlan *p;
+    CHK(spec_plan(e->device, fs_khz, &p));
+    compact_tables(frame_off, offsets, t.h_frame_off, t.h_wave_off);
+    const int nc = (int)t.h_frame_off.size() - 1, FT = frame_off.back();
+    float *lpsN = nullptr, *lpsC = nullptr, *norm = nullptr;
+    int *d_foff = nullptr;
+    long long *d_woff = nullptr;
+    CHK(ws_grow(e, e->ww.lps, (size_t)FT * d.D, &lpsN));
+    CHK(ws_grow(e, e->ww.lps_den, (size_t)FT * d.D, &lpsC));
+    CHK(ws_grow(e, t.norm, (size_t)2 * d.D, &norm));
+    CHK(ws_grow(e, t.frame_off, (size_t)nc + 1, &d_foff));
+    CHK(ws_grow(e, t.wave_off, (size_t)nc + 1, &d_woff));
+    mlggd_engine::RawSet *r;
+    CHK(raw_set_acquire(e, FT, n_samples, ctx, &r));
+    t.h_norm.resize((size_t)2 * d.D);
+    memcpy(t.h_norm.data(), mean, d.D * sizeof(float));
+    memcpy(t.h_norm.data() + d.D, inv, d.D * sizeof(float));
+    HIPCHK(hipMemcpyAsync(norm, t.h_norm.data(), t.h_norm.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_foff, t.h_frame_off.data(), ((size_t)nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_woff, t.h_wave_off.data(), ((size_t)nc + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->first, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int k = 0; k < 2; k++) {  // the spectrum itself is not wanted here: X = nullptr
+        hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, k ? d_clean : d_noisy,
+                           (const long long *)d_woff, (const int *)d_foff, (const int *)nullptr, nc, FT, p->d, p->win, p->tw,
+                           p->tws, (float)exp(-50.0), k ? lpsC : lpsN, (float2 *)nullptr);
+        CHK(launch_check("k_lps_analysis_seg"));
+    }
+    hipLaunchKernelGGL(k_lps_norm_pair, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN, (const float *)lpsC,
+                       d.D, (const float *)norm, (const float *)(norm + d.D), r->feat, r->targ);
+    CHK(launch_check("k_lps_norm_pair"));
+    raw_set_commit(e, *r, FT, n_samples, ctx);
+    e->toff = targ_offset;
+    return MLGGD_OK;
+}
+
+// the packed waves of a batch into ww.wave (noisy, optional) / ww.clean
+int upload_pair(mlggd_engine *e, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_utts,
+                int16_t **d_noisy, int16_t **d_clean) {
+    const size_t n_wave = (size_t)(offsets[n_utts] - offsets[0]);
+    CHK(ws_grow(e, e->ww.wave, n_wave, d_noisy));
+    CHK(ws_grow(e, e->ww.clean, n_wave, d_clean));
+    if (noisy)
+        HIPCHK(hipMemcpyAsync(*d_noisy, noisy + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(*d_clean, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice, e->stream));
+    return MLGGD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mlggd_wave_samples(int fs_khz, int fea_context, int n_utts, const int64_t *offsets, int32_t *first_frame,
+                       int64_t *n_samples) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (fea_context < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", fea_context);
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (!n_samples) return fail(MLGGD_ERR_ARG, "n_samples is NULL");
+    *n_samples = 0;
+    if (n_utts == 0) return MLGGD_OK;
+    if (!offsets) return fail(MLGGD_ERR_ARG, "offsets is NULL");
+    std::vector<int32_t> frame_off;
+    CHK(train_layout(d, n_utts, offsets, frame_off));
+    int64_t n = 0;
+    for (int u = 0; u < n_utts; u++)
+        for (int f = frame_off[u]; f + fea_context <= frame_off[u + 1]; f++, n++)
+            if (first_frame) first_frame[n] = f;
+    *n_samples = n;
+    return MLGGD_OK;
+}
+
+int mlggd_mix_waves(int device, int n_utts, const int16_t *clean, const int64_t *offsets, const int16_t *noise,
+                    int64_t n_noise, const int64_t *noise_lo, const int64_t *noise_len, const int64_t *noise_start,
+                    const double *snr_db, int16_t *noisy, double *gain, int32_t *clipped) {
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (n_utts == 0) return MLGGD_OK;
+    if (!clean || !offsets || !noise || !noise_lo || !noise_len || !noise_start || !snr_db || !noisy)
+        return fail(MLGGD_ERR_ARG, "clean/offsets/noise/noise_lo/noise_len/noise_start/snr_db/noisy is NULL");
+    if (n_noise < 0) return fail(MLGGD_ERR_ARG, "n_noise %lld < 0", (long long)n_noise);
+    char msg[512];
+    if (mix_rule::check(n_utts, offsets, n_noise, noise_lo, noise_len, noise_start, snr_db, msg, sizeof(msg)))
+        return fail(MLGGD_ERR_ARG, "%s", msg);
+    const size_t n_wave = (size_t)(offsets[n_utts] - offsets[0]);
+    if (gain) std::fill(gain, gain + n_utts, 0.0);
+    if (clipped) std::fill(clipped, clipped + n_utts, 0);
+    if (n_wave == 0) return MLGGD_OK;
+    std::vector<mix_rule::Block> blocks;
+    std::vector<double> r;
+    mix_blocks(n_utts, offsets, noise_lo, noise_len, noise_start, blocks);
+    mix_ratios(n_utts, snr_db, r);
+    HIPCHK(hipSetDevice(device));
+    DevBufs b;
+    int16_t *dc = nullptr, *dn = nullptr, *dz = nullptr;
+    mix_rule::Block *db = nullptr;
+    unsigned char *du = nullptr;
+    CHK(b.alloc(&dc, n_wave));
+    CHK(b.alloc(&dn, n_wave));
+    CHK(b.alloc(&dz, (size_t)n_noise));
+    CHK(b.alloc(&db, blocks.size()));
+    CHK(b.alloc(&du, MixUtt::bytes(n_utts)));
+    MixUtt m(du, n_utts);
+    HIPCHK(hipMemcpy(dc, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dz, noise, (size_t)n_noise * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(db, blocks.data(), blocks.size() * sizeof(mix_rule::Block), hipMemcpyHostToDevice));
+    CHK(launch_mix(db, (int)blocks.size(), dc, dz, m, n_utts, r.data(), dn, nullptr));
+    HIPCHK(hipMemcpy(noisy + offsets[0], dn, n_wave * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (gain) HIPCHK(hipMemcpy(gain, m.gain, (size_t)n_utts * sizeof(double), hipMemcpyDeviceToHost));
+    if (clipped) HIPCHK(hipMemcpy(clipped, m.clipped, (size_t)n_utts * sizeof(int), hipMemcpyDeviceToHost));
+    return MLGGD_OK;
+}
+
+int mlggd_lps_stats(int device, int fs_khz, int n_utts, const int16_t *wave, const int64_t *offsets, double *sums,
+                    int64_t *n_frames) {
+    SpecDims d;
+    int slot;
+    CHK(spec_dims(fs_khz, &d, &slot));
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (!sums || !n_frames) return fail(MLGGD_ERR_ARG, "sums/n_frames is NULL");
+    if (n_utts > 0 && (!wave || !offsets)) return fail(MLGGD_ERR_ARG, "wave/offsets is NULL");
+    std::vector<int32_t> frame_off(1, 0);
+    if (n_utts > 0) CHK(train_layout(d, n_utts, offsets, frame_off));
+    const int FT = frame_off.back();
+    std::fill(sums, sums + (size_t)2 * d.D, 0.0);
+    *n_frames = FT;
+    if (FT == 0) return MLGGD_OK;
+    std::vector<int32_t> cf;
+    std::vector<long long> cw;
+    compact_tables(frame_off, offsets, cf, cw);
+    const int nc = (int)cf.size() - 1, chunks = (FT + CS_ROWS - 1) / CS_ROWS;
+    const size_t n_wave = (size_t)(offsets[n_utts] - offsets[0]);
+    HIPCHK(hipSetDevice(device));
+    const SpecPlan *p;
+    CHK(spec_plan(device, fs_khz, &p));
+    DevBufs b;
+    int16_t *dw = nullptr;
+    float *dl = nullptr;
+    double *part = nullptr, *ds = nullptr;
+    int *d_foff = nullptr;
+    long long *d_woff = nullptr;
+    CHK(b.alloc(&dw, n_wave));
+    CHK(b.alloc(&dl, (size_t)FT * d.D));
+    CHK(b.alloc(&part, (size_t)chunks * 2 * d.D));
+    CHK(b.alloc(&ds, (size_t)2 * d.D));
+    CHK(b.alloc(&d_foff, (size_t)nc + 1));
+    CHK(b.alloc(&d_woff, (size_t)nc + 1));
+    HIPCHK(hipMemcpy(dw, wave + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_foff, cf.data(), ((size_t)nc + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_woff, cw.data(), ((size_t)nc + 1) * sizeof(long long), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, nullptr, (const int16_t *)dw,
+                       (const long long *)d_woff, (const int *)d_foff, (const int *)nullptr, nc, FT, p->d, p->win, p->tw,
+                       p->tws, (float)exp(-50.0), dl, (float2 *)nullptr);
+    CHK(launch_check("k_lps_analysis_seg"));
+    hipLaunchKernelGGL(k_lps_colstats, dim3((unsigned)((d.D + CS_BINS - 1) / CS_BINS), (unsigned)chunks), dim3(256), 0,
+                       nullptr, (const float *)dl, FT, d.D, part);
+    CHK(launch_check("k_lps_colstats"));
+    hipLaunchKernelGGL(k_lps_colfold, dim3((unsigned)((2 * d.D + 255) / 256)), dim3(256), 0, nullptr,
+                       (const double *)part, chunks, 2 * d.D, ds);
+    CHK(launch_check("k_lps_colfold"));
+    HIPCHK(hipMemcpy(sums, ds, (size_t)2 * d.D * sizeof(double), hipMemcpyDeviceToHost));
+    return MLGGD_OK;
+}
+
+int mlggd_norm_from_stats(int D, int64_t n, const double *sums, float *mean, float *inv_std) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n < 1) return fail(MLGGD_ERR_ARG, "n %lld < 1", (long long)n);
+    if (!sums || !mean || !inv_std) return fail(MLGGD_ERR_ARG, "sums/mean/inv_std is NULL");
+    for (int d = 0; d < D; d++) {
+        const double m = sums[d] / (double)n;
+        const double var = sums[(size_t)D + d] / (double)n - m * m;
+        if (!(var > 0.0) || !std::isfinite(var))
+            return fail(MLGGD_ERR_ARG, "bin %d: variance %g, no inverse standard deviation", d, var);
+    }
+    for (int d = 0; d < D; d++) {
+        const double m = sums[d] / (double)n;
+        const double var = sums[(size_t)D + d] / (double)n - m * m;
+        mean[d] = (float)m;
+        inv_std[d] = (float)(1.0 / sqrt(var));
+    }
+    return MLGGD_OK;
+}
+
+int mlggd_load_waves(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                     int n_utts, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_samples,
+                     const int32_t *first_frame, int targ_offset) {
+    SpecDims d;
+    std::vector<int32_t> frame_off;
+    bool empty = false;
+    CHK(wave_pair_check(e, "mlggd_load_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, offsets, n_samples,
+                        first_frame, targ_offset, &d, frame_off, &empty));
+    if (empty) return MLGGD_OK;
+    if (!noisy || !clean) return fail(MLGGD_ERR_ARG, "noisy/clean is NULL");
+    HIPCHK(hipSetDevice(e->device));
+    int16_t *dn = nullptr, *dc = nullptr;
+    CHK(upload_pair(e, noisy, clean, offsets, n_utts, &dn, &dc));
+    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, frame_off, offsets, dn, dc, n_samples,
+                       first_frame, targ_offset));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_cv_all_waves(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                       int n_utts, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_samples,
+                       const int32_t *first_frame, int targ_offset, float *sqerr, float *abserr, float *loglik) {
+    SpecDims d;
+    std::vector<int32_t> frame_off;
+    bool empty = false;
+    CHK(wave_pair_check(e, "mlggd_cv_all_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, offsets,
+                        n_samples, first_frame, targ_offset, &d, frame_off, &empty));
+    if (empty) {
+        if (sqerr) *sqerr = 0.0f;
+        if (abserr) *abserr = 0.0f;
+        if (loglik) *loglik = 0.0f;
+        return MLGGD_OK;
+    }
+    if (!noisy || !clean) return fail(MLGGD_ERR_ARG, "noisy/clean is NULL");
+    HIPCHK(hipSetDevice(e->device));
+    int16_t *dn = nullptr, *dc = nullptr;
+    CHK(upload_pair(e, noisy, clean, offsets, n_utts, &dn, &dc));
+    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, frame_off, offsets, dn, dc, n_samples,
+                       first_frame, targ_offset));
+    float *ll = (e->cfg.MLflag == 1) ? loglik : nullptr;
+    int rc;
+    if (e->cv_device) {
+        rc = cv_device_reduce(e, n_samples, sqerr, abserr, ll);
+    } else {  // the host-order sums read the targets on the host: the normalised clean rows come back once
+        const int D = e->D;
+        std::vector<float> targ((size_t)frame_off.back() * D);
+        HIPCHK(hipMemcpyAsync(targ.data(), e->raw_targ, targ.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        rc = cv_accumulate(
+            e, n_samples, [&](int i) { return targ.data() + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr,
+            ll);
+    }
+    HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return rc;
+}
+
+int mlggd_set_noise(mlggd_handle e, int64_t n_noise, const int16_t *noise) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (n_noise < 0) return fail(MLGGD_ERR_ARG, "n_noise %lld < 0", (long long)n_noise);
+    if (n_noise > 0 && !noise) return fail(MLGGD_ERR_ARG, "noise is NULL");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    mlggd_engine::TrainWs &t = e->tw;
+    if (n_noise == 0 || !noise) {
+        if (t.noise.p) hipFree(t.noise.p);
+        t.noise.p = nullptr;
+        t.noise.cap = 0;
+        t.n_noise = 0;
+        return MLGGD_OK;
+    }
+    int16_t *dz = nullptr;
+    t.n_noise = 0;
+    CHK(ws_grow(e, t.noise, (size_t)n_noise, &dz));
+    HIPCHK(hipMemcpyAsync(dz, noise, (size_t)n_noise * sizeof(int16_t), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    t.n_noise = n_noise;
+    return MLGGD_OK;
+}
+
+int mlggd_train_waves(mlggd_handle e, int fs_khz, int fea_context, const float *norm_mean, const float *norm_inv_std,
+                      int n_utts, const int16_t *clean, const int64_t *offsets, const int64_t *noise_lo,
+                      const int64_t *noise_len, const int64_t *noise_start, const double *snr_db, int n_samples,
+                      const int32_t *first_frame, int targ_offset, int16_t *noisy_out, double *gain, int32_t *clipped,
+                      int *bunches_trained) {
+    if (bunches_trained) *bunches_trained = 0;
+    SpecDims d;
+    std::vector<int32_t> frame_off;
+    bool empty = false;
+    CHK(wave_pair_check(e, "mlggd_train_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, offsets, n_samples,
+                        first_frame, targ_offset, &d, frame_off, &empty));
+    mlggd_engine::TrainWs &t = e->tw;
+    if (!t.noise.p || t.n_noise == 0)
+        return fail(MLGGD_ERR_STATE, "mlggd_train_waves: the engine has no noise bank (mlggd_set_noise)");
+    if (empty) return MLGGD_OK;
+    if (!clean || !noise_lo || !noise_len || !noise_start || !snr_db)
+        return fail(MLGGD_ERR_ARG, "clean/noise_lo/noise_len/noise_start/snr_db is NULL");
+    char msg[512];
+    if (mix_rule::check(n_utts, offsets, t.n_noise, noise_lo, noise_len, noise_start, snr_db, msg, sizeof(msg)))
+        return fail(MLGGD_ERR_ARG, "%s", msg);
+    mix_blocks(n_utts, offsets, noise_lo, noise_len, noise_start, t.h_blocks);
+    mix_ratios(n_utts, snr_db, t.h_r);
+    HIPCHK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const size_t n_wave = (size_t)(offsets[n_utts] - offsets[0]);
+    int16_t *dn = nullptr, *dc = nullptr;
+    mix_rule::Block *db = nullptr;
+    unsigned char *du = nullptr;
+    CHK(upload_pair(e, nullptr, clean, offsets, n_utts, &dn, &dc));
+    CHK(ws_grow(e, t.blocks, t.h_blocks.size(), &db));
+    CHK(ws_grow(e, t.utt, MixUtt::bytes(n_utts), &du));
+    MixUtt m(du, n_utts);
+    HIPCHK(hipMemcpyAsync(db, t.h_blocks.data(), t.h_blocks.size() * sizeof(mix_rule::Block), hipMemcpyHostToDevice, st));
+    CHK(launch_mix(db, (int)t.h_blocks.size(), dc, (const int16_t *)t.noise.p, m, n_utts, t.h_r.data(), dn, st));
+    if (noisy_out)
+        HIPCHK(hipMemcpyAsync(noisy_out + offsets[0], dn, n_wave * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+    if (gain) HIPCHK(hipMemcpyAsync(gain, m.gain, (size_t)n_utts * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (clipped) HIPCHK(hipMemcpyAsync(clipped, m.clipped, (size_t)n_utts * sizeof(int), hipMemcpyDeviceToHost, st));
+    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, frame_off, offsets, dn, dc, n_samples,
+                       first_frame, targ_offset));
+    CHK(mlggd_train_resident(e, 0, n_samples, bunches_trained));
+    return mlggd_sync(e);
 }
 
 }  // extern "C"
