@@ -36,6 +36,12 @@ enum {
     MLGGD_ERR_STATE = 4    /* call not valid in the engine's current state */
 };
 
+/* mlggd_config.activation: what every hidden layer applies to x = sum + bias.  The output layer is linear either way.
+ * MLGGD_ACT_RELU: y = (x < 0) ? 0 : x -- a NaN stays a NaN -- and dE/dx = (y > 0) ? dE/dy : 0; the rectifier sibling of
+ * the reference's BPtrain_Sigmoid (its Gen_rand_wts_for_ReLUs.pl initialises such nets).  Any other value is
+ * MLGGD_ERR_ARG at mlggd_create, found before a device is touched. */
+enum { MLGGD_ACT_SIGMOID = 0, MLGGD_ACT_RELU = 1 };
+
 typedef struct mlggd_engine *mlggd_handle;
 
 /* Constructor arguments of BP_GPU (BP_GPU.h:48-49, BP_GPU.cu:9-11), same meaning. */
@@ -55,7 +61,8 @@ typedef struct mlggd_config {
     float visible_omit;
     float hid_omit;
     int32_t max_cache_frames; /* rows of the resident chunk buffers; 0 -> MLGGD_MAXCACHEFRAME */
-    int32_t reserved[7];
+    int32_t activation;      /* hidden units: MLGGD_ACT_SIGMOID (0, the default of a zeroed struct) or MLGGD_ACT_RELU */
+    int32_t reserved[6];
 } mlggd_config;
 
 /* ---- lifetime: BP_GPU::BP_GPU / ~BP_GPU (BP_GPU.cu:9-150) ---- */
@@ -391,6 +398,7 @@ int mlggd_get_shapefactors(mlggd_handle h, float *betas /* [D] */);
  * file. */
 int mlggd_read_shapefactors(const char *path, int D, float fallback, float *betas /* [D] */);
 int mlggd_set_lrate(mlggd_handle h, float lrate);
+int mlggd_get_activation(mlggd_handle h, int *act); /* MLGGD_ACT_* the engine was created with */
 /* CV metrics: on = the three sums are formed on the device (per-tile partials in double, combined
  * on the host; no n x D copy, no host loop); off (default, or env MLGGD_CV_DEVICE=0) = outputs copied back and
  * accumulated on the host in fp32 in the reference's frame-major order (BP_GPU.cu:207-213), the values the
@@ -482,7 +490,7 @@ int mlggd_debug_gemm_plan(mlggd_handle h, int layer, int *fwd_waves, int *dx_wav
 
 /* Diagnostic: out[i] = fn(x[i], y) evaluated on the device -- fn "pow_det" (the loss chain's power: kernindex2 / kernfunc2 /
  * kernSubClean2, DevFunc.cu:219-227,468-489,376-398), "exp_det", "sigmoid" = 1 / (1 + exp_det(-x)) (kernSigmoid,
- * DevFunc.cu:36-51): what the kernels themselves evaluate, IEEE operations only, restated in the oracle's MFMA-order twin --
+ * DevFunc.cu:36-51), "relu" = (x < 0) ? 0 : x (the MLGGD_ACT_RELU epilogues' rule): what the kernels themselves evaluate, IEEE operations only, restated in the oracle's MFMA-order twin --
  * the parity tests require the SAME BITS on both sides for every argument; "div" = x / y (IEEE); and, for the record only,
  * ocml's own "powf" and "expf", which no kernel calls: how far they sit from the correctly rounded values, in ulps. */
 int mlggd_debug_math(mlggd_handle h, const char *fn, const float *x, float y, float *out, size_t n);

@@ -33,8 +33,20 @@ class _Config(C.Structure):
         ("lrate", C.c_float), ("momentum", C.c_float), ("weightcost", C.c_float),
         ("shapefactor", C.c_float), ("MLflag", C.c_int32), ("dropoutflag", C.c_int32),
         ("visible_omit", C.c_float), ("hid_omit", C.c_float), ("max_cache_frames", C.c_int32),
-        ("reserved", C.c_int32 * 7),
+        ("activation", C.c_int32), ("reserved", C.c_int32 * 6),
     ]
+
+
+ACTIVATIONS = ("sigmoid", "relu")  # MLGGD_ACT_SIGMOID = 0, MLGGD_ACT_RELU = 1 (include/mlggd.h)
+
+
+def activation_code(activation):
+    """"sigmoid" | "relu" | 0 | 1 -> the MLGGD_ACT_* value of mlggd_config.activation; anything else is a ValueError."""
+    if isinstance(activation, str) and activation in ACTIVATIONS:
+        return ACTIVATIONS.index(activation)
+    if isinstance(activation, (int, np.integer)) and not isinstance(activation, bool) and 0 <= activation < len(ACTIVATIONS):
+        return int(activation)
+    raise ValueError("activation %r: must be one of %s or 0 / 1" % (activation, " / ".join(map(repr, ACTIVATIONS))))
 
 
 # every symbol include/mlggd.h declares (tests check the library exports all of them)
@@ -43,6 +55,7 @@ EXPORTS = [
     "mlggd_load_chunk", "mlggd_train_resident", "mlggd_sync", "mlggd_cv_sqerr", "mlggd_cv_abserr",
     "mlggd_cv_loglik", "mlggd_cv_all", "mlggd_forward", "mlggd_get_weights", "mlggd_set_weights",
     "mlggd_get_scalefactor", "mlggd_set_scalefactor", "mlggd_set_lrate", "mlggd_gamma",
+    "mlggd_get_activation",
     "mlggd_debug_tensor", "mlggd_comm_unique_id", "mlggd_comm_init", "mlggd_last_train_ms",
     "mlggd_profile_select", "mlggd_profile_stride", "mlggd_profile_read", "mlggd_profile_overhead",
     "mlggd_kernel_work", "mlggd_dw_launches_per_step", "mlggd_dp_mode", "mlggd_debug_fake_world",
@@ -108,6 +121,7 @@ def load():
     L.mlggd_get_scalefactor.argtypes = [C.c_void_p, _fp]
     L.mlggd_set_scalefactor.argtypes = [C.c_void_p, _fp]
     L.mlggd_set_lrate.argtypes = [C.c_void_p, C.c_float]
+    L.mlggd_get_activation.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.mlggd_set_cv_device_reduce.argtypes = [C.c_void_p, C.c_int]
     L.mlggd_alloc_pinned_on.argtypes = [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]
     L.mlggd_debug_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _fp, C.c_size_t]
@@ -583,8 +597,9 @@ class BPGpu:
     """Same constructor arguments and methods as the reference's BP_GPU (BP_GPU.h:48-59)."""
 
     def __init__(self, random_seed, gpu, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
-                 shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0):
+                 shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0, activation="sigmoid"):
         self._h = None
+        act = activation_code(activation)  # hidden units: "sigmoid" (the reference's BPtrain_Sigmoid) or "relu"
         self._lives = []
         self._n_noise = 0
         self.layersizes = [int(x) for x in layersizes]
@@ -610,6 +625,7 @@ class BPGpu:
         cfg.shapefactor, cfg.MLflag = shapefactor, int(MLflag)
         cfg.dropoutflag, cfg.visible_omit, cfg.hid_omit = int(dropoutflag), visible_omit, hid_omit
         cfg.max_cache_frames = int(max_cache_frames)
+        cfg.activation = act
         h = C.c_void_p()
         rc = load().mlggd_create(C.byref(cfg), _ptr_array(ws), _ptr_array(bs), C.byref(h))
         if rc != 0:
@@ -618,6 +634,13 @@ class BPGpu:
                 load().mlggd_destroy(h)
             raise MlggdError("mlggd_create failed (%d): %s" % (rc, msg))
         self._h = h
+
+    @property
+    def activation(self):
+        """"sigmoid" or "relu": what the engine's hidden layers apply (mlggd_get_activation)."""
+        a = C.c_int()
+        _check(load().mlggd_get_activation(self._h, C.byref(a)))
+        return ACTIVATIONS[a.value]
 
     # -- lifetime
     def close(self):

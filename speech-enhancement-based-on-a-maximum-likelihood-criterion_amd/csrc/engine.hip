@@ -644,6 +644,7 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
     const int b_tiles = e->Bp / 32;
     const bool drop = training && e->cfg.dropoutflag == 1;
     const bool cvscale = !training && e->cfg.dropoutflag == 1;
+    const bool relu = e->cfg.activation == MLGGD_ACT_RELU;  // the hidden layers' epilogue: a host-side choice of instantiation
     if (drop) CHK(run_dropout(e, 0, in_rows));
     for (int l = 1; l < e->L; l++) {
         const int Kp = e->lsp[l - 1], Np = e->lsp[l], n_tiles = Np / 32;
@@ -663,7 +664,10 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
                 fa.b_tiles = e->Bp / 64;
                 fa.b_shift = log2_or_minus1(fa.b_tiles);
                 const size_t lds = t64_lds_floats() * sizeof(float);
-                if (l != e->L - 1) {
+                if (l != e->L - 1 && relu) {
+                    CHK(ensure_lds(e, k_fwd64<FWD_RELU>, lds));
+                    launch_timed(e, k_fwd64<FWD_RELU>, dim3(fa.n_tiles * fa.b_tiles), dim3(256), lds, e->stream, fa);
+                } else if (l != e->L - 1) {
                     CHK(ensure_lds(e, k_fwd64<FWD_SIGMOID>, lds));
                     launch_timed(e, k_fwd64<FWD_SIGMOID>, dim3(fa.n_tiles * fa.b_tiles), dim3(256), lds, e->stream, fa);
                 } else {
@@ -675,8 +679,13 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
 #define LAUNCH_FWD(NW, PIPE)                                                                                \
     {                                                                                                       \
         const size_t lds = fwd_lds_floats<NW, PIPE>() * sizeof(float);                                      \
-        CHK(ensure_lds(e, k_fwd<FWD_SIGMOID, NW, PIPE>, lds));                                              \
-        launch_timed(e, k_fwd<FWD_SIGMOID, NW, PIPE>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
+        if (relu) {                                                                                         \
+            CHK(ensure_lds(e, k_fwd<FWD_RELU, NW, PIPE>, lds));                                             \
+            launch_timed(e, k_fwd<FWD_RELU, NW, PIPE>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
+        } else {                                                                                            \
+            CHK(ensure_lds(e, k_fwd<FWD_SIGMOID, NW, PIPE>, lds));                                          \
+            launch_timed(e, k_fwd<FWD_SIGMOID, NW, PIPE>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
+        }                                                                                                   \
     }
                 // PIPE 4 (default): main loop software-pipelined inside the wave, operands by LDS-DMA; 1: the same
                 // pipeline through staging registers (MLGGD_FWD_PIPE=1); 0: the round-1 loop (MLGGD_FWD_PIPE=0, and the
@@ -1245,9 +1254,10 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
     return launch_check("k_loss_grad");
 }
 
-// dEdX_{l-1} from dEdX_l and the OLD W_l (+ sigmoid derivative of layer l-1): BP_GPU.cu:402,430
+// dEdX_{l-1} from dEdX_l and the OLD W_l (+ the derivative of layer l-1's activation): BP_GPU.cu:402,430
 static int run_dx(mlggd_engine *e, int l) {
     const int Kp = e->lsp[l - 1], b_tiles = e->Bp / 32;
+    const bool relu = e->cfg.activation == MLGGD_ACT_RELU;
     ProfScope ps(e, KC_DX, l);
     DxArgs xa = dx_args(e, l);
     if (dx64_used(e, l)) {
@@ -1255,16 +1265,26 @@ static int run_dx(mlggd_engine *e, int l) {
         xa.b_tiles = e->Bp / 64;
         xa.b_shift = log2_or_minus1(xa.b_tiles);
         const size_t lds = t64_lds_floats() * sizeof(float);
-        CHK(ensure_lds(e, k_dx64, lds));
-        launch_timed(e, k_dx64, dim3(xa.k_tiles * xa.b_tiles), dim3(256), lds, e->stream, xa);
+        if (relu) {
+            CHK(ensure_lds(e, k_dx64<ACT_RELU>, lds));
+            launch_timed(e, k_dx64<ACT_RELU>, dim3(xa.k_tiles * xa.b_tiles), dim3(256), lds, e->stream, xa);
+        } else {
+            CHK(ensure_lds(e, k_dx64<ACT_SIGMOID>, lds));
+            launch_timed(e, k_dx64<ACT_SIGMOID>, dim3(xa.k_tiles * xa.b_tiles), dim3(256), lds, e->stream, xa);
+        }
         return launch_check("k_dx64");
     }
     long long *st = stamps_for(e, KC_DX, l, (Kp / 32) * b_tiles);  // k_dx64 carries no stamps: it leaves the selection alone
 #define LAUNCH_DX(NW, PIPE)                                                                                  \
     {                                                                                                        \
         const size_t lds = dx_lds_floats<NW, PIPE>() * sizeof(float);                                        \
-        CHK(ensure_lds(e, k_dx<NW, PIPE>, lds));                                                             \
-        launch_timed(e, k_dx<NW, PIPE>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st);      \
+        if (relu) {                                                                                          \
+            CHK(ensure_lds(e, k_dx<NW, PIPE, ACT_RELU>, lds));                                               \
+            launch_timed(e, k_dx<NW, PIPE, ACT_RELU>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st); \
+        } else {                                                                                             \
+            CHK(ensure_lds(e, k_dx<NW, PIPE>, lds));                                                         \
+            launch_timed(e, k_dx<NW, PIPE>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st);  \
+        }                                                                                                    \
     }
     // PIPE 4 (default where one workgroup per CU is all there is: <= 256 workgroups): main loop software-pipelined
     // inside the wave, operands by LDS-DMA (136 KB of LDS); 1: the same pipeline through staging registers (71 KB: two
@@ -1667,6 +1687,9 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     if (cfg->numlayers < 2 || cfg->numlayers > MLGGD_MAXLAYER)
         return fail(MLGGD_ERR_ARG, "numlayers %d not in 2..%d", cfg->numlayers, MLGGD_MAXLAYER);
     if (cfg->bunchsize < 1) return fail(MLGGD_ERR_ARG, "bunchsize %d < 1", cfg->bunchsize);
+    if (cfg->activation != MLGGD_ACT_SIGMOID && cfg->activation != MLGGD_ACT_RELU)
+        return fail(MLGGD_ERR_ARG, "activation %d: must be %d (sigmoid) or %d (relu)", cfg->activation, MLGGD_ACT_SIGMOID,
+                    MLGGD_ACT_RELU);
     for (int i = 0; i < cfg->numlayers; i++)
         if (cfg->layersizes[i] < 1) return fail(MLGGD_ERR_ARG, "layersizes[%d] = %d", i, cfg->layersizes[i]);
     for (int i = 1; i < cfg->numlayers; i++) {
@@ -2822,6 +2845,11 @@ int mlggd_debug_out_slabs(mlggd_handle e, int *slabs) {
     *slabs = e->S_out;
     return MLGGD_OK;
 }
+int mlggd_get_activation(mlggd_handle e, int *act) {
+    if (!e || !act) return fail(MLGGD_ERR_ARG, "NULL argument");
+    *act = e->cfg.activation;
+    return MLGGD_OK;
+}
 int mlggd_dp_mode(mlggd_handle e, int *mode) {
     if (!e || !mode) return fail(MLGGD_ERR_ARG, "NULL argument");
     // 0 single device, 1 all-reduce, 2 gather, 3 gather + sharded update, 4 = 3 with the activations by all-to-all
@@ -2833,7 +2861,7 @@ int mlggd_dp_mode(mlggd_handle e, int *mode) {
 // ("powf" "expf" "sigmoid" "div"); tests measure their distance to the oracle's host libm in ulps.
 int mlggd_debug_math(mlggd_handle e, const char *fn, const float *x, float y, float *out, size_t n) {
     if (!e || !fn || (n > 0 && (!x || !out))) return fail(MLGGD_ERR_ARG, "NULL argument");
-    const int f = !strcmp(fn, "powf") ? 0 : !strcmp(fn, "expf") ? 1 : !strcmp(fn, "sigmoid") ? 2 : !strcmp(fn, "div") ? 3 : !strcmp(fn, "exp_det") ? 4 : !strcmp(fn, "pow_det") ? 5 : !strcmp(fn, "sigmoid4") ? 6 : -1;
+    const int f = !strcmp(fn, "powf") ? 0 : !strcmp(fn, "expf") ? 1 : !strcmp(fn, "sigmoid") ? 2 : !strcmp(fn, "div") ? 3 : !strcmp(fn, "exp_det") ? 4 : !strcmp(fn, "pow_det") ? 5 : !strcmp(fn, "sigmoid4") ? 6 : !strcmp(fn, "relu") ? 7 : -1;
     if (f < 0) return fail(MLGGD_ERR_ARG, "unknown function '%s'", fn);
     if (n == 0) return MLGGD_OK;
     HIPCHK(hipSetDevice(e->device));
@@ -2989,6 +3017,9 @@ int mlggd_kernel_work(mlggd_handle e, const char *kernel_class, int layer, doubl
     // sharded (dp_mode 2) on this rank's 1/world of the weight rows
     const bool dpx = (e->comm != nullptr || e->fake_world) && e->dp_mode >= 1 && !strcmp(kernel_class, "dw");
     const double W = e->world, B = e->B;
+    // algorithmic figures: the multiply-adds of the GEMM and the tensors it reads and writes.  The activation epilogue
+    // is not counted -- neither the sigmoid's exponential and division nor the rectifier's comparison -- so the
+    // figures, and the roofline fractions built on them, are the same for both activations.
     auto gemm = [&](const char *cls, int l, double &ff, double &bb) {
         if (l < 1 || l >= e->L) return;
         const double K = e->ls[l - 1], N = e->ls[l];

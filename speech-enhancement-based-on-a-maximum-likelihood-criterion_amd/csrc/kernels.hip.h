@@ -170,6 +170,21 @@ __device__ __forceinline__ float4 sigmoid_det4(float4 v, float b, bool live) {
     y.w = live ? 1.0f / e1.y : 0.0f;
     return y;
 }
+// The rectifier's counterpart (FWD_RELU): y = x where x = v + b is not negative, else +0; 0 where `live` is false.  A
+// comparison and a select, not fmaxf: v_max_f32 returns the other operand for a NaN, and a diverged net must show in
+// the log as it does with the sigmoid.  x itself is the fp32 sum the sigmoid's epilogue forms, nothing is fused into it.
+__device__ __forceinline__ float relu_det(float x) { return (x < 0.0f) ? 0.0f : x; }
+__device__ __forceinline__ float4 relu4(float4 v, float b, bool live) {
+    float4 y;
+    y.x = live ? relu_det(v.x + b) : 0.0f;
+    y.y = live ? relu_det(v.y + b) : 0.0f;
+    y.z = live ? relu_det(v.z + b) : 0.0f;
+    y.w = live ? relu_det(v.w + b) : 0.0f;
+    return y;
+}
+// Its derivative for the dX epilogues (ACT_RELU): the gradient passes where the unit fired, exactly +0 elsewhere -- a
+// dropped unit (y == 0) gets none, as y (1 - y) gives for the sigmoid
+__device__ __forceinline__ float drelu(float y, float dedy) { return (y > 0.0f) ? dedy : 0.0f; }
 
 // The power of the loss chain (pow_or_self below; kernindex2 / kernfunc2, DevFunc.cu:219-227,468-489): pow_det, x^y (x >= 0) as exp(y log x) in IEEE DOUBLE operations only -- adds, multiplies,
 // one division, one floor, exact bit manipulation; no fused multiply-add, no libm, no hardware transcendental -- so that
@@ -242,8 +257,12 @@ __device__ __forceinline__ float pow_det(float xf, float yf) {
 // MODE FWD_SIGMOID: fused epilogue writes y=1/(1+expf(-x)) (0 for pad units) to Yt_out and Y_out.
 // MODE FWD_SLAB   : inter-workgroup K split S (small output layers); writes raw partial sums
 //                   slab[s][n][b]; the consumer adds the bias and the S slabs in order.
+// MODE FWD_RELU   : FWD_SIGMOID with the rectifier y = (x < 0) ? 0 : x as the activation (relu4); same stores, same
+//                   layouts.  The activation is a template parameter, never a run-time branch: the sigmoid
+//                   instantiations compile from the statements they had before there was a choice.
 // ---------------------------------------------------------------------------------------
-enum { FWD_SIGMOID = 0, FWD_SLAB = 1 };
+enum { FWD_SIGMOID = 0, FWD_SLAB = 1, FWD_RELU = 2 };
+enum { ACT_SIGMOID = 0, ACT_RELU = 1 };  // the dX kernels' switch; the values of MLGGD_ACT_* (include/mlggd.h)
 
 struct FwdArgs {
     const float *W, *Yt_in, *bias;
@@ -321,8 +340,8 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
     static_assert(1024 % NT_ == 0, "every thread owns EPT_ whole output elements");
     float bias_pre[EPT_];
 #pragma unroll
-    for (int q = 0; q < EPT_; q++) bias_pre[q] = MODE == FWD_SIGMOID ? bias[n0 + ((tid + NT_ * q) >> 5)] : 0.0f;
-    const float bias_row = (MODE == FWD_SIGMOID && NW == 4) ? bias[n0 + (tid >> 3)] : 0.0f;  // 4-wave epilogue
+    for (int q = 0; q < EPT_; q++) bias_pre[q] = MODE != FWD_SLAB ? bias[n0 + ((tid + NT_ * q) >> 5)] : 0.0f;
+    const float bias_row = (MODE != FWD_SLAB && NW == 4) ? bias[n0 + (tid >> 3)] : 0.0f;  // 4-wave epilogue
     asm volatile("" ::: "memory");
 
     if constexpr (PIPE == 4) {
@@ -571,7 +590,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
             *reinterpret_cast<float4 *>(&slab[((size_t)s * Np + n0 + row) * Bp + b0 + col4]) = v4;
         } else {
             const int n = n0 + row;
-            const float4 y4 = sigmoid_det4(v4, bias_row, n < N);  // kernSigmoid, DevFunc.cu:48
+            const float4 y4 = MODE == FWD_RELU ? relu4(v4, bias_row, n < N) : sigmoid_det4(v4, bias_row, n < N);  // kernSigmoid, DevFunc.cu:48
             *reinterpret_cast<float4 *>(&Yt_out[(size_t)n * Bp + b0 + col4]) = y4;
             tileT[col4][row] = y4.x;
             tileT[col4 + 1][row] = y4.y;
@@ -614,7 +633,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
             if (e < 1024) {
                 const int n = n0 + row;
                 const float x = v[q] + bias_pre[q];
-                const float y = (n < N) ? sigmoid_det(x) : 0.0f;  // kernSigmoid, DevFunc.cu:48
+                const float y = (n < N) ? (MODE == FWD_RELU ? relu_det(x) : sigmoid_det(x)) : 0.0f;  // kernSigmoid, DevFunc.cu:48
                 Yt_out[(size_t)n * Bp + b0 + col] = y;
                 tileT[col][row] = y;
             }
@@ -651,7 +670,7 @@ struct DxArgs {
 // per wave: W piece [32][66] + dEdXt piece [64][32]; LDS-DMA form (PIPE 4): two sets of two unpadded 8 KB tiles
 template <int NW, int PIPE> constexpr int dx_lds_floats() { return NW * (PIPE == 4 ? 8192 : 32 * DX_LDW + 2048) + 32 * 36; }
 
-template <int NW, int PIPE = 1>
+template <int NW, int PIPE = 1, int ACT = ACT_SIGMOID>
 __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *smem, long long *stamps) {
     const float *__restrict__ W = A.W, *__restrict__ dEdXt = A.dEdXt, *__restrict__ Yt_prev = A.Yt_prev;
     float *__restrict__ dEdXt_prev = A.dEdXt_prev, *__restrict__ dEdX_prev = A.dEdX_prev;
@@ -965,10 +984,17 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
             d4.w += p4.w;
         }
         float4 g4;  // kernDsigmoid, DevFunc.cu:67-68
-        g4.x = (1.0f - y_pre4.x) * y_pre4.x * d4.x;
-        g4.y = (1.0f - y_pre4.y) * y_pre4.y * d4.y;
-        g4.z = (1.0f - y_pre4.z) * y_pre4.z * d4.z;
-        g4.w = (1.0f - y_pre4.w) * y_pre4.w * d4.w;
+        if constexpr (ACT == ACT_RELU) {
+            g4.x = drelu(y_pre4.x, d4.x);
+            g4.y = drelu(y_pre4.y, d4.y);
+            g4.z = drelu(y_pre4.z, d4.z);
+            g4.w = drelu(y_pre4.w, d4.w);
+        } else {
+            g4.x = (1.0f - y_pre4.x) * y_pre4.x * d4.x;
+            g4.y = (1.0f - y_pre4.y) * y_pre4.y * d4.y;
+            g4.z = (1.0f - y_pre4.z) * y_pre4.z * d4.z;
+            g4.w = (1.0f - y_pre4.w) * y_pre4.w * d4.w;
+        }
         *reinterpret_cast<float4 *>(&dEdXt_prev[(size_t)(k0 + row) * Bp + b0 + col4]) = g4;
         tileT[col4][row] = g4.x;
         tileT[col4 + 1][row] = g4.y;
@@ -990,7 +1016,7 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
             for (int w = 1; w < NW; w++) dedy += red[w][e];
             const size_t o = (size_t)(k0 + row) * Bp + b0 + col;
             const float y = y_pre[q];
-            const float g = (1.0f - y) * y * dedy;  // kernDsigmoid, DevFunc.cu:67-68
+            const float g = ACT == ACT_RELU ? drelu(y, dedy) : (1.0f - y) * y * dedy;  // kernDsigmoid, DevFunc.cu:67-68
             dEdXt_prev[o] = g;
             tileT[col][row] = g;
         }
@@ -1691,9 +1717,9 @@ template <int MODE, int NW, int PIPE = 1>
 __global__ __launch_bounds__(64 * NW) void k_fwd(FwdArgs A, long long *stamps) {
     fwd_body<MODE, NW, PIPE>(A, (int)blockIdx.x, g_dyn_lds, stamps);
 }
-template <int NW, int PIPE = 1>
+template <int NW, int PIPE = 1, int ACT = ACT_SIGMOID>
 __global__ __launch_bounds__(64 * NW) void k_dx(DxArgs A, long long *stamps) {
-    dx_body<NW, PIPE>(A, (int)blockIdx.x, g_dyn_lds, stamps);
+    dx_body<NW, PIPE, ACT>(A, (int)blockIdx.x, g_dyn_lds, stamps);
 }
 #include "kernels64.hip.h"  // k_fwd64 / k_dx64: the 64 x 64-tile forms for large minibatches
 template <int H, bool FUSED, bool POW2>
@@ -1747,12 +1773,13 @@ __global__ __launch_bounds__(256) void k_apply_update(float *__restrict__ Wt, fl
 // the oracle's glibc -- the only arithmetic of the loss chain that is not IEEE-exact on both sides.
 //   fn 0: powf(x, y)   1: expf(x) (ocml; no kernel uses it any more)   2: sigmoid_det(x), the forward epilogues' sigmoid
 //   3: x / y   4: exp_det(x)   5: pow_det(x, y), the loss chain's power   6: the packed form of the sigmoid (sigmoid_det4)
+//   7: relu4(x), the rectifier of the FWD_RELU epilogues
 __global__ __launch_bounds__(256) void k_debug_math(int fn, const float *__restrict__ x, float y, float *__restrict__ out,
                                                     size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float v = x[i];
-    out[i] = fn == 0 ? powf(v, y) : fn == 1 ? expf(v) : fn == 2 ? sigmoid_det(v) : fn == 6 ? sigmoid_det4(make_float4(v, v, v, v), 0.0f, true).z : fn == 4 ? exp_det(v) : fn == 5 ? pow_det(v, y) : v / y;
+    out[i] = fn == 0 ? powf(v, y) : fn == 1 ? expf(v) : fn == 2 ? sigmoid_det(v) : fn == 6 ? sigmoid_det4(make_float4(v, v, v, v), 0.0f, true).z : fn == 7 ? relu4(make_float4(v, v, v, v), 0.0f, true).z : fn == 4 ? exp_det(v) : fn == 5 ? pow_det(v, y) : v / y;
 }
 
 // keeps one wave busy for `ticks` of the 100 MHz wall clock (bounded: at most `ticks` iterations of a loop whose

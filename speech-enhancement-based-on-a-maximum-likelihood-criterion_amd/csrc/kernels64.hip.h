@@ -136,6 +136,7 @@ __device__ __forceinline__ void t64_rowmajor_loop(const rsrc_t rA, const rsrc_t 
 // ---------------------------------------------------------------------------------------
 // Forward + bias + sigmoid (hidden layers):  X^T[n][b] = sum_k W[k][n] Yt_in[k][b] + bias[n];  y = 1/(1+expf(-x))
 // replaces kernMultiCopy + cublasSgemm(N,N) + kernSigmoid (BP_GPU.cu:360-364).  A.n_tiles = Np/64, A.b_tiles = Bp/64.
+// MODE FWD_RELU: the rectifier in the sigmoid's place (relu4), the same stores.
 // MODE FWD_SLAB: an output layer wide enough for this tiling (one slab: the raw sums go to slab[0][n][b]; the loss
 // kernel adds the bias) -- also what lets a test read this kernel's sums back bit for bit.
 // ---------------------------------------------------------------------------------------
@@ -166,7 +167,7 @@ __device__ __forceinline__ void fwd64_body(const FwdArgs &A, const int bid, floa
     const int er = lane >> 3, ec = lane & 7;
     float bias_pre[4];
 #pragma unroll
-    for (int q = 0; q < 4; q++) bias_pre[q] = MODE == FWD_SIGMOID ? bias[n0 + 32 * wm + er + 8 * q] : 0.0f;
+    for (int q = 0; q < 4; q++) bias_pre[q] = MODE != FWD_SLAB ? bias[n0 + 32 * wm + er + 8 * q] : 0.0f;
     asm volatile("" ::: "memory");
 
     t64_rowmajor_loop<0>(rW, rY, voW, voY, Np * 4, Bp * 4, endW, endY, nch, smem, wave, wm, wn, fo, acc, [] {});
@@ -188,7 +189,7 @@ __device__ __forceinline__ void fwd64_body(const FwdArgs &A, const int bid, floa
             continue;
         }
         const float bn = bias_pre[q];
-        const float4 y4 = sigmoid_det4(v4, bn, n < N);  // kernSigmoid, DevFunc.cu:48
+        const float4 y4 = MODE == FWD_RELU ? relu4(v4, bn, n < N) : sigmoid_det4(v4, bn, n < N);  // kernSigmoid, DevFunc.cu:48
         *reinterpret_cast<float4 *>(&Yt_out[(size_t)n * Bp + b0 + 32 * wn + col4]) = y4;
         T[col4][row] = y4.x;
         T[col4 + 1][row] = y4.y;
@@ -208,6 +209,7 @@ __device__ __forceinline__ void fwd64_body(const FwdArgs &A, const int bid, floa
 
 // ---------------------------------------------------------------------------------------
 // dX + sigmoid derivative:  dEdY^T[k][b] = sum_n W[k][n] dEdXt[n][b];  dEdX_prev = (1 - y) y dEdY
+// (ACT_RELU: dEdX_prev = (y > 0) ? dEdY : 0)
 // replaces cublasSgemm(T,N) + kernDsigmoid (BP_GPU.cu:430,402).  A.k_tiles = Kp/64, A.b_tiles = Bp/64.
 // The reduction index n is the CONTIGUOUS index of W: a chunk is [64 k][32 n] of W (8 slots of 16 B per row) and
 // [32 n][64 b] of dEdXt.  The W piece is stored with slot s of row k holding quad s ^ ((k >> 1) & 7) (the permutation
@@ -215,6 +217,7 @@ __device__ __forceinline__ void fwd64_body(const FwdArgs &A, const int bid, floa
 // the same quad, ds_read_b64) spread over all 16 (row parity, slot) positions of the 256-byte bank row instead of
 // one: a 2-way conflict is left (lanes k and k + 16), as in k_dx.
 // ---------------------------------------------------------------------------------------
+template <int ACT>
 __device__ __forceinline__ void dx64_body(const DxArgs &A, const int bid, float *smem) {
     const float *__restrict__ W = A.W, *__restrict__ dEdXt = A.dEdXt, *__restrict__ Yt_prev = A.Yt_prev;
     float *__restrict__ dEdXt_prev = A.dEdXt_prev, *__restrict__ dEdX_prev = A.dEdX_prev;
@@ -337,10 +340,17 @@ __device__ __forceinline__ void dx64_body(const DxArgs &A, const int bid, float 
         const float4 d4 = *reinterpret_cast<const float4 *>(&S[row * 32 + col4]);
         const float4 y4 = y_pre[q];
         float4 g4;  // kernDsigmoid, DevFunc.cu:67-68
-        g4.x = (1.0f - y4.x) * y4.x * d4.x;
-        g4.y = (1.0f - y4.y) * y4.y * d4.y;
-        g4.z = (1.0f - y4.z) * y4.z * d4.z;
-        g4.w = (1.0f - y4.w) * y4.w * d4.w;
+        if constexpr (ACT == ACT_RELU) {
+            g4.x = drelu(y4.x, d4.x);
+            g4.y = drelu(y4.y, d4.y);
+            g4.z = drelu(y4.z, d4.z);
+            g4.w = drelu(y4.w, d4.w);
+        } else {
+            g4.x = (1.0f - y4.x) * y4.x * d4.x;
+            g4.y = (1.0f - y4.y) * y4.y * d4.y;
+            g4.z = (1.0f - y4.z) * y4.z * d4.z;
+            g4.w = (1.0f - y4.w) * y4.w * d4.w;
+        }
         *reinterpret_cast<float4 *>(&dEdXt_prev[(size_t)(k0 + 32 * wm + row) * Bp + b0 + 32 * wn + col4]) = g4;
         T[col4][row] = g4.x;
         T[col4 + 1][row] = g4.y;
@@ -358,4 +368,5 @@ __device__ __forceinline__ void dx64_body(const DxArgs &A, const int bid, float 
 
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void k_fwd64(FwdArgs A) { fwd64_body<MODE>(A, (int)blockIdx.x, g_dyn_lds); }
-__global__ __launch_bounds__(256, 2) void k_dx64(DxArgs A) { dx64_body(A, (int)blockIdx.x, g_dyn_lds); }
+template <int ACT = ACT_SIGMOID>
+__global__ __launch_bounds__(256, 2) void k_dx64(DxArgs A) { dx64_body<ACT>(A, (int)blockIdx.x, g_dyn_lds); }

@@ -13,10 +13,10 @@ void BP_GPU::check(int rc, const char *what) {
 
 BP_GPU::BP_GPU(int random_seed, int a_GPU_selected, int a_numlayers, int *a_layersizes, int a_bunchsize, float a_lrate,
                float a_momentum, float a_weightcost, float **weights, float **bias, float a_shapefactor, int a_MLflag,
-               int a_dropoutflag, float a_visible_omit, float a_hid_omit)
+               int a_dropoutflag, float a_visible_omit, float a_hid_omit, int a_activation)
     : numlayers(a_numlayers), bunchsize(a_bunchsize), lrate(a_lrate), shapefactor(a_shapefactor),
       momentum(a_momentum), weightcost(a_weightcost), dropoutflag(a_dropoutflag), MLflag(a_MLflag),
-      visible_omit(a_visible_omit), hid_omit(a_hid_omit) {
+      visible_omit(a_visible_omit), hid_omit(a_hid_omit), activation(a_activation) {
     int ndev = 0;
     check(mlggd_device_count(&ndev), "mlggd_device_count");
     printf("Total GPU Device : %d\n", ndev);  // BP_GPU.cu:16
@@ -36,6 +36,7 @@ BP_GPU::BP_GPU(int random_seed, int a_GPU_selected, int a_numlayers, int *a_laye
     cfg.dropoutflag = a_dropoutflag;
     cfg.visible_omit = a_visible_omit;
     cfg.hid_omit = a_hid_omit;
+    cfg.activation = a_activation;
     check(mlggd_create(&cfg, weights, bias, &h_), "mlggd_create");
     printf("Use GPU Device : %d\n", a_GPU_selected);                                        // BP_GPU.cu:23
     printf("Created net with %d layers, bunchsize %d.\n", numlayers, bunchsize);            // BP_GPU.cu:110

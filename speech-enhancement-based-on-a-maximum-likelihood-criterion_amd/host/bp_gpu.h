@@ -10,7 +10,7 @@ class BP_GPU {
   public:
     BP_GPU(int random_seed, int a_GPU_selected, int a_numlayers, int *a_layersizes, int a_bunchsize, float a_lrate,
            float a_momentum, float a_weightcost, float **weights, float **bias, float shapefactor, int MLflag,
-           int dropoutflag, float visible_omit, float hid_omit);
+           int dropoutflag, float visible_omit, float hid_omit, int activation = MLGGD_ACT_SIGMOID);
     ~BP_GPU();
     void train(int n_frames, float *in, const float *targ);
     // One SGD step on n_frames = bunchsize rows (BP_GPU.h:53, BP_GPU.cu:308-440).  The reference's member is public
@@ -51,6 +51,7 @@ class BP_GPU {
     float lrate, shapefactor, momentum, weightcost;
     int dropoutflag, MLflag;
     float visible_omit, hid_omit;
+    int activation;  // MLGGD_ACT_SIGMOID (the reference's class) or MLGGD_ACT_RELU: not in the reference
 
   private:
     void check(int rc, const char *what);

@@ -23,6 +23,11 @@
 // (mlggd_set_shapefactors).  One stderr line names the file and the minimum, maximum and mean shape; the command line
 // and the form of the log lines do not change, the CV log likelihood is then the vector's.  Needs MLflag=1.
 //
+// Activation (new): activation=sigmoid|relu selects the hidden units (mlggd_config.activation).  Without the key the
+// program's own name decides: installed as BPtrain_ReLU -- the same program -- it trains rectified-linear nets, under
+// any other name sigmoid ones, so a finetune.pl edited only in its $exe line trains a ReLU net.  Any other value ends
+// the run before a file or a device is opened.  The banner line names the choice; the log file does not change.
+//
 // Data parallel (new): when WORLD_SIZE > 1 (torchrun-style env: RANK,
 // LOCAL_RANK, WORLD_SIZE; MLGGD_ID_FILE names a file on a shared filesystem used to hand the
 // RCCL unique id from rank 0 to the others) every rank reads the same chunks with the same
@@ -71,6 +76,24 @@ void exchange_id(int world, int rank, unsigned char id[MLGGD_UNIQUE_ID_BYTES]) {
     const char *path = getenv("MLGGD_ID_FILE");
     if (rank == 0 && mlggd_comm_unique_id(id) != MLGGD_OK) throw IoError(mlggd_last_error());
     mlggd_host::rendezvous(path ? path : "", world, rank, id, (double)env_int("MLGGD_RENDEZVOUS_TIMEOUT", 600));
+}
+
+// activation=sigmoid|relu; without the key, BPtrain_ReLU trains ReLU nets and every other name sigmoid ones
+int activation_from_args(int argc, char **argv) {
+    const char *slash = argc > 0 ? strrchr(argv[0], '/') : nullptr;
+    const std::string prog = argc > 0 ? (slash ? slash + 1 : argv[0]) : "";
+    int act = prog == "BPtrain_ReLU" ? MLGGD_ACT_RELU : MLGGD_ACT_SIGMOID;
+    for (int a = 1; a < argc; a++) {
+        if (strncmp(argv[a], "activation=", 11)) continue;
+        const std::string v = argv[a] + 11;
+        if (v == "sigmoid") act = MLGGD_ACT_SIGMOID;
+        else if (v == "relu") act = MLGGD_ACT_RELU;
+        else {
+            fprintf(stderr, "activation=%s: must be sigmoid or relu\n", v.c_str());
+            exit(1);
+        }
+    }
+    return act;
 }
 
 }  // namespace
@@ -123,9 +146,11 @@ static void phase(const char *name, double &t_last) {
 int main(int argc, char *argv[]) {
     const double t_start = (double)time(NULL);
     double t_phase = now_s();
+    const int activation = activation_from_args(argc, argv);
+    const char *act_name = activation == MLGGD_ACT_RELU ? "relu" : "sigmoid";
     // BPtrain.cc:71: black on red when stdout is a terminal, as the reference prints it; plain text into pipes / logs
-    printf(isatty(STDOUT_FILENO) ? "\033[41;30m--------activation functin is sigmoid--------\033[0m\n"
-                                 : "--------activation functin is sigmoid--------\n");
+    printf(isatty(STDOUT_FILENO) ? "\033[41;30m--------activation functin is %s--------\033[0m\n"
+                                 : "--------activation functin is %s--------\n", act_name);
     const int world = env_int("WORLD_SIZE", 1), rank = env_int("RANK", 0);
     const int local_rank = env_int("LOCAL_RANK", rank);
     Interface *io = new Interface;
@@ -202,7 +227,7 @@ int main(int argc, char *argv[]) {
         progress("engine + communicator");
         BP_GPU *net = new BP_GPU(p->init_randem_seed, device, io->numlayers, p->layersizes, p->bunchsize, p->lrate,
                                  p->momentum, p->weightcost, p->weights, p->bias, p->shapefactor, p->MLflag,
-                                 p->dropoutflag, p->visible_omit, p->hid_omit);
+                                 p->dropoutflag, p->visible_omit, p->hid_omit, activation);
         if (world > 1) {
             unsigned char id[MLGGD_UNIQUE_ID_BYTES];
             exchange_id(world, rank, id);

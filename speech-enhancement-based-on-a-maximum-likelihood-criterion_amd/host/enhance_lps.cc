@@ -9,7 +9,8 @@
 // of the first / last frame, so the forward runs through mlggd_forward_frames.
 //
 //   enhance_lps wts=mlp.50.wts norm_file=train_noisy.norm in=noisy.lps out=enhanced.htk
-//               [fea_context=7] [gpu_used=0] [bunchsize=512] [scp=list of "in out" lines]
+//               [fea_context=7] [gpu_used=0] [bunchsize=512] [scp=list of "in out" lines] [activation=sigmoid|relu]
+// activation: the hidden units the net was trained with (BPtrain_Sigmoid / BPtrain_ReLU); the .wts file does not say.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -31,7 +32,7 @@ using tool_io::write_htk;
 
 int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp;
-    int ctx = 7, gpu = 0, bunch = 512;
+    int ctx = 7, gpu = 0, bunch = 512, act = MLGGD_ACT_SIGMOID;
     for (int a = 1; a < argc; a++) {
         const std::string arg(argv[a]);
         const size_t eq = arg.find('=');
@@ -45,9 +46,10 @@ int main(int argc, char **argv) {
         else if (k == "fea_context") ctx = atoi(v.c_str());
         else if (k == "gpu_used") gpu = atoi(v.c_str());
         else if (k == "bunchsize") bunch = atoi(v.c_str());
+        else if (k == "activation") act = tool_io::parse_activation(v);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
-        die("usage: enhance_lps wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512]");
+        die("usage: enhance_lps wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] [activation=sigmoid|relu]");
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
 
     // ---- model: the trainer's .wts container (Interface.cc:484-516)
@@ -62,7 +64,7 @@ int main(int argc, char **argv) {
     tool_io::read_norm(norm_file, dim, mean, inv);
     if (D % dim) die("output dimension is not a multiple of the feature dimension");
 
-    mlggd_handle h = tool_io::create_engine(model, gpu, bunch);
+    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act);
 
     std::vector<std::pair<std::string, std::string>> jobs;
     if (!scp.empty()) {

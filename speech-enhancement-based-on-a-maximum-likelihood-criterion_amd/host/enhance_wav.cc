@@ -6,8 +6,9 @@
 //
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
-//               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]]
+//               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu]
 //
+// activation: the hidden units the net was trained with (BPtrain_Sigmoid / BPtrain_ReLU); the .wts file does not say.
 // scp lists "in out" or "in out clean info" lines.  A list is decoded in batches of batch_s seconds of audio by
 // mlggd_enhance_waves: the utterances of a batch form one frame stream, so the forward bunches are full, and the
 // quality report takes the network's output rows from the same pass.  A batch ends early where the sample rate
@@ -85,8 +86,8 @@ int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp, clean, info, score = "host";
     const char *usage =
         "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
-        "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]]";
-    int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64;
+        "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu]";
+    int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64, act = MLGGD_ACT_SIGMOID;
     bool live = false, score_given = false, want_stoi = false;
     double batch_s = 300.0;
     for (int a = 1; a < argc; a++) {
@@ -109,6 +110,7 @@ int main(int argc, char **argv) {
         else if (k == "stoi") want_stoi = atoi(v.c_str()) != 0;
         else if (k == "live") live_block = atoi(v.c_str()), live = true;
         else if (k == "sessions") n_slots = atoi(v.c_str());
+        else if (k == "activation") act = tool_io::parse_activation(v);
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
@@ -132,7 +134,7 @@ int main(int argc, char **argv) {
     if (model.ls[0] != ctx * D) die("layersizes[0] is not fea_context x the output dimension");
     std::vector<float> mean, inv;
     tool_io::read_norm(norm_file, D, mean, inv);
-    mlggd_handle h = tool_io::create_engine(model, gpu, bunch);
+    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act);
 
     std::vector<Job> jobs;
     if (!scp.empty()) {

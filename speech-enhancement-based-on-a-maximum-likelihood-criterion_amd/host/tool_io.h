@@ -115,7 +115,16 @@ inline void read_norm(const std::string &norm_file, int dim, std::vector<float> 
 }
 
 // an engine for inference with the model (bunchsize frames per forward bunch)
-inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_cache_frames = 0) {
+// activation=sigmoid|relu of the decoders: the .wts container carries no such flag, so the decoder is told what the
+// trainer was told.  Anything else ends the run here, before a device is opened.
+inline int parse_activation(const std::string &v) {
+    if (v == "sigmoid") return MLGGD_ACT_SIGMOID;
+    if (v == "relu") return MLGGD_ACT_RELU;
+    die("activation=" + v + ": must be sigmoid or relu");
+}
+
+inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_cache_frames = 0,
+                                  int activation = MLGGD_ACT_SIGMOID) {
     const int L = (int)m.ls.size();
     mlggd_config cfg;
     memset(&cfg, 0, sizeof(cfg));
@@ -126,6 +135,7 @@ inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_ca
     cfg.bunchsize = bunch;
     cfg.shapefactor = 2.0f;
     cfg.max_cache_frames = max_cache_frames;
+    cfg.activation = activation;
     std::vector<const float *> wp(L, nullptr), bp(L, nullptr);
     for (int l = 1; l < L; l++) { wp[l] = m.W[l].data(); bp[l] = m.B[l].data(); }
     mlggd_handle h = nullptr;
