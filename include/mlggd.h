@@ -62,7 +62,9 @@ typedef struct mlggd_config {
     float hid_omit;
     int32_t max_cache_frames; /* rows of the resident chunk buffers; 0 -> MLGGD_MAXCACHEFRAME */
     int32_t activation;      /* hidden units: MLGGD_ACT_SIGMOID (0, the default of a zeroed struct) or MLGGD_ACT_RELU */
-    int32_t reserved[6];
+    int32_t nat_frames;      /* noise-aware training: 0 (a zeroed struct) = off; T >= 1: every input row ends in its utterance's
+                              * noise row over the first T frames, layersizes[0] = (fea_context + 1) * D; < 0: MLGGD_ERR_ARG */
+    int32_t reserved[5];
 } mlggd_config;
 
 /* ---- lifetime: BP_GPU::BP_GPU / ~BP_GPU (BP_GPU.cu:9-150) ---- */
@@ -124,6 +126,50 @@ int mlggd_cv_all_frames(mlggd_handle h, int n_frames, int fea_context, const flo
                         float *loglik);
 int mlggd_forward_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat, int n_samples,
                          const int32_t *first_frame, float *out);
+/* ---- noise-aware training, NAT (csrc/nat_rule.h; Xu, Du, Dai and Lee 2014 / 2015; no counterpart in the reference).
+ * An engine created with mlggd_config.nat_frames = T >= 1 takes input rows that end in a noise estimate of their
+ * utterance: the window of fea_context frames, then the D values of the utterance's noise row, so layersizes[0] =
+ * (fea_context + 1) * D and a stream row is layersizes[0] / (fea_context + 1) wide.  The rule: an utterance u of
+ * F_u >= 1 frames uses T_u = min(T, F_u) of them; with x_t[k] = (lps_t[k] - mean[k]) * inv_std[k] (two fp32
+ * operations, the stream's own) its noise row is z_u[k] = (((x_0[k] + x_1[k]) + x_2[k]) + ... + x_{T_u-1}[k]) /
+ * (float)T_u: fp32 additions from left to right, one fp32 division, nothing contracted.  An utterance without frames
+ * has a zero row.  Targets are unchanged.
+ *
+ * The *_frames_nat entries are the *_frames entries with the noise table nat [n_nat][fdim] and, per sample row, the
+ * index nat_row[i] of its noise row (rows may repeat and come in any order); the staging kernel gathers both parts, and
+ * every result equals, bit for bit, the expanded entry (mlggd_train_chunk, mlggd_cv_all, mlggd_forward, ...) on rows
+ * [window | nat[nat_row[i]]] built by the caller -- the expanded entries work on a NAT engine as they are.  After
+ * mlggd_load_frames_nat, mlggd_train_resident indexes these samples.  A nat_row outside [0, n_nat) (the message names
+ * the sample), NULL pointers and a fea_context with (fea_context + 1) * fdim != layersizes[0] are MLGGD_ERR_ARG, found
+ * before any device call.  The _nat entries on an engine with nat_frames = 0, and the plain *_frames entries
+ * (mlggd_error_stats_frames and mlggd_train_frames_async included) on a NAT engine, are MLGGD_ERR_STATE; the engine
+ * stays usable and unchanged.
+ * On a NAT engine mlggd_load_waves / mlggd_cv_all_waves / mlggd_train_waves and mlggd_enhance_wave / _waves / _scored /
+ * _scored_stoi keep their signatures, need (fea_context + 1) * D == layersizes[0] and form every utterance's noise row
+ * on the device from its noisy LPS rows (once per call, before any chunk: the decoders' results still do not depend on
+ * max_cache_frames, the batch or the position); neither the noisy rows nor the noise rows visit the host.
+ * mlggd_live_open, mlggd_comm_init and mlggd_debug_fake_world on a NAT engine are MLGGD_ERR_STATE.
+ * mlggd_nat_estimate / mlggd_nat_rows: host only, no device.  rows [sum F][D] are NORMALISED rows, utterance u's from
+ * frame_off[u] (frame_off [n_utts+1], non-decreasing); out [n_utts][D].  nat_row[i] = the utterance that holds packed
+ * frame first_frame[i] (utterances without frames are stepped over). */
+int mlggd_load_frames_nat(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,
+                          int n_samples, const int32_t *first_frame, int targ_offset, int n_nat,
+                          const float *nat /* [n_nat][fdim] */, const int32_t *nat_row /* [n_samples] */);
+int mlggd_train_frames_nat(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,
+                           int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
+                           const int32_t *nat_row, int *bunches_trained);
+int mlggd_cv_all_frames_nat(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,
+                            int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
+                            const int32_t *nat_row, float *sqerr, float *abserr, float *loglik);
+int mlggd_forward_frames_nat(mlggd_handle h, int n_frames, int fea_context, const float *feat, int n_samples,
+                             const int32_t *first_frame, int n_nat, const float *nat, const int32_t *nat_row,
+                             float *out);
+int mlggd_nat_estimate(int D, int n_utts, const int32_t *frame_off /* [n_utts+1] */, const float *rows,
+                       int nat_frames, float *out /* [n_utts][D] */);
+int mlggd_nat_rows(int n_utts, const int32_t *frame_off /* [n_utts+1] */, int n_samples, const int32_t *first_frame,
+                   int32_t *nat_row /* [n_samples] */);
+int mlggd_get_nat_frames(mlggd_handle h, int *nat_frames); /* the nat_frames the engine was created with */
+
 /* ---- the GGD error model on the device (no counterpart in the reference, which only ever holds the alpha of the
  * last training minibatch and evaluates CrossValid2 at it, BP_GPU.cu:271-301).  The ML criterion models the error
  * e = out - targ of every output bin d as a generalized Gaussian  beta / (2 alpha_d Gamma(1/beta)) exp(-(|e|/alpha_d)^beta);

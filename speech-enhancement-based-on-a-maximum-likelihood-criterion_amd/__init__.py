@@ -33,7 +33,7 @@ class _Config(C.Structure):
         ("lrate", C.c_float), ("momentum", C.c_float), ("weightcost", C.c_float),
         ("shapefactor", C.c_float), ("MLflag", C.c_int32), ("dropoutflag", C.c_int32),
         ("visible_omit", C.c_float), ("hid_omit", C.c_float), ("max_cache_frames", C.c_int32),
-        ("activation", C.c_int32), ("reserved", C.c_int32 * 6),
+        ("activation", C.c_int32), ("nat_frames", C.c_int32), ("reserved", C.c_int32 * 5),
     ]
 
 
@@ -73,6 +73,8 @@ EXPORTS = [
     "mlggd_set_shapefactors", "mlggd_get_shapefactors", "mlggd_read_shapefactors",
     "mlggd_wave_samples", "mlggd_mix_waves", "mlggd_lps_stats", "mlggd_norm_from_stats",
     "mlggd_load_waves", "mlggd_cv_all_waves", "mlggd_set_noise", "mlggd_train_waves",
+    "mlggd_load_frames_nat", "mlggd_train_frames_nat", "mlggd_cv_all_frames_nat", "mlggd_forward_frames_nat",
+    "mlggd_nat_estimate", "mlggd_nat_rows", "mlggd_get_nat_frames",
 ]
 MAX_BETAS = 32
 
@@ -83,7 +85,7 @@ def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "mix.hip.h",
-                                             "mix_rule.h")]
+                                             "mix_rule.h", "nat_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     stale = not os.path.exists(LIB_PATH) or any(
@@ -189,6 +191,13 @@ def load():
     L.mlggd_set_noise.argtypes = [C.c_void_p, C.c_int64, _sp]
     L.mlggd_train_waves.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _sp, _lp, _lp, _lp, _lp, _dp, C.c_int,
                                     _ip, C.c_int, _sp, _dp, _ip, C.POINTER(C.c_int)]
+    L.mlggd_load_frames_nat.argtypes = L.mlggd_load_frames.argtypes + [C.c_int, _fp, _ip]
+    L.mlggd_train_frames_nat.argtypes = L.mlggd_load_frames_nat.argtypes + [C.POINTER(C.c_int)]
+    L.mlggd_cv_all_frames_nat.argtypes = L.mlggd_load_frames_nat.argtypes + [_fp, _fp, _fp]
+    L.mlggd_forward_frames_nat.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, C.c_int, _ip, C.c_int, _fp, _ip, _fp]
+    L.mlggd_nat_estimate.argtypes = [C.c_int, C.c_int, _ip, _fp, C.c_int, _fp]
+    L.mlggd_nat_rows.argtypes = [C.c_int, _ip, C.c_int, _ip, _ip]
+    L.mlggd_get_nat_frames.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     _lib = L
     return L
 
@@ -225,6 +234,43 @@ def device_count():
 
 def gamma(x):
     return float(load().mlggd_gamma(float(x)))
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _frame_off(frame_off):
+    fo = np.ascontiguousarray(frame_off, dtype=np.int32)
+    if fo.ndim != 1 or fo.size < 1:
+        raise ValueError("frame_off is a 1-D table of n_utts + 1 frame indices")
+    return fo
+
+
+def nat_estimate(rows, frame_off, nat_frames):
+    """The noise rows [n_utts][D] float32 of noise-aware training (csrc/nat_rule.h, mlggd_nat_estimate): utterance u
+    holds the NORMALISED rows rows[frame_off[u]:frame_off[u+1]]; its row is the mean of its first min(nat_frames, F_u)
+    rows, added from left to right in fp32 and divided once; zeros for an utterance without frames.  A host call: needs
+    no device."""
+    rows = _f32(rows)
+    fo = _frame_off(frame_off)
+    if rows.ndim != 2 or rows.shape[0] < int(fo[-1]):
+        raise ValueError("rows must be [frame_off[-1]][D]")
+    out = np.zeros((fo.size - 1, rows.shape[1]), np.float32)
+    _check(load().mlggd_nat_estimate(rows.shape[1], fo.size - 1, _i32p(fo), _p(rows), int(nat_frames), _p(out)))
+    return out
+
+
+def nat_rows(frame_off, first_frame):
+    """nat_row [n_samples] int32: the utterance that holds each sample's first frame (mlggd_nat_rows); utterances
+    without frames are stepped over.  A host call: needs no device."""
+    fo = _frame_off(frame_off)
+    first = np.ascontiguousarray(first_frame, dtype=np.int32)
+    if first.ndim != 1:
+        raise ValueError("first_frame is a 1-D table of frame indices")
+    out = np.zeros(first.size, np.int32)
+    _check(load().mlggd_nat_rows(fo.size - 1, _i32p(fo), first.size, _i32p(first), _i32p(out)))
+    return out
 
 
 # frame length L, hop S and FFT length N of the spectral front end per sampling rate in kHz (Wav2LogSpec_be.c)
@@ -597,11 +643,13 @@ class BPGpu:
     """Same constructor arguments and methods as the reference's BP_GPU (BP_GPU.h:48-59)."""
 
     def __init__(self, random_seed, gpu, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
-                 shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0, activation="sigmoid"):
+                 shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0, activation="sigmoid",
+                 nat_frames=0):
         self._h = None
         act = activation_code(activation)  # hidden units: "sigmoid" (the reference's BPtrain_Sigmoid) or "relu"
         self._lives = []
         self._n_noise = 0
+        self._nat = int(nat_frames) > 0
         self.layersizes = [int(x) for x in layersizes]
         self.numlayers = len(self.layersizes)
         if not 2 <= self.numlayers <= MAXLAYER:
@@ -626,6 +674,7 @@ class BPGpu:
         cfg.dropoutflag, cfg.visible_omit, cfg.hid_omit = int(dropoutflag), visible_omit, hid_omit
         cfg.max_cache_frames = int(max_cache_frames)
         cfg.activation = act
+        cfg.nat_frames = int(nat_frames)  # noise-aware training: every input row ends in its utterance's noise row
         h = C.c_void_p()
         rc = load().mlggd_create(C.byref(cfg), _ptr_array(ws), _ptr_array(bs), C.byref(h))
         if rc != 0:
@@ -641,6 +690,13 @@ class BPGpu:
         a = C.c_int()
         _check(load().mlggd_get_activation(self._h, C.byref(a)))
         return ACTIVATIONS[a.value]
+
+    @property
+    def nat_frames(self):
+        """0, or the T of noise-aware training the engine was created with (mlggd_get_nat_frames)."""
+        n = C.c_int()
+        _check(load().mlggd_get_nat_frames(self._h, C.byref(n)))
+        return n.value
 
     # -- lifetime
     def close(self):
@@ -750,6 +806,52 @@ class BPGpu:
                                            first.ctypes.data_as(C.POINTER(C.c_int32)), _p(out)))
         return out
 
+    # -- the same on a NAT engine: a stream row is K0 / (fea_context + 1) wide, nat [n_nat][that] is the noise table and
+    # nat_row[i] the noise row of sample i (mlggd_*_frames_nat)
+    def _frames_nat_args(self, feat, targ, first_frame, fea_context, nat, nat_row):
+        feat = _f32(feat)
+        first = np.ascontiguousarray(first_frame, dtype=np.int32)
+        if feat.ndim != 2 or feat.shape[1] * (fea_context + 1) != self.K0:
+            raise ValueError("feat must be [n_frames][%d/(fea_context+1)]" % self.K0)
+        if targ is not None:
+            targ = _f32(targ, (feat.shape[0], self.D))
+        nat = _f32(nat)
+        rows = np.ascontiguousarray(nat_row, dtype=np.int32)
+        if nat.ndim != 2 or nat.shape[1] != feat.shape[1]:
+            raise ValueError("nat must be [n_nat][%d]" % feat.shape[1])
+        if rows.shape != first.shape or first.ndim != 1:
+            raise ValueError("nat_row holds one index per sample of first_frame")
+        return feat, targ, first, nat, rows
+
+    def load_frames_nat(self, feat, targ, first_frame, fea_context, targ_offset, nat, nat_row):
+        feat, targ, first, nat, rows = self._frames_nat_args(feat, targ, first_frame, fea_context, nat, nat_row)
+        _check(load().mlggd_load_frames_nat(self._h, feat.shape[0], int(fea_context), _p(feat),
+                                            _p(targ) if targ is not None else None, first.size, _i32p(first),
+                                            int(targ_offset), nat.shape[0], _p(nat), _i32p(rows)))
+
+    def train_frames_nat(self, feat, targ, first_frame, fea_context, targ_offset, nat, nat_row):
+        feat, targ, first, nat, rows = self._frames_nat_args(feat, targ, first_frame, fea_context, nat, nat_row)
+        trained = C.c_int(0)
+        _check(load().mlggd_train_frames_nat(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
+                                             _i32p(first), int(targ_offset), nat.shape[0], _p(nat), _i32p(rows),
+                                             C.byref(trained)))
+        return trained.value
+
+    def cv_all_frames_nat(self, feat, targ, first_frame, fea_context, targ_offset, nat, nat_row):
+        feat, targ, first, nat, rows = self._frames_nat_args(feat, targ, first_frame, fea_context, nat, nat_row)
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        _check(load().mlggd_cv_all_frames_nat(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
+                                              _i32p(first), int(targ_offset), nat.shape[0], _p(nat), _i32p(rows),
+                                              C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def forward_frames_nat(self, feat, first_frame, fea_context, nat, nat_row):
+        feat, _, first, nat, rows = self._frames_nat_args(feat, None, first_frame, fea_context, nat, nat_row)
+        out = np.empty((first.size, self.D), np.float32)
+        _check(load().mlggd_forward_frames_nat(self._h, feat.shape[0], int(fea_context), _p(feat), first.size,
+                                               _i32p(first), nat.shape[0], _p(nat), _i32p(rows), _p(out)))
+        return out
+
     def sync(self):
         _check(load().mlggd_sync(self._h))
 
@@ -759,7 +861,7 @@ class BPGpu:
         cleans = [_wave(w) for w in cleans]
         D = SPECTRAL_PARAMS.get(int(fs_khz), (0, 0, 2 * self.D - 2))[2] // 2 + 1
         if fea_context is None:
-            fea_context = self.K0 // D
+            fea_context = self.K0 // D - (1 if self._nat else 0)  # a NAT engine's last D inputs are the noise row
         first = np.ascontiguousarray(first_frame, dtype=np.int32)
         if first.ndim != 1:
             raise ValueError("first_frame is a 1-D table of frame indices")
@@ -855,7 +957,7 @@ class BPGpu:
         mean = _f32(mean, (D,))
         inv = _f32(inv_std, (D,))
         if fea_context is None:
-            fea_context = self.K0 // D
+            fea_context = self.K0 // D - (1 if self._nat else 0)  # a NAT engine's last D inputs are the noise row
         frames, frame_off, out_off = enhance_waves_layout([w.size for w in waves], fs_khz)
         n = len(waves)
         packed = np.concatenate(waves) if n else np.zeros(0, np.int16)

@@ -32,6 +32,7 @@
 #include "errstats.hip.h"
 #include "mix.hip.h"
 #include "mix_rule.h"
+#include "nat_rule.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -218,6 +219,12 @@ struct mlggd_engine {
     float *in_bunch_buf[2] = {nullptr, nullptr};  // in_bunch alternates between them when bunches are staged ahead
     int *first_frame = nullptr;
     size_t raw_cap = 0, first_cap = 0;
+    // noise-aware training (nat_rule.h): nat_frames = cfg.nat_frames > 0 makes layer 0 one stream row wider; nat /
+    // nat_row are the noise table and the per-sample noise rows of the CURRENT indexed chunk (a raw set's own, or the
+    // decoder's table of the whole batch), switched together with raw_feat / first_frame
+    int nat_frames = 0;
+    const float *nat = nullptr;
+    const int *nat_row = nullptr;
     // Frame-stream chunks ping-pong between two device buffer sets: the next chunk is uploaded on copy_stream
     // while the kernels of the current one are still running (raw_feat / raw_targ / first_frame / *_cap above
     // always describe the CURRENT set).
@@ -225,6 +232,10 @@ struct mlggd_engine {
         float *feat = nullptr, *targ = nullptr;
         int *first = nullptr;
         size_t raw_cap = 0, first_cap = 0;
+        // a NAT engine (nat_rule.h): the noise table [nat_cap rows][fdim] and the noise row of every sample
+        float *nat = nullptr;
+        int *nat_row = nullptr;
+        size_t nat_cap = 0, nat_row_cap = 0;
         hipEvent_t last_use = nullptr;  // recorded on the main stream after the last kernel that reads the set
     } raw[2];
     int raw_cur = 0;
@@ -237,6 +248,7 @@ struct mlggd_engine {
     };
     struct WavesWs {
         WsBuf wave, lps, X, blk, out_i, out_f, lps_den, norm, frame_off, out_off, wave_off, utt_of;
+        WsBuf nat;  // a NAT engine: the noise rows [n_utts][D] of the batch being decoded
         WsBuf clean, Xc, fstat, sframes, scores;  // mlggd_enhance_waves_scored (score.hip.h)
         WsBuf stoi_utt, stoi_x, stoi_f, stoi_i, stoi_res;  // mlggd_enhance_waves_scored_stoi (stoi.hip.h)
         std::vector<int32_t> h_frame_off, h_utt_of;
@@ -255,7 +267,7 @@ struct mlggd_engine {
         WsBuf norm, frame_off, wave_off, blocks, utt, noise;
         long long n_noise = 0;
         std::vector<float> h_norm;
-        std::vector<int32_t> h_frame_off;
+        std::vector<int32_t> h_frame_off, h_nat_row;
         std::vector<long long> h_wave_off;
         std::vector<mix_rule::Block> h_blocks;
         std::vector<double> h_r;
@@ -528,6 +540,7 @@ struct Bunch {
     const float *in;    // expanded: first row of the bunch; indexed: the raw feature stream
     const float *targ;  // expanded: first target row;       indexed: the raw target stream
     const int *first;   // indexed: first frame of each sample row of this bunch, else nullptr
+    const int *nat_row; // indexed chunk of a NAT engine: the noise row of each sample row of this bunch, else nullptr
 };
 static Bunch bunch_at(mlggd_engine *e, int sample) {
     Bunch b;
@@ -535,10 +548,12 @@ static Bunch bunch_at(mlggd_engine *e, int sample) {
         b.in = e->raw_feat;
         b.targ = e->raw_targ;
         b.first = e->first_frame + sample;
+        b.nat_row = e->nat_frames ? e->nat_row + sample : nullptr;
     } else {
         b.in = e->chunk_in + (size_t)sample * e->K0;
         b.targ = e->chunk_targ + (size_t)sample * e->D;
         b.first = nullptr;
+        b.nat_row = nullptr;
     }
     return b;
 }
@@ -585,6 +600,11 @@ static bool dx64_used(const mlggd_engine *e, int l) {
 
 static int run_transpose(mlggd_engine *e, const Bunch &bn, int frames) {
     ProfScope ps(e, KC_TRANSPOSE, 0);
+    if (bn.nat_row) {  // a NAT engine's frame stream: the window, then the noise row of the sample's utterance
+        hipLaunchKernelGGL(k_transpose_in_nat, dim3(stage_blocks(e)), dim3(256), 0, e->stream,
+                           stage_args(e, bn, frames, e->in_bunch), e->nat, bn.nat_row);
+        return launch_check("k_transpose_in_nat");
+    }
     hipLaunchKernelGGL(k_transpose_in, dim3(stage_blocks(e)), dim3(256), 0, e->stream,
                        stage_args(e, bn, frames, e->in_bunch));
     return launch_check("k_transpose_in");
@@ -1690,6 +1710,7 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     if (cfg->activation != MLGGD_ACT_SIGMOID && cfg->activation != MLGGD_ACT_RELU)
         return fail(MLGGD_ERR_ARG, "activation %d: must be %d (sigmoid) or %d (relu)", cfg->activation, MLGGD_ACT_SIGMOID,
                     MLGGD_ACT_RELU);
+    if (cfg->nat_frames < 0) return fail(MLGGD_ERR_ARG, "nat_frames %d < 0", cfg->nat_frames);
     for (int i = 0; i < cfg->numlayers; i++)
         if (cfg->layersizes[i] < 1) return fail(MLGGD_ERR_ARG, "layersizes[%d] = %d", i, cfg->layersizes[i]);
     for (int i = 1; i < cfg->numlayers; i++) {
@@ -1722,6 +1743,7 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     e->K0 = e->ls[0];
     e->D = e->ls[e->L - 1];
     e->Dp = e->lsp[e->L - 1];
+    e->nat_frames = cfg->nat_frames;
     if (const char *v = getenv("MLGGD_FWD_NW")) e->fwd_nw = atoi(v);
     if (const char *v = getenv("MLGGD_WAVES_LOOKUP")) e->ww.lookup_table = !strcmp(v, "table");
     if (const char *v = getenv("MLGGD_DX_NW")) e->dx_nw = atoi(v);
@@ -1824,12 +1846,14 @@ int mlggd_destroy(mlggd_handle e) {
         if (r.feat) hipFree(r.feat);
         if (r.targ) hipFree(r.targ);
         if (r.first) hipFree(r.first);
+        if (r.nat) hipFree(r.nat);
+        if (r.nat_row) hipFree(r.nat_row);
         if (r.last_use) hipEventDestroy(r.last_use);
     }
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
     for (mlggd_engine::WsBuf *b : {&e->ww.wave, &e->ww.lps, &e->ww.X, &e->ww.blk, &e->ww.out_i, &e->ww.out_f,
                                    &e->ww.lps_den, &e->ww.norm, &e->ww.frame_off, &e->ww.out_off, &e->ww.wave_off,
-                                   &e->ww.utt_of, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores,
+                                   &e->ww.utt_of, &e->ww.nat, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores,
                                    &e->ww.stoi_utt, &e->ww.stoi_x, &e->ww.stoi_f, &e->ww.stoi_i, &e->ww.stoi_res,
                                    &e->tw.norm, &e->tw.frame_off, &e->tw.wave_off, &e->tw.blocks, &e->tw.utt,
                                    &e->tw.noise})
@@ -1994,13 +2018,46 @@ int mlggd_load_chunk(mlggd_handle e, int n_frames, const float *in, const float 
     return MLGGD_OK;
 }
 
-// the chunk as raw frame streams + the first frame of every sample row.
-int mlggd_load_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
-                      int n_samples, const int32_t *first_frame, int targ_offset) {
-    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
-    if (fea_context < 1 || e->K0 % fea_context != 0)
-        return fail(MLGGD_ERR_ARG, "fea_context %d does not divide layersizes[0] = %d", fea_context, e->K0);
-    const int fdim = e->K0 / fea_context;
+}  // extern "C"
+
+// width of a stream row: layersizes[0] / fea_context, or / (fea_context + 1) on a NAT engine (0: it does not divide)
+static int stream_fdim(const mlggd_engine *e, int ctx) { return nat_rule::stream_width(e->K0, ctx, e->nat_frames > 0); }
+
+// the noise table and the nat_row array of a raw set, grown to n_nat rows of fdim floats and n samples; the caller has
+// made sure that nothing on the device still reads the set
+static int raw_set_nat_grow(mlggd_engine *e, mlggd_engine::RawSet &r, size_t n_nat, size_t n, int fdim, hipStream_t st) {
+    const size_t need = n_nat + 8;
+    if (need > r.nat_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (r.nat) hipFree(r.nat);
+        r.nat = nullptr;
+        r.nat_cap = 0;
+        HIPCHK(hipMalloc((void **)&r.nat, need * fdim * sizeof(float)));
+        HIPCHK(hipMemsetAsync(r.nat, 0, need * fdim * sizeof(float), st));
+        r.nat_cap = need;
+    }
+    const size_t need_s = n + e->Bp + 32;
+    if (need_s > r.nat_row_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (r.nat_row) hipFree(r.nat_row);
+        r.nat_row = nullptr;
+        r.nat_row_cap = 0;
+        HIPCHK(hipMalloc((void **)&r.nat_row, need_s * sizeof(int)));
+        HIPCHK(hipMemsetAsync(r.nat_row, 0, need_s * sizeof(int), st));
+        r.nat_row_cap = need_s;
+    }
+    return MLGGD_OK;
+}
+
+// mlggd_load_frames and, on a NAT engine, mlggd_load_frames_nat (n_nat / nat / nat_row are read only there)
+static int load_frames_impl(mlggd_engine *e, int n_frames, int fea_context, const float *feat, const float *targ,
+                            int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
+                            const int32_t *nat_row) {
+    const bool natm = e->nat_frames > 0;
+    const int fdim = stream_fdim(e, fea_context);
+    if (fdim == 0 && natm)
+        return fail(MLGGD_ERR_ARG, "(fea_context %d + 1) does not divide layersizes[0] = %d", fea_context, e->K0);
+    if (fdim == 0) return fail(MLGGD_ERR_ARG, "fea_context %d does not divide layersizes[0] = %d", fea_context, e->K0);
     if (n_frames < 0 || n_samples < 0) return fail(MLGGD_ERR_ARG, "negative size");
     CHK(check_frames(e, n_samples));
     if (n_samples > 0 && (!feat || !first_frame)) return fail(MLGGD_ERR_ARG, "feat/first_frame is NULL");
@@ -2010,6 +2067,13 @@ int mlggd_load_frames(mlggd_handle e, int n_frames, int fea_context, const float
         if (first_frame[s] < 0 || first_frame[s] + fea_context > n_frames)
             return fail(MLGGD_ERR_ARG, "sample %d: window [%d,%d) outside the %d uploaded frames", s, first_frame[s],
                         first_frame[s] + fea_context, n_frames);
+    if (natm) {
+        if (n_nat < 0) return fail(MLGGD_ERR_ARG, "n_nat %d < 0", n_nat);
+        if (n_samples > 0 && (!nat || !nat_row)) return fail(MLGGD_ERR_ARG, "nat/nat_row is NULL");
+        for (int s = 0; s < n_samples; s++)
+            if (nat_row[s] < 0 || nat_row[s] >= n_nat)
+                return fail(MLGGD_ERR_ARG, "sample %d: nat_row %d outside the %d noise rows", s, nat_row[s], n_nat);
+    }
     HIPCHK(hipSetDevice(e->device));
     if (!e->copy_stream) {
         CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));  // must not queue behind the chunk's kernels
@@ -2040,6 +2104,13 @@ int mlggd_load_frames(mlggd_handle e, int n_frames, int fea_context, const float
         HIPCHK(hipMemsetAsync(r.first, 0, need_s * sizeof(int), e->copy_stream));
         r.first_cap = need_s;
     }
+    if (natm) {
+        CHK(raw_set_nat_grow(e, r, (size_t)n_nat, (size_t)n_samples, fdim, e->copy_stream));
+        if (n_samples > 0) {
+            HIPCHK(hipMemcpyAsync(r.nat, nat, (size_t)n_nat * fdim * 4, hipMemcpyHostToDevice, e->copy_stream));
+            HIPCHK(hipMemcpyAsync(r.nat_row, nat_row, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, e->copy_stream));
+        }
+    }
     if (n_frames > 0) {
         HIPCHK(hipMemcpyAsync(r.feat, feat, (size_t)n_frames * fdim * 4, hipMemcpyHostToDevice, e->copy_stream));
         if (targ) HIPCHK(hipMemcpyAsync(r.targ, targ, (size_t)n_frames * e->D * 4, hipMemcpyHostToDevice, e->copy_stream));
@@ -2053,6 +2124,8 @@ int mlggd_load_frames(mlggd_handle e, int n_frames, int fea_context, const float
     e->raw_feat = r.feat;
     e->raw_targ = r.targ;
     e->first_frame = r.first;
+    e->nat = r.nat;
+    e->nat_row = r.nat_row;
     e->raw_cap = r.raw_cap;
     e->first_cap = r.first_cap;
     e->chunk_frames = n_samples;
@@ -2061,6 +2134,41 @@ int mlggd_load_frames(mlggd_handle e, int n_frames, int fea_context, const float
     e->fdim = fdim;
     e->toff = targ_offset;
     return MLGGD_OK;
+}
+
+// the _nat entries need a NAT engine, the plain frames entries one without
+static int nat_entry_state(mlggd_engine *e, const char *who) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (e->nat_frames == 0) return fail(MLGGD_ERR_STATE, "%s needs an engine with nat_frames > 0", who);
+    return MLGGD_OK;
+}
+
+extern "C" {
+
+int mlggd_load_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                      int n_samples, const int32_t *first_frame, int targ_offset) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (e->nat_frames > 0)
+        return fail(MLGGD_ERR_STATE, "the plain frames entries have no noise rows: an engine with nat_frames = %d takes "
+                                     "mlggd_*_frames_nat", e->nat_frames);
+    return load_frames_impl(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, 0, nullptr, nullptr);
+}
+
+int mlggd_load_frames_nat(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                          int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
+                          const int32_t *nat_row) {
+    CHK(nat_entry_state(e, "mlggd_load_frames_nat"));
+    return load_frames_impl(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, n_nat, nat, nat_row);
+}
+
+int mlggd_train_frames_nat(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                           int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
+                           const int32_t *nat_row, int *bunches_trained) {
+    CHK(nat_entry_state(e, "mlggd_train_frames_nat"));
+    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
+    CHK(load_frames_impl(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, n_nat, nat, nat_row));
+    CHK(mlggd_train_resident(e, 0, n_samples, bunches_trained));
+    return mlggd_sync(e);
 }
 
 int mlggd_train_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
@@ -2121,7 +2229,9 @@ int mlggd_train_resident(mlggd_handle e, int first_frame, int n_frames, int *bun
     // an emulated world consumes one GLOBAL minibatch of world*B rows per step (and stages nothing ahead)
     const int per_step = e->fake_world ? e->B * e->world : e->B;
     for (int i = 0; i + per_step <= n_frames; i += per_step) {
-        const bool has_next = e->stage_ahead && !e->fake_world && i + 2 * e->B <= n_frames;
+        // (a NAT engine's frame stream is staged by k_transpose_in_nat in front of every step: the loss kernels'
+        // ride-along staging gathers the plain window only)
+        const bool has_next = e->stage_ahead && !e->fake_world && !(e->nat_frames && e->indexed) && i + 2 * e->B <= n_frames;
         Bunch next;
         if (has_next) next = bunch_at(e, first_frame + i + e->B);
         CHK(run_step(e, first_frame + i, prestaged, has_next ? &next : nullptr));
@@ -2377,6 +2487,77 @@ int mlggd_cv_all(mlggd_handle e, int n, const float *in, const float *targ, floa
                  float *loglik) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     return cv_metrics(e, n, in, targ, sqerr, abserr, (e->cfg.MLflag == 1) ? loglik : nullptr);
+}
+
+int mlggd_cv_all_frames_nat(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                            int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
+                            const int32_t *nat_row, float *sqerr, float *abserr, float *loglik) {
+    CHK(nat_entry_state(e, "mlggd_cv_all_frames_nat"));
+    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
+    if (e->cv_device) {
+        CHK(load_frames_impl(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, n_nat, nat, nat_row));
+        return cv_device_reduce(e, n_samples, sqerr, abserr, (e->cfg.MLflag == 1) ? loglik : nullptr);
+    }
+    CHK(load_frames_impl(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, targ_offset, n_nat, nat, nat_row));
+    const int D = e->D;
+    return cv_accumulate(
+        e, n_samples, [&](int i) { return targ + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr,
+        (e->cfg.MLflag == 1) ? loglik : nullptr);
+}
+
+int mlggd_forward_frames_nat(mlggd_handle e, int n_frames, int fea_context, const float *feat, int n_samples,
+                             const int32_t *first_frame, int n_nat, const float *nat, const int32_t *nat_row,
+                             float *out) {
+    CHK(nat_entry_state(e, "mlggd_forward_frames_nat"));
+    if (n_samples > 0 && !out) return fail(MLGGD_ERR_ARG, "out is NULL");
+    CHK(load_frames_impl(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, 0, n_nat, nat, nat_row));
+    if (n_samples == 0) return MLGGD_OK;
+    CHK(forward_resident(e, n_samples));
+    HIPCHK(hipMemcpyAsync(out, e->chunk_out, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+// Host only, no device (nat_rule.h): the noise rows of n_utts utterances from their normalised rows, and the utterance
+// of every sample.
+int mlggd_nat_estimate(int D, int n_utts, const int32_t *frame_off, const float *rows, int nat_frames, float *out) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
+    if (nat_frames < 1) return fail(MLGGD_ERR_ARG, "nat_frames %d < 1", nat_frames);
+    if (n_utts == 0) return MLGGD_OK;
+    if (!frame_off || !out) return fail(MLGGD_ERR_ARG, "frame_off/out is NULL");
+    for (int u = 0; u < n_utts; u++)
+        if (frame_off[u] < 0 || frame_off[u + 1] < frame_off[u])
+            return fail(MLGGD_ERR_ARG, "frame_off decreases at utterance %d (%d after %d)", u, frame_off[u + 1], frame_off[u]);
+    if (frame_off[n_utts] > frame_off[0] && !rows) return fail(MLGGD_ERR_ARG, "rows is NULL");
+    for (int u = 0; u < n_utts; u++) {
+        const int Tu = nat_rule::frames_used(nat_frames, frame_off[u + 1] - frame_off[u]);
+        for (int k = 0; k < D; k++)
+            out[(size_t)u * D + k] = Tu ? nat_rule::chain(rows + (size_t)frame_off[u] * D + k, (size_t)D, Tu) : 0.0f;
+    }
+    return MLGGD_OK;
+}
+
+int mlggd_nat_rows(int n_utts, const int32_t *frame_off, int n_samples, const int32_t *first_frame, int32_t *nat_row) {
+    if (n_utts < 0 || n_samples < 0) return fail(MLGGD_ERR_ARG, "negative size");
+    if (n_samples == 0) return MLGGD_OK;
+    if (!frame_off || !first_frame || !nat_row) return fail(MLGGD_ERR_ARG, "frame_off/first_frame/nat_row is NULL");
+    for (int u = 0; u < n_utts; u++)
+        if (frame_off[u] < 0 || frame_off[u + 1] < frame_off[u])
+            return fail(MLGGD_ERR_ARG, "frame_off decreases at utterance %d (%d after %d)", u, frame_off[u + 1], frame_off[u]);
+    const int FT = n_utts ? frame_off[n_utts] : 0, F0 = n_utts ? frame_off[0] : 0;
+    for (int s = 0; s < n_samples; s++) {
+        if (first_frame[s] < F0 || first_frame[s] >= FT)
+            return fail(MLGGD_ERR_ARG, "sample %d: frame %d outside the %d packed frames", s, first_frame[s], FT);
+        nat_row[s] = nat_rule::utt_of_frame(n_utts, frame_off, first_frame[s]);
+    }
+    return MLGGD_OK;
+}
+
+int mlggd_get_nat_frames(mlggd_handle e, int *nat_frames) {
+    if (!e || !nat_frames) return fail(MLGGD_ERR_ARG, "NULL argument");
+    *nat_frames = e->nat_frames;
+    return MLGGD_OK;
 }
 
 int mlggd_cv_all_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
@@ -2729,6 +2910,7 @@ int mlggd_comm_init(mlggd_handle e, const void *id, int world_size, int rank) {
     if (world_size < 1 || rank < 0 || rank >= world_size)
         return fail(MLGGD_ERR_ARG, "rank %d / world_size %d invalid", rank, world_size);
     if (e->comm) return fail(MLGGD_ERR_STATE, "communicator already initialised");
+    if (e->nat_frames > 0) return fail(MLGGD_ERR_STATE, "mlggd_comm_init: an engine with nat_frames = %d runs on a single device", e->nat_frames);
     if (e->cfg.dropoutflag == 1 && world_size > 1)
         return fail(MLGGD_ERR_ARG, "dropout is not supported on the data-parallel path");
     // the exchange mode first: a request the shape rules out must fail BEFORE a communicator exists (every rank takes
@@ -2783,6 +2965,7 @@ int mlggd_comm_init(mlggd_handle e, const void *id, int world_size, int rank) {
 int mlggd_debug_fake_world(mlggd_handle e, int world_size, int mode) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     if (e->comm || e->fake_world) return fail(MLGGD_ERR_STATE, "communicator already initialised");
+    if (e->nat_frames > 0) return fail(MLGGD_ERR_STATE, "mlggd_debug_fake_world: an engine with nat_frames = %d runs on a single device", e->nat_frames);
     if (mode < 0 || mode > 3) return fail(MLGGD_ERR_ARG, "mode %d not in 0..3", mode);
     if (world_size < 1 || (mode != 2 && !gather_usable(e, world_size)))
         return fail(MLGGD_ERR_ARG, "fake world of %d ranks: needs bunchsize %% 32 == 0 and world*bunchsize in {64,...,1024}", world_size);
@@ -3179,14 +3362,15 @@ int ola_to_host(const SpecPlan *p, const float *blk, int F, int16_t *out, float 
 
 // the engine's idle raw buffer set, grown to `rows` stream rows and n samples, for a frame stream written on the
 // device; raw_set_commit then makes it the current one: the device-side counterpart of mlggd_load_frames (no targets)
-int raw_set_acquire(mlggd_engine *e, int rows, int n, int ctx, mlggd_engine::RawSet **out) {
+int raw_set_acquire(mlggd_engine *e, int rows, int n, int ctx, mlggd_engine::RawSet **out, int n_nat = 0) {
     if (!e->copy_stream) {
         CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));
         for (auto &r : e->raw) HIPCHK(hipEventCreateWithFlags(&r.last_use, hipEventDisableTiming));
     }
-    const int fdim = e->K0 / ctx;
+    const int fdim = stream_fdim(e, ctx);
     mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
     HIPCHK(hipEventSynchronize(r.last_use));
+    if (e->nat_frames) CHK(raw_set_nat_grow(e, r, (size_t)n_nat, (size_t)n, fdim, e->stream));
     const size_t need = (size_t)rows + ctx + 8;
     if (need > r.raw_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
@@ -3219,26 +3403,52 @@ void raw_set_commit(mlggd_engine *e, mlggd_engine::RawSet &r, int rows, int n, i
     e->raw_feat = r.feat;
     e->raw_targ = r.targ;
     e->first_frame = r.first;
+    e->nat = r.nat;  // a decoding call then points it at its table of the whole batch
+    e->nat_row = r.nat_row;
     e->raw_cap = r.raw_cap;
     e->first_cap = r.first_cap;
     e->chunk_frames = n;
     e->raw_frames = rows;
     e->indexed = true;
-    e->fdim = e->K0 / ctx;
+    e->fdim = stream_fdim(e, ctx);
     e->toff = 0;
 }
 
+// fea_context frames of D bins, plus the noise row on a NAT engine, must fill layer 0
+int check_input_width(const mlggd_engine *e, int ctx, int D) {
+    if (e->nat_frames > 0) {
+        if (((long long)ctx + 1) * D != e->K0)
+            return fail(MLGGD_ERR_ARG, "(fea_context %d + 1) x %d bins != layersizes[0] = %d (nat_frames = %d)", ctx, D,
+                        e->K0, e->nat_frames);
+        return MLGGD_OK;
+    }
+    if ((long long)ctx * D != e->K0)
+        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", ctx, D, e->K0);
+    return MLGGD_OK;
+}
+
+int launch_nat_estimate(const mlggd_engine *e, const float *rows, const int *d_frame_off, int n_utts, int D,
+                        const float *mean, const float *inv, float *out) {
+    const size_t work = (size_t)n_utts * D;
+    hipLaunchKernelGGL(k_nat_estimate, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, rows, d_frame_off,
+                       n_utts, D, e->nat_frames, mean, inv, out);
+    return launch_check("k_nat_estimate");
+}
+
 // the frame stream of output frames [a, a + n) of an F-frame utterance, written by k_lps_stream (first_frame[i] = i)
+// (nat: on a NAT engine the one noise row of the utterance, which every sample takes)
 int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, int ctx, const float *mean,
-                       const float *inv) {
-    const int fdim = e->K0 / ctx, rows = n + ctx - 1;
+                       const float *inv, const float *nat) {
+    const int fdim = stream_fdim(e, ctx), rows = n + ctx - 1;
     mlggd_engine::RawSet *r;
     CHK(raw_set_acquire(e, rows, n, ctx, &r));
     const size_t work = std::max((size_t)rows * fdim, (size_t)n);
     hipLaunchKernelGGL(k_lps_stream, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, lps, F, fdim, a,
                        rows, (ctx - 1) / 2, mean, inv, r->feat, r->first, n);
     CHK(launch_check("k_lps_stream"));
+    if (e->nat_frames) HIPCHK(hipMemsetAsync(r->nat_row, 0, (size_t)n * sizeof(int), e->stream));
     raw_set_commit(e, *r, rows, n, ctx);
+    if (e->nat_frames) e->nat = nat;
     return MLGGD_OK;
 }
 
@@ -3500,8 +3710,7 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
     int slot;
     CHK(spec_dims(fs_khz, &d, &slot));
     if (fea_context < 1 || fea_context % 2 == 0) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", fea_context);
-    if ((long long)fea_context * d.D != e->K0)
-        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
+    CHK(check_input_width(e, fea_context, d.D));
     if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
     if (e->world > 1 || e->fake_world)
         return fail(MLGGD_ERR_STATE, "mlggd_enhance_wave runs on a single-device engine");
@@ -3528,12 +3737,21 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
     HIPCHK(hipMemcpyAsync(mean, norm_mean, d.D * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(inv, norm_inv_std, d.D * sizeof(float), hipMemcpyHostToDevice, st));
     CHK(launch_analysis(p, dw, F, dl, X, st));  // the noisy wave is transformed once
+    float *natz = nullptr;
+    const int h_foff[2] = {0, F};
+    if (e->nat_frames) {  // the utterance's noise row, once, from the analysed rows
+        int *d_foff = nullptr;
+        CHK(b.alloc(&natz, d.D));
+        CHK(b.alloc(&d_foff, 2));
+        HIPCHK(hipMemcpyAsync(d_foff, h_foff, sizeof(h_foff), hipMemcpyHostToDevice, st));
+        CHK(launch_nat_estimate(e, dl, d_foff, 1, d.D, mean, inv, natz));
+    }
     // chunks of at most the chunk capacity; each one's stream carries (ctx - 1) / 2 context frames on either side,
     // so consecutive streams overlap by ctx - 1 frames and every output frame sees the same input rows
     const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
     for (int a = 0; a < F; a += cap) {
         const int n = std::min(cap, F - a);
-        CHK(load_frames_device(e, dl, F, a, n, fea_context, mean, inv));
+        CHK(load_frames_device(e, dl, F, a, n, fea_context, mean, inv, natz));
         CHK(forward_resident(e, n));
         CHK(launch_synthesis(p, e->chunk_out, mean, inv, X, a, n, blk, st));
         HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
@@ -3560,8 +3778,7 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
     int slot;
     CHK(spec_dims(fs_khz, &d, &slot));
     if (fea_context < 1 || fea_context % 2 == 0) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", fea_context);
-    if ((long long)fea_context * d.D != e->K0)
-        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
+    CHK(check_input_width(e, fea_context, d.D));
     if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
     if (e->world > 1 || e->fake_world)
         return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
@@ -3667,6 +3884,11 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
     hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, dw, d_woff, d_foff, d_utt,
                        n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0), dl, X);
     CHK(launch_check("k_lps_analysis_seg"));
+    float *natz = nullptr;
+    if (e->nat_frames) {  // every utterance's noise row, once per call, from the analysed rows of the whole batch
+        CHK(ws_grow(e, w.nat, (size_t)n_utts * d.D, &natz));
+        CHK(launch_nat_estimate(e, dl, d_foff, n_utts, d.D, mean, inv, natz));
+    }
     // chunks over the packed frame index: a chunk's stream carries the context rows of every utterance it touches, so
     // an output frame sees the same input rows wherever the boundaries fall; bunches run across utterances
     for (int a = 0, u0 = 0; a < FT; a += cap) {
@@ -3680,7 +3902,13 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
         hipLaunchKernelGGL(k_lps_stream_seg, dim3((unsigned)rows), dim3(256), 0, st, dl, d_foff, d_utt, n_utts, d.D, a, n,
                            u0, u1, fea_context, mean, inv, r->feat, r->first);
         CHK(launch_check("k_lps_stream_seg"));
+        if (e->nat_frames) {
+            hipLaunchKernelGGL(k_nat_rows_seg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int *)d_foff,
+                               (const int *)d_utt, n_utts, a, n, r->nat_row);
+            CHK(launch_check("k_nat_rows_seg"));
+        }
         raw_set_commit(e, *r, rows, n, fea_context);
+        if (e->nat_frames) e->nat = natz;
         CHK(forward_resident(e, n));
         CHK(launch_synthesis(p, e->chunk_out, mean, inv, X, a, n, blk, st, den));
         HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
@@ -3963,6 +4191,8 @@ int mlggd_live_open(mlggd_handle e, int fs_khz, int fea_context, const float *no
                     int n_sessions, mlggd_live_handle *out) {
     if (!e || !out) return fail(MLGGD_ERR_ARG, "NULL handle / out");
     *out = nullptr;
+    if (e->nat_frames > 0)  // a session would have to hold its output back until nat_frames frames have arrived
+        return fail(MLGGD_ERR_STATE, "mlggd_live_open: live decoding of an engine with nat_frames = %d is not built", e->nat_frames);
     char msg[256];
     int L, S, slot;
     if (live_rule::check_group(fs_khz, fea_context, n_sessions, &L, &S, msg, sizeof msg))
@@ -4260,8 +4490,7 @@ int wave_pair_check(mlggd_engine *e, const char *who, int fs_khz, int ctx, const
     int slot;
     CHK(spec_dims(fs_khz, d, &slot));
     if (ctx < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", ctx);
-    if ((long long)ctx * d->D != e->K0)
-        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", ctx, d->D, e->K0);
+    CHK(check_input_width(e, ctx, d->D));
     if (e->D != d->D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d->D, fs_khz);
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (targ_offset < 0 || targ_offset >= ctx)
@@ -4296,7 +4525,7 @@ int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, cons
     CHK(ws_grow(e, t.frame_off, (size_t)nc + 1, &d_foff));
     CHK(ws_grow(e, t.wave_off, (size_t)nc + 1, &d_woff));
     mlggd_engine::RawSet *r;
-    CHK(raw_set_acquire(e, FT, n_samples, ctx, &r));
+    CHK(raw_set_acquire(e, FT, n_samples, ctx, &r, nc));
     t.h_norm.resize((size_t)2 * d.D);
     memcpy(t.h_norm.data(), mean, d.D * sizeof(float));
     memcpy(t.h_norm.data() + d.D, inv, d.D * sizeof(float));
@@ -4313,6 +4542,13 @@ int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, cons
     hipLaunchKernelGGL(k_lps_norm_pair, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN, (const float *)lpsC,
                        d.D, (const float *)norm, (const float *)(norm + d.D), r->feat, r->targ);
     CHK(launch_check("k_lps_norm_pair"));
+    if (e->nat_frames) {  // the noise rows from the normalised noisy rows, over the utterances that have frames
+        CHK(launch_nat_estimate(e, r->feat, d_foff, nc, d.D, nullptr, nullptr, r->nat));
+        t.h_nat_row.resize((size_t)n_samples);
+        for (int s = 0; s < n_samples; s++)
+            t.h_nat_row[s] = nat_rule::utt_of_frame(nc, t.h_frame_off.data(), first_frame[s]);
+        HIPCHK(hipMemcpyAsync(r->nat_row, t.h_nat_row.data(), (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
+    }
     raw_set_commit(e, *r, FT, n_samples, ctx);
     e->toff = targ_offset;
     return MLGGD_OK;

@@ -16,6 +16,7 @@
 // B: lane l holds B[k=l>>5][j=l&31]; C/D reg r: row=(r&3)+8*(r>>2)+4*(l>>5), col=l&31.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "nat_rule.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1899,6 +1900,76 @@ __device__ __forceinline__ void transpose_in_body(const StageArgs &A, const int 
     }
 }
 __global__ __launch_bounds__(256) void k_transpose_in(StageArgs A) { transpose_in_body(A, (int)blockIdx.x); }
+
+// Input staging of a noise-aware (NAT) engine, nat_rule.h: row b is its window of the frame stream, K - fdim columns
+// from in + first[b] * fdim as above, followed by the fdim values of its utterance's noise row, nat + nat_row[b] * fdim.
+// The same 32 x 32 LDS tiles, grid and outputs as k_transpose_in (inT, rows_out in either form, zero pads); a launch of
+// its own in front of the forward pass -- the loss kernels stage the plain form only.  A.first is never NULL here.
+__global__ __launch_bounds__(256) void k_transpose_in_nat(StageArgs A, const float *__restrict__ nat,
+                                                          const int *__restrict__ nat_row) {
+    const float *__restrict__ in = A.in;
+    float *__restrict__ inT = A.inT, *__restrict__ rows_out = A.rows_out;
+    const int *__restrict__ first = A.first;
+    const int B = A.B, K = A.K, Bp = A.Bp, b_tiles = A.b_tiles, fdim = A.fdim, Kwin = A.K - A.fdim;
+    __shared__ float t[32][33];
+    const int tile = (int)blockIdx.x;
+    const int kt = tile / b_tiles, bt = tile % b_tiles;
+    const int k0 = kt * 32, b0 = bt * 32;
+    const int tx = threadIdx.x & 31, ty = (threadIdx.x >> 5) & 7;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int b = b0 + ty + 8 * q, k = k0 + tx;
+        float v = 0.0f;
+        if (b < B && k < K) {
+            if (k < Kwin) v = in[(size_t)first[b] * fdim + k];
+            else v = nat[(size_t)nat_row[b] * fdim + (k - Kwin)];
+        }
+        if (rows_out) {  // b < Bp, k < Kp: the grid's tiles cover exactly that
+            if (A.yblk) rows_out[y_blocked_base(k0, A.yblk, Bp) + (size_t)b * A.yblk + tx] = v;
+            else rows_out[(size_t)b * A.Kp + k] = v;
+        }
+        t[ty + 8 * q][tx] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int k = k0 + ty + 8 * q;
+        inT[(size_t)k * Bp + b0 + tx] = t[tx][ty + 8 * q];
+    }
+}
+
+// The noise rows of a batch, nat_rule.h: one ordered chain per (utterance, bin).  rows [sum F][D] are the packed frames
+// of n_utts utterances, utterance u's from frame_off[u]; mean == nullptr: the rows are already normalised, else they are
+// LPS rows and every term is (lps - mean) * inv first.  out [n_utts][D]; an utterance without frames gets zeros.
+__global__ __launch_bounds__(256) void k_nat_estimate(const float *__restrict__ rows, const int *__restrict__ frame_off,
+                                                      int n_utts, int D, int T, const float *__restrict__ mean,
+                                                      const float *__restrict__ inv, float *__restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n_utts * D) return;
+    const int u = (int)(i / D), k = (int)(i % D);
+    const int fo = frame_off[u], Tu = nat_rule::frames_used(T, frame_off[u + 1] - fo);
+    const float *x = rows + (size_t)fo * D + k;
+    out[i] = mean ? nat_rule::chain_lps(x, (size_t)D, Tu, mean[k], inv[k]) : nat_rule::chain(x, (size_t)D, Tu);
+}
+
+// nat_row of a decoding chunk: sample i is packed frame a + i, its noise row is its utterance's (frame_off strictly
+// increasing over the n_utts utterances; utt_of, when given, is the per-frame table of the same answer)
+__global__ __launch_bounds__(256) void k_nat_rows_seg(const int *__restrict__ frame_off, const int *__restrict__ utt_of,
+                                                      int n_utts, int a, int n, int *__restrict__ nat_row) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    if (utt_of) {
+        nat_row[i] = utt_of[a + i];
+        return;
+    }
+    int lo = 0, hi = n_utts - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frame_off[mid] <= a + i) lo = mid;
+        else hi = mid - 1;
+    }
+    nat_row[i] = lo;
+}
 
 // Sum of the S split-K slabs of one output element, slabs added in order s = 0..S-1.  All
 // loads are issued before the first add (one memory round trip instead of S).

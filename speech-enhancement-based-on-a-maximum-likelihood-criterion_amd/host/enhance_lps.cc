@@ -9,8 +9,10 @@
 // of the first / last frame, so the forward runs through mlggd_forward_frames.
 //
 //   enhance_lps wts=mlp.50.wts norm_file=train_noisy.norm in=noisy.lps out=enhanced.htk
-//               [fea_context=7] [gpu_used=0] [bunchsize=512] [scp=list of "in out" lines] [activation=sigmoid|relu]
+//               [fea_context=7] [gpu_used=0] [bunchsize=512] [scp=list of "in out" lines] [activation=sigmoid|relu] [nat=T]
 // activation: the hidden units the net was trained with (BPtrain_Sigmoid / BPtrain_ReLU); the .wts file does not say.
+// nat=T: the net was trained noise-aware (csrc/nat_rule.h): every input row ends in the mean of the file's first T
+// normalised frames, layersizes[0] = (fea_context + 1) x the feature dimension; the .wts file does not say that either.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +34,7 @@ using tool_io::write_htk;
 
 int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp;
-    int ctx = 7, gpu = 0, bunch = 512, act = MLGGD_ACT_SIGMOID;
+    int ctx = 7, gpu = 0, bunch = 512, act = MLGGD_ACT_SIGMOID, nat = 0;
     for (int a = 1; a < argc; a++) {
         const std::string arg(argv[a]);
         const size_t eq = arg.find('=');
@@ -47,24 +49,26 @@ int main(int argc, char **argv) {
         else if (k == "gpu_used") gpu = atoi(v.c_str());
         else if (k == "bunchsize") bunch = atoi(v.c_str());
         else if (k == "activation") act = tool_io::parse_activation(v);
+        else if (k == "nat") nat = tool_io::parse_nat(v);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
-        die("usage: enhance_lps wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] [activation=sigmoid|relu]");
+        die("usage: enhance_lps wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] [activation=sigmoid|relu] [nat=T]");
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
 
     // ---- model: the trainer's .wts container (Interface.cc:484-516)
     const tool_io::Model model = tool_io::read_wts(wts);
     const std::vector<int> &ls = model.ls;
     const int L = (int)ls.size(), D = ls[L - 1];
-    if (ls[0] % ctx) die("layersizes[0] is not a multiple of fea_context");
-    const int dim = ls[0] / ctx;
+    const int parts = ctx + (nat > 0 ? 1 : 0);
+    if (ls[0] % parts) die(nat > 0 ? "layersizes[0] is not a multiple of fea_context + 1 (nat=)" : "layersizes[0] is not a multiple of fea_context");
+    const int dim = ls[0] / parts;
 
     // ---- norm file (Interface.cc:373-399 layout: "vec N", N means, "vec N", N inverse std-devs)
     std::vector<float> mean, inv;
     tool_io::read_norm(norm_file, dim, mean, inv);
     if (D % dim) die("output dimension is not a multiple of the feature dimension");
 
-    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act);
+    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act, nat);
 
     std::vector<std::pair<std::string, std::string>> jobs;
     if (!scp.empty()) {
@@ -89,7 +93,15 @@ int main(int argc, char **argv) {
         std::vector<int32_t> first(n);
         for (int t = 0; t < n; t++) first[t] = t;
         std::vector<float> y((size_t)n * D);
-        if (mlggd_forward_frames(h, np, ctx, stream.data(), n, first.data(), y.data()) != MLGGD_OK)
+        if (nat > 0) {  // the noise row from the file's own normalised rows (stream rows half .. half + n)
+            const int32_t foff[2] = {0, n};
+            std::vector<float> z(dim);
+            std::vector<int32_t> zrow(n, 0);
+            if (mlggd_nat_estimate(dim, 1, foff, stream.data() + (size_t)half * dim, nat, z.data()) != MLGGD_OK ||
+                mlggd_forward_frames_nat(h, np, ctx, stream.data(), n, first.data(), 1, z.data(), zrow.data(), y.data()) !=
+                    MLGGD_OK)
+                die(std::string("mlggd_forward_frames_nat: ") + mlggd_last_error());
+        } else if (mlggd_forward_frames(h, np, ctx, stream.data(), n, first.data(), y.data()) != MLGGD_OK)
             die(std::string("mlggd_forward_frames: ") + mlggd_last_error());
         for (int t = 0; t < n; t++)
             for (int j = 0; j < D; j++) y[(size_t)t * D + j] = y[(size_t)t * D + j] / inv[j % dim] + mean[j % dim];  // decode.m:59-61

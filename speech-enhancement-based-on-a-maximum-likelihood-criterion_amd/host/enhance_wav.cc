@@ -6,9 +6,11 @@
 //
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
-//               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu]
+//               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu] [nat=T]
 //
 // activation: the hidden units the net was trained with (BPtrain_Sigmoid / BPtrain_ReLU); the .wts file does not say.
+// nat=T: the net was trained noise-aware (csrc/nat_rule.h): its input rows end in the mean of the utterance's first T
+// normalised frames, layersizes[0] = (fea_context + 1) x bins; the .wts file does not say that either.  Not with live=.
 // scp lists "in out" or "in out clean info" lines.  A list is decoded in batches of batch_s seconds of audio by
 // mlggd_enhance_waves: the utterances of a batch form one frame stream, so the forward bunches are full, and the
 // quality report takes the network's output rows from the same pass.  A batch ends early where the sample rate
@@ -86,8 +88,9 @@ int main(int argc, char **argv) {
     std::string wts, norm_file, in, out, scp, clean, info, score = "host";
     const char *usage =
         "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
-        "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu]";
-    int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64, act = MLGGD_ACT_SIGMOID;
+        "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu] "
+        "[nat=T]";
+    int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64, act = MLGGD_ACT_SIGMOID, nat = 0;
     bool live = false, score_given = false, want_stoi = false;
     double batch_s = 300.0;
     for (int a = 1; a < argc; a++) {
@@ -111,6 +114,7 @@ int main(int argc, char **argv) {
         else if (k == "live") live_block = atoi(v.c_str()), live = true;
         else if (k == "sessions") n_slots = atoi(v.c_str());
         else if (k == "activation") act = tool_io::parse_activation(v);
+        else if (k == "nat") nat = tool_io::parse_nat(v);
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
@@ -127,14 +131,16 @@ int main(int argc, char **argv) {
         if (scp.empty()) die("live= needs an scp= list");
         if (live_block < 1) die("live= must be a block of at least one sample");
         if (n_slots < 1) die("sessions= must be at least 1");
+        if (nat > 0) die("live= and nat= do not go together: a live session of a noise-aware net is not built");
     }
 
     const tool_io::Model model = tool_io::read_wts(wts);
     const int D = model.ls.back();
-    if (model.ls[0] != ctx * D) die("layersizes[0] is not fea_context x the output dimension");
+    if (nat > 0 && model.ls[0] != (ctx + 1) * D) die("layersizes[0] is not (fea_context + 1) x the output dimension (nat=)");
+    if (nat == 0 && model.ls[0] != ctx * D) die("layersizes[0] is not fea_context x the output dimension");
     std::vector<float> mean, inv;
     tool_io::read_norm(norm_file, D, mean, inv);
-    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act);
+    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act, nat);
 
     std::vector<Job> jobs;
     if (!scp.empty()) {
@@ -370,7 +376,15 @@ int main(int argc, char **argv) {
             std::vector<int32_t> first(F);
             for (int t = 0; t < F; t++) first[t] = t;
             std::vector<float> y((size_t)F * D);
-            if (mlggd_forward_frames(h, np, ctx, stream.data(), F, first.data(), y.data()) != MLGGD_OK)
+            if (nat > 0) {  // the noise row from the utterance's own normalised rows (stream rows half .. half + F)
+                const int32_t foff[2] = {0, F};
+                std::vector<float> z(D);
+                std::vector<int32_t> zrow(F, 0);
+                if (mlggd_nat_estimate(D, 1, foff, stream.data() + (size_t)half * D, nat, z.data()) != MLGGD_OK ||
+                    mlggd_forward_frames_nat(h, np, ctx, stream.data(), F, first.data(), 1, z.data(), zrow.data(),
+                                             y.data()) != MLGGD_OK)
+                    die(std::string("mlggd_forward_frames_nat: ") + mlggd_last_error());
+            } else if (mlggd_forward_frames(h, np, ctx, stream.data(), F, first.data(), y.data()) != MLGGD_OK)
                 die(std::string("mlggd_forward_frames: ") + mlggd_last_error());
             for (size_t i = 0; i < y.size(); i++) y[i] = y[i] / inv[i % D] + mean[i % D];
             report(it, y.data());

@@ -123,8 +123,16 @@ inline int parse_activation(const std::string &v) {
     die("activation=" + v + ": must be sigmoid or relu");
 }
 
+// nat=T of the decoding tools: the net was trained noise-aware over the first T frames (mlggd_config.nat_frames)
+inline int parse_nat(const std::string &v) {
+    char *end = nullptr;
+    const long t = strtol(v.c_str(), &end, 10);
+    if (v.empty() || *end || t < 0 || t > 1000000) die("nat=" + v + ": must be a number of frames, 0 = off");
+    return (int)t;
+}
+
 inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_cache_frames = 0,
-                                  int activation = MLGGD_ACT_SIGMOID) {
+                                  int activation = MLGGD_ACT_SIGMOID, int nat_frames = 0) {
     const int L = (int)m.ls.size();
     mlggd_config cfg;
     memset(&cfg, 0, sizeof(cfg));
@@ -136,6 +144,7 @@ inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_ca
     cfg.shapefactor = 2.0f;
     cfg.max_cache_frames = max_cache_frames;
     cfg.activation = activation;
+    cfg.nat_frames = nat_frames;
     std::vector<const float *> wp(L, nullptr), bp(L, nullptr);
     for (int l = 1; l < L; l++) { wp[l] = m.W[l].data(); bp[l] = m.B[l].data(); }
     mlggd_handle h = nullptr;
