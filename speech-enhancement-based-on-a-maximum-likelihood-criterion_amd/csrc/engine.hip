@@ -699,13 +699,16 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
 #define LAUNCH_FWD(NW, PIPE)                                                                                \
     {                                                                                                       \
         const size_t lds = fwd_lds_floats<NW, PIPE>() * sizeof(float);                                      \
-        if (relu) {                                                                                         \
-            CHK(ensure_lds(e, k_fwd<FWD_RELU, NW, PIPE>, lds));                                             \
-            launch_timed(e, k_fwd<FWD_RELU, NW, PIPE>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
-        } else {                                                                                            \
-            CHK(ensure_lds(e, k_fwd<FWD_SIGMOID, NW, PIPE>, lds));                                          \
-            launch_timed(e, k_fwd<FWD_SIGMOID, NW, PIPE>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
-        }                                                                                                   \
+        if (relu && st) LAUNCH_FWD_(FWD_RELU, NW, PIPE, true)                                               \
+        else if (relu) LAUNCH_FWD_(FWD_RELU, NW, PIPE, false)                                               \
+        else if (st) LAUNCH_FWD_(FWD_SIGMOID, NW, PIPE, true)                                               \
+        else LAUNCH_FWD_(FWD_SIGMOID, NW, PIPE, false)                                                      \
+    }
+    // the stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd)
+#define LAUNCH_FWD_(MODE, NW, PIPE, STAMPED)                                                                \
+    {                                                                                                       \
+        CHK(ensure_lds(e, k_fwd<MODE, NW, PIPE, STAMPED>, lds));                                            \
+        launch_timed(e, k_fwd<MODE, NW, PIPE, STAMPED>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
     }
                 // PIPE 4 (default): main loop software-pipelined inside the wave, operands by LDS-DMA; 1: the same
                 // pipeline through staging registers (MLGGD_FWD_PIPE=1); 0: the round-1 loop (MLGGD_FWD_PIPE=0, and the
@@ -718,6 +721,7 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
                 else if (e->fwd_pipe) LAUNCH_FWD(4, 1)
                 else LAUNCH_FWD(4, 0)
 #undef LAUNCH_FWD
+#undef LAUNCH_FWD_
             } else {
                 const int nwg = n_tiles * b_tiles * e->S_out;
                 if (e->fwd_pipe == 4) {
@@ -826,6 +830,8 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
     size_t n = 0;
     for (int j = 0; j < J.njobs; j++) {
         const DwpArgs &a = J.job[j];
+        // the kernel's out-of-range vector offset + 24 rows must stay below 2^31 (kernels.hip.h DWP_OFF0)
+        if (a.Np >= (1 << 17)) return fail(MLGGD_ERR_ARG, "dW tile table: layer of %d units is too wide", a.Np);
         for (int tl = 0; tl < a.ntiles; tl++, n++) {
             const int kt = a.k_first + tl / a.n_wg, nt = tl % a.n_wg;
             const int k0 = kt * 64, n0 = nt * 64;
@@ -843,7 +849,11 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
             } else {
                 d.W = (fused ? a.Wt : a.G) + base;
                 d.D = fused ? a.delta + base : nullptr;
-                d.szW = (unsigned)(((size_t)a.Kp * a.Np - base) * sizeof(float));
+                // the stores may touch the tile's real rows and nothing behind them: rows >= `rows` lie beyond
+                // num_records, so the range check is the row test (pad rows are never written)
+                const size_t to_end = ((size_t)a.Kp * a.Np - base) * sizeof(float);
+                const size_t to_row = (size_t)rows * a.Np * sizeof(float);
+                d.szW = (unsigned)(to_end < to_row ? to_end : to_row);
             }
             const int colsw = a.Np - n0 < 64 ? a.Np - n0 : 64;
             int nbias = (a.do_bias && kt == 0) ? a.N - n0 : 0;
@@ -918,30 +928,36 @@ static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream
             }
         }
     }
-    long long *stamps = stamps_for(e, KC_DW, stamp_layer, grid);
     if constexpr (H == 2) {
         static const int abl = getenv("MLGGD_DWP_ABLATE") ? atoi(getenv("MLGGD_DWP_ABLATE")) : 0;
         if (abl && fused) {  // timing-only diagnostics: results are wrong by construction
 #define DWP_ABL(A_)                                                                                       \
     case A_:                                                                                              \
         CHK(ensure_lds(e, k_dwp_ablate<H, A_>, lds));                                                     \
-        launch_timed(e, k_dwp_ablate<H, A_>, dim3(grid), dim3(256), lds, st, table, J.total, C, stamps);  \
+        launch_timed(e, k_dwp_ablate<H, A_>, dim3(grid), dim3(256), lds, st, table, J.total, C, (long long *)nullptr); \
         return launch_check("k_dwp_ablate");
             switch (abl) {
-                DWP_ABL(1) DWP_ABL(2) DWP_ABL(3) DWP_ABL(4) DWP_ABL(7) DWP_ABL(15) DWP_ABL(31) DWP_ABL(63) DWP_ABL(16) DWP_ABL(48) DWP_ABL(256) DWP_ABL(512) DWP_ABL(576)
+                DWP_ABL(1) DWP_ABL(2) DWP_ABL(3) DWP_ABL(4) DWP_ABL(7) DWP_ABL(15) DWP_ABL(31) DWP_ABL(63) DWP_ABL(16) DWP_ABL(48) DWP_ABL(256) DWP_ABL(1024) DWP_ABL(2048) DWP_ABL(512) DWP_ABL(576)
             default: return fail(MLGGD_ERR_ARG, "MLGGD_DWP_ABLATE=%d is not built", abl);
             }
 #undef DWP_ABL
         }
     }
+    long long *stamps = stamps_for(e, KC_DW, stamp_layer, grid);  // (the ablation twins carry none: they are timed against k_dwp)
     // G / n is a multiply when n is a power of two (bit-identical, see kernels.hip.h POW2)
     unsigned nfbits;
     memcpy(&nfbits, &C.nf, sizeof(nfbits));
     const bool pow2 = (nfbits & 0x007FFFFFu) == 0u && C.nf >= 1.0f;
+    // the stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd)
 #define DWP_LAUNCH(FUSED_, POW2_)                                                                         \
     {                                                                                                     \
-        CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_>, lds));                                                 \
-        launch_timed(e, k_dwp<H, FUSED_, POW2_>, dim3(grid), dim3(256), lds, st, table, J.total, C, stamps); \
+        if (stamps) {                                                                                     \
+            CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_, true>, lds));                                       \
+            launch_timed(e, k_dwp<H, FUSED_, POW2_, true>, dim3(grid), dim3(256), lds, st, table, J.total, C, stamps); \
+        } else {                                                                                          \
+            CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_>, lds));                                             \
+            launch_timed(e, k_dwp<H, FUSED_, POW2_>, dim3(grid), dim3(256), lds, st, table, J.total, C, stamps); \
+        }                                                                                                 \
     }
     if (fused && pow2) DWP_LAUNCH(true, true)
     else if (fused) DWP_LAUNCH(true, false)
@@ -1298,13 +1314,16 @@ static int run_dx(mlggd_engine *e, int l) {
 #define LAUNCH_DX(NW, PIPE)                                                                                  \
     {                                                                                                        \
         const size_t lds = dx_lds_floats<NW, PIPE>() * sizeof(float);                                        \
-        if (relu) {                                                                                          \
-            CHK(ensure_lds(e, k_dx<NW, PIPE, ACT_RELU>, lds));                                               \
-            launch_timed(e, k_dx<NW, PIPE, ACT_RELU>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st); \
-        } else {                                                                                             \
-            CHK(ensure_lds(e, k_dx<NW, PIPE>, lds));                                                         \
-            launch_timed(e, k_dx<NW, PIPE>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st);  \
-        }                                                                                                    \
+        if (relu && st) LAUNCH_DX_(NW, PIPE, ACT_RELU, true)                                                 \
+        else if (relu) LAUNCH_DX_(NW, PIPE, ACT_RELU, false)                                                 \
+        else if (st) LAUNCH_DX_(NW, PIPE, ACT_SIGMOID, true)                                                 \
+        else LAUNCH_DX_(NW, PIPE, ACT_SIGMOID, false)                                                        \
+    }
+    // the stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd)
+#define LAUNCH_DX_(NW, PIPE, ACT, STAMPED)                                                                   \
+    {                                                                                                        \
+        CHK(ensure_lds(e, k_dx<NW, PIPE, ACT, STAMPED>, lds));                                               \
+        launch_timed(e, k_dx<NW, PIPE, ACT, STAMPED>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st); \
     }
     // PIPE 4 (default where one workgroup per CU is all there is: <= 256 workgroups): main loop software-pipelined
     // inside the wave, operands by LDS-DMA (136 KB of LDS); 1: the same pipeline through staging registers (71 KB: two
@@ -1316,6 +1335,7 @@ static int run_dx(mlggd_engine *e, int l) {
     else if (e->dx_pipe) LAUNCH_DX(4, 1)
     else LAUNCH_DX(4, 0)
 #undef LAUNCH_DX
+#undef LAUNCH_DX_
     return launch_check("k_dx");
 }
 

@@ -26,9 +26,11 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
 res = {}
 names[512] = "operands staged through registers + ds_write_b128 instead of LDS-DMA (correct results)"
 names[576] = "... and written to LDS after the last MFMA instead of inside the block (correct results)"
-names[256] = "update in scalar fp32 instructions instead of packed pairs (correct results)"
+names[256] = "update in scalar fp32 instructions (correct results)"
+names[1024] = "update in packed fp32 pairs, constants pinned in VGPR pairs (correct results)"
+names[2048] = "update as the compiler lowers the packed source: a mixture (correct results)"
 variants = [int(x) for x in sys.argv[1:]] or [0, 1, 2, 3, 4, 16, 48, 7, 15, 31, 63]
-for rnd in range(3 if len(variants) <= 3 else 2):
+for rnd in range(3 if len(variants) <= 4 else 2):
     for abl in variants:
         env = dict(os.environ); env["MLGGD_DWP_ABLATE"] = str(abl)
         if abl == 0: env.pop("MLGGD_DWP_ABLATE")
