@@ -60,6 +60,9 @@ struct ora_net {
     float visible_omit, hid_omit;
     unsigned seed, step_counter;
     float *in_drop; /* the minibatch's input rows with the visible units dropped (the reference masks `in` in place) */
+    /* the HIP engine's two extensions of the reference (no reference line to cite): ora_set_activation, ora_set_shapefactors */
+    int activation; /* 0 sigmoid (the reference), 1 rectified-linear hidden units */
+    float *betas;   /* [D] one shape factor per output bin, or NULL: the scalar `shapefactor` for every bin */
 };
 
 static float *zalloc(size_t n) { /* devnew_vf zero-fills, BP_GPU.cu:528-543 */
@@ -146,8 +149,27 @@ void ora_destroy(ora_net *net) {
         free(net->layer_ydedx[l]); free(net->layer_sumdedx[l]);
     }
     free(net->in_drop);
+    free(net->betas);
     free(net);
 }
+
+/* Hidden units of the HIP engine's activation="relu" (csrc/kernels.hip.h relu_det / drelu): y = (x < 0) ? 0 : x on the fp32
+ * pre-activation the sigmoid consumes, dE/dx = (y > 0) ? dE/dy : 0 -- a comparison and a select each, in both readings of
+ * the GEMMs.  Dropout needs nothing of its own: dropout_rows zeroes y, and y > 0 then gives the dropped unit no gradient. */
+void ora_set_activation(ora_net *net, int act) { net->activation = act == 1; }
+
+/* One shape factor per output bin (the HIP engine's mlggd_set_shapefactors): column d of the ML-GGD loss chain and of the
+ * CV log-likelihood reads betas[d] wherever it read the scalar shapefactor; NULL goes back to the scalar. */
+void ora_set_shapefactors(ora_net *net, const float *betas) {
+    const int D = net->layersizes[net->numlayers - 1];
+    free(net->betas);
+    net->betas = NULL;
+    if (!betas) return;
+    net->betas = (float *)malloc((size_t)D * sizeof(float));
+    if (!net->betas) abort();
+    memcpy(net->betas, betas, (size_t)D * sizeof(float));
+}
+static inline float beta_of(const ora_net *net, int d) { return net->betas ? net->betas[d] : net->shapefactor; }
 
 static void ensure_frames(ora_net *net, int frames) {
     if (frames > net->cap_frames) alloc_bunch_buffers(net, frames);
@@ -827,11 +849,13 @@ static void forward_impl(ora_net *net, int n, const float *in, int cv) {
         else gemm_fwd(n, K, N, prev_y, net->weights[l], x); /* :361 */
         if (cvscale) scale_weights(net->weights[l], (size_t)K * N, 1.0f / keep); /* :496-501 */
         if (l != L - 1) {
-            /* kernSigmoid, DevFunc.cu:36-51 <- :364 */
+            /* kernSigmoid, DevFunc.cu:36-51 <- :364 (or the rectifier, ora_set_activation) */
             float *y = net->layer_y[l];
             const size_t sz = (size_t)n * N;
 #pragma omp parallel for schedule(static)
-            for (size_t i = 0; i < sz; i++) y[i] = 1.0f / (1.0f + (g_gemm_order == 1 ? ora_exp_det(-x[i]) : expf(-x[i])));
+            for (size_t i = 0; i < sz; i++)
+                y[i] = net->activation == 1 ? ((x[i] < 0.0f) ? 0.0f : x[i])
+                                            : 1.0f / (1.0f + (g_gemm_order == 1 ? ora_exp_det(-x[i]) : expf(-x[i])));
         } else {
             memcpy(net->out, x, (size_t)n * N * sizeof(float)); /* cudaMemcpy D2D, :367 */
         }
@@ -844,13 +868,12 @@ void ora_forward(ora_net *net, int n, const float *in) { forward_impl(net, n, in
  *  kernSumcol :167-185: thread per column, rows summed sequentially in fp32). */
 void ora_loss_colsum(ora_net *net, int n, const float *targ, float *colsum) {
     const int D = net->layersizes[net->numlayers - 1];
-    const float beta = net->shapefactor;
     for (int b = 0; b < n; b++)
         for (int d = 0; d < D; d++) {
             const size_t i = (size_t)b * D + d;
             net->realerror[i] = net->out[i] - targ[i];
             net->errorabsolute[i] = fabsf(net->realerror[i]);
-            net->errorabsolute2[i] = lpow(net->errorabsolute[i], beta);
+            net->errorabsolute2[i] = lpow(net->errorabsolute[i], beta_of(net, d));
         }
     if (g_gemm_order == 1 && g_dp_world > 1 && n % g_dp_world == 0) { /* k_colsum per rank, ranks in order */
         const int B = n / g_dp_world;
@@ -885,13 +908,13 @@ void ora_loss_colsum(ora_net *net, int n, const float *targ, float *colsum) {
  * minibatch of |e|^beta per dimension (only read when MLflag==1). */
 void ora_loss_grad(ora_net *net, int n, int n_global, const float *targ, const float *colsum_global) {
     const int L = net->numlayers, D = net->layersizes[L - 1];
-    const float beta = net->shapefactor;
     float *dedx = net->layer_dedx[L - 1];
     /* kernSubClean2, DevFunc.cu:376-398 <- :408 */
     for (int b = 0; b < n; b++)
         for (int d = 0; d < D; d++) {
             const size_t i = (size_t)b * D + d;
             const float o = net->out[i], t = targ[i];
+            const float beta = beta_of(net, d);
             float g;
             if (o > t) g = beta * lpow(o - t, beta - 1);
             else if (o == t) g = 0;
@@ -906,8 +929,9 @@ void ora_loss_grad(ora_net *net, int n, int n_global, const float *targ, const f
         for (size_t i = 0; i < (size_t)n * D; i++) net->realerror[i] = net->out[i] - targ[i];
         /* kernDivide, DevFunc.cu:445-450 <- :417 ; kernVecMulNum <- :418 ; kernindex2 <- :420 */
         const float nf = (float)n_global;
-        const float ppp = 1.0f / beta;
         for (int d = 0; d < D; d++) {
+            const float beta = beta_of(net, d);
+            const float ppp = 1.0f / beta;
             net->vec1[d] = colsum_global[d] / nf;
             net->vec2[d] = net->vec1[d] * beta;
             net->scalefactor[d] = lpow(net->vec2[d], ppp);
@@ -917,6 +941,7 @@ void ora_loss_grad(ora_net *net, int n, int n_global, const float *targ, const f
             for (int d = 0; d < D; d++) {
                 const size_t i = (size_t)b * D + d;
                 const float e = net->realerror[i];
+                const float beta = beta_of(net, d);
                 float g;
                 if (e > 0) g = lpow(e, beta - 1.0f) * beta / lpow(net->scalefactor[d], beta);
                 else if (e == 0) g = 0;
@@ -940,11 +965,12 @@ void ora_backward(ora_net *net, int n, const float *in) {
         const float *prev_y = (l == 1) ? in : net->layer_y[l - 1];
         float *dedx = net->layer_dedx[l];
         if (l != L - 1) {
-            /* kernDsigmoid, DevFunc.cu:53-71 <- :402 */
+            /* kernDsigmoid, DevFunc.cu:53-71 <- :402 (or the rectifier's select on y > 0) */
             const float *y = net->layer_y[l], *dedy = net->layer_dedy[l];
             const size_t sz = (size_t)n * N;
 #pragma omp parallel for schedule(static)
-            for (size_t i = 0; i < sz; i++) dedx[i] = (1.0f - y[i]) * y[i] * dedy[i];
+            for (size_t i = 0; i < sz; i++)
+                dedx[i] = net->activation == 1 ? ((y[i] > 0.0f) ? dedy[i] : 0.0f) : (1.0f - y[i]) * y[i] * dedy[i];
         }
         const int ranks = (g_gemm_order == 1 && g_dp_allreduce && g_dp_world > 1 && n % g_dp_world == 0) ? g_dp_world : 1;
         if (g_gemm_order == 1) {
@@ -1111,6 +1137,21 @@ float ora_cv_loglik(ora_net *net, int n_frames, const float *in, const float *ta
     }
     float density1, density2 = 0, density3 = 0, density;
     const float *scalefac = net->scalefactor; /* fromdev_vf_vf(dev.scalefactor), :287 */
+    if (net->betas) { /* csrc/engine.hip cv_accumulate, per-bin branch: the same three terms with beta_d; the first is a
+                       * sum over the bins of fp32 logarithms, kept in double and rounded once */
+        const float *betas = net->betas;
+        double d1 = 0;
+        for (int d = 0; d < D; d++) d1 += (double)n_frames * logf(betas[d] / (2 * ora_gamma((float)(1.0 / betas[d]))));
+        for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
+        density2 = density2 * n_frames;
+        for (int uu = 0; uu < n_frames; uu++)
+            for (int uuu = 0; uuu < D; uuu++)
+                density3 += powf(fabsf(err[(size_t)uu * D + uuu]) / scalefac[uuu], betas[uuu]);
+        density = (float)d1 - density2 - density3;
+        free(out);
+        free(err);
+        return density;
+    }
     density1 = n_frames * D * logf(shapefactor / (2 * ora_gamma((float)(1.0 / shapefactor)))); /* :288 */
     for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
     density2 = density2 * n_frames;

@@ -34,6 +34,8 @@ def lib(variant="strict"):
                                  C.c_float, C.c_float, C.c_int, _fpp, _fpp]
         L.ora_destroy.argtypes = [C.c_void_p]
         L.ora_set_dropout.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]
+        L.ora_set_activation.argtypes = [C.c_void_p, C.c_int]
+        L.ora_set_shapefactors.argtypes = [C.c_void_p, _fp]
         L.ora_train.restype = C.c_int
         L.ora_train.argtypes = [C.c_void_p, C.c_int, _fp, _fp]
         L.ora_train_bunch.argtypes = [C.c_void_p, C.c_int, _fp, _fp]
@@ -113,7 +115,10 @@ class OracleNet:
     """Mirror of the reference's class BP_GPU (BP_GPU.h:45-70) on the CPU oracle."""
 
     def __init__(self, layersizes, bunchsize, lrate, momentum, weightcost, shapefactor, MLflag,
-                 weights, bias, variant="strict", dropoutflag=0, visible_omit=0.0, hid_omit=0.0, random_seed=0):
+                 weights, bias, variant="strict", dropoutflag=0, visible_omit=0.0, hid_omit=0.0, random_seed=0,
+                 activation="sigmoid", shapefactors=None):
+        if activation not in ("sigmoid", "relu"):
+            raise ValueError("activation %r: must be 'sigmoid' or 'relu'" % (activation,))
         self._lib = lib(variant)
         self.layersizes = [int(x) for x in layersizes]
         self.L = len(self.layersizes)
@@ -130,6 +135,21 @@ class OracleNet:
         assert self._h
         if dropoutflag == 1:  # the HIP engine's counter-hash generator, restated (documented deviation from cuRAND)
             self._lib.ora_set_dropout(self._h, 1, visible_omit, hid_omit, int(random_seed))
+        self.activation = activation
+        if activation == "relu":       # the engine's activation="relu": y = (x < 0) ? 0 : x, dE/dx = (y > 0) ? dE/dy : 0
+            self._lib.ora_set_activation(self._h, 1)
+        if shapefactors is not None:
+            self.set_shapefactors(shapefactors)
+
+    def set_shapefactors(self, v):
+        """One shape factor per output bin ([D], the engine's BPGpu.set_shapefactors) for the ML-GGD loss chain and the
+        CV log-likelihood; None goes back to the scalar shapefactor."""
+        if v is None:
+            self._lib.ora_set_shapefactors(self._h, None)
+            return
+        a, pa = _f32(v)
+        assert a.shape == (self.D,)
+        self._lib.ora_set_shapefactors(self._h, pa)
 
     def close(self):
         if self._h:

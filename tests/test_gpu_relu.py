@@ -1,6 +1,7 @@
 """GPU: rectified-linear hidden units (BPGpu(..., activation="relu")) through every layer of the engine.
 
-The oracle is sigmoid-only, so the ReLU kernels are pinned by the float64 model of tests/relu64.py: every kernel of a
+Beside the bit-for-bit runs against the oracle's twin (tests/test_gpu_twin_relu_bins.py: 4-wave and 64 x 64 kernels), the
+ReLU kernels -- every loop variant included -- are held to the float64 model of tests/relu64.py: every kernel of a
 training step against its own fp32 inputs with derived per-element bounds (tests/test_relu_model.py shows on the CPU
 that the bounds pass the rules and refuse the slips they are meant for), one step on exactly representable data with no
 bound at all, the special values of the rule itself, and then the features built on run_forward / the dX launcher --

@@ -3,7 +3,9 @@
 the CPU oracle (weights 2e-5 of max|W|, like tests/test_gpu_parity.py).  Expanded and frame-stream chunks,
 emulated data-parallel ranks where the shape allows.  SEED / N env vars.  ALIGN64=1: hidden widths in multiples of 64 and
 minibatches of 64 / 128 / 256 frames -- with MLGGD_TILE64=2 in the environment every hidden forward / dX then runs through
-the 64 x 64-tile kernels (csrc/kernels64.hip.h)."""
+the 64 x 64-tile kernels (csrc/kernels64.hip.h).  ACT=relu: rectified-linear hidden units (lrate 0.01, as tests/relu64.py
+CASE_HP: the activations are unbounded); BINS=1: a random shape vector, U(0.5, 2.2) per output bin, for every ML case.  Both
+pass through to the engine, the oracle and the twin."""
 import importlib, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,7 +15,9 @@ from oracle import pyoracle
 
 rng = np.random.default_rng(int(os.environ.get("SEED", "1")))
 N = int(os.environ.get("N", "40"))
-HP = (0.1, 0.9, 1e-5)
+ACT = os.environ.get("ACT", "sigmoid")
+BINS = os.environ.get("BINS") == "1"
+HP = (0.01 if ACT == "relu" else 0.1, 0.9, 1e-5)
 
 
 def relmax(a, b):
@@ -31,6 +35,8 @@ for case in range(N):
     if os.environ.get("ALIGN64") == "1":
         ls = [dim * ctx] + [64 * int(rng.integers(1, 6)) for _ in range(max(nh, 1))] + [dim]
         B = int(rng.choice([64, 128, 256]))
+    if ACT == "relu" and B < 7:
+        B = 7  # one-frame minibatches make a deep rectifier net diverge to inf / NaN within a few steps: not a parity case
     ml, beta = [(0, 2.0), (0, 1.0), (1, 2.0), (1, 1.2), (1, 1.0), (1, 0.9)][int(rng.integers(0, 6))]
     if ml == 1 and B < 7:
         ml, beta = 0, 2.0  # the ML gradient is ~1/|e| with a one-frame minibatch: ill-conditioned, not a parity case
@@ -53,10 +59,13 @@ for case in range(N):
     idx = first[:, None] + np.arange(ctx)[None, :]
     inp = np.ascontiguousarray(feat[idx].reshape(len(first), ctx * dim))
     tg = np.ascontiguousarray(targ_fr[first + toff])
-    eng = pkg.BPGpu(1, 0, ls, B, *HP, ws, bs, beta, ml)
+    betas = rng.uniform(0.5, 2.2, dim).astype(np.float32) if BINS and ml == 1 else None
+    eng = pkg.BPGpu(1, 0, ls, B, *HP, ws, bs, beta, ml, activation=ACT)
+    if betas is not None:
+        eng.set_shapefactors(betas)
     if world > 1:
         eng.fake_world(world, sharded=dp == 'shard', allreduce=dp == 'allreduce', a2a=dp == 'shard_a2a')  # rank r: rows [r*B,(r+1)*B) of each global minibatch
-    ora = pyoracle.OracleNet(ls, world * B, *HP, beta, ml, ws, bs)
+    ora = pyoracle.OracleNet(ls, world * B, *HP, beta, ml, ws, bs, activation=ACT, shapefactors=betas)
     if frames_mode:
         got = eng.train_frames(feat, targ_fr, first, ctx, toff)
     else:
@@ -68,7 +77,7 @@ for case in range(N):
     worst = max(worst, err)
     # one-frame minibatches take steps of the order of the weights themselves: rounding differences are amplified
     tol = 2e-5 if B >= 7 else 2e-4
-    if beta <= 1.0:  # (beta = 1, either objective: the gradient is a pure sign -- it jumps by 2 / n or 2 / sum|e| at e = 0)
+    if beta <= 1.0 or (betas is not None and betas.min() <= 1.0):  # (beta = 1, either objective: the gradient is a pure sign -- it jumps by 2 / n or 2 / sum|e| at e = 0)
         # the beta < 1 gradient sgn(e)|e|^(beta-1) is largest, and changes sign, where e -> 0: an output that differs
         # in its last bits (GEMM summation order) flips one such element and moves a bias by ~1e-4 of max|b| in a few
         # steps (SEED=22 case 12: out equal to 7e-7, alpha to 1e-7, one of 7,424 gradient elements with the other sign)
@@ -80,7 +89,7 @@ for case in range(N):
     if True:
         pyoracle.set_gemm_order("hip", eng.out_slabs(), plan=eng.gemm_plan(), dp_world=world, dp_allreduce=dp == "allreduce")
         try:
-            tw = pyoracle.OracleNet(ls, world * B, *HP, beta, ml, ws, bs)
+            tw = pyoracle.OracleNet(ls, world * B, *HP, beta, ml, ws, bs, activation=ACT, shapefactors=betas)
             assert tw.train(inp, tg) == steps
             wt, bt = tw.get_weights()
             same = all(np.array_equal(a, b) for a, b in zip(list(we) + list(be), list(wt) + list(bt)))
@@ -95,9 +104,11 @@ for case in range(N):
         # (the HIP path equals the twin in every bit) -- SEED=91 case 92, 5 layers, 4 steps of one frame: 3.4e-4 of max|W|
         tol = 2e-3
     tag = "ok " if err < tol else "BAD"
-    print("%s case %2d: layers %-28s B %3d  loss (%d,%.1f) steps %d world %d%s%s  err %.1e%s" %
-          (tag, case, ls, B, ml, beta, steps, world, " " + dp if dp else "", " frames" if frames_mode else "", err, bits),
+    print("%s case %2d: layers %-28s B %3d  loss (%d,%.1f)%s steps %d world %d%s%s  err %.1e%s" %
+          (tag, case, ls, B, ml, beta, " bins" if betas is not None else "", steps, world, " " + dp if dp else "",
+           " frames" if frames_mode else "", err, bits),
           flush=True)
     assert err < tol
     eng.close(); ora.close()
-print("all %d cases within tolerance; worst %.1e; %d of them checked against the MFMA-order twin: every bit equal" % (N, worst, n_bits))
+print("all %d cases%s%s within tolerance; worst %.1e; %d of them checked against the MFMA-order twin: every bit equal" %
+      (N, " ACT=relu" if ACT == "relu" else "", " BINS=1" if BINS else "", worst, n_bits))
