@@ -112,7 +112,9 @@ int mlggd_forward(mlggd_handle h, int n_frames, const float *in, float *out);
  * every sample ROW (in the shuffled row order Readchunk would have produced), the index of its
  * first frame; sample i's target is frame first_frame[i] + targ_offset.  Rows are gathered by
  * the input-staging kernel; results are bit-identical to the expanded path.
- * After mlggd_load_frames, mlggd_train_resident indexes SAMPLES of this chunk. */
+ * After mlggd_load_frames, mlggd_train_resident indexes SAMPLES of this chunk.
+ * fea_context may differ from call to call on one engine (any value that divides layersizes[0]):
+ * the device buffers are sized in floats for the context of the call at hand. */
 int mlggd_load_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,
                       int n_samples, const int32_t *first_frame, int targ_offset);
 int mlggd_train_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,

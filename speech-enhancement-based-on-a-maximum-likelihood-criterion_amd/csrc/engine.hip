@@ -218,7 +218,7 @@ struct mlggd_engine {
     float *raw_feat = nullptr, *raw_targ = nullptr, *in_bunch = nullptr;
     float *in_bunch_buf[2] = {nullptr, nullptr};  // in_bunch alternates between them when bunches are staged ahead
     int *first_frame = nullptr;
-    size_t raw_cap = 0, first_cap = 0;
+    size_t raw_cap = 0, feat_cap = 0, first_cap = 0;
     // noise-aware training (nat_rule.h): nat_frames = cfg.nat_frames > 0 makes layer 0 one stream row wider; nat /
     // nat_row are the noise table and the per-sample noise rows of the CURRENT indexed chunk (a raw set's own, or the
     // decoder's table of the whole batch), switched together with raw_feat / first_frame
@@ -231,8 +231,11 @@ struct mlggd_engine {
     struct RawSet {
         float *feat = nullptr, *targ = nullptr;
         int *first = nullptr;
-        size_t raw_cap = 0, first_cap = 0;
-        // a NAT engine (nat_rule.h): the noise table [nat_cap rows][fdim] and the noise row of every sample
+        // raw_cap counts the rows of targ (D wide, a constant of the engine); feat_cap and nat_cap count FLOATS: a
+        // stream row is K0 / fea_context wide (stream_fdim) and fea_context is an argument of every call, so a row
+        // count says nothing about what feat and nat hold
+        size_t raw_cap = 0, feat_cap = 0, first_cap = 0;
+        // a NAT engine (nat_rule.h): the noise table [n_nat rows][fdim] and the noise row of every sample
         float *nat = nullptr;
         int *nat_row = nullptr;
         size_t nat_cap = 0, nat_row_cap = 0;
@@ -2046,14 +2049,14 @@ static int stream_fdim(const mlggd_engine *e, int ctx) { return nat_rule::stream
 // the noise table and the nat_row array of a raw set, grown to n_nat rows of fdim floats and n samples; the caller has
 // made sure that nothing on the device still reads the set
 static int raw_set_nat_grow(mlggd_engine *e, mlggd_engine::RawSet &r, size_t n_nat, size_t n, int fdim, hipStream_t st) {
-    const size_t need = n_nat + 8;
+    const size_t need = (n_nat + 8) * (size_t)fdim;  // floats
     if (need > r.nat_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
         if (r.nat) hipFree(r.nat);
         r.nat = nullptr;
         r.nat_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.nat, need * fdim * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.nat, 0, need * fdim * sizeof(float), st));
+        HIPCHK(hipMalloc((void **)&r.nat, need * sizeof(float)));
+        HIPCHK(hipMemsetAsync(r.nat, 0, need * sizeof(float), st));
         r.nat_cap = need;
     }
     const size_t need_s = n + e->Bp + 32;
@@ -2103,15 +2106,20 @@ static int load_frames_impl(mlggd_engine *e, int n_frames, int fea_context, cons
     // on the host before touching the allocation, then copy beside whatever the main stream is still running
     mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
     HIPCHK(hipEventSynchronize(r.last_use));
-    const size_t need = (size_t)n_frames + fea_context + 8;
-    if (need > r.raw_cap) {
+    const size_t need = (size_t)n_frames + fea_context + 8, need_f = need * fdim;  // rows of targ, floats of feat
+    if (need_f > r.feat_cap) {
         if (r.feat) hipFree(r.feat);
+        r.feat = nullptr;
+        r.feat_cap = 0;
+        HIPCHK(hipMalloc((void **)&r.feat, need_f * sizeof(float)));
+        HIPCHK(hipMemsetAsync(r.feat, 0, need_f * sizeof(float), e->copy_stream));
+        r.feat_cap = need_f;
+    }
+    if (need > r.raw_cap) {
         if (r.targ) hipFree(r.targ);
-        r.feat = r.targ = nullptr;
+        r.targ = nullptr;
         r.raw_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.feat, need * fdim * sizeof(float)));
         HIPCHK(hipMalloc((void **)&r.targ, need * e->D * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.feat, 0, need * fdim * sizeof(float), e->copy_stream));
         HIPCHK(hipMemsetAsync(r.targ, 0, need * e->D * sizeof(float), e->copy_stream));
         r.raw_cap = need;
     }
@@ -2147,6 +2155,7 @@ static int load_frames_impl(mlggd_engine *e, int n_frames, int fea_context, cons
     e->nat = r.nat;
     e->nat_row = r.nat_row;
     e->raw_cap = r.raw_cap;
+    e->feat_cap = r.feat_cap;
     e->first_cap = r.first_cap;
     e->chunk_frames = n_samples;
     e->raw_frames = n_frames;
@@ -3391,16 +3400,22 @@ int raw_set_acquire(mlggd_engine *e, int rows, int n, int ctx, mlggd_engine::Raw
     mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
     HIPCHK(hipEventSynchronize(r.last_use));
     if (e->nat_frames) CHK(raw_set_nat_grow(e, r, (size_t)n_nat, (size_t)n, fdim, e->stream));
-    const size_t need = (size_t)rows + ctx + 8;
-    if (need > r.raw_cap) {
+    const size_t need = (size_t)rows + ctx + 8, need_f = need * fdim;  // rows of targ, floats of feat
+    if (need_f > r.feat_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
         if (r.feat) hipFree(r.feat);
+        r.feat = nullptr;
+        r.feat_cap = 0;
+        HIPCHK(hipMalloc((void **)&r.feat, need_f * sizeof(float)));
+        HIPCHK(hipMemsetAsync(r.feat, 0, need_f * sizeof(float), e->stream));
+        r.feat_cap = need_f;
+    }
+    if (need > r.raw_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
         if (r.targ) hipFree(r.targ);
-        r.feat = r.targ = nullptr;
+        r.targ = nullptr;
         r.raw_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.feat, need * fdim * sizeof(float)));
         HIPCHK(hipMalloc((void **)&r.targ, need * e->D * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.feat, 0, need * fdim * sizeof(float), e->stream));
         HIPCHK(hipMemsetAsync(r.targ, 0, need * e->D * sizeof(float), e->stream));
         r.raw_cap = need;
     }
@@ -3426,6 +3441,7 @@ void raw_set_commit(mlggd_engine *e, mlggd_engine::RawSet &r, int rows, int n, i
     e->nat = r.nat;  // a decoding call then points it at its table of the whole batch
     e->nat_row = r.nat_row;
     e->raw_cap = r.raw_cap;
+    e->feat_cap = r.feat_cap;
     e->first_cap = r.first_cap;
     e->chunk_frames = n;
     e->raw_frames = rows;

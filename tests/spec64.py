@@ -415,13 +415,15 @@ def context_index(F, ctx, mut=None):
     return np.clip(idx, 0, F - 1)
 
 
-def decode64(lps, mean, inv, ctx, Ws, bs, slabs=1):
+def decode64(lps, mean, inv, ctx, Ws, bs, slabs=1, nat=None):
     """float64 decode.m target LPS [F][D] from the engine's own fp32 analysis rows `lps` (exact input: the analysis is
     bounded on its own), and a per-element bound lps_eps on any correct fp32 evaluation of the same chain:
     * x = fl(fl(lps - mean) * inv): two roundings, |dx| <= (2 u + u^2) |x|, which enter the network as x_err;
     * the forward chain: bounds64.expect_forward_chain, propagated through the layers;
     * out = fl(fl(y / inv) + mean) of the network's y = z + dz: |dz| / |inv| propagated, one rounding of the quotient
       and one of the sum.
+    nat: on a noise-aware net the utterance's fp32 noise row [D] (tests/nat_model.py fixes its every bit from the fp32
+    normalised rows), which closes every input row: an exact input like `lps`, no error of its own.
     Returns (target LPS float64, lps_eps) -- the inputs of synthesis_bound."""
     import bounds64
     lps = np.asarray(lps, np.float64)
@@ -430,7 +432,11 @@ def decode64(lps, mean, inv, ctx, Ws, bs, slabs=1):
     x = (lps - mean) * inv
     idx = context_index(F, ctx)
     a = x[idx].reshape(F, ctx * D)
-    ex = bounds64.expect_forward_chain(a, Ws, bs, slabs=slabs, x_err=(2.0 * U + U * U) * np.abs(a))
+    a_err = (2.0 * U + U * U) * np.abs(a)
+    if nat is not None:
+        a = np.concatenate([a, np.broadcast_to(np.asarray(nat, np.float64).reshape(1, D), (F, D))], axis=1)
+        a_err = np.concatenate([a_err, np.zeros((F, D))], axis=1)
+    ex = bounds64.expect_forward_chain(a, Ws, bs, slabs=slabs, x_err=a_err)
     z, Ez = ex.ref, ex.bound * bounds64.SECOND_ORDER
     ainv = np.abs(inv)
     q = z / inv

@@ -1,7 +1,8 @@
 """GPU: noise-aware training from waves -- train_waves / load_waves / cv_all_waves on a NAT engine against
 train_frames_nat / cv_all_frames_nat on rows built on the host: mix_waves, wave_to_lps per utterance, (lps - mean) *
 inv_std in numpy float32 as two operations, and the noise rows of tests/nat_model.py.  Every bit of every weight and
-bias, of scalefactor() and of the three CV sums."""
+bias, of scalefactor() and of the three CV sums; with a chunk capacity of exactly n_samples the same bits, with one
+sample more an argument error that moves nothing."""
 import numpy as np
 import pytest
 
@@ -131,5 +132,51 @@ def test_the_context_must_fill_layer_0_with_the_noise_row(case):
     eng.load_waves(case.noisys, case.cleans, case.mean, case.inv, case.first, case.toff, case.ctx, case.fs)
     assert eng.train_resident(0, case.n) == case.n // B
     eng.sync()
+    same_bits(state(eng), case.ref)
+    eng.close()
+
+
+def test_the_chunk_capacity_admits_n_samples(case):
+    """max_cache_frames == n_samples: train_waves, load_waves and cv_all_waves give the uncapped bits"""
+    eng = case.engine(cap=case.n)
+    eng.set_noise(case.noise)
+    assert eng.train_waves(case.cleans, case.snr, case.start, case.mean, case.inv, case.first, case.toff,
+                           noise_seg=case.seg, fea_context=case.ctx, fs_khz=case.fs) == case.n // B
+    same_bits(state(eng), case.ref)
+    eng.close()
+    eng = case.engine(cap=case.n)
+    args = (case.noisys, case.cleans, case.mean, case.inv, case.first, case.toff, case.ctx, case.fs)
+    eng.load_waves(*args)
+    assert eng.train_resident(0, case.n) == case.n // B
+    eng.sync()
+    same_bits(state(eng), case.ref)
+    got = eng.cv_all_waves(*args)
+    assert np.array(got, np.float32).tobytes() == np.array(case.ref_cv, np.float32).tobytes()
+    eng.set_cv_device_reduce(True)
+    got = eng.cv_all_waves(*args)
+    assert np.array(got, np.float32).tobytes() == np.array(case.ref_cv_dev, np.float32).tobytes()
+    eng.close()
+
+
+def test_one_sample_beyond_the_chunk_capacity_is_refused(case):
+    """max_cache_frames == n_samples - 1: an argument error from each of the three that moves nothing; the engine then
+    trains the table without its last sample -- part of the trailing bunch that is skipped either way -- to the bits"""
+    pkg = case.pkg
+    eng = case.engine(cap=case.n - 1)
+    eng.set_noise(case.noise)
+    start = state(eng)
+    pair = (case.noisys, case.cleans, case.mean, case.inv, case.first, case.toff, case.ctx, case.fs)
+    refusal = r"error 1: n_frames %d exceeds the chunk capacity %d" % (case.n, case.n - 1)
+    with pytest.raises(pkg.MlggdError, match=refusal):
+        eng.train_waves(case.cleans, case.snr, case.start, case.mean, case.inv, case.first, case.toff,
+                        noise_seg=case.seg, fea_context=case.ctx, fs_khz=case.fs)
+    with pytest.raises(pkg.MlggdError, match=refusal):
+        eng.load_waves(*pair)
+    with pytest.raises(pkg.MlggdError, match=refusal):
+        eng.cv_all_waves(*pair)
+    same_bits(state(eng), start)
+    assert case.n % B >= 1
+    assert eng.train_waves(case.cleans, case.snr, case.start, case.mean, case.inv, case.first[:-1], case.toff,
+                           noise_seg=case.seg, fea_context=case.ctx, fs_khz=case.fs) == case.n // B
     same_bits(state(eng), case.ref)
     eng.close()

@@ -227,3 +227,45 @@ def test_nothing_to_train(case):
                            fs_khz=case.fs) == 0
     same_bits(state(eng)[:-1], case.ws + case.bs)
     eng.close()
+
+
+def test_the_chunk_capacity_admits_n_samples(case):
+    """max_cache_frames == n_samples: train_waves, load_waves and cv_all_waves give the uncapped bits"""
+    eng = case.engine(case.n)
+    eng.set_noise(case.noise)
+    assert case.train_waves(eng) == case.n // B
+    same_bits(state(eng), case.ref)
+    eng.close()
+    eng = case.engine(case.n)
+    assert case.load_and_train(eng) == case.n // B
+    same_bits(state(eng), case.ref)
+    args = (case.noisys, case.cleans, case.mean, case.inv, case.first, case.toff, case.ctx, case.fs)
+    got = eng.cv_all_waves(*args)
+    assert np.array(got, np.float32).tobytes() == np.array(case.ref_cv, np.float32).tobytes()
+    eng.set_cv_device_reduce(True)
+    got = eng.cv_all_waves(*args)
+    assert np.array(got, np.float32).tobytes() == np.array(case.ref_cv_dev, np.float32).tobytes()
+    eng.close()
+
+
+def test_one_sample_beyond_the_chunk_capacity_is_refused(case):
+    """max_cache_frames == n_samples - 1: an argument error from each of the three that moves nothing; the engine then
+    trains the table without its last sample -- part of the trailing bunch that is skipped either way -- to the bits"""
+    pkg = case.pkg
+    eng = case.engine(case.n - 1)
+    eng.set_noise(case.noise)
+    start = state(eng)
+    pair = (case.noisys, case.cleans, case.mean, case.inv, case.first, case.toff, case.ctx, case.fs)
+    refusal = r"error 1: n_frames %d exceeds the chunk capacity %d" % (case.n, case.n - 1)
+    with pytest.raises(pkg.MlggdError, match=refusal):
+        case.train_waves(eng)
+    with pytest.raises(pkg.MlggdError, match=refusal):
+        eng.load_waves(*pair)
+    with pytest.raises(pkg.MlggdError, match=refusal):
+        eng.cv_all_waves(*pair)
+    same_bits(state(eng), start)
+    assert case.n % B >= 1
+    assert eng.train_waves(case.cleans, case.snr, case.start, case.mean, case.inv, case.first[:-1], case.toff,
+                           noise_seg=case.seg, fea_context=case.ctx, fs_khz=case.fs) == case.n // B
+    same_bits(state(eng), case.ref)
+    eng.close()
