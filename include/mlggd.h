@@ -527,6 +527,11 @@ int mlggd_debug_rank_tensor(mlggd_handle h, const char *name, int layer, int ran
 /* Test hook: number of launch plans (tile-record tables) the persistent dW kernel has cached; constant after the
  * first steps of a run (2 on one GPU, a few in the data-parallel modes). */
 int mlggd_debug_plan_count(mlggd_handle h, int *plans);
+/* Test hook: the engine's growable device buffers (csrc/devbuf.h: raw sets, chunk buffers, workspaces, launch-plan
+ * tables) and those of its open live groups.  allocations: device allocations they have made since mlggd_create, a
+ * count that never falls; bytes: what they hold now.  A call in the steady state -- no capacity exceeded -- leaves
+ * `allocations` as it was; mlggd_live_close lowers `bytes` by what the group held. */
+int mlggd_debug_buffers(mlggd_handle h, int64_t *allocations, int64_t *bytes);
 
 /* Test hook: the number of split-K slabs of the output-layer forward GEMM (the loss kernel adds them in order).  The
  * oracle's MFMA-order twin needs it to restate the HIP path's summation order (oracle/mlggd_oracle.c). */

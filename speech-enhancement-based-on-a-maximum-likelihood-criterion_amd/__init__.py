@@ -62,7 +62,7 @@ EXPORTS = [
     "mlggd_debug_stamp_select", "mlggd_debug_stamp_read",
     "mlggd_load_frames", "mlggd_train_frames", "mlggd_train_frames_async", "mlggd_cv_all_frames", "mlggd_forward_frames",
     "mlggd_alloc_pinned", "mlggd_alloc_pinned_on", "mlggd_free_pinned", "mlggd_set_cv_device_reduce",
-    "mlggd_comm_info", "mlggd_debug_plan_count", "mlggd_debug_math", "mlggd_debug_out_slabs", "mlggd_debug_gemm_plan",
+    "mlggd_comm_info", "mlggd_debug_plan_count", "mlggd_debug_buffers", "mlggd_debug_math", "mlggd_debug_out_slabs", "mlggd_debug_gemm_plan",
     "mlggd_debug_keep_ranks", "mlggd_debug_rank_tensor",
     "mlggd_wave_to_lps", "mlggd_lps_to_wave", "mlggd_enhance_wave",
     "mlggd_enhance_waves_layout", "mlggd_enhance_waves",
@@ -85,7 +85,7 @@ def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "mix.hip.h",
-                                             "mix_rule.h", "nat_rule.h")]
+                                             "mix_rule.h", "nat_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     stale = not os.path.exists(LIB_PATH) or any(
@@ -143,6 +143,7 @@ def load():
     L.mlggd_debug_rank_tensor.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _fp, C.c_size_t]
     L.mlggd_comm_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mlggd_debug_plan_count.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.mlggd_debug_buffers.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.mlggd_debug_out_slabs.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.mlggd_debug_gemm_plan.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.mlggd_debug_math.argtypes = [C.c_void_p, C.c_char_p, _fp, C.c_float, _fp, C.c_size_t]
@@ -1164,6 +1165,13 @@ class BPGpu:
         n = C.c_int(0)
         _check(load().mlggd_debug_plan_count(self._h, C.byref(n)))
         return n.value
+
+    def buffer_stats(self):
+        """(allocations, bytes) of the engine's growable device buffers and of its open live groups: device allocations
+        made since creation (never falls) and bytes held now.  A call that exceeds no capacity adds no allocation."""
+        n, b = C.c_int64(0), C.c_int64(0)
+        _check(load().mlggd_debug_buffers(self._h, C.byref(n), C.byref(b)))
+        return n.value, b.value
 
     def set_cv_device_reduce(self, on=True):
         """CV sums formed on the device (no n x D copy back) instead of the reference-order host loop."""

@@ -33,6 +33,7 @@
 #include "mix.hip.h"
 #include "mix_rule.h"
 #include "nat_rule.h"
+#include "devbuf.h"
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[1024] = "";
@@ -175,6 +176,7 @@ enum KernelClass { KC_TRANSPOSE = 0, KC_FWD, KC_LOSS, KC_DX, KC_DW, KC_UPDATE, K
 static const char *kKernelClassName[KC_COUNT] = {"transpose", "fwd", "loss", "dx", "dw", "update"};
 
 struct mlggd_engine {
+    DevBufStats bufs;  // of every DevBuf below and of the engine's live groups; declared first: destroyed last
     mlggd_config cfg;
     int L = 0;
     int ls[MLGGD_MAXLAYER] = {0};   // true units
@@ -205,50 +207,35 @@ struct mlggd_engine {
     bool per_bin = false;
     float *betas_dev = nullptr;
     std::vector<float> betas_host;
-    float *chunk_in = nullptr, *chunk_targ = nullptr, *chunk_out = nullptr;
+    DevBuf<float> chunk_in, chunk_targ, chunk_out;
     // CV metrics: 0 = outputs copied back, host fp32 accumulation in the reference's order (default: it is what
     // the log lines are compared on); 1 = sums formed on the device (k_cv_reduce), nothing of size n x D leaves it
     int cv_device = 0;
-    double *cv_partial = nullptr;
-    size_t cv_partial_cap = 0;
-    double *es_acc = nullptr;  // mlggd_error_stats: [4 + MLGGD_MAX_BETAS][D] sums of the call, allocated on first use
-    size_t chunk_cap = 0, out_cap = 0;
+    DevBuf<double> cv_partial;
+    DevBuf<double> es_acc;  // mlggd_error_stats: [4 + MLGGD_MAX_BETAS][D] sums of the call, allocated on first use
     int chunk_frames = 0;
-    // indexed chunk: raw frame streams + first frame of every sample row
-    float *raw_feat = nullptr, *raw_targ = nullptr, *in_bunch = nullptr;
+    float *in_bunch = nullptr;
     float *in_bunch_buf[2] = {nullptr, nullptr};  // in_bunch alternates between them when bunches are staged ahead
-    int *first_frame = nullptr;
-    size_t raw_cap = 0, feat_cap = 0, first_cap = 0;
-    // noise-aware training (nat_rule.h): nat_frames = cfg.nat_frames > 0 makes layer 0 one stream row wider; nat /
-    // nat_row are the noise table and the per-sample noise rows of the CURRENT indexed chunk (a raw set's own, or the
-    // decoder's table of the whole batch), switched together with raw_feat / first_frame
+    // noise-aware training (nat_rule.h): nat_frames = cfg.nat_frames > 0 makes layer 0 one stream row wider; nat is the
+    // noise table of the CURRENT indexed chunk: the current raw set's own, or the decoder's table of the whole batch
     int nat_frames = 0;
     const float *nat = nullptr;
-    const int *nat_row = nullptr;
-    // Frame-stream chunks ping-pong between two device buffer sets: the next chunk is uploaded on copy_stream
-    // while the kernels of the current one are still running (raw_feat / raw_targ / first_frame / *_cap above
-    // always describe the CURRENT set).
+    // indexed chunk: raw frame streams + first frame of every sample row.  Frame-stream chunks ping-pong
+    // between two device buffer sets: the next chunk is uploaded on copy_stream while the kernels of the current one,
+    // raw[raw_cur], are still running.  The sizes are those of devbuf_rule.h (feat and nat count FLOATS).
     struct RawSet {
-        float *feat = nullptr, *targ = nullptr;
-        int *first = nullptr;
-        // raw_cap counts the rows of targ (D wide, a constant of the engine); feat_cap and nat_cap count FLOATS: a
-        // stream row is K0 / fea_context wide (stream_fdim) and fea_context is an argument of every call, so a row
-        // count says nothing about what feat and nat hold
-        size_t raw_cap = 0, feat_cap = 0, first_cap = 0;
+        DevBuf<float> feat, targ;
+        DevBuf<int> first;
         // a NAT engine (nat_rule.h): the noise table [n_nat rows][fdim] and the noise row of every sample
-        float *nat = nullptr;
-        int *nat_row = nullptr;
-        size_t nat_cap = 0, nat_row_cap = 0;
+        DevBuf<float> nat;
+        DevBuf<int> nat_row;
         hipEvent_t last_use = nullptr;  // recorded on the main stream after the last kernel that reads the set
     } raw[2];
     int raw_cur = 0;
     hipStream_t copy_stream = nullptr;
-    // mlggd_enhance_waves: device workspace that only grows (freed in mlggd_destroy) and the host copies of the
-    // tables and norm vectors it holds, so a call in the steady state allocates nothing and uploads the wave alone
-    struct WsBuf {
-        void *p = nullptr;
-        size_t cap = 0;  // bytes
-    };
+    // mlggd_enhance_waves: device workspace that only grows (ws_grow) and the host copies of the tables and norm
+    // vectors it holds, so a call in the steady state allocates nothing and uploads the wave alone
+    typedef DevBuf<char> WsBuf;  // bytes: a call takes it as whatever type it needs
     struct WavesWs {
         WsBuf wave, lps, X, blk, out_i, out_f, lps_den, norm, frame_off, out_off, wave_off, utt_of;
         WsBuf nat;  // a NAT engine: the noise rows [n_utts][D] of the batch being decoded
@@ -356,14 +343,13 @@ struct mlggd_engine {
 
     // diagnostic in-kernel phase stamps (one launch of one (class, layer))
     int stamp_class = -1, stamp_layer = 0, stamp_blocks = 0;
-    long long *stamp_buf = nullptr;
-    size_t stamp_cap = 0;
+    DevBuf<long long> stamp_buf;  // 8 stamps for each of 8192 blocks, allocated by the first select
 
     struct DwpTable {  // one cached launch plan of the persistent dW kernel (dwp_table)
         DwpJobs key;
         bool fused;
         int grid;
-        DwpDesc *dev;
+        DevBuf<DwpDesc> dev;
     };
     std::vector<DwpTable> dwp_tables;
     std::vector<void *> allocs;
@@ -372,12 +358,28 @@ struct mlggd_engine {
 
 // buffer for the selected launch, nullptr otherwise; one-shot
 static long long *stamps_for(mlggd_engine *e, int cls, int layer, int blocks) {
-    if (e->stamp_class != cls || e->stamp_layer != layer || !e->stamp_buf) return nullptr;
-    if ((size_t)blocks * 8 > e->stamp_cap) return nullptr;
+    if (e->stamp_class != cls || e->stamp_layer != layer || !e->stamp_buf.p) return nullptr;
+    if ((size_t)blocks * 8 > e->stamp_buf.cap) return nullptr;
     e->stamp_class = -1;
     e->stamp_blocks = blocks;
-    return e->stamp_buf;
+    return e->stamp_buf.p;
 }
+
+// device buffers of one call, freed on every return path
+struct DevBufs {
+    std::vector<void *> p;
+    ~DevBufs() {
+        for (void *q : p) hipFree(q);
+    }
+    template <typename T>
+    int alloc(T **out, size_t count) {
+        void *q = nullptr;
+        HIPCHK(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
+        p.push_back(q);
+        *out = (T *)q;
+        return MLGGD_OK;
+    }
+};
 
 static int dev_alloc(mlggd_engine *e, float **p, size_t count) {
     // +64 floats of slack; zero-filled like the reference's devnew_vf (BP_GPU.cu:528-543)
@@ -548,13 +550,14 @@ struct Bunch {
 static Bunch bunch_at(mlggd_engine *e, int sample) {
     Bunch b;
     if (e->indexed) {
-        b.in = e->raw_feat;
-        b.targ = e->raw_targ;
-        b.first = e->first_frame + sample;
-        b.nat_row = e->nat_frames ? e->nat_row + sample : nullptr;
+        const mlggd_engine::RawSet &r = e->raw[e->raw_cur];
+        b.in = r.feat.p;
+        b.targ = r.targ.p;
+        b.first = r.first.p + sample;
+        b.nat_row = e->nat_frames ? r.nat_row.p + sample : nullptr;
     } else {
-        b.in = e->chunk_in + (size_t)sample * e->K0;
-        b.targ = e->chunk_targ + (size_t)sample * e->D;
+        b.in = e->chunk_in.p + (size_t)sample * e->K0;
+        b.targ = e->chunk_targ.p + (size_t)sample * e->D;
         b.first = nullptr;
         b.nat_row = nullptr;
     }
@@ -820,7 +823,7 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
     key.total = J.total;
     for (const auto &t : e->dwp_tables)
         if (t.fused == fused && t.grid == grid && memcmp(&t.key, &key, sizeof(key)) == 0) {
-            *out = t.dev;
+            *out = t.dev.p;
             return MLGGD_OK;
         }
     // A run uses two plans on one GPU (the layer-1 operand alternates between the two staged-row buffers) and a
@@ -879,12 +882,11 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
     t.key = key;
     t.fused = fused;
     t.grid = grid;
-    t.dev = nullptr;
-    HIPCHK(hipMalloc((void **)&t.dev, recs.size() * sizeof(DwpDesc)));
+    HIPCHK(t.dev.grow(recs.size(), recs.size(), e->bufs, nullptr, nullptr));
     // pageable source, synchronous copy: complete when the call returns, so the launch that follows sees it
-    HIPCHK(hipMemcpy(t.dev, recs.data(), recs.size() * sizeof(DwpDesc), hipMemcpyHostToDevice));
-    e->dwp_tables.push_back(t);
-    *out = t.dev;
+    HIPCHK(hipMemcpy(t.dev.p, recs.data(), recs.size() * sizeof(DwpDesc), hipMemcpyHostToDevice));
+    *out = t.dev.p;
+    e->dwp_tables.push_back(std::move(t));
     return MLGGD_OK;
 }
 
@@ -921,7 +923,7 @@ static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream
     }
     CHK(dwp_table(e, J, fused, grid, &table));
     if constexpr (H == 2 || H == 8) {
-        if (e->stamp_class == KC_DW && e->stamp_layer == -1 && e->stamp_buf && fused && C.nf == 128.0f) {
+        if (e->stamp_class == KC_DW && e->stamp_layer == -1 && e->stamp_buf.p && fused && C.nf == 128.0f) {
             // diagnostic: the twin kernel with per-phase cycle sums (rows grid .. 2*grid-1 of the stamp buffer)
             long long *sp = stamps_for(e, KC_DW, -1, 2 * grid);
             if (sp) {
@@ -1122,8 +1124,7 @@ static int shard_alloc(mlggd_engine *e) {
             HIPCHK(hipMemcpyAsync(nw, e->W[l], (size_t)Kp * Np * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
             HIPCHK(hipStreamSynchronize(e->stream));
             e->W[l] = nw;  // the old buffer stays on the free list
-            for (auto &t : e->dwp_tables) hipFree(t.dev);  // tile records built so far point into the old buffer
-            e->dwp_tables.clear();
+            e->dwp_tables.clear();  // tile records built so far point into the old buffer
         }
         HIPCHK(hipEventCreateWithFlags(&e->ev_W[l], hipEventDisableTiming));
     }
@@ -1858,29 +1859,10 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->stat_comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->stat_comm);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (void *p : e->allocs) hipFree(p);
-    if (e->chunk_in) hipFree(e->chunk_in);
-    if (e->chunk_targ) hipFree(e->chunk_targ);
-    if (e->chunk_out) hipFree(e->chunk_out);
-    if (e->cv_partial) hipFree(e->cv_partial);
-    if (e->es_acc) hipFree(e->es_acc);
-    for (auto &t : e->dwp_tables) hipFree(t.dev);
     if (e->copy_stream) hipStreamSynchronize(e->copy_stream);
-    for (auto &r : e->raw) {
-        if (r.feat) hipFree(r.feat);
-        if (r.targ) hipFree(r.targ);
-        if (r.first) hipFree(r.first);
-        if (r.nat) hipFree(r.nat);
-        if (r.nat_row) hipFree(r.nat_row);
+    for (auto &r : e->raw)
         if (r.last_use) hipEventDestroy(r.last_use);
-    }
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
-    for (mlggd_engine::WsBuf *b : {&e->ww.wave, &e->ww.lps, &e->ww.X, &e->ww.blk, &e->ww.out_i, &e->ww.out_f,
-                                   &e->ww.lps_den, &e->ww.norm, &e->ww.frame_off, &e->ww.out_off, &e->ww.wave_off,
-                                   &e->ww.utt_of, &e->ww.nat, &e->ww.clean, &e->ww.Xc, &e->ww.fstat, &e->ww.sframes, &e->ww.scores,
-                                   &e->ww.stoi_utt, &e->ww.stoi_x, &e->ww.stoi_f, &e->ww.stoi_i, &e->ww.stoi_res,
-                                   &e->tw.norm, &e->tw.frame_off, &e->tw.wave_off, &e->tw.blocks, &e->tw.utt,
-                                   &e->tw.noise})
-        if (b->p) hipFree(b->p);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
     for (int l = 0; l < MLGGD_MAXLAYER; l++) {
         if (e->ev_grad[l]) hipEventDestroy(e->ev_grad[l]);
@@ -1903,7 +1885,7 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->ev_upd) hipEventDestroy(e->ev_upd);
     if (e->dw_stream) hipStreamDestroy(e->dw_stream);
     if (e->stream) hipStreamDestroy(e->stream);
-    delete e;
+    delete e;  // every DevBuf frees itself here: all streams have been synchronised above
     return MLGGD_OK;
 }
 
@@ -2002,17 +1984,9 @@ int mlggd_set_lrate(mlggd_handle e, float lrate) {
 }
 
 static int ensure_chunk(mlggd_engine *e, int n_frames) {
-    const size_t need = (size_t)n_frames + e->Bp + 32;  // slack rows: padded tiles may read past the last frame
-    if (need <= e->chunk_cap) return MLGGD_OK;
-    if (e->chunk_in) hipFree(e->chunk_in);
-    if (e->chunk_targ) hipFree(e->chunk_targ);
-    e->chunk_in = e->chunk_targ = nullptr;
-    e->chunk_cap = 0;
-    HIPCHK(hipMalloc((void **)&e->chunk_in, need * e->K0 * sizeof(float)));
-    HIPCHK(hipMalloc((void **)&e->chunk_targ, need * e->D * sizeof(float)));
-    HIPCHK(hipMemsetAsync(e->chunk_in, 0, need * e->K0 * sizeof(float), e->stream));
-    HIPCHK(hipMemsetAsync(e->chunk_targ, 0, need * e->D * sizeof(float), e->stream));
-    e->chunk_cap = need;
+    const size_t need = devbuf_rule::sample_slots((size_t)n_frames, (size_t)e->Bp);  // rows
+    HIPCHK(e->chunk_in.grow(need * e->K0, need * e->K0, e->bufs, &e->stream, nullptr));
+    HIPCHK(e->chunk_targ.grow(need * e->D, need * e->D, e->bufs, &e->stream, nullptr));
     return MLGGD_OK;
 }
 
@@ -2031,9 +2005,9 @@ int mlggd_load_chunk(mlggd_handle e, int n_frames, const float *in, const float 
     CHK(ensure_chunk(e, n_frames));
     // todev_vf_vf("in"/"targ"), BP_GPU.cu:163-164
     if (n_frames > 0) {
-        HIPCHK(hipMemcpyAsync(e->chunk_in, in, (size_t)n_frames * e->K0 * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->chunk_in.p, in, (size_t)n_frames * e->K0 * 4, hipMemcpyHostToDevice, e->stream));
         if (targ)
-            HIPCHK(hipMemcpyAsync(e->chunk_targ, targ, (size_t)n_frames * e->D * 4, hipMemcpyHostToDevice, e->stream));
+            HIPCHK(hipMemcpyAsync(e->chunk_targ.p, targ, (size_t)n_frames * e->D * 4, hipMemcpyHostToDevice, e->stream));
     }
     HIPCHK(hipStreamSynchronize(e->stream));
     e->chunk_frames = n_frames;
@@ -2046,30 +2020,44 @@ int mlggd_load_chunk(mlggd_handle e, int n_frames, const float *in, const float 
 // width of a stream row: layersizes[0] / fea_context, or / (fea_context + 1) on a NAT engine (0: it does not divide)
 static int stream_fdim(const mlggd_engine *e, int ctx) { return nat_rule::stream_width(e->K0, ctx, e->nat_frames > 0); }
 
-// the noise table and the nat_row array of a raw set, grown to n_nat rows of fdim floats and n samples; the caller has
-// made sure that nothing on the device still reads the set
-static int raw_set_nat_grow(mlggd_engine *e, mlggd_engine::RawSet &r, size_t n_nat, size_t n, int fdim, hipStream_t st) {
-    const size_t need = (n_nat + 8) * (size_t)fdim;  // floats
-    if (need > r.nat_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (r.nat) hipFree(r.nat);
-        r.nat = nullptr;
-        r.nat_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.nat, need * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.nat, 0, need * sizeof(float), st));
-        r.nat_cap = need;
+// The engine's idle raw buffer set, grown (devbuf_rule.h) for a stream of `rows` rows read through windows of ctx rows,
+// n samples and, on a NAT engine, n_nat noise rows; raw_set_commit then makes it the current one.  upload: the caller
+// fills the set from host memory on copy_stream (mlggd_load_frames), else with kernels on the main stream; a fresh
+// allocation is zero-filled on that stream.  The set's last reader (two chunks ago) has finished or is about to: it is
+// waited for on the host before the allocation is touched.  A buffer that regrows drains the main stream first.
+static int raw_set_acquire(mlggd_engine *e, int rows, int n, int ctx, int n_nat, bool upload, mlggd_engine::RawSet **out) {
+    if (!e->copy_stream) {
+        CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));  // must not queue behind the chunk's kernels
+        for (auto &r : e->raw) HIPCHK(hipEventCreateWithFlags(&r.last_use, hipEventDisableTiming));
     }
-    const size_t need_s = n + e->Bp + 32;
-    if (need_s > r.nat_row_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (r.nat_row) hipFree(r.nat_row);
-        r.nat_row = nullptr;
-        r.nat_row_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.nat_row, need_s * sizeof(int)));
-        HIPCHK(hipMemsetAsync(r.nat_row, 0, need_s * sizeof(int), st));
-        r.nat_row_cap = need_s;
+    const hipStream_t *zero = upload ? &e->copy_stream : &e->stream, *drain = &e->stream;
+    const size_t fdim = (size_t)stream_fdim(e, ctx);
+    mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
+    HIPCHK(hipEventSynchronize(r.last_use));
+    const size_t n_feat = devbuf_rule::raw_feat_floats((size_t)rows, (size_t)ctx, fdim);
+    const size_t n_targ = devbuf_rule::raw_rows((size_t)rows, (size_t)ctx) * e->D;
+    const size_t n_slots = devbuf_rule::sample_slots((size_t)n, (size_t)e->Bp);
+    HIPCHK(r.feat.grow(n_feat, n_feat, e->bufs, zero, drain));
+    HIPCHK(r.targ.grow(n_targ, n_targ, e->bufs, zero, drain));
+    HIPCHK(r.first.grow(n_slots, n_slots, e->bufs, zero, drain));
+    if (e->nat_frames) {
+        const size_t n_tab = devbuf_rule::nat_floats((size_t)n_nat, fdim);
+        HIPCHK(r.nat.grow(n_tab, n_tab, e->bufs, zero, drain));
+        HIPCHK(r.nat_row.grow(n_slots, n_slots, e->bufs, zero, drain));
     }
+    *out = &r;
     return MLGGD_OK;
+}
+
+// the set just acquired and filled becomes the current indexed chunk: n samples over `rows` stream rows
+static void raw_set_commit(mlggd_engine *e, int rows, int n, int ctx, int toff) {
+    e->raw_cur ^= 1;
+    e->nat = e->raw[e->raw_cur].nat.p;  // a decoding call then points it at its table of the whole batch
+    e->chunk_frames = n;
+    e->raw_frames = rows;
+    e->indexed = true;
+    e->fdim = stream_fdim(e, ctx);
+    e->toff = toff;
 }
 
 // mlggd_load_frames and, on a NAT engine, mlggd_load_frames_nat (n_nat / nat / nat_row are read only there)
@@ -2098,70 +2086,23 @@ static int load_frames_impl(mlggd_engine *e, int n_frames, int fea_context, cons
                 return fail(MLGGD_ERR_ARG, "sample %d: nat_row %d outside the %d noise rows", s, nat_row[s], n_nat);
     }
     HIPCHK(hipSetDevice(e->device));
-    if (!e->copy_stream) {
-        CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));  // must not queue behind the chunk's kernels
-        for (auto &r : e->raw) HIPCHK(hipEventCreateWithFlags(&r.last_use, hipEventDisableTiming));
-    }
-    // the set that is NOT current: its last reader (two chunks ago) has finished or is about to; wait for it
-    // on the host before touching the allocation, then copy beside whatever the main stream is still running
-    mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
-    HIPCHK(hipEventSynchronize(r.last_use));
-    const size_t need = (size_t)n_frames + fea_context + 8, need_f = need * fdim;  // rows of targ, floats of feat
-    if (need_f > r.feat_cap) {
-        if (r.feat) hipFree(r.feat);
-        r.feat = nullptr;
-        r.feat_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.feat, need_f * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.feat, 0, need_f * sizeof(float), e->copy_stream));
-        r.feat_cap = need_f;
-    }
-    if (need > r.raw_cap) {
-        if (r.targ) hipFree(r.targ);
-        r.targ = nullptr;
-        r.raw_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.targ, need * e->D * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.targ, 0, need * e->D * sizeof(float), e->copy_stream));
-        r.raw_cap = need;
-    }
-    const size_t need_s = (size_t)n_samples + e->Bp + 32;
-    if (need_s > r.first_cap) {
-        if (r.first) hipFree(r.first);
-        r.first = nullptr;
-        r.first_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.first, need_s * sizeof(int)));
-        HIPCHK(hipMemsetAsync(r.first, 0, need_s * sizeof(int), e->copy_stream));
-        r.first_cap = need_s;
-    }
-    if (natm) {
-        CHK(raw_set_nat_grow(e, r, (size_t)n_nat, (size_t)n_samples, fdim, e->copy_stream));
-        if (n_samples > 0) {
-            HIPCHK(hipMemcpyAsync(r.nat, nat, (size_t)n_nat * fdim * 4, hipMemcpyHostToDevice, e->copy_stream));
-            HIPCHK(hipMemcpyAsync(r.nat_row, nat_row, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, e->copy_stream));
-        }
+    // the set that is NOT current: copy beside whatever the main stream is still running
+    mlggd_engine::RawSet *r;
+    CHK(raw_set_acquire(e, n_frames, n_samples, fea_context, n_nat, true, &r));
+    if (natm && n_samples > 0) {
+        HIPCHK(hipMemcpyAsync(r->nat.p, nat, (size_t)n_nat * fdim * 4, hipMemcpyHostToDevice, e->copy_stream));
+        HIPCHK(hipMemcpyAsync(r->nat_row.p, nat_row, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, e->copy_stream));
     }
     if (n_frames > 0) {
-        HIPCHK(hipMemcpyAsync(r.feat, feat, (size_t)n_frames * fdim * 4, hipMemcpyHostToDevice, e->copy_stream));
-        if (targ) HIPCHK(hipMemcpyAsync(r.targ, targ, (size_t)n_frames * e->D * 4, hipMemcpyHostToDevice, e->copy_stream));
+        HIPCHK(hipMemcpyAsync(r->feat.p, feat, (size_t)n_frames * fdim * 4, hipMemcpyHostToDevice, e->copy_stream));
+        if (targ) HIPCHK(hipMemcpyAsync(r->targ.p, targ, (size_t)n_frames * e->D * 4, hipMemcpyHostToDevice, e->copy_stream));
     }
     if (n_samples > 0)
-        HIPCHK(hipMemcpyAsync(r.first, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, e->copy_stream));
+        HIPCHK(hipMemcpyAsync(r->first.p, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, e->copy_stream));
     // the caller's buffers are free when this returns; kernels enqueued from now on see the data (the host has
     // observed the copies complete)
     HIPCHK(hipStreamSynchronize(e->copy_stream));
-    e->raw_cur ^= 1;
-    e->raw_feat = r.feat;
-    e->raw_targ = r.targ;
-    e->first_frame = r.first;
-    e->nat = r.nat;
-    e->nat_row = r.nat_row;
-    e->raw_cap = r.raw_cap;
-    e->feat_cap = r.feat_cap;
-    e->first_cap = r.first_cap;
-    e->chunk_frames = n_samples;
-    e->raw_frames = n_frames;
-    e->indexed = true;
-    e->fdim = fdim;
-    e->toff = targ_offset;
+    raw_set_commit(e, n_frames, n_samples, fea_context, targ_offset);
     return MLGGD_OK;
 }
 
@@ -2305,20 +2246,15 @@ int mlggd_last_train_ms(mlggd_handle e, float *ms, int *steps) {
 
 // Forward over a chunk whose inputs are resident: outputs into chunk_out[n][D].
 static int forward_resident(mlggd_engine *e, int n_frames) {
-    if ((size_t)n_frames > e->out_cap) {
-        if (e->chunk_out) hipFree(e->chunk_out);
-        e->chunk_out = nullptr;
-        e->out_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->chunk_out, ((size_t)n_frames + 32) * e->D * sizeof(float)));
-        e->out_cap = n_frames;
-    }
+    const size_t n_out = devbuf_rule::out_rows((size_t)n_frames) * e->D;
+    HIPCHK(e->chunk_out.grow(n_out, n_out, e->bufs, nullptr, nullptr));
     const int b_tiles = e->Bp / 32;
     // bunch loop of CrossValid*, BP_GPU.cu:202-216: INCLUDES the trailing partial bunch
     for (int i = 0; i < n_frames; i += e->B) {
         const int fb = (e->B > n_frames - i) ? (n_frames - i) : e->B;
         CHK(run_forward(e, bunch_at(e, i), fb, false));
         hipLaunchKernelGGL(k_out_rowmajor, dim3((e->Dp / 32) * b_tiles), dim3(256), 0, e->stream, e->slab, e->S_out,
-                           e->bias[e->L - 1], fb, e->D, e->Dp, e->Bp, e->chunk_out + (size_t)i * e->D, b_tiles);
+                           e->bias[e->L - 1], fb, e->D, e->Dp, e->Bp, e->chunk_out.p + (size_t)i * e->D, b_tiles);
         CHK(launch_check("k_out_rowmajor"));
     }
     return MLGGD_OK;
@@ -2330,7 +2266,7 @@ int mlggd_forward(mlggd_handle e, int n_frames, const float *in, float *out) {
     CHK(mlggd_load_chunk(e, n_frames, in, nullptr));
     if (n_frames == 0) return MLGGD_OK;
     CHK(forward_resident(e, n_frames));
-    HIPCHK(hipMemcpyAsync(out, e->chunk_out, (size_t)n_frames * e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n_frames * e->D * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }
@@ -2372,7 +2308,7 @@ static int cv_accumulate(mlggd_engine *e, int n_frames, const std::function<cons
     std::vector<float> out((size_t)n_frames * D);
     if (n_frames > 0) {
         CHK(forward_resident(e, n_frames));
-        HIPCHK(hipMemcpyAsync(out.data(), e->chunk_out, (size_t)n_frames * D * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(out.data(), e->chunk_out.p, (size_t)n_frames * D * 4, hipMemcpyDeviceToHost, e->stream));
     }
     std::vector<float> scalefac(D);
     if (loglik)
@@ -2434,13 +2370,7 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
     const int D = e->D, b_tiles = e->Bp / 32, tiles = (e->Dp / 32) * b_tiles;
     const int nb = (n_frames + e->B - 1) / e->B;
     const size_t need = (size_t)(nb > 0 ? nb : 1) * tiles * 3;
-    if (need > e->cv_partial_cap) {
-        if (e->cv_partial) hipFree(e->cv_partial);
-        e->cv_partial = nullptr;
-        e->cv_partial_cap = 0;
-        HIPCHK(hipMalloc((void **)&e->cv_partial, need * sizeof(double)));
-        e->cv_partial_cap = need;
-    }
+    HIPCHK(e->cv_partial.grow(need, need, e->bufs, nullptr, nullptr));
     // bunch loop of CrossValid*, BP_GPU.cu:202-216: INCLUDES the trailing partial bunch
     for (int i = 0, k = 0; i < n_frames; i += e->B, k++) {
         const int fb = (e->B > n_frames - i) ? (n_frames - i) : e->B;
@@ -2451,7 +2381,7 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
         a.B = fb; a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.beta = e->cfg.shapefactor;
         a.alpha = loglik ? e->scalefactor : nullptr;
         a.first = bn.first; a.toff = e->toff; a.b_tiles = b_tiles;
-        a.partial = e->cv_partial + (size_t)k * tiles * 3;
+        a.partial = e->cv_partial.p + (size_t)k * tiles * 3;
         if (loglik && e->per_bin) {
             hipLaunchKernelGGL(k_cv_reduce_bins, dim3(tiles), dim3(256), 0, e->stream, a, (const float *)e->betas_dev);
             CHK(launch_check("k_cv_reduce_bins"));
@@ -2463,7 +2393,7 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
     std::vector<double> part((size_t)nb * tiles * 3);
     std::vector<float> scalefac(D);
     if (nb > 0)
-        HIPCHK(hipMemcpyAsync(part.data(), e->cv_partial, part.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(part.data(), e->cv_partial.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     if (loglik) HIPCHK(hipMemcpyAsync(scalefac.data(), e->scalefactor, (size_t)D * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     double s[3] = {0, 0, 0};
@@ -2542,7 +2472,7 @@ int mlggd_forward_frames_nat(mlggd_handle e, int n_frames, int fea_context, cons
     CHK(load_frames_impl(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, 0, n_nat, nat, nat_row));
     if (n_samples == 0) return MLGGD_OK;
     CHK(forward_resident(e, n_samples));
-    HIPCHK(hipMemcpyAsync(out, e->chunk_out, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }
@@ -2612,7 +2542,7 @@ int mlggd_forward_frames(mlggd_handle e, int n_frames, int fea_context, const fl
     CHK(mlggd_load_frames(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, 0));
     if (n_samples == 0) return MLGGD_OK;
     CHK(forward_resident(e, n_samples));
-    HIPCHK(hipMemcpyAsync(out, e->chunk_out, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }
@@ -2637,10 +2567,11 @@ static int error_stats_state(mlggd_engine *e, const char *who) {
 // followed by ONE k_err_stats launch that folds the bunch into es_acc; one download and one synchronise.
 static int error_stats_resident(mlggd_engine *e, int n, int n_betas, const float *betas, double *sums) {
     const int D = e->D, rows = 4 + n_betas;
-    if (!e->es_acc) HIPCHK(hipMalloc((void **)&e->es_acc, (size_t)(4 + MLGGD_MAX_BETAS) * D * sizeof(double)));
+    const size_t n_acc = (size_t)(4 + MLGGD_MAX_BETAS) * D;
+    HIPCHK(e->es_acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
     ErrStatsArgs a;
     a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
-    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = e->es_acc;
+    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = e->es_acc.p;
     for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < n_betas ? betas[k] : 1.0f;
     for (int i = 0; i < n; i += e->B) {
         const int fb = (e->B > n - i) ? (n - i) : e->B;
@@ -2650,7 +2581,7 @@ static int error_stats_resident(mlggd_engine *e, int n, int n_betas, const float
         hipLaunchKernelGGL(k_err_stats, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
         CHK(launch_check("k_err_stats"));
     }
-    HIPCHK(hipMemcpyAsync(sums, e->es_acc, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(sums, e->es_acc.p, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }
@@ -3045,6 +2976,14 @@ int mlggd_debug_plan_count(mlggd_handle e, int *plans) {
     *plans = (int)e->dwp_tables.size();
     return MLGGD_OK;
 }
+// the engine's growable buffers (devbuf.h) and those of its live groups: device allocations they have made since the
+// engine was created, and the bytes they hold now (tests: no call in the steady state allocates)
+int mlggd_debug_buffers(mlggd_handle e, int64_t *allocations, int64_t *bytes) {
+    if (!e || !allocations || !bytes) return fail(MLGGD_ERR_ARG, "NULL argument");
+    *allocations = e->bufs.allocs;
+    *bytes = e->bufs.bytes;
+    return MLGGD_OK;
+}
 int mlggd_debug_gemm_plan(mlggd_handle e, int layer, int *fwd_waves, int *dx_waves) {
     if (!e || !fwd_waves || !dx_waves) return fail(MLGGD_ERR_ARG, "NULL argument");
     if (layer < 1 || layer >= e->L) return fail(MLGGD_ERR_ARG, "layer %d not in 1..%d", layer, e->L - 1);
@@ -3077,24 +3016,17 @@ int mlggd_debug_math(mlggd_handle e, const char *fn, const float *x, float y, fl
     if (f < 0) return fail(MLGGD_ERR_ARG, "unknown function '%s'", fn);
     if (n == 0) return MLGGD_OK;
     HIPCHK(hipSetDevice(e->device));
+    DevBufs b;
     float *dx = nullptr, *dout = nullptr;
-    HIPCHK(hipMalloc((void **)&dx, n * sizeof(float)));
-    if (hipMalloc((void **)&dout, n * sizeof(float)) != hipSuccess) {
-        hipFree(dx);
-        return fail(MLGGD_ERR_DEVICE, "hipMalloc of %zu bytes failed", n * sizeof(float));
-    }
-    int rc = MLGGD_OK;
-    if (hipMemcpyAsync(dx, x, n * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) rc = MLGGD_ERR_DEVICE;
-    if (rc == MLGGD_OK) {
-        hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, f, dx, y, dout, n);
-        rc = launch_check("k_debug_math");
-    }
-    if (rc == MLGGD_OK && (hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
-                           hipStreamSynchronize(e->stream) != hipSuccess))
-        rc = fail(MLGGD_ERR_DEVICE, "mlggd_debug_math: copy back failed");
-    hipFree(dx);
-    hipFree(dout);
-    return rc;
+    CHK(b.alloc(&dx, n));
+    CHK(b.alloc(&dout, n));
+    if (hipMemcpyAsync(dx, x, n * sizeof(float), hipMemcpyHostToDevice, e->stream) != hipSuccess) return MLGGD_ERR_DEVICE;
+    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, f, dx, y, dout, n);
+    CHK(launch_check("k_debug_math"));
+    if (hipMemcpyAsync(out, dout, n * sizeof(float), hipMemcpyDeviceToHost, e->stream) != hipSuccess ||
+        hipStreamSynchronize(e->stream) != hipSuccess)  // the buffers are freed on return
+        return fail(MLGGD_ERR_DEVICE, "mlggd_debug_math: copy back failed");
+    return MLGGD_OK;
 }
 
 // ---- per-kernel-class timing inside the timed region (bench.py roofline object)
@@ -3147,12 +3079,8 @@ int mlggd_profile_read(mlggd_handle e, float *mean_usec, int *launches) {
 int mlggd_debug_stamp_select(mlggd_handle e, const char *kernel_class, int layer) {
     if (!e || !kernel_class) return fail(MLGGD_ERR_ARG, "NULL argument");
     HIPCHK(hipSetDevice(e->device));
-    if (!e->stamp_buf) {
-        e->stamp_cap = 8 * 8192;
-        HIPCHK(hipMalloc((void **)&e->stamp_buf, e->stamp_cap * sizeof(long long)));
-        e->allocs.push_back(e->stamp_buf);
-    }
-    HIPCHK(hipMemsetAsync(e->stamp_buf, 0, e->stamp_cap * sizeof(long long), e->stream));
+    HIPCHK(e->stamp_buf.grow(8 * 8192, 8 * 8192, e->bufs, nullptr, nullptr));
+    HIPCHK(hipMemsetAsync(e->stamp_buf.p, 0, e->stamp_buf.cap * sizeof(long long), e->stream));
     e->stamp_class = -1;
     for (int c = 0; c < KC_COUNT; c++)
         if (!strcmp(kernel_class, kKernelClassName[c])) e->stamp_class = c;
@@ -3167,7 +3095,7 @@ int mlggd_debug_stamp_read(mlggd_handle e, long long *out, int cap_blocks, int *
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
     const int n = e->stamp_blocks < cap_blocks ? e->stamp_blocks : cap_blocks;
-    if (n > 0) HIPCHK(hipMemcpy(out, e->stamp_buf, (size_t)n * 8 * sizeof(long long), hipMemcpyDeviceToHost));
+    if (n > 0) HIPCHK(hipMemcpy(out, e->stamp_buf.p, (size_t)n * 8 * sizeof(long long), hipMemcpyDeviceToHost));
     *blocks = n;
     return MLGGD_OK;
 }
@@ -3304,6 +3232,16 @@ float2 twiddle(int k, int n) {
     return make_float2((float)c, (float)s);
 }
 
+// a table of a process-lifetime plan: allocated on the current device and filled by a blocking copy
+template <typename T>
+int upload_table(const std::vector<T> &h, T **out) {
+    T *d = nullptr;
+    HIPCHK(hipMalloc((void **)&d, h.size() * sizeof(T)));
+    HIPCHK(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+    *out = d;
+    return MLGGD_OK;
+}
+
 // the plan of (current device, rate); the caller has selected the device
 int spec_plan(int device, int fs_khz, const SpecPlan **out) {
     SpecDims d;
@@ -3321,12 +3259,9 @@ int spec_plan(int device, int fs_khz, const SpecPlan **out) {
         for (int k = 0; k < d.D; k++) tws[k] = twiddle(k, d.N);
         float *w = nullptr;
         float2 *a = nullptr, *b = nullptr;
-        HIPCHK(hipMalloc((void **)&w, win.size() * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&a, tw.size() * sizeof(float2)));
-        HIPCHK(hipMalloc((void **)&b, tws.size() * sizeof(float2)));
-        HIPCHK(hipMemcpy(w, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(a, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(b, tws.data(), tws.size() * sizeof(float2), hipMemcpyHostToDevice));
+        CHK(upload_table(win, &w));
+        CHK(upload_table(tw, &a));
+        CHK(upload_table(tws, &b));
         p.d = d, p.win = w, p.tw = a, p.tws = b;
     }
     *out = &p;
@@ -3334,22 +3269,6 @@ int spec_plan(int device, int fs_khz, const SpecPlan **out) {
 }
 
 int spec_frames(const SpecDims &d, int n_samples) { return n_samples < d.L ? 0 : (n_samples - (d.L - d.S)) / d.S; }
-
-// device buffers of one call, freed on every return path
-struct DevBufs {
-    std::vector<void *> p;
-    ~DevBufs() {
-        for (void *q : p) hipFree(q);
-    }
-    template <typename T>
-    int alloc(T **out, size_t count) {
-        void *q = nullptr;
-        HIPCHK(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
-        p.push_back(q);
-        *out = (T *)q;
-        return MLGGD_OK;
-    }
-};
 
 unsigned spec_grid(int frames) { return (unsigned)((frames + SPEC_FRAMES - 1) / SPEC_FRAMES); }
 
@@ -3389,67 +3308,6 @@ int ola_to_host(const SpecPlan *p, const float *blk, int F, int16_t *out, float 
     return MLGGD_OK;
 }
 
-// the engine's idle raw buffer set, grown to `rows` stream rows and n samples, for a frame stream written on the
-// device; raw_set_commit then makes it the current one: the device-side counterpart of mlggd_load_frames (no targets)
-int raw_set_acquire(mlggd_engine *e, int rows, int n, int ctx, mlggd_engine::RawSet **out, int n_nat = 0) {
-    if (!e->copy_stream) {
-        CHK(create_concurrent_stream(e, &e->copy_stream, "upload"));
-        for (auto &r : e->raw) HIPCHK(hipEventCreateWithFlags(&r.last_use, hipEventDisableTiming));
-    }
-    const int fdim = stream_fdim(e, ctx);
-    mlggd_engine::RawSet &r = e->raw[e->raw_cur ^ 1];
-    HIPCHK(hipEventSynchronize(r.last_use));
-    if (e->nat_frames) CHK(raw_set_nat_grow(e, r, (size_t)n_nat, (size_t)n, fdim, e->stream));
-    const size_t need = (size_t)rows + ctx + 8, need_f = need * fdim;  // rows of targ, floats of feat
-    if (need_f > r.feat_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (r.feat) hipFree(r.feat);
-        r.feat = nullptr;
-        r.feat_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.feat, need_f * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.feat, 0, need_f * sizeof(float), e->stream));
-        r.feat_cap = need_f;
-    }
-    if (need > r.raw_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (r.targ) hipFree(r.targ);
-        r.targ = nullptr;
-        r.raw_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.targ, need * e->D * sizeof(float)));
-        HIPCHK(hipMemsetAsync(r.targ, 0, need * e->D * sizeof(float), e->stream));
-        r.raw_cap = need;
-    }
-    const size_t need_s = (size_t)n + e->Bp + 32;
-    if (need_s > r.first_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (r.first) hipFree(r.first);
-        r.first = nullptr;
-        r.first_cap = 0;
-        HIPCHK(hipMalloc((void **)&r.first, need_s * sizeof(int)));
-        HIPCHK(hipMemsetAsync(r.first, 0, need_s * sizeof(int), e->stream));
-        r.first_cap = need_s;
-    }
-    *out = &r;
-    return MLGGD_OK;
-}
-
-void raw_set_commit(mlggd_engine *e, mlggd_engine::RawSet &r, int rows, int n, int ctx) {
-    e->raw_cur ^= 1;
-    e->raw_feat = r.feat;
-    e->raw_targ = r.targ;
-    e->first_frame = r.first;
-    e->nat = r.nat;  // a decoding call then points it at its table of the whole batch
-    e->nat_row = r.nat_row;
-    e->raw_cap = r.raw_cap;
-    e->feat_cap = r.feat_cap;
-    e->first_cap = r.first_cap;
-    e->chunk_frames = n;
-    e->raw_frames = rows;
-    e->indexed = true;
-    e->fdim = stream_fdim(e, ctx);
-    e->toff = 0;
-}
-
 // fea_context frames of D bins, plus the noise row on a NAT engine, must fill layer 0
 int check_input_width(const mlggd_engine *e, int ctx, int D) {
     if (e->nat_frames > 0) {
@@ -3477,13 +3335,13 @@ int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, i
                        const float *inv, const float *nat) {
     const int fdim = stream_fdim(e, ctx), rows = n + ctx - 1;
     mlggd_engine::RawSet *r;
-    CHK(raw_set_acquire(e, rows, n, ctx, &r));
+    CHK(raw_set_acquire(e, rows, n, ctx, 0, false, &r));
     const size_t work = std::max((size_t)rows * fdim, (size_t)n);
     hipLaunchKernelGGL(k_lps_stream, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, lps, F, fdim, a,
-                       rows, (ctx - 1) / 2, mean, inv, r->feat, r->first, n);
+                       rows, (ctx - 1) / 2, mean, inv, r->feat.p, r->first.p, n);
     CHK(launch_check("k_lps_stream"));
-    if (e->nat_frames) HIPCHK(hipMemsetAsync(r->nat_row, 0, (size_t)n * sizeof(int), e->stream));
-    raw_set_commit(e, *r, rows, n, ctx);
+    if (e->nat_frames) HIPCHK(hipMemsetAsync(r->nat_row.p, 0, (size_t)n * sizeof(int), e->stream));
+    raw_set_commit(e, rows, n, ctx, 0);
     if (e->nat_frames) e->nat = nat;
     return MLGGD_OK;
 }
@@ -3515,20 +3373,11 @@ int waves_layout(const SpecDims &d, int n_utts, const int64_t *offsets, int32_t 
     return MLGGD_OK;
 }
 
-// a workspace buffer of at least `bytes` (plus an eighth of headroom when it has to grow, so that batches of slightly
-// different sizes settle after the first few); the old contents are dropped
+// a workspace buffer as `count` elements of T (devbuf_rule::ws_bytes when it has to grow); the old contents are dropped
 template <typename T>
 int ws_grow(mlggd_engine *e, mlggd_engine::WsBuf &b, size_t count, T **out) {
     const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (bytes > b.cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (b.p) hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-        const size_t want = bytes + bytes / 8 + 256;
-        HIPCHK(hipMalloc(&b.p, want));
-        b.cap = want;
-    }
+    HIPCHK(b.grow(bytes, devbuf_rule::ws_bytes(bytes), e->bufs, nullptr, &e->stream));
     *out = (T *)b.p;
     return MLGGD_OK;
 }
@@ -3578,14 +3427,10 @@ int stoi_plan(int device, const StoiPlan **out, const SpecPlan **fft) {
         for (int r : rates) {
             int pp, qq, slot;
             stoi_rule::rate(r, &pp, &qq, &slot);
-            const std::vector<float> h = stoi_rule::filter(pp, qq);
-            HIPCHK(hipMalloc((void **)&p.h[slot], h.size() * sizeof(float)));
-            HIPCHK(hipMemcpy(p.h[slot], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+            CHK(upload_table(stoi_rule::filter(pp, qq), &p.h[slot]));
         }
-        const std::vector<float> w = stoi_rule::window();
         float *dw = nullptr;
-        HIPCHK(hipMalloc((void **)&dw, w.size() * sizeof(float)));
-        HIPCHK(hipMemcpy(dw, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+        CHK(upload_table(stoi_rule::window(), &dw));
         p.win = dw;
     }
     *out = &p;
@@ -3789,7 +3634,7 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
         const int n = std::min(cap, F - a);
         CHK(load_frames_device(e, dl, F, a, n, fea_context, mean, inv, natz));
         CHK(forward_resident(e, n));
-        CHK(launch_synthesis(p, e->chunk_out, mean, inv, X, a, n, blk, st));
+        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, a, n, blk, st));
         HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
     }
     return ola_to_host(p, blk, F, out, out_f32, st);
@@ -3934,19 +3779,19 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
         while (w.h_frame_off[u1 + 1] < a + n) u1++;
         const int rows = n + (u1 - u0 + 1) * (fea_context - 1);
         mlggd_engine::RawSet *r;
-        CHK(raw_set_acquire(e, rows, n, fea_context, &r));
+        CHK(raw_set_acquire(e, rows, n, fea_context, 0, false, &r));
         hipLaunchKernelGGL(k_lps_stream_seg, dim3((unsigned)rows), dim3(256), 0, st, dl, d_foff, d_utt, n_utts, d.D, a, n,
-                           u0, u1, fea_context, mean, inv, r->feat, r->first);
+                           u0, u1, fea_context, mean, inv, r->feat.p, r->first.p);
         CHK(launch_check("k_lps_stream_seg"));
         if (e->nat_frames) {
             hipLaunchKernelGGL(k_nat_rows_seg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int *)d_foff,
-                               (const int *)d_utt, n_utts, a, n, r->nat_row);
+                               (const int *)d_utt, n_utts, a, n, r->nat_row.p);
             CHK(launch_check("k_nat_rows_seg"));
         }
-        raw_set_commit(e, *r, rows, n, fea_context);
+        raw_set_commit(e, rows, n, fea_context, 0);
         if (e->nat_frames) e->nat = natz;
         CHK(forward_resident(e, n));
-        CHK(launch_synthesis(p, e->chunk_out, mean, inv, X, a, n, blk, st, den));
+        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, a, n, blk, st, den));
         HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
     }
     hipLaunchKernelGGL(k_ola_seg, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, blk, d_foff, d_ooff, n_utts,
@@ -4132,12 +3977,13 @@ struct mlggd_live {
     SpecDims d;
     std::vector<long long> had;  // samples each session has received since it began
     int cur = 0;                 // the copy of the state that is current
-    int16_t *tail[2] = {nullptr, nullptr};
-    float *lps[2] = {nullptr, nullptr}, *blk[2] = {nullptr, nullptr}, *norm = nullptr;
-    float2 *X[2] = {nullptr, nullptr};
+    DevBuf<int16_t> tail[2];
+    DevBuf<float> lps[2], blk[2], norm;
+    DevBuf<float2> X[2];
     // the tables of one push, one block of pinned host memory and its device twin: win_off [NS + 1], out_off [NS + 1],
     // a_woff [NS] (long long), sess [NS], dk_off [NS + 1], dk_slot [NS], a_foff [NS + 1] (int)
-    char *h_tab = nullptr, *d_tab = nullptr;
+    char *h_tab = nullptr;
+    DevBuf<char> d_tab;
     size_t tab_bytes = 0;
     mlggd_engine::WsBuf in, win, lps_new, X_new, X_dec, blk_new, out_i, out_f;  // per push; they only grow
     std::vector<live_rule::Step> steps;
@@ -4169,18 +4015,8 @@ size_t live_tables(char *base, int NS, LiveTables *t) {
 }
 
 void live_free(mlggd_live *s) {
-    for (int c = 0; c < 2; c++) {
-        if (s->tail[c]) hipFree(s->tail[c]);
-        if (s->lps[c]) hipFree(s->lps[c]);
-        if (s->X[c]) hipFree(s->X[c]);
-        if (s->blk[c]) hipFree(s->blk[c]);
-    }
-    if (s->norm) hipFree(s->norm);
-    if (s->d_tab) hipFree(s->d_tab);
     if (s->h_tab) hipHostFree(s->h_tab);
-    for (mlggd_engine::WsBuf *b : {&s->in, &s->win, &s->lps_new, &s->X_new, &s->X_dec, &s->blk_new, &s->out_i, &s->out_f})
-        if (b->p) hipFree(b->p);
-    delete s;
+    delete s;  // the device buffers free themselves; the caller has synchronised the engine's stream
 }
 
 int live_alloc(mlggd_live *s, const float *norm_mean, const float *norm_inv_std) {
@@ -4190,22 +4026,18 @@ int live_alloc(mlggd_live *s, const float *norm_mean, const float *norm_inv_std)
     const size_t n_lps = std::max<size_t>(1, NS * (s->ctx - 1) * d.D), n_X = std::max<size_t>(1, NS * s->half * d.D);
     const size_t n_blk = NS * s->K * d.L, n_tail = NS * d.L;
     for (int c = 0; c < 2; c++) {
-        HIPCHK(hipMalloc((void **)&s->tail[c], n_tail * sizeof(int16_t)));
-        HIPCHK(hipMalloc((void **)&s->lps[c], n_lps * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&s->X[c], n_X * sizeof(float2)));
-        HIPCHK(hipMalloc((void **)&s->blk[c], n_blk * sizeof(float)));
-        HIPCHK(hipMemsetAsync(s->tail[c], 0, n_tail * sizeof(int16_t), e->stream));
-        HIPCHK(hipMemsetAsync(s->lps[c], 0, n_lps * sizeof(float), e->stream));
-        HIPCHK(hipMemsetAsync(s->X[c], 0, n_X * sizeof(float2), e->stream));
-        HIPCHK(hipMemsetAsync(s->blk[c], 0, n_blk * sizeof(float), e->stream));
+        HIPCHK(s->tail[c].grow(n_tail, n_tail, e->bufs, &e->stream, nullptr));
+        HIPCHK(s->lps[c].grow(n_lps, n_lps, e->bufs, &e->stream, nullptr));
+        HIPCHK(s->X[c].grow(n_X, n_X, e->bufs, &e->stream, nullptr));
+        HIPCHK(s->blk[c].grow(n_blk, n_blk, e->bufs, &e->stream, nullptr));
     }
-    HIPCHK(hipMalloc((void **)&s->norm, (size_t)2 * d.D * sizeof(float)));
-    HIPCHK(hipMemcpyAsync(s->norm, norm_mean, d.D * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipMemcpyAsync(s->norm + d.D, norm_inv_std, d.D * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(s->norm.grow((size_t)2 * d.D, (size_t)2 * d.D, e->bufs, nullptr, nullptr));
+    HIPCHK(hipMemcpyAsync(s->norm.p, norm_mean, d.D * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(s->norm.p + d.D, norm_inv_std, d.D * sizeof(float), hipMemcpyHostToDevice, e->stream));
     LiveTables t;
     s->tab_bytes = live_tables(nullptr, s->NS, &t);
     HIPCHK(hipHostMalloc((void **)&s->h_tab, s->tab_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void **)&s->d_tab, s->tab_bytes));
+    HIPCHK(s->d_tab.grow(s->tab_bytes, s->tab_bytes, e->bufs, nullptr, nullptr));
     memset(s->h_tab, 0, s->tab_bytes);
     HIPCHK(hipStreamSynchronize(e->stream));  // the norm vectors are the caller's
     return MLGGD_OK;
@@ -4311,7 +4143,7 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
         return fail(MLGGD_ERR_ARG, "a push of %lld new frames over %d sessions is too large", std::max(NF, ND), NS);
     LiveTables h, dv;
     live_tables(s->h_tab, NS, &h);
-    live_tables(s->d_tab, NS, &dv);
+    live_tables(s->d_tab.p, NS, &dv);
     int n_act = 0, n_dk = 0;
     h.win_off[0] = h.out_off[0] = 0;
     h.dk_off[0] = h.a_foff[0] = 0;
@@ -4356,13 +4188,13 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
     CHK(ws_grow(e, s->out_i, (size_t)n_emit, &oi));
     if (out_f32) CHK(ws_grow(e, s->out_f, (size_t)n_emit, &of));
     const int c0 = s->cur, c1 = s->cur ^ 1;
-    const float *mean = s->norm, *inv = s->norm + d.D;
+    const float *mean = s->norm.p, *inv = s->norm.p + d.D;
     if (n_in > 0)
         HIPCHK(hipMemcpyAsync(d_in, samples + offsets[0], (size_t)n_in * sizeof(int16_t), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(s->d_tab, s->h_tab, s->tab_bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_tab.p, s->h_tab, s->tab_bytes, hipMemcpyHostToDevice, st));
     if (n_win > 0) {
-        hipLaunchKernelGGL(k_live_window, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, d_in, s->tail[c0],
-                           s->tail[c1], dv.sess, dv.win_off, NS, d.L, d_win, n_win);
+        hipLaunchKernelGGL(k_live_window, dim3((unsigned)((n_win + 255) / 256)), dim3(256), 0, st, d_in, s->tail[c0].p,
+                           s->tail[c1].p, dv.sess, dv.win_off, NS, d.L, d_win, n_win);
         CHK(launch_check("k_live_window"));
     }
     if (NF > 0) {
@@ -4372,7 +4204,7 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
         CHK(launch_check("k_lps_analysis_seg"));
     }
     if (ND > 0) {
-        hipLaunchKernelGGL(k_live_gather_x, dim3((unsigned)ND), dim3(256), 0, st, s->X[c0], X_new, dv.sess, dv.dk_off,
+        hipLaunchKernelGGL(k_live_gather_x, dim3((unsigned)ND), dim3(256), 0, st, s->X[c0].p, X_new, dv.sess, dv.dk_off,
                            dv.dk_slot, n_dk, d.D, half, X_dec);
         CHK(launch_check("k_live_gather_x"));
     }
@@ -4384,24 +4216,24 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
         while (h.dk_off[k1 + 1] < a + n) k1++;
         const int rows = n + (k1 - k0 + 1) * (ctx - 1);
         mlggd_engine::RawSet *r;
-        CHK(raw_set_acquire(e, rows, n, ctx, &r));
-        hipLaunchKernelGGL(k_live_stream, dim3((unsigned)rows), dim3(256), 0, st, s->lps[c0], lps_new, dv.sess, dv.dk_off,
-                           dv.dk_slot, n_dk, d.D, a, n, k0, k1, ctx, mean, inv, r->feat, r->first);
+        CHK(raw_set_acquire(e, rows, n, ctx, 0, false, &r));
+        hipLaunchKernelGGL(k_live_stream, dim3((unsigned)rows), dim3(256), 0, st, s->lps[c0].p, lps_new, dv.sess, dv.dk_off,
+                           dv.dk_slot, n_dk, d.D, a, n, k0, k1, ctx, mean, inv, r->feat.p, r->first.p);
         CHK(launch_check("k_live_stream"));
-        raw_set_commit(e, *r, rows, n, ctx);
+        raw_set_commit(e, rows, n, ctx, 0);
         CHK(forward_resident(e, n));
-        CHK(launch_synthesis(p, e->chunk_out, mean, inv, X_dec, a, n, blk_new, st));
+        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X_dec, a, n, blk_new, st));
         HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
     }
     if (n_emit > 0) {
-        hipLaunchKernelGGL(k_live_ola, dim3((unsigned)((n_emit + 255) / 256)), dim3(256), 0, st, s->blk[c0], blk_new,
+        hipLaunchKernelGGL(k_live_ola, dim3((unsigned)((n_emit + 255) / 256)), dim3(256), 0, st, s->blk[c0].p, blk_new,
                            dv.sess, dv.out_off, NS, K, p->d, p->win, of, oi, n_emit);
         CHK(launch_check("k_live_ola"));
         HIPCHK(hipMemcpyAsync(out, oi, (size_t)n_emit * sizeof(int16_t), hipMemcpyDeviceToHost, st));
         if (out_f32) HIPCHK(hipMemcpyAsync(out_f32, of, (size_t)n_emit * sizeof(float), hipMemcpyDeviceToHost, st));
     }
     hipLaunchKernelGGL(k_live_carry, dim3((unsigned)(NS * (ctx - 1 + half + K))), dim3(256), 0, st, dv.sess, ctx, K, d.D,
-                       d.L, s->lps[c0], lps_new, s->lps[c1], s->X[c0], X_new, s->X[c1], s->blk[c0], blk_new, s->blk[c1]);
+                       d.L, s->lps[c0].p, lps_new, s->lps[c1].p, s->X[c0].p, X_new, s->X[c1].p, s->blk[c0].p, blk_new, s->blk[c1].p);
     CHK(launch_check("k_live_carry"));
     HIPCHK(hipStreamSynchronize(st));
     s->cur = c1;
@@ -4561,14 +4393,14 @@ int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, cons
     CHK(ws_grow(e, t.frame_off, (size_t)nc + 1, &d_foff));
     CHK(ws_grow(e, t.wave_off, (size_t)nc + 1, &d_woff));
     mlggd_engine::RawSet *r;
-    CHK(raw_set_acquire(e, FT, n_samples, ctx, &r, nc));
+    CHK(raw_set_acquire(e, FT, n_samples, ctx, nc, false, &r));
     t.h_norm.resize((size_t)2 * d.D);
     memcpy(t.h_norm.data(), mean, d.D * sizeof(float));
     memcpy(t.h_norm.data() + d.D, inv, d.D * sizeof(float));
     HIPCHK(hipMemcpyAsync(norm, t.h_norm.data(), t.h_norm.size() * sizeof(float), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_foff, t.h_frame_off.data(), ((size_t)nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_woff, t.h_wave_off.data(), ((size_t)nc + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(r->first, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(r->first.p, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
     for (int k = 0; k < 2; k++) {  // the spectrum itself is not wanted here: X = nullptr
         hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, k ? d_clean : d_noisy,
                            (const long long *)d_woff, (const int *)d_foff, (const int *)nullptr, nc, FT, p->d, p->win, p->tw,
@@ -4576,17 +4408,16 @@ int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, cons
         CHK(launch_check("k_lps_analysis_seg"));
     }
     hipLaunchKernelGGL(k_lps_norm_pair, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN, (const float *)lpsC,
-                       d.D, (const float *)norm, (const float *)(norm + d.D), r->feat, r->targ);
+                       d.D, (const float *)norm, (const float *)(norm + d.D), r->feat.p, r->targ.p);
     CHK(launch_check("k_lps_norm_pair"));
     if (e->nat_frames) {  // the noise rows from the normalised noisy rows, over the utterances that have frames
-        CHK(launch_nat_estimate(e, r->feat, d_foff, nc, d.D, nullptr, nullptr, r->nat));
+        CHK(launch_nat_estimate(e, r->feat.p, d_foff, nc, d.D, nullptr, nullptr, r->nat.p));
         t.h_nat_row.resize((size_t)n_samples);
         for (int s = 0; s < n_samples; s++)
             t.h_nat_row[s] = nat_rule::utt_of_frame(nc, t.h_frame_off.data(), first_frame[s]);
-        HIPCHK(hipMemcpyAsync(r->nat_row, t.h_nat_row.data(), (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(r->nat_row.p, t.h_nat_row.data(), (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
     }
-    raw_set_commit(e, *r, FT, n_samples, ctx);
-    e->toff = targ_offset;
+    raw_set_commit(e, FT, n_samples, ctx, targ_offset);
     return MLGGD_OK;
 }
 
@@ -4783,7 +4614,7 @@ int mlggd_cv_all_waves(mlggd_handle e, int fs_khz, int fea_context, const float 
     } else {  // the host-order sums read the targets on the host: the normalised clean rows come back once
         const int D = e->D;
         std::vector<float> targ((size_t)frame_off.back() * D);
-        HIPCHK(hipMemcpyAsync(targ.data(), e->raw_targ, targ.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(targ.data(), e->raw[e->raw_cur].targ.p, targ.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         rc = cv_accumulate(
             e, n_samples, [&](int i) { return targ.data() + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr,
@@ -4802,9 +4633,7 @@ int mlggd_set_noise(mlggd_handle e, int64_t n_noise, const int16_t *noise) {
     HIPCHK(hipStreamSynchronize(e->stream));
     mlggd_engine::TrainWs &t = e->tw;
     if (n_noise == 0 || !noise) {
-        if (t.noise.p) hipFree(t.noise.p);
-        t.noise.p = nullptr;
-        t.noise.cap = 0;
+        t.noise.release();
         t.n_noise = 0;
         return MLGGD_OK;
     }

@@ -3,7 +3,8 @@ of the decoders.  An engine keeps two alternating raw buffer sets (feat, targ, f
 and nat_row) and grows them only when a capacity is exceeded.  A stream row is layersizes[0] / fea_context floats wide
 (/ (fea_context + 1) on a NAT engine), so a capacity counted in ROWS says nothing about the floats a set holds: a call
 with a smaller context and no more rows than the set was grown for writes past the allocation.  The sets count feat
-and nat in floats (csrc/engine.hip: load_frames_impl, raw_set_acquire, raw_set_nat_grow); these tests hold them to it.
+and nat in floats (one place: raw_set_acquire in csrc/engine.hip, by the rule of csrc/devbuf_rule.h); these tests hold
+them to it.
 
 The principle throughout: a long-lived engine goes through a sequence of calls, and after every call its result equals,
 in every bit, that of a fresh engine given only that call (same weights): outputs, CV sums, weights, biases and
@@ -13,7 +14,10 @@ decoded waves to the float64 chain of tests/spec64.py.
 
 The precondition (pure Python, checked when this file is imported and by a test that needs no device): every sequence
 below would have overrun a set whose capacity is counted in rows.  It is what keeps these tests from passing for the
-wrong reason."""
+wrong reason.
+
+The last section counts device allocations (BPGpu.buffer_stats, mlggd_debug_buffers): "grows only when a capacity is
+exceeded" is observed, with the outputs still those of a fresh engine."""
 import numpy as np
 import pytest
 
@@ -404,4 +408,128 @@ def test_decoding_after_a_narrow_stream(pkg, kind):
         st = state(ref)
         ref.close()
         same_bits(state(long), st, "ctx %d after decoding" % s[3])
+    long.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# growth is counted: a call that exceeds no capacity makes no device allocation
+class Growth:
+    """the engine's buffer counter from call to call: bytes held never fall while nothing is closed"""
+
+    def __init__(self, eng):
+        self.eng = eng
+        self.allocs, self.bytes = eng.buffer_stats()
+        assert self.allocs >= 0 and self.bytes >= 0
+
+    def added(self):
+        """device allocations since the last look"""
+        n, b = self.eng.buffer_stats()
+        d, self.allocs = n - self.allocs, n
+        assert d >= 0 and b >= self.bytes, (d, b, self.bytes)
+        self.bytes = b
+        return d
+
+
+def fresh_forward(pkg, kind, ch):
+    ref = engine(pkg, kind, alpha=ALPHA)
+    want = ch.forward(ref)
+    ref.close()
+    return want
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["plain", "nat"])
+def test_frames_allocate_only_when_a_capacity_is_exceeded(pkg, kind):
+    """the first two calls of the sequence warm the two alternating sets (and chunk_out); a third identical call and a
+    shorter stream of the same context allocate nothing; the sequence's first wider row (context 1: 48 or 24 floats a
+    row where the sets hold rows of 8) regrows its set.  Every output is a fresh engine's."""
+    nat = kind == "nat"
+    seq = chunks(kind)
+    first, wide = seq[0], seq[2]
+    assert wide.fdim > first.fdim and NFR * wide.fdim > (NFR + first.ctx + 8) * first.fdim      # SEQUENCES[kind][2]
+    short = Chunk(first.ctx, 90, nat, nfr=44, frames=[23, 21] if nat else None)
+    want = fresh_forward(pkg, kind, first)
+    long = engine(pkg, kind, alpha=ALPHA)
+    g = Growth(long)
+    grown = []
+    for _ in range(3):
+        assert first.forward(long).tobytes() == want.tobytes()
+        grown.append(g.added())
+    print("%s: allocations of three identical calls %s, %d bytes held" % (kind, grown, g.bytes))
+    assert grown[0] >= 1 and grown[1] >= 1 and grown[2] == 0, grown
+    assert short.forward(long).tobytes() == fresh_forward(pkg, kind, short).tobytes()
+    assert g.added() == 0
+    assert wide.forward(long).tobytes() == fresh_forward(pkg, kind, wide).tobytes()
+    assert g.added() >= 1
+    long.close()
+
+
+@gpu
+@pytest.mark.parametrize("kind", ["decode", "decode_nat"])
+def test_decoding_again_allocates_nothing(pkg, kind):
+    """enhance_waves on the batch (the chunk capacity splits it: the first call warms both sets), twice more, then its
+    first utterance alone through both decoders: no allocation after the first call, every wave a fresh engine's"""
+    dc = Decode(kind)
+    ref = dc.engine(pkg)
+    r_one, r_many = dc.decode(ref)
+    ref.close()
+    long = dc.engine(pkg)
+    g = Growth(long)
+    grown = []
+    for _ in range(3):
+        many = long.enhance_waves(dc.waves, dc.mean, dc.inv, fs_khz=FS, fea_context=DCTX, return_f32=True, return_lps=True)
+        for k in range(3):
+            same_bits(many[k], r_many[k], "enhance_waves[%d]" % k)
+        grown.append(g.added())
+    print("%s: allocations of three identical calls %s, %d bytes held" % (kind, grown, g.bytes))
+    assert grown[0] >= 1 and grown[1:] == [0, 0], grown
+    alone = long.enhance_waves(dc.waves[:1], dc.mean, dc.inv, fs_khz=FS, fea_context=DCTX, return_f32=True, return_lps=True)
+    for k in range(3):
+        same_bits(alone[k], r_many[k][:1], "alone[%d]" % k)
+    assert g.added() == 0
+    # (enhance_wave borrows the raw sets and chunk_out; its other buffers live for the call and are not counted)
+    same_bits(long.enhance_wave(dc.waves[0], dc.mean, dc.inv, fea_context=DCTX, fs_khz=FS, return_float=True), r_one,
+              "enhance_wave")
+    assert g.added() == 0
+    long.close()
+
+
+LIVE_K = 103                                             # a block of 128 (K + 1) samples: see the test below
+
+
+@gpu
+def test_a_second_live_push_allocates_nothing(pkg):
+    """Two sessions, two pushes of 128 (K + 1) = 13312 samples each, the second ending both.  At 8 kHz (frames of 256
+    samples every 128, 3 frames of look-ahead) the first push decodes K - 3 = 100 frames a session, the second K + 4 =
+    107: by the chunk capacity of 64 that is four chunks either time, the one chunk that touches both sessions (76
+    stream rows, the most a chunk can have) is the second either time and, four being even, lands on the same raw set;
+    the group's per-push workspaces grow by less than their eighth of headroom.  So the second push allocates nothing.
+    The group's buffers are counted ON THE ENGINE (mlggd_debug_buffers): the allocation count stays where it is when
+    the group closes, the bytes fall by what the group held.  What the sessions emitted is enhance_wave of the whole
+    recording on a fresh engine."""
+    dc = Decode("decode")
+    n = 128 * (LIVE_K + 1)
+    waves = [spec64.synth_speech(2 * n, FS, seed=40 + u) for u in range(2)]
+    ref = dc.engine(pkg)
+    want = [ref.enhance_wave(w, dc.mean, dc.inv, fea_context=DCTX, fs_khz=FS) for w in waves]
+    ref.close()
+    long = dc.engine(pkg)
+    g = Growth(long)
+    before = g.bytes
+    grp = long.live(dc.mean, dc.inv, 2, fs_khz=FS, fea_context=DCTX)
+    opened = g.added()
+    out1 = grp.push([w[:n] for w in waves])
+    pushed = g.added()
+    assert [o.size for o in out1] == [128 * (LIVE_K - 3)] * 2
+    out2 = grp.push([w[n:] for w in waves], end=[True, True])
+    again = g.added()
+    print("live: allocations at open %d, first push %d, second push %d, %d bytes held" % (opened, pushed, again, g.bytes))
+    assert opened >= 1 and pushed >= 1 and again == 0
+    for u in range(2):
+        got = np.concatenate([out1[u], out2[u]])
+        assert got.dtype == want[u].dtype and got.tobytes() == want[u].tobytes(), u
+    held, count = g.bytes, g.allocs
+    grp.close()
+    n_after, b_after = long.buffer_stats()
+    assert n_after == count and before < b_after < held, (n_after, count, before, b_after, held)
     long.close()
