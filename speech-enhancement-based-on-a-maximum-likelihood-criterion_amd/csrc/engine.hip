@@ -55,6 +55,10 @@ static int fail(int code, const char *fmt, ...) {
         int _rc = (expr);         \
         if (_rc != MLGGD_OK) return _rc; \
     } while (0)
+// a check of a *_rule.h header (host only, no fail()): 0, or -1 with its message written to RULE_MSG
+static thread_local char g_rule_msg[512];
+#define RULE_MSG g_rule_msg, sizeof(g_rule_msg)
+#define RULE(expr) CHK((expr) != 0 ? fail(MLGGD_ERR_ARG, "%s", g_rule_msg) : MLGGD_OK)
 
 static inline int ceil32(int x) { return (x + 31) & ~31; }
 
@@ -377,6 +381,13 @@ struct DevBufs {
         HIPCHK(hipMalloc(&q, (count ? count : 1) * sizeof(T)));
         p.push_back(q);
         *out = (T *)q;
+        return MLGGD_OK;
+    }
+    // ... and filled from host memory by a blocking copy on the null stream (the one-shot device entries)
+    template <typename T>
+    int upload(T **out, const T *host, size_t count) {
+        CHK(alloc(out, count));
+        if (count) HIPCHK(hipMemcpy(*out, host, count * sizeof(T), hipMemcpyHostToDevice));
         return MLGGD_OK;
     }
 };
@@ -1990,9 +2001,14 @@ static int ensure_chunk(mlggd_engine *e, int n_frames) {
     return MLGGD_OK;
 }
 
+// the most samples one chunk may hold
+static int chunk_cap(const mlggd_engine *e) {
+    return e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+}
+
 static int check_frames(mlggd_engine *e, int n_frames) {
     if (n_frames < 0) return fail(MLGGD_ERR_ARG, "n_frames %d < 0", n_frames);
-    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    const int cap = chunk_cap(e);
     if (n_frames > cap) return fail(MLGGD_ERR_ARG, "n_frames %d exceeds the chunk capacity %d", n_frames, cap);
     return MLGGD_OK;
 }
@@ -2260,15 +2276,20 @@ static int forward_resident(mlggd_engine *e, int n_frames) {
     return MLGGD_OK;
 }
 
+// ... and out [n][D] on the host when it returns (n = 0: nothing to do)
+static int forward_to_host(mlggd_engine *e, int n, float *out) {
+    if (n == 0) return MLGGD_OK;
+    CHK(forward_resident(e, n));
+    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n * e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
 int mlggd_forward(mlggd_handle e, int n_frames, const float *in, float *out) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     if (n_frames > 0 && (!in || !out)) return fail(MLGGD_ERR_ARG, "in/out is NULL");
     CHK(mlggd_load_chunk(e, n_frames, in, nullptr));
-    if (n_frames == 0) return MLGGD_OK;
-    CHK(forward_resident(e, n_frames));
-    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n_frames * e->D * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return MLGGD_OK;
+    return forward_to_host(e, n_frames, out);
 }
 
 // BP_GPU::Gamma, BP_GPU.cu:593-640: 10th-order polynomial on (2,3] in double powers, each
@@ -2448,20 +2469,25 @@ int mlggd_cv_all(mlggd_handle e, int n, const float *in, const float *targ, floa
     return cv_metrics(e, n, in, targ, sqerr, abserr, (e->cfg.MLflag == 1) ? loglik : nullptr);
 }
 
+// the three numbers of the indexed chunk that is current: the sums formed on the device read the set's own targets,
+// the host-order sums read host_targ [.][D], in both cases row first_frame[i] + targ_offset for sample i
+static int cv_indexed(mlggd_engine *e, int n_samples, const int32_t *first_frame, int targ_offset, const float *host_targ,
+                      float *sqerr, float *abserr, float *loglik) {
+    float *ll = (e->cfg.MLflag == 1) ? loglik : nullptr;
+    if (e->cv_device) return cv_device_reduce(e, n_samples, sqerr, abserr, ll);
+    const int D = e->D;
+    return cv_accumulate(
+        e, n_samples, [&](int i) { return host_targ + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr, ll);
+}
+
 int mlggd_cv_all_frames_nat(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
                             int n_samples, const int32_t *first_frame, int targ_offset, int n_nat, const float *nat,
                             const int32_t *nat_row, float *sqerr, float *abserr, float *loglik) {
     CHK(nat_entry_state(e, "mlggd_cv_all_frames_nat"));
     if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
-    if (e->cv_device) {
-        CHK(load_frames_impl(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, n_nat, nat, nat_row));
-        return cv_device_reduce(e, n_samples, sqerr, abserr, (e->cfg.MLflag == 1) ? loglik : nullptr);
-    }
-    CHK(load_frames_impl(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, targ_offset, n_nat, nat, nat_row));
-    const int D = e->D;
-    return cv_accumulate(
-        e, n_samples, [&](int i) { return targ + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr,
-        (e->cfg.MLflag == 1) ? loglik : nullptr);
+    CHK(load_frames_impl(e, n_frames, fea_context, feat, e->cv_device ? targ : nullptr, n_samples, first_frame,
+                         targ_offset, n_nat, nat, nat_row));
+    return cv_indexed(e, n_samples, first_frame, targ_offset, targ, sqerr, abserr, loglik);
 }
 
 int mlggd_forward_frames_nat(mlggd_handle e, int n_frames, int fea_context, const float *feat, int n_samples,
@@ -2470,11 +2496,7 @@ int mlggd_forward_frames_nat(mlggd_handle e, int n_frames, int fea_context, cons
     CHK(nat_entry_state(e, "mlggd_forward_frames_nat"));
     if (n_samples > 0 && !out) return fail(MLGGD_ERR_ARG, "out is NULL");
     CHK(load_frames_impl(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, 0, n_nat, nat, nat_row));
-    if (n_samples == 0) return MLGGD_OK;
-    CHK(forward_resident(e, n_samples));
-    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return MLGGD_OK;
+    return forward_to_host(e, n_samples, out);
 }
 
 // Host only, no device (nat_rule.h): the noise rows of n_utts utterances from their normalised rows, and the utterance
@@ -2524,15 +2546,9 @@ int mlggd_cv_all_frames(mlggd_handle e, int n_frames, int fea_context, const flo
                         float *loglik) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
-    if (e->cv_device) {
-        CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
-        return cv_device_reduce(e, n_samples, sqerr, abserr, (e->cfg.MLflag == 1) ? loglik : nullptr);
-    }
-    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, targ_offset));
-    const int D = e->D;
-    return cv_accumulate(
-        e, n_samples, [&](int i) { return targ + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr,
-        (e->cfg.MLflag == 1) ? loglik : nullptr);
+    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, e->cv_device ? targ : nullptr, n_samples, first_frame,
+                          targ_offset));
+    return cv_indexed(e, n_samples, first_frame, targ_offset, targ, sqerr, abserr, loglik);
 }
 
 int mlggd_forward_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, int n_samples,
@@ -2540,11 +2556,7 @@ int mlggd_forward_frames(mlggd_handle e, int n_frames, int fea_context, const fl
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     if (n_samples > 0 && !out) return fail(MLGGD_ERR_ARG, "out is NULL");
     CHK(mlggd_load_frames(e, n_frames, fea_context, feat, nullptr, n_samples, first_frame, 0));
-    if (n_samples == 0) return MLGGD_OK;
-    CHK(forward_resident(e, n_samples));
-    HIPCHK(hipMemcpyAsync(out, e->chunk_out.p, (size_t)n_samples * e->D * 4, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return MLGGD_OK;
+    return forward_to_host(e, n_samples, out);
 }
 
 // ------------------------------------------------------------------ error model (errstats.hip.h)
@@ -3209,17 +3221,11 @@ constexpr int SPEC_MAX_DEVICES = 64;
 std::mutex g_spec_mu;
 SpecPlan g_spec[SPEC_MAX_DEVICES][3];
 
-int spec_dims(int fs_khz, SpecDims *d, int *slot) {
-    int L, S, N;
-    switch (fs_khz) {  // Wav2LogSpec_be.c / LogSpec2Wav.c #defines
-        case 8: L = 256, S = 128, N = 256, *slot = 0; break;
-        case 11: L = 256, S = 110, N = 256, *slot = 1; break;
-        case 16: L = 512, S = 256, N = 512, *slot = 2; break;
-        default: return fail(MLGGD_ERR_ARG, "fs_khz %d: must be 8, 11 or 16", fs_khz);
-    }
-    d->L = L, d->S = S, d->N = N, d->M = N / 2, d->D = N / 2 + 1;
-    d->logM = 0;
-    while ((1 << d->logM) < d->M) d->logM++;
+// floor of the power spectrum before its log, and of exp(lps) on the way back
+const float kSpecFloor = (float)exp(-50.0);
+
+int spec_dims(int fs_khz, SpecDims *d, int *slot = nullptr) {
+    if (!spec_rule::rate(fs_khz, d, slot)) return fail(MLGGD_ERR_ARG, "fs_khz %d: must be 8, 11 or 16", fs_khz);
     return MLGGD_OK;
 }
 
@@ -3268,34 +3274,47 @@ int spec_plan(int device, int fs_khz, const SpecPlan **out) {
     return MLGGD_OK;
 }
 
-int spec_frames(const SpecDims &d, int n_samples) { return n_samples < d.L ? 0 : (n_samples - (d.L - d.S)) / d.S; }
+// ... after making that device the current one
+int spec_plan_on(int device, int fs_khz, const SpecPlan **out) {
+    HIPCHK(hipSetDevice(device));
+    return spec_plan(device, fs_khz, out);
+}
 
 unsigned spec_grid(int frames) { return (unsigned)((frames + SPEC_FRAMES - 1) / SPEC_FRAMES); }
 
 int launch_analysis(const SpecPlan *p, const int16_t *wave, int F, float *lps, float2 *X, hipStream_t st) {
     if (F == 0) return MLGGD_OK;
     hipLaunchKernelGGL(k_lps_analysis, dim3(spec_grid(F)), dim3(64 * SPEC_FRAMES), 0, st, wave, F, p->d, p->win, p->tw,
-                       p->tws, (float)exp(-50.0), lps, X);
+                       p->tws, kSpecFloor, lps, X);
     return launch_check("k_lps_analysis");
+}
+
+// the same over FT >= 1 packed frames of n utterances that all have frames: wave_off / frame_off [n + 1] and utt_of
+// [FT] (or NULL: the kernel searches frame_off) are on the device; lps or X may be NULL
+int launch_analysis_seg(const SpecPlan *p, const int16_t *wave, const long long *wave_off, const int *frame_off,
+                        const int *utt_of, int n, int FT, float *lps, float2 *X, hipStream_t st) {
+    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, wave, wave_off, frame_off,
+                       utt_of, n, FT, p->d, p->win, p->tw, p->tws, kSpecFloor, lps, X);
+    return launch_check("k_lps_analysis_seg");
 }
 
 int launch_synthesis(const SpecPlan *p, const float *src, const float *mean, const float *inv, const float2 *X, int t0,
                      int nf, float *blk, hipStream_t st, float *lps_den = nullptr) {
     if (nf == 0) return MLGGD_OK;
     hipLaunchKernelGGL(k_lps_synthesis, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, X, t0, nf,
-                       p->d, p->win, p->tw, p->tws, (float)exp(-50.0), blk, lps_den);
+                       p->d, p->win, p->tw, p->tws, kSpecFloor, blk, lps_den);
     return launch_check("k_lps_synthesis");
 }
 
 int launch_ola(const SpecPlan *p, const float *blk, int F, float *out_f, int16_t *out_i, hipStream_t st) {
-    const int n_out = F * p->d.S + p->d.L - p->d.S;
+    const int n_out = (int)spec_rule::out_samples(p->d, F);
     hipLaunchKernelGGL(k_ola, dim3((n_out + 255) / 256), dim3(256), 0, st, blk, F, p->d, p->win, out_f, out_i, n_out);
     return launch_check("k_ola");
 }
 
 // out (int16) and out_f32 (optional) of n_out samples from the time blocks of F frames
 int ola_to_host(const SpecPlan *p, const float *blk, int F, int16_t *out, float *out_f32, hipStream_t st) {
-    const size_t n_out = (size_t)F * p->d.S + p->d.L - p->d.S;
+    const size_t n_out = (size_t)spec_rule::out_samples(p->d, F);
     DevBufs b;
     float *of = nullptr;
     int16_t *oi = nullptr;
@@ -3308,19 +3327,6 @@ int ola_to_host(const SpecPlan *p, const float *blk, int F, int16_t *out, float 
     return MLGGD_OK;
 }
 
-// fea_context frames of D bins, plus the noise row on a NAT engine, must fill layer 0
-int check_input_width(const mlggd_engine *e, int ctx, int D) {
-    if (e->nat_frames > 0) {
-        if (((long long)ctx + 1) * D != e->K0)
-            return fail(MLGGD_ERR_ARG, "(fea_context %d + 1) x %d bins != layersizes[0] = %d (nat_frames = %d)", ctx, D,
-                        e->K0, e->nat_frames);
-        return MLGGD_OK;
-    }
-    if ((long long)ctx * D != e->K0)
-        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", ctx, D, e->K0);
-    return MLGGD_OK;
-}
-
 int launch_nat_estimate(const mlggd_engine *e, const float *rows, const int *d_frame_off, int n_utts, int D,
                         const float *mean, const float *inv, float *out) {
     const size_t work = (size_t)n_utts * D;
@@ -3329,47 +3335,58 @@ int launch_nat_estimate(const mlggd_engine *e, const float *rows, const int *d_f
     return launch_check("k_nat_estimate");
 }
 
-// the frame stream of output frames [a, a + n) of an F-frame utterance, written by k_lps_stream (first_frame[i] = i)
-// (nat: on a NAT engine the one noise row of the utterance, which every sample takes)
-int load_frames_device(mlggd_engine *e, const float *lps, int F, int a, int n, int ctx, const float *mean,
-                       const float *inv, const float *nat) {
-    const int fdim = stream_fdim(e, ctx), rows = n + ctx - 1;
+// What a wave entry asks of its engine: the rate exists (*d receives its dimensions), fea_context is odd (decoding: a
+// frame sits in the middle of its window) or at least 1 (loading), fea_context frames of D bins, plus the noise row on
+// a NAT engine, fill layer 0 and the net puts out one frame of D bins.
+int check_wave_engine(const mlggd_engine *e, int fs_khz, int ctx, bool decoding, SpecDims *d) {
+    CHK(spec_dims(fs_khz, d));
+    if (decoding && (ctx < 1 || ctx % 2 == 0)) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", ctx);
+    if (ctx < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", ctx);
+    if (e->nat_frames > 0 && ((long long)ctx + 1) * d->D != e->K0)
+        return fail(MLGGD_ERR_ARG, "(fea_context %d + 1) x %d bins != layersizes[0] = %d (nat_frames = %d)", ctx, d->D,
+                    e->K0, e->nat_frames);
+    if (e->nat_frames == 0 && (long long)ctx * d->D != e->K0)
+        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", ctx, d->D, e->K0);
+    if (e->D != d->D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d->D, fs_khz);
+    return MLGGD_OK;
+}
+
+// ... and that it stands alone.  The decode entries take an engine that has joined a communicator of one rank; the
+// loaders and live groups (no_comm) take none that has joined any.
+int check_single_device(const mlggd_engine *e, const char *who, bool no_comm) {
+    if ((no_comm && e->comm) || e->world > 1 || e->fake_world)
+        return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
+    return MLGGD_OK;
+}
+
+// One decode chunk: n output frames read through windows of ctx rows over a stream of `rows` rows.  The idle raw set is
+// borrowed, fill(set) writes its stream and first_frame (and nat_row on a NAT engine, whose samples then read the
+// noise table `nat`), the set becomes current, the net runs and its n rows are resynthesised against X into blk from
+// frame t0 on (lps_den: the de-normalised rows, optional).  The set is marked in use until that has run.
+template <typename Fill>
+int decode_chunk(mlggd_engine *e, const SpecPlan *p, int rows, int n, int ctx, const Fill &fill, const float *nat,
+                 const float *mean, const float *inv, const float2 *X, int t0, float *blk, float *lps_den) {
     mlggd_engine::RawSet *r;
     CHK(raw_set_acquire(e, rows, n, ctx, 0, false, &r));
+    CHK(fill(r));
+    raw_set_commit(e, rows, n, ctx, 0);
+    if (e->nat_frames) e->nat = nat;
+    CHK(forward_resident(e, n));
+    CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, t0, n, blk, e->stream, lps_den));
+    HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, e->stream));
+    return MLGGD_OK;
+}
+
+// the frame stream of output frames [a, a + n) of an F-frame utterance, written by k_lps_stream (first_frame[i] = i)
+// into the set r; on a NAT engine every sample takes row 0 of the noise table, the one noise row of the utterance
+int load_frames_device(mlggd_engine *e, mlggd_engine::RawSet *r, const float *lps, int F, int a, int n, int ctx,
+                       const float *mean, const float *inv) {
+    const int fdim = stream_fdim(e, ctx), rows = n + ctx - 1;
     const size_t work = std::max((size_t)rows * fdim, (size_t)n);
     hipLaunchKernelGGL(k_lps_stream, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, e->stream, lps, F, fdim, a,
                        rows, (ctx - 1) / 2, mean, inv, r->feat.p, r->first.p, n);
     CHK(launch_check("k_lps_stream"));
     if (e->nat_frames) HIPCHK(hipMemsetAsync(r->nat_row.p, 0, (size_t)n * sizeof(int), e->stream));
-    raw_set_commit(e, rows, n, ctx, 0);
-    if (e->nat_frames) e->nat = nat;
-    return MLGGD_OK;
-}
-
-// frames, frame offsets and output offsets of a packed batch (mlggd_enhance_waves_layout); frame_off / out_off may
-// be NULL
-int waves_layout(const SpecDims &d, int n_utts, const int64_t *offsets, int32_t *frame_off, int64_t *out_off) {
-    if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
-    if (frame_off) frame_off[0] = 0;
-    if (out_off) out_off[0] = 0;
-    if (n_utts == 0) return MLGGD_OK;
-    if (!offsets) return fail(MLGGD_ERR_ARG, "offsets is NULL");
-    long long fsum = 0, osum = 0;
-    for (int u = 0; u < n_utts; u++) {
-        if (offsets[u + 1] < offsets[u])
-            return fail(MLGGD_ERR_ARG, "offsets decrease at utterance %d (%lld after %lld)", u, (long long)offsets[u + 1],
-                        (long long)offsets[u]);
-        const long long len = (long long)offsets[u + 1] - (long long)offsets[u];
-        if (len < d.L)
-            return fail(MLGGD_ERR_ARG, "utterance %d: %lld samples is shorter than one frame (%d)", u, len, d.L);
-        const long long F = (len - (d.L - d.S)) / d.S;
-        fsum += F;
-        osum += F * d.S + d.L - d.S;
-        if (fsum > INT32_MAX)
-            return fail(MLGGD_ERR_ARG, "the batch has more than %d frames (reached at utterance %d)", INT32_MAX, u);
-        if (frame_off) frame_off[u + 1] = (int32_t)fsum;
-        if (out_off) out_off[u + 1] = osum;
-    }
     return MLGGD_OK;
 }
 
@@ -3382,18 +3399,6 @@ int ws_grow(mlggd_engine *e, mlggd_engine::WsBuf &b, size_t count, T **out) {
     return MLGGD_OK;
 }
 
-// score_frames[u] (NULL: every frame) against the frames of the layout
-int check_score_frames(int n_utts, const int32_t *frame_off, const int32_t *score_frames) {
-    if (!score_frames) return MLGGD_OK;
-    for (int u = 0; u < n_utts; u++) {
-        const int Fu = frame_off[u + 1] - frame_off[u];
-        if (score_frames[u] < 0 || score_frames[u] > Fu)
-            return fail(MLGGD_ERR_ARG, "utterance %d: score_frames %d is outside 0..%d, its frames", u,
-                        (int)score_frames[u], Fu);
-    }
-    return MLGGD_OK;
-}
-
 // the quality report (score.hip.h) of FT packed frames: clean wave, LPS rows and noisy spectrum X on the device ->
 // scores [2 n_utts] = segsnr, lsd.  Xc [FT][D] and fstat [3 FT] are scratch; sframes / utt_of may be NULL.
 int launch_score(const SpecPlan *p, const int16_t *clean, const long long *wave_off, const int *frame_off,
@@ -3401,11 +3406,11 @@ int launch_score(const SpecPlan *p, const int16_t *clean, const long long *wave_
                  float2 *Xc, float *fstat, float *scores, hipStream_t st) {
     float *snr = fstat, *maxc = fstat + FT, *maxd = fstat + (size_t)2 * FT;
     hipLaunchKernelGGL(k_score_frames, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, clean, wave_off, frame_off,
-                       utt_of, sframes, n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0), (float)exp(-50.0),
+                       utt_of, sframes, n_utts, FT, p->d, p->win, p->tw, p->tws, kSpecFloor, kSpecFloor,
                        lps, X, Xc, snr, maxc, maxd);
     CHK(launch_check("k_score_frames"));
     hipLaunchKernelGGL(k_score_utt, dim3((unsigned)n_utts), dim3(64 * SCORE_UTT_WAVES), 0, st, frame_off, sframes,
-                       p->d.D, (float)exp(-50.0), lps, (const float2 *)Xc, (const float *)snr, (const float *)maxc,
+                       p->d.D, kSpecFloor, lps, (const float2 *)Xc, (const float *)snr, (const float *)maxc,
                        (const float *)maxd, scores, scores + n_utts);
     return launch_check("k_score_utt");
 }
@@ -3532,24 +3537,20 @@ extern "C" {
 
 int mlggd_wave_to_lps(int device, int fs_khz, int n_samples, const int16_t *wave, int *n_frames, float *lps) {
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
+    CHK(spec_dims(fs_khz, &d));
     if (n_samples < 0) return fail(MLGGD_ERR_ARG, "n_samples %d < 0", n_samples);
     if (!n_frames) return fail(MLGGD_ERR_ARG, "n_frames is NULL");
-    const int F = spec_frames(d, n_samples);
+    const int F = (int)spec_rule::frames(d, n_samples);
     *n_frames = F;
     if (!lps || F == 0) return MLGGD_OK;
     if (!wave) return fail(MLGGD_ERR_ARG, "wave is NULL");
-    HIPCHK(hipSetDevice(device));
     const SpecPlan *p;
-    CHK(spec_plan(device, fs_khz, &p));
+    CHK(spec_plan_on(device, fs_khz, &p));
     DevBufs b;
     int16_t *dw = nullptr;
     float *dl = nullptr;
-    const size_t used = (size_t)F * d.S + d.L - d.S;  // the samples the frames cover
-    CHK(b.alloc(&dw, used));
+    CHK(b.upload(&dw, wave, (size_t)spec_rule::out_samples(d, F)));  // the samples the frames cover
     CHK(b.alloc(&dl, (size_t)F * d.D));
-    HIPCHK(hipMemcpy(dw, wave, used * sizeof(int16_t), hipMemcpyHostToDevice));
     CHK(launch_analysis(p, dw, F, dl, nullptr, nullptr));
     HIPCHK(hipMemcpy(lps, dl, (size_t)F * d.D * sizeof(float), hipMemcpyDeviceToHost));
     return MLGGD_OK;
@@ -3558,27 +3559,22 @@ int mlggd_wave_to_lps(int device, int fs_khz, int n_samples, const int16_t *wave
 int mlggd_lps_to_wave(int device, int fs_khz, int n_samples, const int16_t *noisy, int n_frames, const float *lps,
                       int16_t *out, float *out_f32) {
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
+    CHK(spec_dims(fs_khz, &d));
     if (n_samples < d.L) return fail(MLGGD_ERR_ARG, "n_samples %d is shorter than one frame (%d)", n_samples, d.L);
-    const int F = spec_frames(d, n_samples);
+    const int F = (int)spec_rule::frames(d, n_samples);
     if (n_frames != F)
         return fail(MLGGD_ERR_ARG, "n_frames %d: the %d noisy samples give %d frames", n_frames, n_samples, F);
     if (!noisy || !lps || !out) return fail(MLGGD_ERR_ARG, "noisy/lps/out is NULL");
-    HIPCHK(hipSetDevice(device));
     const SpecPlan *p;
-    CHK(spec_plan(device, fs_khz, &p));
+    CHK(spec_plan_on(device, fs_khz, &p));
     DevBufs b;
     int16_t *dw = nullptr;
     float *dl = nullptr, *blk = nullptr;
     float2 *X = nullptr;
-    const size_t used = (size_t)F * d.S + d.L - d.S;
-    CHK(b.alloc(&dw, used));
-    CHK(b.alloc(&dl, (size_t)F * d.D));
+    CHK(b.upload(&dw, noisy, (size_t)spec_rule::out_samples(d, F)));
+    CHK(b.upload(&dl, lps, (size_t)F * d.D));
     CHK(b.alloc(&X, (size_t)F * d.D));
     CHK(b.alloc(&blk, (size_t)F * d.L));
-    HIPCHK(hipMemcpy(dw, noisy, used * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dl, lps, (size_t)F * d.D * sizeof(float), hipMemcpyHostToDevice));
     CHK(launch_analysis(p, dw, F, nullptr, X, nullptr));
     CHK(launch_synthesis(p, dl, nullptr, nullptr, X, 0, F, blk, nullptr));
     return ola_to_host(p, blk, F, out, out_f32, nullptr);
@@ -3588,21 +3584,15 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
                        int n_samples, const int16_t *noisy, int16_t *out, float *out_f32, int *n_out) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
-    if (fea_context < 1 || fea_context % 2 == 0) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", fea_context);
-    CHK(check_input_width(e, fea_context, d.D));
-    if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
-    if (e->world > 1 || e->fake_world)
-        return fail(MLGGD_ERR_STATE, "mlggd_enhance_wave runs on a single-device engine");
+    CHK(check_wave_engine(e, fs_khz, fea_context, true, &d));
+    CHK(check_single_device(e, "mlggd_enhance_wave", false));
     if (n_samples < d.L) return fail(MLGGD_ERR_ARG, "n_samples %d is shorter than one frame (%d)", n_samples, d.L);
     if (!noisy || !norm_mean || !norm_inv_std || !out) return fail(MLGGD_ERR_ARG, "noisy/norm/out is NULL");
-    const int F = spec_frames(d, n_samples);
-    const size_t used = (size_t)F * d.S + d.L - d.S;
+    const int F = (int)spec_rule::frames(d, n_samples);
+    const size_t used = (size_t)spec_rule::out_samples(d, F);
     if (n_out) *n_out = (int)used;
-    HIPCHK(hipSetDevice(e->device));
     const SpecPlan *p;
-    CHK(spec_plan(e->device, fs_khz, &p));
+    CHK(spec_plan_on(e->device, fs_khz, &p));
     hipStream_t st = e->stream;
     DevBufs b;
     int16_t *dw = nullptr;
@@ -3629,22 +3619,23 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
     }
     // chunks of at most the chunk capacity; each one's stream carries (ctx - 1) / 2 context frames on either side,
     // so consecutive streams overlap by ctx - 1 frames and every output frame sees the same input rows
-    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    const int cap = chunk_cap(e);
     for (int a = 0; a < F; a += cap) {
         const int n = std::min(cap, F - a);
-        CHK(load_frames_device(e, dl, F, a, n, fea_context, mean, inv, natz));
-        CHK(forward_resident(e, n));
-        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, a, n, blk, st));
-        HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
+        auto fill = [&](mlggd_engine::RawSet *r) { return load_frames_device(e, r, dl, F, a, n, fea_context, mean, inv); };
+        CHK(decode_chunk(e, p, n + fea_context - 1, n, fea_context, fill, natz, mean, inv, X, a, blk, nullptr));
     }
     return ola_to_host(p, blk, F, out, out_f32, st);
 }
 
 int mlggd_enhance_waves_layout(int fs_khz, int n_utts, const int64_t *offsets, int32_t *frame_off, int64_t *out_off) {
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
-    return waves_layout(d, n_utts, offsets, frame_off, out_off);
+    CHK(spec_dims(fs_khz, &d));
+    std::vector<long long> oo(out_off ? (size_t)std::max(n_utts, 0) + 1 : 0);  // the rule's tables are the device's types
+    RULE(spec_rule::layout(d, n_utts, offsets, spec_rule::kShortFails, frame_off, out_off ? oo.data() : nullptr, nullptr,
+                           RULE_MSG));
+    std::copy(oo.begin(), oo.end(), out_off);
+    return MLGGD_OK;
 }
 
 // mlggd_enhance_waves, and with clean != NULL mlggd_enhance_waves_scored (`who` names the entry point): the report is
@@ -3656,13 +3647,8 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
                              float *stoi = nullptr, int32_t *segments = nullptr) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
-    if (fea_context < 1 || fea_context % 2 == 0) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", fea_context);
-    CHK(check_input_width(e, fea_context, d.D));
-    if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
-    if (e->world > 1 || e->fake_world)
-        return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
+    CHK(check_wave_engine(e, fs_khz, fea_context, true, &d));
+    CHK(check_single_device(e, who, false));
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (n_utts == 0) return MLGGD_OK;
     if (!noisy || !offsets || !norm_mean || !norm_inv_std || !out)
@@ -3671,15 +3657,9 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
     w.h_frame_off.resize((size_t)n_utts + 1);
     w.h_out_off.resize((size_t)n_utts + 1);
     w.h_wave_off.resize((size_t)n_utts + 1);
-    {
-        std::vector<int64_t> oo((size_t)n_utts + 1);
-        CHK(waves_layout(d, n_utts, offsets, w.h_frame_off.data(), oo.data()));
-        for (int u = 0; u <= n_utts; u++) {
-            w.h_out_off[u] = oo[u];
-            w.h_wave_off[u] = (long long)offsets[u] - (long long)offsets[0];
-        }
-    }
-    if (clean) CHK(check_score_frames(n_utts, w.h_frame_off.data(), score_frames));
+    RULE(spec_rule::layout(d, n_utts, offsets, spec_rule::kShortFails, w.h_frame_off.data(), w.h_out_off.data(),
+                           w.h_wave_off.data(), RULE_MSG));
+    if (clean) RULE(spec_rule::check_score_frames(n_utts, w.h_frame_off.data(), score_frames, RULE_MSG));
     StoiJob sjob;
     if (stoi) {  // the enhanced wave of utterance u has out_off[u + 1] - out_off[u] samples: no more can be scored
         std::vector<long long> len((size_t)n_utts), have((size_t)n_utts);
@@ -3692,13 +3672,12 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
     }
     const int FT = w.h_frame_off[n_utts];  // every utterance has a frame: FT >= n_utts
     const size_t n_wave = (size_t)w.h_wave_off[n_utts], n_out = (size_t)w.h_out_off[n_utts];
-    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    const int cap = chunk_cap(e);
     // the stream rows of a chunk: its frames + (ctx - 1) per utterance it touches, in int
     if ((long long)std::min(cap, FT) + (long long)std::min(n_utts, cap) * (fea_context - 1) > INT32_MAX / 2)
         return fail(MLGGD_ERR_ARG, "a chunk of %d frames over %d utterances is too large", std::min(cap, FT), n_utts);
-    HIPCHK(hipSetDevice(e->device));
     const SpecPlan *p;
-    CHK(spec_plan(e->device, fs_khz, &p));
+    CHK(spec_plan_on(e->device, fs_khz, &p));
     hipStream_t st = e->stream;
     int16_t *dw = nullptr, *oi = nullptr;
     float *dl = nullptr, *blk = nullptr, *of = nullptr, *den = nullptr, *norm = nullptr;
@@ -3762,9 +3741,7 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
         CHK(ws_grow(e, w.utt_of, (size_t)FT, &d_utt));
         HIPCHK(hipMemcpyAsync(d_utt, w.h_utt_of.data(), (size_t)FT * sizeof(int), hipMemcpyHostToDevice, st));
     }
-    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, dw, d_woff, d_foff, d_utt,
-                       n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0), dl, X);
-    CHK(launch_check("k_lps_analysis_seg"));
+    CHK(launch_analysis_seg(p, dw, d_woff, d_foff, d_utt, n_utts, FT, dl, X, st));
     float *natz = nullptr;
     if (e->nat_frames) {  // every utterance's noise row, once per call, from the analysed rows of the whole batch
         CHK(ws_grow(e, w.nat, (size_t)n_utts * d.D, &natz));
@@ -3774,25 +3751,17 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
     // an output frame sees the same input rows wherever the boundaries fall; bunches run across utterances
     for (int a = 0, u0 = 0; a < FT; a += cap) {
         const int n = std::min(cap, FT - a);
-        while (w.h_frame_off[u0 + 1] <= a) u0++;
-        int u1 = u0;
-        while (w.h_frame_off[u1 + 1] < a + n) u1++;
-        const int rows = n + (u1 - u0 + 1) * (fea_context - 1);
-        mlggd_engine::RawSet *r;
-        CHK(raw_set_acquire(e, rows, n, fea_context, 0, false, &r));
-        hipLaunchKernelGGL(k_lps_stream_seg, dim3((unsigned)rows), dim3(256), 0, st, dl, d_foff, d_utt, n_utts, d.D, a, n,
-                           u0, u1, fea_context, mean, inv, r->feat.p, r->first.p);
-        CHK(launch_check("k_lps_stream_seg"));
-        if (e->nat_frames) {
+        const spec_rule::Span sp = spec_rule::chunk_span(w.h_frame_off.data(), &u0, a, n, fea_context);
+        auto fill = [&](mlggd_engine::RawSet *r) -> int {
+            hipLaunchKernelGGL(k_lps_stream_seg, dim3((unsigned)sp.rows), dim3(256), 0, st, dl, d_foff, d_utt, n_utts, d.D,
+                               a, n, sp.u0, sp.u1, fea_context, mean, inv, r->feat.p, r->first.p);
+            CHK(launch_check("k_lps_stream_seg"));
+            if (!e->nat_frames) return MLGGD_OK;
             hipLaunchKernelGGL(k_nat_rows_seg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int *)d_foff,
                                (const int *)d_utt, n_utts, a, n, r->nat_row.p);
-            CHK(launch_check("k_nat_rows_seg"));
-        }
-        raw_set_commit(e, rows, n, fea_context, 0);
-        if (e->nat_frames) e->nat = natz;
-        CHK(forward_resident(e, n));
-        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, a, n, blk, st, den));
-        HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
+            return launch_check("k_nat_rows_seg");
+        };
+        CHK(decode_chunk(e, p, sp.rows, n, fea_context, fill, natz, mean, inv, X, a, blk, den));
     }
     hipLaunchKernelGGL(k_ola_seg, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, blk, d_foff, d_ooff, n_utts,
                        p->d, p->win, of, oi, (long long)n_out);
@@ -3842,50 +3811,37 @@ int mlggd_enhance_waves_scored(mlggd_handle e, int fs_khz, int fea_context, cons
 int mlggd_score_waves(int device, int fs_khz, int n_utts, const int16_t *clean, const int16_t *noisy,
                       const int64_t *offsets, const float *lps, const int32_t *score_frames, float *segsnr, float *lsd) {
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
+    CHK(spec_dims(fs_khz, &d));
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (n_utts == 0) return MLGGD_OK;
     if (!clean || !noisy || !offsets || !lps || !segsnr || !lsd)
         return fail(MLGGD_ERR_ARG, "clean/noisy/offsets/lps/segsnr/lsd is NULL");
     std::vector<int32_t> frame_off((size_t)n_utts + 1);
     std::vector<long long> wave_off((size_t)n_utts + 1);
-    CHK(waves_layout(d, n_utts, offsets, frame_off.data(), nullptr));
-    CHK(check_score_frames(n_utts, frame_off.data(), score_frames));
-    for (int u = 0; u <= n_utts; u++) wave_off[u] = (long long)offsets[u] - (long long)offsets[0];
+    RULE(spec_rule::layout(d, n_utts, offsets, spec_rule::kShortFails, frame_off.data(), nullptr, wave_off.data(),
+                           RULE_MSG));
+    RULE(spec_rule::check_score_frames(n_utts, frame_off.data(), score_frames, RULE_MSG));
     const int FT = frame_off[n_utts];
     const size_t n_wave = (size_t)wave_off[n_utts];
-    HIPCHK(hipSetDevice(device));
     const SpecPlan *p;
-    CHK(spec_plan(device, fs_khz, &p));
+    CHK(spec_plan_on(device, fs_khz, &p));
     DevBufs b;
     int16_t *dn = nullptr, *dc = nullptr;
     float *dl = nullptr, *fstat = nullptr, *scores = nullptr;
     float2 *X = nullptr, *Xc = nullptr;
     int *d_foff = nullptr, *d_sf = nullptr;
     long long *d_woff = nullptr;
-    CHK(b.alloc(&dn, n_wave));
-    CHK(b.alloc(&dc, n_wave));
-    CHK(b.alloc(&dl, (size_t)FT * d.D));
+    CHK(b.upload(&dn, noisy + offsets[0], n_wave));
+    CHK(b.upload(&dc, clean + offsets[0], n_wave));
+    CHK(b.upload(&dl, lps, (size_t)FT * d.D));
     CHK(b.alloc(&X, (size_t)FT * d.D));
     CHK(b.alloc(&Xc, (size_t)FT * d.D));
     CHK(b.alloc(&fstat, (size_t)3 * FT));
     CHK(b.alloc(&scores, (size_t)2 * n_utts));
-    CHK(b.alloc(&d_foff, (size_t)n_utts + 1));
-    CHK(b.alloc(&d_woff, (size_t)n_utts + 1));
-    HIPCHK(hipMemcpy(dn, noisy + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dc, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dl, lps, (size_t)FT * d.D * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_foff, frame_off.data(), ((size_t)n_utts + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_woff, wave_off.data(), ((size_t)n_utts + 1) * sizeof(long long), hipMemcpyHostToDevice));
-    if (score_frames) {
-        CHK(b.alloc(&d_sf, (size_t)n_utts));
-        HIPCHK(hipMemcpy(d_sf, score_frames, (size_t)n_utts * sizeof(int), hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, nullptr, dn, d_woff, d_foff,
-                       (const int *)nullptr, n_utts, FT, p->d, p->win, p->tw, p->tws, (float)exp(-50.0),
-                       (float *)nullptr, X);
-    CHK(launch_check("k_lps_analysis_seg"));
+    CHK(b.upload(&d_foff, frame_off.data(), (size_t)n_utts + 1));
+    CHK(b.upload(&d_woff, wave_off.data(), (size_t)n_utts + 1));
+    if (score_frames) CHK(b.upload(&d_sf, score_frames, (size_t)n_utts));
+    CHK(launch_analysis_seg(p, dn, d_woff, d_foff, nullptr, n_utts, FT, nullptr, X, nullptr));
     CHK(launch_score(p, dc, d_woff, d_foff, nullptr, d_sf, n_utts, FT, dl, X, Xc, fstat, scores, nullptr));
     std::vector<float> h((size_t)2 * n_utts);
     HIPCHK(hipMemcpy(h.data(), scores, h.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -3926,18 +3882,13 @@ int mlggd_stoi_waves(int device, int fs_khz, int n_utts, const int16_t *clean, c
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (n_utts == 0) return MLGGD_OK;
     if (!clean || !proc || !offsets || !stoi) return fail(MLGGD_ERR_ARG, "clean/proc/offsets/stoi is NULL");
-    std::vector<long long> off((size_t)n_utts), len((size_t)n_utts);
-    for (int u = 0; u < n_utts; u++) {
-        if (offsets[u + 1] < offsets[u])
-            return fail(MLGGD_ERR_ARG, "offsets decrease at utterance %d (%lld after %lld)", u, (long long)offsets[u + 1],
-                        (long long)offsets[u]);
-        off[u] = (long long)offsets[u] - (long long)offsets[0];
-        len[u] = (long long)offsets[u + 1] - (long long)offsets[u];
-    }
+    std::vector<long long> off((size_t)n_utts + 1), len((size_t)n_utts);
+    RULE(spec_rule::layout(SpecDims(), n_utts, offsets, spec_rule::kUnframed, nullptr, nullptr, off.data(), RULE_MSG));
+    for (int u = 0; u < n_utts; u++) len[u] = off[u + 1] - off[u];
     std::vector<StoiUtt> utt;
     StoiJob job;
     CHK(stoi_job(fs_khz, n_utts, off.data(), off.data(), len.data(), len.data(), stoi_samples, utt, &job));
-    const size_t n_wave = (size_t)((long long)offsets[n_utts] - (long long)offsets[0]);
+    const size_t n_wave = (size_t)off[n_utts];
     HIPCHK(hipSetDevice(device));
     const StoiPlan *sp;
     const SpecPlan *fft;
@@ -3945,18 +3896,13 @@ int mlggd_stoi_waves(int device, int fs_khz, int n_utts, const int16_t *clean, c
     DevBufs b;
     int16_t *dc = nullptr, *dp = nullptr;
     StoiDev sd = {};
-    CHK(b.alloc(&dc, n_wave));
-    CHK(b.alloc(&dp, n_wave));
-    CHK(b.alloc(&sd.utt, (size_t)n_utts));
+    CHK(b.upload(&dc, clean + offsets[0], n_wave));
+    CHK(b.upload(&dp, proc + offsets[0], n_wave));
+    CHK(b.upload(&sd.utt, utt.data(), (size_t)n_utts));
     CHK(b.alloc(&sd.x, (size_t)2 * job.T10));
     CHK(b.alloc(&sd.f, (size_t)(1 + 2 * STOI_BANDS) * job.FT));
     CHK(b.alloc(&sd.i, (size_t)job.FT + n_utts));
     CHK(b.alloc(&sd.res, (size_t)2 * n_utts));
-    if (n_wave) {
-        HIPCHK(hipMemcpy(dc, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dp, proc + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(sd.utt, utt.data(), (size_t)n_utts * sizeof(StoiUtt), hipMemcpyHostToDevice));
     CHK(launch_stoi(sp, fft, job, dc, dp, n_utts, sd, nullptr));
     std::vector<float> h((size_t)2 * n_utts);
     HIPCHK(hipMemcpy(h.data(), sd.res, h.size() * sizeof(float), hipMemcpyDeviceToHost));
@@ -4049,9 +3995,7 @@ extern "C" {
 
 int mlggd_live_layout(int fs_khz, int fea_context, int n_sessions, const int64_t *had, const int64_t *add,
                       const uint8_t *end, int64_t *out_off) {
-    char msg[256];
-    if (live_rule::layout(fs_khz, fea_context, n_sessions, had, add, end, out_off, msg, sizeof msg))
-        return fail(MLGGD_ERR_ARG, "%s", msg);
+    RULE(live_rule::layout(fs_khz, fea_context, n_sessions, had, add, end, out_off, RULE_MSG));
     return MLGGD_OK;
 }
 
@@ -4061,23 +4005,16 @@ int mlggd_live_open(mlggd_handle e, int fs_khz, int fea_context, const float *no
     *out = nullptr;
     if (e->nat_frames > 0)  // a session would have to hold its output back until nat_frames frames have arrived
         return fail(MLGGD_ERR_STATE, "mlggd_live_open: live decoding of an engine with nat_frames = %d is not built", e->nat_frames);
-    char msg[256];
-    int L, S, slot;
-    if (live_rule::check_group(fs_khz, fea_context, n_sessions, &L, &S, msg, sizeof msg))
-        return fail(MLGGD_ERR_ARG, "%s", msg);
+    int L, S;
+    RULE(live_rule::check_group(fs_khz, fea_context, n_sessions, &L, &S, RULE_MSG));
     SpecDims d;
-    CHK(spec_dims(fs_khz, &d, &slot));
-    if ((long long)fea_context * d.D != e->K0)
-        return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", fea_context, d.D, e->K0);
-    if (e->D != d.D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d.D, fs_khz);
-    if (e->comm || e->world > 1 || e->fake_world)
-        return fail(MLGGD_ERR_STATE, "mlggd_live_open runs on a single-device engine");
+    CHK(check_wave_engine(e, fs_khz, fea_context, true, &d));
+    CHK(check_single_device(e, "mlggd_live_open", true));
     if (!norm_mean || !norm_inv_std) return fail(MLGGD_ERR_ARG, "norm_mean/norm_inv_std is NULL");
     if ((long long)n_sessions * (d.L + (long long)fea_context * d.D) > INT32_MAX / 2)
         return fail(MLGGD_ERR_ARG, "n_sessions %d is too large", n_sessions);
-    HIPCHK(hipSetDevice(e->device));
     const SpecPlan *p;
-    CHK(spec_plan(e->device, fs_khz, &p));
+    CHK(spec_plan_on(e->device, fs_khz, &p));
     mlggd_live *s = new mlggd_live;
     s->e = e, s->fs = fs_khz, s->ctx = fea_context, s->half = (fea_context - 1) / 2, s->NS = n_sessions, s->d = d;
     s->K = (d.L + d.S - 1) / d.S - 1;
@@ -4137,7 +4074,7 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
     if (n_emit > 0 && !out) return fail(MLGGD_ERR_ARG, "out is NULL");
     if (n_emit > out_capacity)
         return fail(MLGGD_ERR_ARG, "out_capacity %lld: the push emits %lld samples", (long long)out_capacity, n_emit);
-    const int cap = e->cfg.max_cache_frames > 0 ? e->cfg.max_cache_frames : MLGGD_MAXCACHEFRAME;
+    const int cap = chunk_cap(e);
     if (NF > INT32_MAX / 2 || ND > INT32_MAX / 2 ||
         std::min<long long>(cap, ND) + (long long)std::min(NS, cap) * (ctx - 1) > INT32_MAX / 2)
         return fail(MLGGD_ERR_ARG, "a push of %lld new frames over %d sessions is too large", std::max(NF, ND), NS);
@@ -4172,9 +4109,8 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
         out_off[u + 1] = h.out_off[u + 1];
     }
     // ---- the device
-    HIPCHK(hipSetDevice(e->device));
     const SpecPlan *p;
-    CHK(spec_plan(e->device, s->fs, &p));
+    CHK(spec_plan_on(e->device, s->fs, &p));
     hipStream_t st = e->stream;
     int16_t *d_in = nullptr, *d_win = nullptr, *oi = nullptr;
     float *lps_new = nullptr, *blk_new = nullptr, *of = nullptr;
@@ -4197,12 +4133,7 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
                            s->tail[c1].p, dv.sess, dv.win_off, NS, d.L, d_win, n_win);
         CHK(launch_check("k_live_window"));
     }
-    if (NF > 0) {
-        hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid((int)NF)), dim3(64 * SPEC_FRAMES), 0, st, d_win, dv.a_woff,
-                           dv.a_foff, (const int *)nullptr, n_act, (int)NF, p->d, p->win, p->tw, p->tws, (float)exp(-50.0),
-                           lps_new, X_new);
-        CHK(launch_check("k_lps_analysis_seg"));
-    }
+    if (NF > 0) CHK(launch_analysis_seg(p, d_win, dv.a_woff, dv.a_foff, nullptr, n_act, (int)NF, lps_new, X_new, st));
     if (ND > 0) {
         hipLaunchKernelGGL(k_live_gather_x, dim3((unsigned)ND), dim3(256), 0, st, s->X[c0].p, X_new, dv.sess, dv.dk_off,
                            dv.dk_slot, n_dk, d.D, half, X_dec);
@@ -4211,19 +4142,13 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
     // chunks over the packed decoded frames, as in mlggd_enhance_waves
     for (int a = 0, k0 = 0; a < (int)ND; a += cap) {
         const int n = std::min(cap, (int)ND - a);
-        while (h.dk_off[k0 + 1] <= a) k0++;
-        int k1 = k0;
-        while (h.dk_off[k1 + 1] < a + n) k1++;
-        const int rows = n + (k1 - k0 + 1) * (ctx - 1);
-        mlggd_engine::RawSet *r;
-        CHK(raw_set_acquire(e, rows, n, ctx, 0, false, &r));
-        hipLaunchKernelGGL(k_live_stream, dim3((unsigned)rows), dim3(256), 0, st, s->lps[c0].p, lps_new, dv.sess, dv.dk_off,
-                           dv.dk_slot, n_dk, d.D, a, n, k0, k1, ctx, mean, inv, r->feat.p, r->first.p);
-        CHK(launch_check("k_live_stream"));
-        raw_set_commit(e, rows, n, ctx, 0);
-        CHK(forward_resident(e, n));
-        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X_dec, a, n, blk_new, st));
-        HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, st));
+        const spec_rule::Span sp = spec_rule::chunk_span(h.dk_off, &k0, a, n, ctx);
+        auto fill = [&](mlggd_engine::RawSet *r) {
+            hipLaunchKernelGGL(k_live_stream, dim3((unsigned)sp.rows), dim3(256), 0, st, s->lps[c0].p, lps_new, dv.sess,
+                               dv.dk_off, dv.dk_slot, n_dk, d.D, a, n, sp.u0, sp.u1, ctx, mean, inv, r->feat.p, r->first.p);
+            return launch_check("k_live_stream");
+        };
+        CHK(decode_chunk(e, p, sp.rows, n, ctx, fill, nullptr, mean, inv, X_dec, a, blk_new, nullptr));
     }
     if (n_emit > 0) {
         hipLaunchKernelGGL(k_live_ola, dim3((unsigned)((n_emit + 255) / 256)), dim3(256), 0, st, s->blk[c0].p, blk_new,
@@ -4248,52 +4173,17 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
 // The mixer, the norm statistics and the wave-pair loader: int16 waves in, the raw set of the training loop out.
 namespace {
 
-// frame_off [n_utts + 1] over ALL utterances of a batch; one shorter than a frame has none (that is no error here)
-int train_layout(const SpecDims &d, int n_utts, const int64_t *offsets, std::vector<int32_t> &frame_off) {
-    frame_off.assign((size_t)n_utts + 1, 0);
-    long long fsum = 0;
-    for (int u = 0; u < n_utts; u++) {
-        if (offsets[u + 1] < offsets[u])
-            return fail(MLGGD_ERR_ARG, "offsets decrease at utterance %d (%lld after %lld)", u, (long long)offsets[u + 1],
-                        (long long)offsets[u]);
-        const long long len = (long long)offsets[u + 1] - (long long)offsets[u];
-        fsum += len < d.L ? 0 : (len - (d.L - d.S)) / d.S;
-        if (fsum > INT32_MAX)
-            return fail(MLGGD_ERR_ARG, "the batch has more than %d frames (reached at utterance %d)", INT32_MAX, u);
-        frame_off[u + 1] = (int32_t)fsum;
-    }
+// the tables of a batch over ALL its utterances; one shorter than a frame has no frames (that is no error here)
+struct TrainLayout {
+    std::vector<int32_t> frame_off;
+    std::vector<long long> wave_off;
+};
+int train_layout(const SpecDims &d, int n_utts, const int64_t *offsets, TrainLayout *t) {
+    t->frame_off.resize((size_t)n_utts + 1);
+    t->wave_off.resize((size_t)n_utts + 1);
+    RULE(spec_rule::layout(d, n_utts, offsets, spec_rule::kShortEmpty, t->frame_off.data(), nullptr, t->wave_off.data(),
+                           RULE_MSG));
     return MLGGD_OK;
-}
-
-// every window of fea_context frames must lie inside one utterance of the layout; the message names the sample
-int check_windows(const std::vector<int32_t> &frame_off, int ctx, int n_samples, const int32_t *first_frame) {
-    const int FT = frame_off.back();
-    for (int s = 0; s < n_samples; s++) {
-        const long long f = first_frame[s];
-        if (f < 0 || f + ctx > FT)
-            return fail(MLGGD_ERR_ARG, "sample %d: window [%lld,%lld) outside the %d packed frames", s, f, f + ctx, FT);
-        // the last u with frame_off[u] <= f: utterances without frames are stepped over
-        const int u = (int)(std::upper_bound(frame_off.begin(), frame_off.end(), (int32_t)f) - frame_off.begin()) - 1;
-        if (f + ctx > frame_off[u + 1])
-            return fail(MLGGD_ERR_ARG, "sample %d: window [%lld,%lld) crosses the end of utterance %d at frame %d", s, f,
-                        f + ctx, u, (int)frame_off[u + 1]);
-    }
-    return MLGGD_OK;
-}
-
-// the tables k_lps_analysis_seg reads, over the utterances that have frames (its search needs frame_off to increase)
-void compact_tables(const std::vector<int32_t> &frame_off, const int64_t *offsets, std::vector<int32_t> &cf,
-                    std::vector<long long> &cw) {
-    cf.clear();
-    cw.clear();
-    const int n_utts = (int)frame_off.size() - 1;
-    for (int u = 0; u < n_utts; u++)
-        if (frame_off[u + 1] > frame_off[u]) {
-            cf.push_back(frame_off[u]);
-            cw.push_back((long long)offsets[u] - (long long)offsets[0]);
-        }
-    cf.push_back(frame_off[n_utts]);
-    cw.push_back((long long)offsets[n_utts] - (long long)offsets[0]);
 }
 
 // the block table of a batch: utterance u in blocks of mix_rule::kBlock samples (one without samples has none)
@@ -4349,41 +4239,41 @@ void mix_ratios(int n_utts, const double *snr_db, std::vector<double> &r) {
     for (int u = 0; u < n_utts; u++) mix_rule::ratio(snr_db[u], &r[u]);  // checked before
 }
 
-// The checks of mlggd_load_waves / mlggd_cv_all_waves / mlggd_train_waves, all before any device call; frame_off
-// receives the layout over all utterances, *empty is set when there is nothing to load.
+// The checks of mlggd_load_waves / mlggd_cv_all_waves / mlggd_train_waves, all before any device call; *lay receives
+// the layout over all utterances, *empty is set when there is nothing to load.
 int wave_pair_check(mlggd_engine *e, const char *who, int fs_khz, int ctx, const float *mean, const float *inv, int n_utts,
                     const int64_t *offsets, int n_samples, const int32_t *first_frame, int targ_offset, SpecDims *d,
-                    std::vector<int32_t> &frame_off, bool *empty) {
+                    TrainLayout *lay, bool *empty) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
-    int slot;
-    CHK(spec_dims(fs_khz, d, &slot));
-    if (ctx < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", ctx);
-    CHK(check_input_width(e, ctx, d->D));
-    if (e->D != d->D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d->D, fs_khz);
+    CHK(check_wave_engine(e, fs_khz, ctx, false, d));
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (targ_offset < 0 || targ_offset >= ctx)
         return fail(MLGGD_ERR_ARG, "targ_offset %d not in [0, fea_context)", targ_offset);
     CHK(check_frames(e, n_samples));
-    if (e->comm || e->world > 1 || e->fake_world) return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
+    CHK(check_single_device(e, who, true));
     *empty = n_utts == 0 || n_samples == 0;
     if (*empty) return MLGGD_OK;
     if (!mean || !inv || !offsets || !first_frame) return fail(MLGGD_ERR_ARG, "norm/offsets/first_frame is NULL");
-    CHK(train_layout(*d, n_utts, offsets, frame_off));
-    return check_windows(frame_off, ctx, n_samples, first_frame);
+    CHK(train_layout(*d, n_utts, offsets, lay));
+    RULE(spec_rule::check_windows(n_utts, lay->frame_off.data(), ctx, n_samples, first_frame, RULE_MSG));
+    return MLGGD_OK;
 }
 
 // noisy / clean on the device (packed alike, index 0 = the batch's first sample) -> both analysed, normalised with the
 // noisy statistics into the idle raw set, the sample table uploaded, the set made current.  Everything is enqueued on
 // the engine's stream; the caller synchronises.
 int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, const float *mean, const float *inv,
-                   const std::vector<int32_t> &frame_off, const int64_t *offsets, const int16_t *d_noisy,
-                   const int16_t *d_clean, int n_samples, const int32_t *first_frame, int targ_offset) {
+                   const TrainLayout &lay, const int16_t *d_noisy, const int16_t *d_clean, int n_samples,
+                   const int32_t *first_frame, int targ_offset) {
     mlggd_engine::TrainWs &t = e->tw;
     hipStream_t st = e->stream;
     const SpecPlan *p;
     CHK(spec_plan(e->device, fs_khz, &p));
-    compact_tables(frame_off, offsets, t.h_frame_off, t.h_wave_off);
-    const int nc = (int)t.h_frame_off.size() - 1, FT = frame_off.back();
+    t.h_frame_off.resize(lay.frame_off.size());
+    t.h_wave_off.resize(lay.frame_off.size());
+    const int nc = spec_rule::compact_tables((int)lay.frame_off.size() - 1, lay.frame_off.data(), lay.wave_off.data(),
+                                             t.h_frame_off.data(), t.h_wave_off.data());
+    const int FT = lay.frame_off.back();
     float *lpsN = nullptr, *lpsC = nullptr, *norm = nullptr;
     int *d_foff = nullptr;
     long long *d_woff = nullptr;
@@ -4401,12 +4291,8 @@ int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, cons
     HIPCHK(hipMemcpyAsync(d_foff, t.h_frame_off.data(), ((size_t)nc + 1) * sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_woff, t.h_wave_off.data(), ((size_t)nc + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(r->first.p, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
-    for (int k = 0; k < 2; k++) {  // the spectrum itself is not wanted here: X = nullptr
-        hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, st, k ? d_clean : d_noisy,
-                           (const long long *)d_woff, (const int *)d_foff, (const int *)nullptr, nc, FT, p->d, p->win, p->tw,
-                           p->tws, (float)exp(-50.0), k ? lpsC : lpsN, (float2 *)nullptr);
-        CHK(launch_check("k_lps_analysis_seg"));
-    }
+    for (int k = 0; k < 2; k++)  // the spectrum itself is not wanted here: X = nullptr
+        CHK(launch_analysis_seg(p, k ? d_clean : d_noisy, d_woff, d_foff, nullptr, nc, FT, k ? lpsC : lpsN, nullptr, st));
     hipLaunchKernelGGL(k_lps_norm_pair, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN, (const float *)lpsC,
                        d.D, (const float *)norm, (const float *)(norm + d.D), r->feat.p, r->targ.p);
     CHK(launch_check("k_lps_norm_pair"));
@@ -4440,19 +4326,18 @@ extern "C" {
 int mlggd_wave_samples(int fs_khz, int fea_context, int n_utts, const int64_t *offsets, int32_t *first_frame,
                        int64_t *n_samples) {
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
+    CHK(spec_dims(fs_khz, &d));
     if (fea_context < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", fea_context);
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (!n_samples) return fail(MLGGD_ERR_ARG, "n_samples is NULL");
     *n_samples = 0;
     if (n_utts == 0) return MLGGD_OK;
     if (!offsets) return fail(MLGGD_ERR_ARG, "offsets is NULL");
-    std::vector<int32_t> frame_off;
-    CHK(train_layout(d, n_utts, offsets, frame_off));
+    TrainLayout lay;
+    CHK(train_layout(d, n_utts, offsets, &lay));
     int64_t n = 0;
     for (int u = 0; u < n_utts; u++)
-        for (int f = frame_off[u]; f + fea_context <= frame_off[u + 1]; f++, n++)
+        for (int f = lay.frame_off[u]; f + fea_context <= lay.frame_off[u + 1]; f++, n++)
             if (first_frame) first_frame[n] = f;
     *n_samples = n;
     return MLGGD_OK;
@@ -4466,9 +4351,7 @@ int mlggd_mix_waves(int device, int n_utts, const int16_t *clean, const int64_t 
     if (!clean || !offsets || !noise || !noise_lo || !noise_len || !noise_start || !snr_db || !noisy)
         return fail(MLGGD_ERR_ARG, "clean/offsets/noise/noise_lo/noise_len/noise_start/snr_db/noisy is NULL");
     if (n_noise < 0) return fail(MLGGD_ERR_ARG, "n_noise %lld < 0", (long long)n_noise);
-    char msg[512];
-    if (mix_rule::check(n_utts, offsets, n_noise, noise_lo, noise_len, noise_start, snr_db, msg, sizeof(msg)))
-        return fail(MLGGD_ERR_ARG, "%s", msg);
+    RULE(mix_rule::check(n_utts, offsets, n_noise, noise_lo, noise_len, noise_start, snr_db, RULE_MSG));
     const size_t n_wave = (size_t)(offsets[n_utts] - offsets[0]);
     if (gain) std::fill(gain, gain + n_utts, 0.0);
     if (clipped) std::fill(clipped, clipped + n_utts, 0);
@@ -4482,15 +4365,12 @@ int mlggd_mix_waves(int device, int n_utts, const int16_t *clean, const int64_t 
     int16_t *dc = nullptr, *dn = nullptr, *dz = nullptr;
     mix_rule::Block *db = nullptr;
     unsigned char *du = nullptr;
-    CHK(b.alloc(&dc, n_wave));
+    CHK(b.upload(&dc, clean + offsets[0], n_wave));
     CHK(b.alloc(&dn, n_wave));
-    CHK(b.alloc(&dz, (size_t)n_noise));
-    CHK(b.alloc(&db, blocks.size()));
+    CHK(b.upload(&dz, noise, (size_t)n_noise));
+    CHK(b.upload(&db, blocks.data(), blocks.size()));
     CHK(b.alloc(&du, MixUtt::bytes(n_utts)));
     MixUtt m(du, n_utts);
-    HIPCHK(hipMemcpy(dc, clean + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dz, noise, (size_t)n_noise * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db, blocks.data(), blocks.size() * sizeof(mix_rule::Block), hipMemcpyHostToDevice));
     CHK(launch_mix(db, (int)blocks.size(), dc, dz, m, n_utts, r.data(), dn, nullptr));
     HIPCHK(hipMemcpy(noisy + offsets[0], dn, n_wave * sizeof(int16_t), hipMemcpyDeviceToHost));
     if (gain) HIPCHK(hipMemcpy(gain, m.gain, (size_t)n_utts * sizeof(double), hipMemcpyDeviceToHost));
@@ -4501,44 +4381,36 @@ int mlggd_mix_waves(int device, int n_utts, const int16_t *clean, const int64_t 
 int mlggd_lps_stats(int device, int fs_khz, int n_utts, const int16_t *wave, const int64_t *offsets, double *sums,
                     int64_t *n_frames) {
     SpecDims d;
-    int slot;
-    CHK(spec_dims(fs_khz, &d, &slot));
+    CHK(spec_dims(fs_khz, &d));
     if (n_utts < 0) return fail(MLGGD_ERR_ARG, "n_utts %d < 0", n_utts);
     if (!sums || !n_frames) return fail(MLGGD_ERR_ARG, "sums/n_frames is NULL");
     if (n_utts > 0 && (!wave || !offsets)) return fail(MLGGD_ERR_ARG, "wave/offsets is NULL");
-    std::vector<int32_t> frame_off(1, 0);
-    if (n_utts > 0) CHK(train_layout(d, n_utts, offsets, frame_off));
-    const int FT = frame_off.back();
+    TrainLayout lay;
+    CHK(train_layout(d, n_utts, offsets, &lay));
+    const int FT = lay.frame_off.back();
     std::fill(sums, sums + (size_t)2 * d.D, 0.0);
     *n_frames = FT;
     if (FT == 0) return MLGGD_OK;
-    std::vector<int32_t> cf;
-    std::vector<long long> cw;
-    compact_tables(frame_off, offsets, cf, cw);
-    const int nc = (int)cf.size() - 1, chunks = (FT + CS_ROWS - 1) / CS_ROWS;
-    const size_t n_wave = (size_t)(offsets[n_utts] - offsets[0]);
-    HIPCHK(hipSetDevice(device));
+    std::vector<int32_t> cf((size_t)n_utts + 1);
+    std::vector<long long> cw((size_t)n_utts + 1);
+    const int nc = spec_rule::compact_tables(n_utts, lay.frame_off.data(), lay.wave_off.data(), cf.data(), cw.data());
+    const int chunks = (FT + CS_ROWS - 1) / CS_ROWS;
+    const size_t n_wave = (size_t)lay.wave_off[n_utts];
     const SpecPlan *p;
-    CHK(spec_plan(device, fs_khz, &p));
+    CHK(spec_plan_on(device, fs_khz, &p));
     DevBufs b;
     int16_t *dw = nullptr;
     float *dl = nullptr;
     double *part = nullptr, *ds = nullptr;
     int *d_foff = nullptr;
     long long *d_woff = nullptr;
-    CHK(b.alloc(&dw, n_wave));
+    CHK(b.upload(&dw, wave + offsets[0], n_wave));
     CHK(b.alloc(&dl, (size_t)FT * d.D));
     CHK(b.alloc(&part, (size_t)chunks * 2 * d.D));
     CHK(b.alloc(&ds, (size_t)2 * d.D));
-    CHK(b.alloc(&d_foff, (size_t)nc + 1));
-    CHK(b.alloc(&d_woff, (size_t)nc + 1));
-    HIPCHK(hipMemcpy(dw, wave + offsets[0], n_wave * sizeof(int16_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_foff, cf.data(), ((size_t)nc + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(d_woff, cw.data(), ((size_t)nc + 1) * sizeof(long long), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_lps_analysis_seg, dim3(spec_grid(FT)), dim3(64 * SPEC_FRAMES), 0, nullptr, (const int16_t *)dw,
-                       (const long long *)d_woff, (const int *)d_foff, (const int *)nullptr, nc, FT, p->d, p->win, p->tw,
-                       p->tws, (float)exp(-50.0), dl, (float2 *)nullptr);
-    CHK(launch_check("k_lps_analysis_seg"));
+    CHK(b.upload(&d_foff, cf.data(), (size_t)nc + 1));
+    CHK(b.upload(&d_woff, cw.data(), (size_t)nc + 1));
+    CHK(launch_analysis_seg(p, dw, d_woff, d_foff, nullptr, nc, FT, dl, nullptr, nullptr));
     hipLaunchKernelGGL(k_lps_colstats, dim3((unsigned)((d.D + CS_BINS - 1) / CS_BINS), (unsigned)chunks), dim3(256), 0,
                        nullptr, (const float *)dl, FT, d.D, part);
     CHK(launch_check("k_lps_colstats"));
@@ -4572,16 +4444,16 @@ int mlggd_load_waves(mlggd_handle e, int fs_khz, int fea_context, const float *n
                      int n_utts, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_samples,
                      const int32_t *first_frame, int targ_offset) {
     SpecDims d;
-    std::vector<int32_t> frame_off;
+    TrainLayout lay;
     bool empty = false;
     CHK(wave_pair_check(e, "mlggd_load_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, offsets, n_samples,
-                        first_frame, targ_offset, &d, frame_off, &empty));
+                        first_frame, targ_offset, &d, &lay, &empty));
     if (empty) return MLGGD_OK;
     if (!noisy || !clean) return fail(MLGGD_ERR_ARG, "noisy/clean is NULL");
     HIPCHK(hipSetDevice(e->device));
     int16_t *dn = nullptr, *dc = nullptr;
     CHK(upload_pair(e, noisy, clean, offsets, n_utts, &dn, &dc));
-    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, frame_off, offsets, dn, dc, n_samples,
+    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, lay, dn, dc, n_samples,
                        first_frame, targ_offset));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
@@ -4591,10 +4463,10 @@ int mlggd_cv_all_waves(mlggd_handle e, int fs_khz, int fea_context, const float 
                        int n_utts, const int16_t *noisy, const int16_t *clean, const int64_t *offsets, int n_samples,
                        const int32_t *first_frame, int targ_offset, float *sqerr, float *abserr, float *loglik) {
     SpecDims d;
-    std::vector<int32_t> frame_off;
+    TrainLayout lay;
     bool empty = false;
     CHK(wave_pair_check(e, "mlggd_cv_all_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, offsets,
-                        n_samples, first_frame, targ_offset, &d, frame_off, &empty));
+                        n_samples, first_frame, targ_offset, &d, &lay, &empty));
     if (empty) {
         if (sqerr) *sqerr = 0.0f;
         if (abserr) *abserr = 0.0f;
@@ -4605,21 +4477,15 @@ int mlggd_cv_all_waves(mlggd_handle e, int fs_khz, int fea_context, const float 
     HIPCHK(hipSetDevice(e->device));
     int16_t *dn = nullptr, *dc = nullptr;
     CHK(upload_pair(e, noisy, clean, offsets, n_utts, &dn, &dc));
-    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, frame_off, offsets, dn, dc, n_samples,
+    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, lay, dn, dc, n_samples,
                        first_frame, targ_offset));
-    float *ll = (e->cfg.MLflag == 1) ? loglik : nullptr;
-    int rc;
-    if (e->cv_device) {
-        rc = cv_device_reduce(e, n_samples, sqerr, abserr, ll);
-    } else {  // the host-order sums read the targets on the host: the normalised clean rows come back once
-        const int D = e->D;
-        std::vector<float> targ((size_t)frame_off.back() * D);
+    std::vector<float> targ;
+    if (!e->cv_device) {  // the host-order sums read the targets on the host: the normalised clean rows come back once
+        targ.resize((size_t)lay.frame_off.back() * e->D);
         HIPCHK(hipMemcpyAsync(targ.data(), e->raw[e->raw_cur].targ.p, targ.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
-        rc = cv_accumulate(
-            e, n_samples, [&](int i) { return targ.data() + (size_t)(first_frame[i] + targ_offset) * D; }, sqerr, abserr,
-            ll);
     }
+    const int rc = cv_indexed(e, n_samples, first_frame, targ_offset, targ.data(), sqerr, abserr, loglik);
     HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return rc;
@@ -4653,19 +4519,17 @@ int mlggd_train_waves(mlggd_handle e, int fs_khz, int fea_context, const float *
                       int *bunches_trained) {
     if (bunches_trained) *bunches_trained = 0;
     SpecDims d;
-    std::vector<int32_t> frame_off;
+    TrainLayout lay;
     bool empty = false;
     CHK(wave_pair_check(e, "mlggd_train_waves", fs_khz, fea_context, norm_mean, norm_inv_std, n_utts, offsets, n_samples,
-                        first_frame, targ_offset, &d, frame_off, &empty));
+                        first_frame, targ_offset, &d, &lay, &empty));
     mlggd_engine::TrainWs &t = e->tw;
     if (!t.noise.p || t.n_noise == 0)
         return fail(MLGGD_ERR_STATE, "mlggd_train_waves: the engine has no noise bank (mlggd_set_noise)");
     if (empty) return MLGGD_OK;
     if (!clean || !noise_lo || !noise_len || !noise_start || !snr_db)
         return fail(MLGGD_ERR_ARG, "clean/noise_lo/noise_len/noise_start/snr_db is NULL");
-    char msg[512];
-    if (mix_rule::check(n_utts, offsets, t.n_noise, noise_lo, noise_len, noise_start, snr_db, msg, sizeof(msg)))
-        return fail(MLGGD_ERR_ARG, "%s", msg);
+    RULE(mix_rule::check(n_utts, offsets, t.n_noise, noise_lo, noise_len, noise_start, snr_db, RULE_MSG));
     mix_blocks(n_utts, offsets, noise_lo, noise_len, noise_start, t.h_blocks);
     mix_ratios(n_utts, snr_db, t.h_r);
     HIPCHK(hipSetDevice(e->device));
@@ -4684,7 +4548,7 @@ int mlggd_train_waves(mlggd_handle e, int fs_khz, int fea_context, const float *
         HIPCHK(hipMemcpyAsync(noisy_out + offsets[0], dn, n_wave * sizeof(int16_t), hipMemcpyDeviceToHost, st));
     if (gain) HIPCHK(hipMemcpyAsync(gain, m.gain, (size_t)n_utts * sizeof(double), hipMemcpyDeviceToHost, st));
     if (clipped) HIPCHK(hipMemcpyAsync(clipped, m.clipped, (size_t)n_utts * sizeof(int), hipMemcpyDeviceToHost, st));
-    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, frame_off, offsets, dn, dc, n_samples,
+    CHK(wave_pair_load(e, d, fs_khz, fea_context, norm_mean, norm_inv_std, lay, dn, dc, n_samples,
                        first_frame, targ_offset));
     CHK(mlggd_train_resident(e, 0, n_samples, bunches_trained));
     return mlggd_sync(e);

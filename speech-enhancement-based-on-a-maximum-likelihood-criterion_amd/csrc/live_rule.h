@@ -4,25 +4,18 @@
 // A session that has received n samples has analysed F(n) frames, the frame count of the offline calls.  While it
 // runs it has decoded T = max(0, F(n) - half) of them (frame t needs the rows up to t + half) and emitted T S samples;
 // the push that ends it decodes the rest against the right edge and emits up to F S + L - S (nothing if F = 0).
+// The rate table, F(n) and F S + L - S are spec_rule.h's, as for every wave entry.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 
+#include "spec_rule.h"
+
 namespace live_rule {
+using spec_rule::refuse;
 
 // a recording is indexed in int on the device: its samples stay below this
 constexpr int64_t kMaxSamples = INT32_MAX - 1024;
-
-inline bool rate(int fs_khz, int *L, int *S) {
-    switch (fs_khz) {
-        case 8: *L = 256, *S = 128; return true;
-        case 11: *L = 256, *S = 110; return true;
-        case 16: *L = 512, *S = 256; return true;
-    }
-    return false;
-}
-
-inline int64_t frames(int L, int S, int64_t n) { return n < L ? 0 : (n - (L - S)) / S; }
 
 // what one push does to one session
 struct Step {
@@ -35,31 +28,22 @@ struct Step {
 inline Step step(int L, int S, int half, int64_t had, int64_t add, bool end) {
     Step s;
     const int64_t n1 = had + add;
-    s.A0 = frames(L, S, had);
-    s.A1 = frames(L, S, n1);
+    s.A0 = spec_rule::frames(L, S, had);
+    s.A1 = spec_rule::frames(L, S, n1);
     s.T0 = s.A0 > half ? s.A0 - half : 0;
     s.T1 = end ? s.A1 : (s.A1 > half ? s.A1 - half : 0);
     s.p0 = had - s.A0 * S;  // n < L: all of them; else the L - S .. L - 1 samples from the next frame's start on
     s.p1 = n1 - s.A1 * S;
-    const int64_t upto = end ? (s.A1 > 0 ? s.A1 * S + L - S : 0) : s.T1 * S;
+    const int64_t upto = end ? (s.A1 > 0 ? spec_rule::out_samples(L, S, s.A1) : 0) : s.T1 * S;
     s.emit = upto - s.T0 * S;
     return s;
 }
 
 // the checks shared by mlggd_live_layout and mlggd_live_open; 0 or -1 with msg filled
 inline int check_group(int fs_khz, int fea_context, int n_sessions, int *L, int *S, char *msg, size_t cap) {
-    if (!rate(fs_khz, L, S)) {
-        snprintf(msg, cap, "fs_khz %d: must be 8, 11 or 16", fs_khz);
-        return -1;
-    }
-    if (fea_context < 1 || fea_context % 2 == 0) {
-        snprintf(msg, cap, "fea_context %d must be odd", fea_context);
-        return -1;
-    }
-    if (n_sessions < 1) {
-        snprintf(msg, cap, "n_sessions %d < 1", n_sessions);
-        return -1;
-    }
+    if (!spec_rule::rate(fs_khz, L, S)) return refuse(msg, cap, "fs_khz %d: must be 8, 11 or 16", fs_khz);
+    if (fea_context < 1 || fea_context % 2 == 0) return refuse(msg, cap, "fea_context %d must be odd", fea_context);
+    if (n_sessions < 1) return refuse(msg, cap, "n_sessions %d < 1", n_sessions);
     return 0;
 }
 
@@ -68,22 +52,16 @@ inline int layout(int fs_khz, int fea_context, int n_sessions, const int64_t *ha
                   const uint8_t *end, int64_t *out_off, char *msg, size_t cap) {
     int L, S;
     if (check_group(fs_khz, fea_context, n_sessions, &L, &S, msg, cap)) return -1;
-    if (!had || !add || !out_off) {
-        snprintf(msg, cap, "had/add/out_off is NULL");
-        return -1;
-    }
+    if (!had || !add || !out_off) return refuse(msg, cap, "had/add/out_off is NULL");
     const int half = (fea_context - 1) / 2;
     out_off[0] = 0;
     for (int u = 0; u < n_sessions; u++) {
-        if (had[u] < 0 || add[u] < 0) {
-            snprintf(msg, cap, "session %d: had %lld / add %lld is negative", u, (long long)had[u], (long long)add[u]);
-            return -1;
-        }
-        if (had[u] > kMaxSamples || add[u] > kMaxSamples - had[u]) {
-            snprintf(msg, cap, "session %d: %lld + %lld samples exceed the %lld one recording may have: end it", u,
-                     (long long)had[u], (long long)add[u], (long long)kMaxSamples);
-            return -1;
-        }
+        if (had[u] < 0 || add[u] < 0)
+            return refuse(msg, cap, "session %d: had %lld / add %lld is negative", u, (long long)had[u],
+                          (long long)add[u]);
+        if (had[u] > kMaxSamples || add[u] > kMaxSamples - had[u])
+            return refuse(msg, cap, "session %d: %lld + %lld samples exceed the %lld one recording may have: end it", u,
+                          (long long)had[u], (long long)add[u], (long long)kMaxSamples);
         out_off[u + 1] = out_off[u] + step(L, S, half, had[u], add[u], end && end[u]).emit;
     }
     return 0;

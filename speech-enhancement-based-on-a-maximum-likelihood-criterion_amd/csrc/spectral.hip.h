@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "spec_rule.h"  // SpecDims
+
 #define SPEC_FRAMES 4     // frames (= wavefronts) per workgroup
 #define SPEC_MAXM 256     // largest complex FFT (N = 512)
 #define SPEC_FLOOR (-50.0f)
@@ -29,10 +31,6 @@
 // one bank (cdna_hip_programming.md Guideline 4)
 __device__ __forceinline__ int spec_pad(int i) { return i + (i >> 5); }
 #define SPEC_ROW (SPEC_MAXM + SPEC_MAXM / 32)
-
-struct SpecDims {
-    int L, S, N, M, logM, D;  // frame length, hop, FFT length, N/2, log2(M), N/2 + 1
-};
 
 // forward complex FFT of the M points in (re, im) of one wavefront's LDS row, data already in bit-reversed order
 __device__ __forceinline__ void spec_fft_rows(float *re, float *im, const float2 *__restrict__ tw, int M, int logM,

@@ -37,7 +37,7 @@ int main() {
     for (int fs : {8, 11, 16})
         for (int ctx : {1, 7, 11}) {
             int L = 0, S = 0;
-            EXPECT(live_rule::rate(fs, &L, &S));
+            EXPECT(spec_rule::rate(fs, &L, &S));
             const int half = (ctx - 1) / 2;
             // one session, every length around the boundaries, random cuts; the counts telescope
             for (int k = 0; k <= half + 2; k++)

@@ -285,6 +285,31 @@ def test_an_emulated_world_is_refused(pkg):
     eng.close()
 
 
+def test_a_communicator_of_one_rank_may_decode_but_not_load_or_go_live(pkg):
+    """The wave entries share one engine check but not one single-device rule: an engine that has joined a communicator
+    of one rank still decodes (the same bytes as one that has not), while the wave loader and a live group refuse it."""
+    rng = np.random.default_rng(48)
+    ls, ws, bs = small_net(rng, ctx=1, hidden=(32,), D=129)
+    mean, inv = norm_stats(rng, D=129)
+    wave = frames_wave(1, 8, seed=2, extra=0)
+    assert wave.size == 256
+    plain, joined = engine(pkg, ls, ws, bs, 32), engine(pkg, ls, ws, bs, 32)
+    joined.comm_init(pkg.comm_unique_id(), 1, 0)
+    want = plain.enhance_waves([wave], mean, inv, fs_khz=8, fea_context=1, return_f32=True, return_lps=True)
+    got = joined.enhance_waves([wave], mean, inv, fs_khz=8, fea_context=1, return_f32=True, return_lps=True)
+    for g, w in zip(got, want):
+        same(g, w)
+    first = np.zeros(1, np.int32)
+    with pytest.raises(pkg.MlggdError, match=r"error 4: mlggd_load_waves runs on a single-device engine"):
+        joined.load_waves([wave], [wave], mean, inv, first, 0, fea_context=1, fs_khz=8)
+    with pytest.raises(pkg.MlggdError, match=r"error 4: mlggd_live_open runs on a single-device engine"):
+        joined.live(mean, inv, 1, fs_khz=8, fea_context=1)
+    plain.load_waves([wave], [wave], mean, inv, first, 0, fea_context=1, fs_khz=8)   # the engine that stands alone may
+    plain.live(mean, inv, 1, fs_khz=8, fea_context=1).close()
+    plain.close()
+    joined.close()
+
+
 # ---- the tool
 def tool(name):
     return os.path.join(hostlib.HOST, name)
