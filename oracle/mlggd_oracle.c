@@ -223,12 +223,17 @@ void ora_set_gemm_plan(int layer, int fwd_waves, int dx_waves) {
  * (mlggd_debug_fake_world; a real all-reduce's order is RCCL's own).  The ML statistic: every rank sums its frames by
  * the wavefront reduction of csrc/kernels.hip.h k_colsum (lane l takes frames l, l + 64, ...; six butterfly steps),
  * the ranks' sums are added in rank order.  allreduce = 1 (gradient all-reduce): dW and the bias gradient are
- * per-rank chains over the rank's own frames, added in rank order; 0 (factor exchanges): one chain over all frames. */
-static int g_dp_world = 1, g_dp_allreduce = 0;
+ * per-rank chains over the rank's own frames, added in rank order; 0 (factor exchanges): one chain over all frames.
+ * A world of ONE rank (mlggd_debug_fake_world(1, ...), a one-rank communicator) has nothing to meet, but its statistic
+ * still goes through k_colsum -- the exchange path does not know that it is alone: ora_set_dp_one_rank(1) says that
+ * world = 1 is such a world and not a single device.  ora_set_dp_twin resets it. */
+static int g_dp_world = 1, g_dp_allreduce = 0, g_dp_one_rank = 0;
 void ora_set_dp_twin(int world, int allreduce) {
     g_dp_world = world < 1 ? 1 : world;
     g_dp_allreduce = allreduce != 0;
+    g_dp_one_rank = 0;
 }
+void ora_set_dp_one_rank(int on) { g_dp_one_rank = on != 0; }
 #define ORA_FMA __attribute__((target("fma"))) /* fmaf as ONE instruction; -ffp-contract=off still keeps every other a*b+c unfused */
 static int ceil32i(int x) { return (x + 31) & ~31; }
 
@@ -875,7 +880,7 @@ void ora_loss_colsum(ora_net *net, int n, const float *targ, float *colsum) {
             net->errorabsolute[i] = fabsf(net->realerror[i]);
             net->errorabsolute2[i] = lpow(net->errorabsolute[i], beta_of(net, d));
         }
-    if (g_gemm_order == 1 && g_dp_world > 1 && n % g_dp_world == 0) { /* k_colsum per rank, ranks in order */
+    if (g_gemm_order == 1 && (g_dp_world > 1 || g_dp_one_rank) && n % g_dp_world == 0) { /* k_colsum per rank, ranks in order */
         const int B = n / g_dp_world;
         for (int d = 0; d < D; d++) {
             float tot = 0.0f;

@@ -61,6 +61,7 @@ def lib(variant="strict"):
         L.ora_set_gemm_order.argtypes = [C.c_int, C.c_int]
         L.ora_set_gemm_plan.argtypes = [C.c_int, C.c_int, C.c_int]
         L.ora_set_dp_twin.argtypes = [C.c_int, C.c_int]
+        L.ora_set_dp_one_rank.argtypes = [C.c_int]
         L.ora_exp_det_array.argtypes = [_fp, _fp, C.c_long, C.c_int]
         L.ora_pow_det_array.argtypes = [_fp, C.c_float, _fp, C.c_long]
         if "OMP_NUM_THREADS" not in os.environ:
@@ -257,7 +258,7 @@ def set_gemm_blocked(on, variant="strict"):
     lib(variant).ora_set_gemm_blocked(1 if on else 0)
 
 
-def set_gemm_order(order, s_out=1, variant="strict", plan=None, dp_world=1, dp_allreduce=False):
+def set_gemm_order(order, s_out=1, variant="strict", plan=None, dp_world=1, dp_allreduce=False, dp_one_rank=False):
     """MFMA-order twin (process-wide for that library): order "hip" / 1 = the HIP kernels' own summation order with
     fused multiply-adds -- forward / dX reductions over the 4 waves' contiguous ranges, the output layer over `s_out`
     slabs x 4 waves (the engine's choice: BPGpu.out_slabs()), dW over the frames in order; "ref" / 0 = the documented
@@ -267,11 +268,14 @@ def set_gemm_order(order, s_out=1, variant="strict", plan=None, dp_world=1, dp_a
     workgroup (default), 1 = the 64 x 64-tile kernels' single chain per output element.
     dp_world > 1: the data-parallel form -- `dp_world` ranks of bunchsize / dp_world frames whose ML statistic (k_colsum's
     wavefront reduction per rank) and, with dp_allreduce, weight / bias gradients meet in rank order, as the one-GPU
-    emulation of a world (BPGpu.fake_world) does."""
+    emulation of a world (BPGpu.fake_world) does.  dp_one_rank (with dp_world = 1): a WORLD of one rank -- fake_world(1, ...)
+    or a one-rank communicator -- whose ML statistic still goes through k_colsum's wavefront reduction; without it
+    dp_world = 1 is a single device, whose statistic is summed in frame order."""
     lib(variant).ora_set_gemm_order(1 if order in (1, "hip") else 0, int(s_out))
     for l, (fw, dx) in enumerate(plan or [], start=1):  # BPGpu.gemm_plan(): which GEMM kernel each layer takes
         lib(variant).ora_set_gemm_plan(l, int(fw), int(dx))
     lib(variant).ora_set_dp_twin(int(dp_world), 1 if dp_allreduce else 0)
+    lib(variant).ora_set_dp_one_rank(1 if dp_one_rank and int(dp_world) == 1 else 0)
 
 
 def exp_det(x, sigmoid=False, variant="strict"):

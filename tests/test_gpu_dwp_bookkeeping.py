@@ -44,7 +44,8 @@ def random_frames(n, ls, seed):
     (203, 100, 100),    # B not a power of two: the division form of G / n; frames 100..127 padded
     (64, 64, 256),      # no edge at all; four units per tile
     (300, 40, 512),     # eight units per tile
-    (96, 64, 1024),     # sixteen units' worth of frames
+    (96, 64, 1024),     # sixteen units: more than k_dwp takes on one device -- k_dw<1> over sixteen 64-frame chunks (the
+                        # sixteen-unit dwp_body runs over gathered factors only: tests/test_gpu_dw_choices.py)
 ])
 def test_one_layer_nets_equal_the_twin_bitwise(pkg, pyoracle, K, D, B):
     """Two MMSE steps (the second with momentum and weight decay at work): dEdX, delta_w, delta_b, then W and b."""

@@ -18,7 +18,8 @@ SHIPPED = (0.1, 0.9, 1e-5)
 NO_MOM = (0.05, 0.0, 0.0)
 DECAY = (0.3, 0.5, 1e-2)      # lr wc W of the order of the gradient term
 KNOBS = ("MLGGD_TILE64", "MLGGD_S_OUT", "MLGGD_LOSS_FUSE", "MLGGD_DW_MERGE", "MLGGD_STAGE_AHEAD", "MLGGD_FWD_NW",
-         "MLGGD_DX_NW", "MLGGD_FWD_PIPE", "MLGGD_DX_PIPE", "MLGGD_TWO_STREAMS", "MLGGD_CV_DEVICE")
+         "MLGGD_DX_NW", "MLGGD_FWD_PIPE", "MLGGD_DX_PIPE", "MLGGD_TWO_STREAMS", "MLGGD_CV_DEVICE", "MLGGD_DW_TILE",
+         "MLGGD_DW_PERSIST", "MLGGD_DWP_PER_CU", "MLGGD_TILE_MAP")
 TABLE = {}
 
 
@@ -76,7 +77,9 @@ def data(ls, B, steps, seed, W, b):
 
 
 def run_case(pkg, monkeypatch, case, ls, B, hp, beta, ml, env=None, layers=None, steps=2, lrate2=None, seed=1,
-             plan=None, slabs=None, fake_allreduce=False, x=None, t=None, W=None, b=None):
+             plan=None, slabs=None, fake_allreduce=False, x=None, t=None, W=None, b=None, dw_kinds=None):
+    """dw_kinds: the dW kernel of every layer's launch, as test_gpu_dw_choices.dw_kernel names it from the stamp rows
+    (taken by one further step per layer after the checked ones)"""
     L = len(ls)
     if W is None:
         W, b = b6.make_net(ls, seed)
@@ -108,6 +111,12 @@ def run_case(pkg, monkeypatch, case, ls, B, hp, beta, ml, env=None, layers=None,
             record(case, reps)
             bad += ["step %d %s" % (k + 1, ln) for ln in fail_lines(reps)]
             steps_done.append(s)
+        if dw_kinds is not None:
+            from test_gpu_dw_choices import dw_kernel, tiles
+            got = [dw_kernel(eng, l, lambda: eng.train(x[:B], t[:B])) for l in range(1, L)]
+            assert [k for _, k in got] == dw_kinds, (case, [(len(rows), k) for rows, k in got])
+            assert [len(rows) for rows, _ in got] == [tiles(ls, l, 128 if k == "k_dw2" else 64)
+                                                      for l, k in zip(range(1, L), dw_kinds)]
     finally:
         eng.close()
     assert not bad, case + "\n" + "\n".join(bad)
@@ -141,8 +150,11 @@ def test_config5_net(pkg, monkeypatch):
 
 
 def test_global_bunch_1024(pkg, monkeypatch):
-    """2827-2048^3-257, B = 1024, MMSE: the global-bunch k_dwp variant, weight decay of the gradient's order"""
-    run_case(pkg, monkeypatch, "B1024 MMSE", [2827, 2048, 2048, 2048, 257], 1024, DECAY, 2.0, 0, seed=7)
+    """2827-2048^3-257, B = 1024, MMSE, weight decay of the gradient's order.  On one device 1024 frames are sixteen
+    64-frame units, which dwp_usable() does not admit (1, 2, 4, 8): every layer runs k_dw<1> over sixteen chunks, one
+    workgroup per 64 x 64 tile.  (k_dwp<16> runs only over gathered factors: tests/test_gpu_dw_choices.py.)"""
+    run_case(pkg, monkeypatch, "B1024 MMSE", [2827, 2048, 2048, 2048, 257], 1024, DECAY, 2.0, 0, seed=7,
+             dw_kinds=["k_dw1"] * 4)
 
 
 RAGGED = [(1, NO_MOM, 2.0, 0, None), (7, SHIPPED, 1.2, 1, None), (33, DECAY, 1.2, 1, None),
@@ -153,6 +165,33 @@ RAGGED = [(1, NO_MOM, 2.0, 0, None), (7, SHIPPED, 1.2, 1, None), (33, DECAY, 1.2
 def test_ragged_shapes(pkg, monkeypatch, B, hp, beta, ml, lrate2):
     """531-97-33-1-257: no dimension a multiple of 32 or 64, a one-unit hidden layer, ragged bunches"""
     run_case(pkg, monkeypatch, "ragged B%d" % B, [531, 97, 33, 1, 257], B, hp, beta, ml, lrate2=lrate2, seed=B)
+
+
+RAGGED_LS = [531, 97, 33, 1, 257]
+RAGGED_KINDS_128 = ["k_dw2", "k_dw2", "k_dw", "k_dw2"]      # 33 -> 1 is one workgroup at either tile size
+
+
+@pytest.mark.parametrize("B,hp,beta,ml,lrate2", [r for r in RAGGED if r[0] in (7, 96, 200)])
+def test_ragged_shapes_with_128_tiles(pkg, monkeypatch, B, hp, beta, ml, lrate2):
+    """MLGGD_DW_TILE=2: k_dw<2> (128 x 128 tiles, 128-frame chunks staged in two passes of 64 rows) on the ragged net --
+    Bp = 32: one short chunk; 96: one chunk, the second pass masked from row 96; 224: 128 + 96"""
+    run_case(pkg, monkeypatch, "ragged B%d DW_TILE=2" % B, RAGGED_LS, B, hp, beta, ml, lrate2=lrate2, seed=B,
+             env={"MLGGD_DW_TILE": "2"}, dw_kinds=RAGGED_KINDS_128)
+
+
+def test_ragged_shapes_with_128_tiles_unfused(pkg, monkeypatch):
+    """k_dw<2, false> + k_apply_update + k_bias_apply (the unfused launch carries no stamps: the fused cases above and
+    tests/test_gpu_dw_choices.py assert that this configuration selects k_dw<2>)"""
+    B, hp, beta, ml, lrate2 = RAGGED[3]
+    assert B == 96
+    run_case(pkg, monkeypatch, "ragged B96 DW_TILE=2 unfused", RAGGED_LS, B, hp, beta, ml, lrate2=lrate2, seed=B,
+             env={"MLGGD_DW_TILE": "2"}, fake_allreduce=True)
+
+
+def test_128_tiles_where_k_dwp_would_run(pkg, monkeypatch):
+    """MLGGD_DW_PERSIST=0 with MLGGD_DW_TILE=2 at B = 128: k_dw<2> over exactly one full chunk"""
+    run_case(pkg, monkeypatch, "DW_PERSIST=0 DW_TILE=2", [531, 300, 130, 257], 128, DECAY, 1.2, 1, seed=13,
+             env={"MLGGD_DW_PERSIST": "0", "MLGGD_DW_TILE": "2"}, dw_kinds=["k_dw2"] * 3)
 
 
 def test_forced_tile64(pkg, monkeypatch):

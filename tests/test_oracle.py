@@ -385,6 +385,36 @@ def test_data_parallel_form_of_the_twin_is_the_same_step_in_another_order(pyorac
     assert not np.array_equal(a1, ad)                                     # 4 x 16 frames by wavefront sums: other bits
 
 
+def test_a_world_of_one_rank_sums_its_statistic_like_a_rank(pyoracle, synth):
+    """set_gemm_order(dp_world=1, dp_one_rank=True): the emulated world of ONE rank (BPGpu.fake_world(1, ...)) -- nothing
+    meets, but the ML statistic goes through k_colsum's wavefront reduction: the plain twin up to rounding, other bits;
+    MMSE has no statistic and is the plain twin; every later set_gemm_order call switches it off again."""
+    ls, B = [3 * 37, 70, 45, 37], 96
+    ws, bs = synth.make_weights(ls, seed=3)
+    inp, targ = synth.make_frames(2 * B, 37, 3, seed=4)
+
+    def run(ml, beta, **kw):
+        pyoracle.set_gemm_order("hip", 3, **kw)
+        try:
+            o = pyoracle.OracleNet(ls, B, *HP, beta, ml, ws, bs)
+            assert o.train(inp, targ) == 2
+            r = (o.get_weights()[0], o.tensor("scalefactor").copy())
+            o.close()
+            return r
+        finally:
+            pyoracle.set_gemm_order("ref")
+
+    w1, a1 = run(1, 1.2)
+    wr, ar = run(1, 1.2, dp_world=1, dp_allreduce=True, dp_one_rank=True)
+    assert relmax(a1, ar) < 1e-5 and not np.array_equal(a1, ar)
+    assert all(relmax(x, y) < 2e-6 for x, y in zip(w1, wr))
+    w2, a2 = run(1, 1.2)
+    assert np.array_equal(a1, a2) and all(np.array_equal(x, y) for x, y in zip(w1, w2))
+    m1, _ = run(0, 2.0)
+    mr, _ = run(0, 2.0, dp_world=1, dp_allreduce=True, dp_one_rank=True)
+    assert all(np.array_equal(x, y) for x, y in zip(m1, mr))
+
+
 def test_dropout_in_the_oracle(pyoracle, synth):
     """a25 (BP_GPU.cu:344-355, 484-501) in the oracle: omit-probabilities of 0 change nothing (bit for bit); otherwise the
     input / hidden activations are zeroed at the stated rates with NO rescale, another seed gives another mask, the same
