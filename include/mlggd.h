@@ -281,7 +281,9 @@ int mlggd_enhance_waves_scored(mlggd_handle h, int fs_khz, int fea_context, cons
  * than 40 dB below the loudest removed, 15 third-octave bands of 512-point spectra, segments of 30 frames, clipping at
  * -15 dB.  stoi_samples[u] (NULL: all) = the leading samples of utterance u that are scored, 0 <= stoi_samples[u] <=
  * its samples.  An utterance with fewer than 30 frames left after the removal (too short, a silent clean wave,
- * stoi_samples[u] = 0) has no value: stoi[u] = NaN and segments[u] = 0; that is not an error.  segments (optional)
+ * stoi_samples[u] = 0) has no value: stoi[u] = NaN and segments[u] = 0; that is not an error.  Nor has one whose
+ * processed wave is exactly zero in a band over a whole segment (a muted output): NaN with segments[u] counted.
+ * segments (optional)
  * [n_utts] receives the number of 30-frame segments behind each value.  An utterance's value depends on that utterance
  * alone: the same bits whatever its neighbours, its position, the batch, max_cache_frames and the run.  NULL pointers,
  * decreasing offsets, a stoi_samples[u] out of range and a bad fs_khz are MLGGD_ERR_ARG (the message names the

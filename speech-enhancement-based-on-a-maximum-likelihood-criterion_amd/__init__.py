@@ -501,7 +501,8 @@ def stoi_waves(cleans, procs, fs_khz=16, device=0, stoi_samples=None, return_seg
     """STOI [n] float32 (Taal et al. 2011) of the processed int16 waves procs[u] against the clean int16 waves
     cleans[u], in one pass over the device (mlggd_stoi_waves).  stoi_samples[u] = the leading samples that are scored
     (None: as many as both waves have).  NaN where the utterance has no value: fewer than 30 frames after the silent
-    ones are removed.  return_segments: (stoi, segments [n] int32), the 30-frame segments behind each value."""
+    ones are removed, or a processed band of exact zeros over a whole segment (segments still counted).
+    return_segments: (stoi, segments [n] int32), the 30-frame segments behind each value."""
     procs = [_wave(w) for w in procs]
     n = len(procs)
     clean = _clean_like(cleans, procs)

@@ -210,8 +210,13 @@ __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_stoi_bands(
     }
 }
 
+// min(a, b) for b >= 0 that keeps a NaN in a, as the definition's minimum does (fminf would drop it and return b): a
+// band of exact zeros over a segment has alpha = inf and alpha Y = NaN, and the utterance then has no value
+__device__ __forceinline__ float stoi_min_keep_nan(float a, float b) { return b < a ? b : a; }
+
 // grid: n_utts workgroups of 64 * SCORE_UTT_WAVES threads.  clip = (float) 10^(15/20).  Fewer than STOI_SEG compacted
-// frames: stoi = NaN, segments = 0.
+// frames: stoi = NaN, segments = 0.  A band of a segment whose processed signal is exactly zero: stoi = NaN with the
+// segments counted.
 __global__ void __launch_bounds__(64 * SCORE_UTT_WAVES) k_stoi_utt(const StoiUtt *__restrict__ utt,
                                                                    const int *__restrict__ kept,
                                                                    const float *__restrict__ Xb,
@@ -245,13 +250,13 @@ __global__ void __launch_bounds__(64 * SCORE_UTT_WAVES) k_stoi_utt(const StoiUtt
             float sy = 0.0f;
             for (int f = 0; f < STOI_SEG; f++) {
                 const float a = X[f * STOI_BANDS];
-                sy += fminf(alpha * Y[f * STOI_BANDS], a + a * clip);
+                sy += stoi_min_keep_nan(alpha * Y[f * STOI_BANDS], a + a * clip);
             }
             const float mx = sx / (float)STOI_SEG, my = sy / (float)STOI_SEG;
             float sxx = 0.0f, syy = 0.0f, sxy = 0.0f;
             for (int f = 0; f < STOI_SEG; f++) {
                 const float a = X[f * STOI_BANDS];
-                const float xn = a - mx, yn = fminf(alpha * Y[f * STOI_BANDS], a + a * clip) - my;
+                const float xn = a - mx, yn = stoi_min_keep_nan(alpha * Y[f * STOI_BANDS], a + a * clip) - my;
                 sxx += xn * xn;
                 syy += yn * yn;
                 sxy += xn * yn;

@@ -6,7 +6,11 @@ stoi64 is the published algorithm in float64 (numpy's FFT, numpy's sums).  stoi3
 it: every operation in float32 (the FFT in the kernels' radix-2 form, spec64.fft32), only log10 in double, and the
 reductions in the kernels' order (a lane's strided partial sum, the 64-lane xor butterfly, 16 per-wave partials and a
 halving tree).  Both return a Result; `value` is NaN and `segments` 0 when the utterance is too short or its clean wave
-is silent.
+is silent.  A segment in which a band of the processed signal is exactly zero has alpha = inf and alpha Y = NaN, which
+the minimum keeps: `value` is NaN, with the segments still counted.
+
+Hooks for the tests: `kept` replaces the kept frames' list (in the order given: what a wrong scan would have written)
+and `clip=False` leaves the minimum out.
 
 Steps: resample both waves to 10 kHz by p/q with a Kaiser-windowed sinc; drop the frames (256 samples, hop 128, open
 Hann window) whose clean energy is more than 40 dB below the loudest and overlap-add the kept ones; 512-point spectra
@@ -131,8 +135,9 @@ def _cut(clean, proc, samples):
     return clean[:n], proc[:n]
 
 
-def stoi64(clean, proc, fs_khz=16, samples=None, proc_gain=1.0):
-    """proc_gain: a gain on the processed signal applied in float64, after the int16 samples were read"""
+def stoi64(clean, proc, fs_khz=16, samples=None, proc_gain=1.0, kept=None, clip=True):
+    """proc_gain: a gain on the processed signal applied in float64, after the int16 samples were read; kept: the kept
+    frames' indices in compacted order instead of the rule's; clip=False: Y' = alpha Y, without the minimum"""
     clean, proc = _cut(clean, proc, samples)
     x, y = resample(clean, fs_khz), resample(proc, fs_khz) * proc_gain
     l10, w = x.size, window()
@@ -145,11 +150,12 @@ def stoi64(clean, proc, fs_khz=16, samples=None, proc_gain=1.0):
         rel = e - e.max() + DYN_DB
     keep = rel > 0
     margin = float(np.abs(rel[np.isfinite(rel)]).min()) if np.isfinite(rel).any() else float("inf")
-    kept = int(keep.sum())
+    idx = np.flatnonzero(keep) if kept is None else np.asarray(kept, np.int64)
+    kept = int(idx.size)
     if kept == 0:
         return _nan_result(l10, F, 0, 0, margin)
     xs, ys = np.zeros((kept - 1) * K + N), np.zeros((kept - 1) * K + N)
-    for i, t in enumerate(np.flatnonzero(keep)):
+    for i, t in enumerate(idx):
         xs[i * K:i * K + N] += xf[t]
         ys[i * K:i * K + N] += yf[t]
     M = n_frames(xs.size)
@@ -163,13 +169,14 @@ def stoi64(clean, proc, fs_khz=16, samples=None, proc_gain=1.0):
     d, min_var = [], float("inf")
     for m in range(SEG - 1, M):
         Xs, Ys = X[:, m - SEG + 1:m + 1], Y[:, m - SEG + 1:m + 1]
-        alpha = np.sqrt((Xs * Xs).sum(axis=1, keepdims=True) / (Ys * Ys).sum(axis=1, keepdims=True))
-        Yp = np.minimum(alpha * Ys, Xs + Xs * c)
-        xn, yn = Xs - Xs.mean(axis=1, keepdims=True), Yp - Yp.mean(axis=1, keepdims=True)
-        nx, ny = np.sqrt((xn * xn).sum(axis=1)), np.sqrt((yn * yn).sum(axis=1))
-        min_var = min(min_var, float((nx / np.sqrt((Xs * Xs).sum(axis=1))).min()),
-                      float((ny / np.sqrt((Yp * Yp).sum(axis=1))).min()))
-        d.append(((xn / nx[:, None]) * (yn / ny[:, None])).sum(axis=1))
+        with np.errstate(divide="ignore", invalid="ignore"):      # a zero band: alpha = inf, alpha Y = NaN, kept
+            alpha = np.sqrt((Xs * Xs).sum(axis=1, keepdims=True) / (Ys * Ys).sum(axis=1, keepdims=True))
+            Yp = np.minimum(alpha * Ys, Xs + Xs * c) if clip else alpha * Ys
+            xn, yn = Xs - Xs.mean(axis=1, keepdims=True), Yp - Yp.mean(axis=1, keepdims=True)
+            nx, ny = np.sqrt((xn * xn).sum(axis=1)), np.sqrt((yn * yn).sum(axis=1))
+            min_var = min(min_var, float((nx / np.sqrt((Xs * Xs).sum(axis=1))).min()),
+                          float((ny / np.sqrt((Yp * Yp).sum(axis=1))).min()))
+            d.append(((xn / nx[:, None]) * (yn / ny[:, None])).sum(axis=1))
     d = np.array(d)
     return Result(float(d.mean()), l10, F, kept, M, M - SEG + 1, margin, min_var)
 
@@ -233,7 +240,8 @@ def _bands32(P):
     return out
 
 
-def stoi32(clean, proc, fs_khz=16, samples=None):
+def stoi32(clean, proc, fs_khz=16, samples=None, kept=None):
+    """kept: as in stoi64"""
     clean, proc = _cut(clean, proc, samples)
     x, y = resample(clean, fs_khz, F32), resample(proc, fs_khz, F32)
     l10, w = x.size, window().astype(F32)
@@ -251,8 +259,8 @@ def stoi32(clean, proc, fs_khz=16, samples=None):
         rel = (e - e.max()) + F32(DYN_DB)
     keep = rel > 0
     margin = float(np.abs(rel[np.isfinite(rel)]).min()) if np.isfinite(rel).any() else float("inf")
-    idx = np.flatnonzero(keep)
-    kept = idx.size
+    idx = np.flatnonzero(keep) if kept is None else np.asarray(kept, np.int64)
+    kept = int(idx.size)
     M = max(kept - 1, 0)
     if M < SEG:
         return _nan_result(l10, F, kept, M, margin)
@@ -275,8 +283,9 @@ def stoi32(clean, proc, fs_khz=16, samples=None):
     ex, ey, sx = z.copy(), z.copy(), z.copy()
     for f in range(SEG):
         ex, ey, sx = ex + Xs[..., f] * Xs[..., f], ey + Ys[..., f] * Ys[..., f], sx + Xs[..., f]
-    alpha = np.sqrt(ex / ey)
-    Yp = np.minimum(alpha[..., None] * Ys, Xs + Xs * c)
+    with np.errstate(divide="ignore", invalid="ignore"):          # a zero band: as in stoi64
+        alpha = np.sqrt(ex / ey)
+        Yp = np.minimum(alpha[..., None] * Ys, Xs + Xs * c)
     sy = z.copy()
     for f in range(SEG):
         sy = sy + Yp[..., f]

@@ -57,12 +57,16 @@ def check_inputs(models):
             assert m64.min_var > 1e-3, m64
 
 
-def check_case(name, got, seg, models):
-    """the GPU's values against stoi64 with the model's bound; prints the case's row of the table"""
-    valued = [u for u, (m64, _) in enumerate(models) if m64.segments]
+def check_case(name, got, seg, models, muted=()):
+    """the GPU's values against stoi64 with the model's bound; prints the case's row of the table.  muted: the rows
+    whose processed wave has a band of exact zeros over a whole segment: NaN by the definition, with segments counted"""
+    valued = [u for u, (m64, _) in enumerate(models) if m64.segments and u not in muted]
     for u, (m64, _) in enumerate(models):
         assert int(seg[u]) == m64.segments, (name, u)
-        assert np.isnan(got[u]) == (m64.segments == 0), (name, u)
+        if u in muted:
+            assert m64.segments > 0 and np.isnan(m64.value) and np.isnan(got[u]), (name, u, got[u])
+        else:
+            assert np.isnan(got[u]) == (m64.segments == 0), (name, u)
     dm = max(abs(models[u][1].value - models[u][0].value) for u in valued)
     dg = max(abs(float(got[u]) - models[u][0].value) for u in valued)
     print("stoi table | %-34s | model %.3g | GPU %.3g" % (name, dm, dg))

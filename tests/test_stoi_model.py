@@ -1,6 +1,8 @@
 """CPU: the float64 definition of STOI (tests/stoi64.py) and its float32 restatement: the band table against the
 original script's rule, the resampling filter, and properties of the value on a synthetic utterance (1 s at 16 kHz, a
-speech-like signal with two gaps 70 dB down: 77 frames, 65 kept, 35 segments)."""
+speech-like signal with two gaps 70 dB down: 77 frames, 65 kept, 35 segments); and, for the inputs of
+tests/test_gpu_stoi_edges.py (tests/stoi_cases.py): that a wrong order of the kept frames would exceed the GPU's
+allowance, the counts of the sparse utterances, and the rule for a processed band of exact zeros."""
 import os
 import re
 
@@ -8,6 +10,7 @@ import numpy as np
 import pytest
 
 import stoi64
+import stoi_cases as sc
 
 FS = 16
 
@@ -97,6 +100,65 @@ def test_float32_follows_float64(fs):
         assert (a.frames, a.kept, a.segments) == (b.frames, b.kept, b.segments) and a.kept < a.frames
         assert abs(a.value - b.value) < 2e-6
     assert abs(stoi64.stoi32(c, c, fs).value - 1.0) < 2e-6
+
+
+# ---- the inputs of tests/test_gpu_stoi_edges.py (tests/stoi_cases.py)
+def test_a_wrong_scan_order_exceeds_the_allowance():
+    """case A keeps frames 247..263 and 503..519: three kept lists that a broken scan of k_stoi_select would write
+    have the right count, so the segment count cannot see them; each moves the value by more than the GPU is allowed
+    (16 x the model distance of the batch A is scored in)"""
+    fs = 16
+    _, _, models = sc.rows(sc.trips_batch(fs))
+    allowance = 16.0 * sc.model_distance(models)
+    assert 2.0 ** -25 <= allowance / 16.0 < 2e-7
+    true = list(range(247, 264)) + list(range(503, 520))
+    swapped = list(true)
+    i = swapped.index(sc.TRIP)
+    swapped[i - 1], swapped[i] = swapped[i], swapped[i - 1]                    # frames 255 and 256 change places
+    neighbour = list(true)
+    neighbour[i] = 264                                                         # trip 2's first kept frame: the nearest dropped one
+    trip2 = [t for t in true if sc.TRIP <= t < 2 * sc.TRIP]
+    carry = list(true)
+    carry[i:i + len(trip2)] = [0] * len(trip2)                                 # trip 2 written from offset 0: its own
+    carry[:len(trip2)] = trip2                                                 # places keep a cleared buffer's frame 0
+    for snr in (5, -5):
+        c, p = sc.case_a(fs, snr)
+        m64, m32 = sc.models(sc.case_a, fs, snr)
+        assert m64.kept == len(true) and stoi64.stoi64(c, p, fs, kept=true).value == m64.value
+        assert stoi64.stoi32(c, p, fs, kept=true).value == m32.value
+        for name, kept in (("swapped", swapped), ("neighbour", neighbour), ("carry", carry)):
+            assert len(kept) == len(true) and kept != true
+            for f in (stoi64.stoi64, stoi64.stoi32):
+                r = f(c, p, fs, kept=kept)
+                assert r.segments == m64.segments
+                assert abs(r.value - m64.value) > allowance, (name, snr, f.__name__, r.value, m64.value, allowance)
+
+
+@pytest.mark.parametrize("fs", [8, 16])
+def test_counts_of_the_sparse_utterances(pkg, fs):
+    """bursts of one frame keep 2 frames each, a burst of a frame and a half 3: 32, 31 and 30 kept of 300 frames; the
+    compacted frames and segments of a kept count are those mlggd_stoi_layout gives an utterance of that many frames"""
+    for variant, (ones, longs) in sc.C_VARIANTS.items():
+        assert 2 * ones + 3 * longs == variant
+        c, _ = sc.case_c(fs, variant)
+        for m in sc.models(sc.case_c, fs, variant):
+            assert (m.len10, m.frames) == pkg.stoi_layout(c.size, fs_khz=fs)[:2] and m.frames == 300
+            assert (m.kept, m.M) == (variant, variant - 1)
+            assert m.segments == pkg.stoi_layout(stoi64.shortest_with_frames(m.kept, fs), fs_khz=fs)[2] == variant - 30
+            assert np.isnan(m.value) == (variant == 30)
+        assert pkg.stoi_layout(c.size, fs_khz=fs)[2] == 300 - 30               # the bound: every frame kept
+
+
+def test_a_zero_band_over_a_segment_has_no_value():
+    """the definition: sum Y^2 = 0 in a band of a segment -> alpha = inf, alpha Y = NaN, the minimum keeps it"""
+    fs = 16
+    plain = sc.models(sc.case_e, fs, 0)[0]
+    assert plain.segments == 125 and np.isfinite(plain.value)
+    for kind in (1, 2):
+        for m in sc.models(sc.case_e, fs, kind):
+            assert np.isnan(m.value) and (m.frames, m.kept, m.M, m.segments) == (155, 155, 154, 125)
+    for m in sc.models(sc.case_e, fs, 3):
+        assert np.isfinite(m.value) and m.segments == 125 and 0.2 < m.value < plain.value
 
 
 def test_samples_is_the_cut(clean):
