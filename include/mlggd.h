@@ -447,6 +447,59 @@ int mlggd_get_shapefactors(mlggd_handle h, float *betas /* [D] */);
  * finite are MLGGD_ERR_ARG with "PATH line N: ..." as the message; so are a NULL pointer, D < 1 and an unreadable
  * file. */
 int mlggd_read_shapefactors(const char *path, int D, float fallback, float *betas /* [D] */);
+
+/* ---- global variance equalisation (Xu, Du, Dai and Lee 2015; no counterpart in the reference).  A regression net
+ * trained under MMSE or ML over-smooths: per bin the variance of its output is smaller than the clean target's.  The
+ * post-filter is one factor per bin (or one for all bins) multiplied onto the NORMALISED network output before it is
+ * de-normalised.  The rule is csrc/gv_rule.h.
+ *
+ * mlggd_output_stats / mlggd_output_stats_frames mirror mlggd_error_stats / _frames: the chunk is loaded WITH its
+ * targets, the CV forward runs per bunch (trailing partial bunch included) and one kernel per bunch folds the bunch
+ * into sums kept on the device.  Per element y = slab sum + bias in fp32 (the bits mlggd_forward returns), t the fp32
+ * target; on return
+ *   sums[0][d] = sum y    sums[1][d] = sum y*y    sums[2][d] = sum t    sums[3][d] = sum t*t       (sums is [4][D])
+ * every term formed in double from the fp32 value.  OVERWRITTEN, not accumulated: the statistics are additive, a
+ * caller with several chunks adds the arrays.  Two calls return the same bits and the two entries return the same
+ * bits for the same rows; 4 * D doubles come back, nothing of size n x D.  n_frames / n_samples == 0 returns zeros.
+ * NULL pointers and a shape mismatch are MLGGD_ERR_ARG; an engine with a communicator or an emulated world, or with
+ * dropoutflag != 0, and the _frames entry on a NAT engine (the expanded entry works there) are MLGGD_ERR_STATE.  All
+ * are found before any device call and the engine stays usable and unchanged. */
+int mlggd_output_stats(mlggd_handle h, int n_frames, const float *in, const float *targ, double *sums /* [4][D] */);
+int mlggd_output_stats_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat, const float *targ,
+                              int n_samples, const int32_t *first_frame, int targ_offset, double *sums /* [4][D] */);
+/* mlggd_gv_fit: host only, no device, all in double with + - * / sqrt alone: the fit to sums over n samples (added
+ * over the chunks by the caller).  mu = S1/n, r2 = S2/n, gv = r2 - mu*mu for the outputs (gv_est) and the targets
+ * (gv_ref); eta[d] = (float)sqrt(gv_ref[d] / gv_est[d]).  A bin with gv_est <= 0 or gv_ref <= 0 (a constant output, a
+ * constant target, n == 1) has no fit: eta 1, fitted 0.  The shared factor is the same expressions on the sums of the
+ * fitted bins, added in bin order, over n times the number of fitted bins (n * D when every bin has a fit) samples:
+ * the paper's dimension-independent factor.  No fitted bin: eta_shared 1, fitted_shared 0.  Every output pointer is
+ * optional.  n <= 0, D < 1 and NULL sums are MLGGD_ERR_ARG. */
+int mlggd_gv_fit(int D, int64_t n, const double *sums /* [4][D] */, double *gv_est, double *gv_ref, float *eta,
+                 uint8_t *fitted, double *gv_est_shared, double *gv_ref_shared, float *eta_shared,
+                 int32_t *fitted_shared);
+/* mlggd_set_gv: with a vector set, every decoder that de-normalises the net's output -- mlggd_enhance_wave, _waves,
+ * _scored, _scored_stoi and mlggd_live_push -- forms  v = ((y * eta[k]) / inv_std[k]) + mean[k],  three IEEE fp32
+ * operations from left to right; lps_out and the scores are those of the equalised rows, which are what is
+ * synthesised.  A vector of exact ones gives the bits of an engine without factors.  mlggd_lps_to_wave,
+ * mlggd_score_waves, mlggd_forward*, CV, training and mlggd_error_stats* / mlggd_output_stats* are not affected.
+ * The upload is ordered after everything already enqueued and takes effect from the next decode call or push; the
+ * weights, the momentum buffers, the scalefactor and the shape factors stay as they are.  eta NULL: off, the launches
+ * of an engine that never had a vector.  An eta[d] that is not positive and finite is MLGGD_ERR_ARG, found before any
+ * device call, the message names the bin, and the engine stays unchanged.  Works on sigmoid, ReLU and NAT engines.
+ * A live group reads the engine's factors at each push: its bit-identity with mlggd_enhance_wave refers to the
+ * factors in effect and holds while they do not change during a recording.
+ * mlggd_get_gv returns the D values in effect: ones when off. */
+int mlggd_set_gv(mlggd_handle h, const float *eta /* [D], NULL: off */);
+int mlggd_get_gv(mlggd_handle h, float *eta /* [D]; ones when off */);
+/* mlggd_read_gv: host only, no device.  Reads D factors from a plain white-space separated list of exactly D numbers,
+ * or from the file MLGGD_GVFILE writes: '#' lines are skipped ('# shared_eta X' is remembered), the rows
+ * `d gv_ref gv_est eta` must be rows 0..D-1 in order and field 4 of row d is bin d's factor.  A `nan` marks a bin
+ * without a fit and takes 1.  shared != 0 fills all bins with the file's shared_eta (nan: 1); a plain list has none.
+ * A file counts as the trainer's when a '#' line precedes its first number or its first data line has four or more
+ * fields and starts with 0.  A wrong row or number count, a row out of order, a field that is no number, a value that
+ * is not positive and finite and a file that cannot be read are MLGGD_ERR_ARG with "PATH line N: ..." as the
+ * message; a NULL pointer and D < 1 are MLGGD_ERR_ARG too. */
+int mlggd_read_gv(const char *path, int D, int shared, float *eta /* [D] */);
 int mlggd_set_lrate(mlggd_handle h, float lrate);
 int mlggd_get_activation(mlggd_handle h, int *act); /* MLGGD_ACT_* the engine was created with */
 /* CV metrics: on = the three sums are formed on the device (per-tile partials in double, combined

@@ -71,6 +71,7 @@ EXPORTS = [
     "mlggd_live_layout", "mlggd_live_open", "mlggd_live_push", "mlggd_live_received", "mlggd_live_close",
     "mlggd_error_stats", "mlggd_error_stats_frames", "mlggd_ggd_fit",
     "mlggd_set_shapefactors", "mlggd_get_shapefactors", "mlggd_read_shapefactors",
+    "mlggd_output_stats", "mlggd_output_stats_frames", "mlggd_gv_fit", "mlggd_set_gv", "mlggd_get_gv", "mlggd_read_gv",
     "mlggd_wave_samples", "mlggd_mix_waves", "mlggd_lps_stats", "mlggd_norm_from_stats",
     "mlggd_load_waves", "mlggd_cv_all_waves", "mlggd_set_noise", "mlggd_train_waves",
     "mlggd_load_frames_nat", "mlggd_train_frames_nat", "mlggd_cv_all_frames_nat", "mlggd_forward_frames_nat",
@@ -84,10 +85,11 @@ _lib = None
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
-                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "mix.hip.h",
+                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "outstats.hip.h", "gv_rule.h", "mix.hip.h",
                                              "mix_rule.h", "nat_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
+    srcs.append(os.path.join(_HERE, "host", "gvfile.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -183,6 +185,12 @@ def load():
     L.mlggd_set_shapefactors.argtypes = [C.c_void_p, _fp]
     L.mlggd_get_shapefactors.argtypes = [C.c_void_p, _fp]
     L.mlggd_read_shapefactors.argtypes = [C.c_char_p, C.c_int, C.c_float, _fp]
+    L.mlggd_output_stats.argtypes = [C.c_void_p, C.c_int, _fp, _fp, _dp]
+    L.mlggd_output_stats_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, _dp]
+    L.mlggd_gv_fit.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _fp, _bp, _dp, _dp, _fp, _ip]
+    L.mlggd_set_gv.argtypes = [C.c_void_p, _fp]
+    L.mlggd_get_gv.argtypes = [C.c_void_p, _fp]
+    L.mlggd_read_gv.argtypes = [C.c_char_p, C.c_int, C.c_int, _fp]
     L.mlggd_wave_samples.argtypes = [C.c_int, C.c_int, C.c_int, _lp, _ip, _lp]
     L.mlggd_mix_waves.argtypes = [C.c_int, C.c_int, _sp, _lp, _sp, C.c_int64, _lp, _lp, _lp, _dp, _sp, _dp, _ip]
     L.mlggd_lps_stats.argtypes = [C.c_int, C.c_int, C.c_int, _sp, _lp, _dp, _lp]
@@ -635,6 +643,36 @@ def read_shapefactors(path, D, fallback):
     return b
 
 
+GvFit = collections.namedtuple("GvFit", "gv_est gv_ref eta fitted gv_est_shared gv_ref_shared eta_shared fitted_shared")
+
+
+def gv_fit(n, sums):
+    """Fit of the global variance equalisation factors to the [4][D] sums of BPGpu.output_stats over n samples (added
+    over the chunks by the caller): a GvFit of gv_est, gv_ref [D] float64 (variances of the normalised outputs and
+    targets), eta [D] float32 = sqrt(gv_ref / gv_est), fitted [D] bool (False where a variance is not positive: eta 1
+    there), and the same four for the factor shared by all bins.  A host call: needs no device (mlggd_gv_fit)."""
+    s = np.ascontiguousarray(sums, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != 4:
+        raise ValueError("sums must be [4][D]")
+    D = s.shape[1]
+    _dp = C.POINTER(C.c_double)
+    est, ref, eta, fitted = np.zeros(D), np.zeros(D), np.ones(D, np.float32), np.zeros(D, np.uint8)
+    est_s, ref_s, eta_s, fit_s = C.c_double(0), C.c_double(0), C.c_float(1), C.c_int32(0)
+    d = lambda a: a.ctypes.data_as(_dp)
+    _check(load().mlggd_gv_fit(D, int(n), d(s), d(est), d(ref), _p(eta), fitted.ctypes.data_as(C.POINTER(C.c_uint8)),
+                               C.byref(est_s), C.byref(ref_s), C.byref(eta_s), C.byref(fit_s)))
+    return GvFit(est, ref, eta, fitted.astype(bool), est_s.value, ref_s.value, np.float32(eta_s.value), bool(fit_s.value))
+
+
+def read_gv(path, D, shared=False):
+    """[D] float32 equalisation factors from a plain list of D numbers or from the file MLGGD_GVFILE writes (its eta
+    column; a bin without a fit takes 1; shared=True: the file's shared factor in every bin).  A host call: needs no
+    device (mlggd_read_gv); a malformed file raises MlggdError naming the line."""
+    e = np.empty(int(D), np.float32)
+    _check(load().mlggd_read_gv(None if path is None else os.fsencode(path), int(D), 1 if shared else 0, _p(e)))
+    return e
+
+
 def comm_unique_id():
     buf = (C.c_char * UNIQUE_ID_BYTES)()
     _check(load().mlggd_comm_unique_id(buf))
@@ -799,6 +837,27 @@ class BPGpu:
         _check(load().mlggd_error_stats_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
                                                first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset), b.size,
                                                _p(b), sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    # -- global variance equalisation: per-bin sums of y, y^2, t, t^2 over a CV chunk, formed on the device (gv_fit fits them)
+    def output_stats(self, inp, targ):
+        """[4][D] float64: sum y, y^2, t, t^2 per output bin over the rows of inp / targ, y = forward(inp)
+        (mlggd_output_stats).  Additive over chunks."""
+        inp, targ = _f32(inp), _f32(targ)
+        n = inp.shape[0]
+        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
+            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
+        sums = np.zeros((4, self.D), np.float64)
+        _check(load().mlggd_output_stats(self._h, n, _p(inp), _p(targ), sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def output_stats_frames(self, feat, targ, first_frame, fea_context, targ_offset):
+        """The same over a frame-stream chunk (mlggd_output_stats_frames): the same bits for the same rows."""
+        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
+        sums = np.zeros((4, self.D), np.float64)
+        _check(load().mlggd_output_stats_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
+                                                first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset),
+                                                sums.ctypes.data_as(C.POINTER(C.c_double))))
         return sums
 
     def forward_frames(self, feat, first_frame, fea_context):
@@ -1074,6 +1133,22 @@ class BPGpu:
             return
         b = _f32(betas, (self.D,))
         _check(load().mlggd_set_shapefactors(self._h, _p(b)))
+
+    def gv(self):
+        """The D equalisation factors in effect: the vector of set_gv, else ones."""
+        e = np.empty(self.D, np.float32)
+        _check(load().mlggd_get_gv(self._h, _p(e)))
+        return e
+
+    def set_gv(self, eta):
+        """One global variance equalisation factor per output bin, applied by every wave decoder and live push from
+        the next call on: v = ((y * eta) / inv_std) + mean.  None: off.  Weights, momentum, scalefactor and shape
+        factors stay (mlggd_set_gv)."""
+        if eta is None:
+            _check(load().mlggd_set_gv(self._h, None))
+            return
+        e = _f32(eta, (self.D,))
+        _check(load().mlggd_set_gv(self._h, _p(e)))
 
     def set_lrate(self, lrate):
         _check(load().mlggd_set_lrate(self._h, float(lrate)))

@@ -22,6 +22,7 @@
 
 #include "../../include/mlggd.h"
 #include "../host/errmodel.h"  // parse_shapefactors: one file format, one reader and one writer
+#include "../host/gvfile.h"    // parse_gv: the same for the global variance file
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
@@ -30,6 +31,8 @@
 #include "live.hip.h"
 #include "live_rule.h"
 #include "errstats.hip.h"
+#include "outstats.hip.h"
+#include "gv_rule.h"
 #include "mix.hip.h"
 #include "mix_rule.h"
 #include "nat_rule.h"
@@ -217,6 +220,12 @@ struct mlggd_engine {
     int cv_device = 0;
     DevBuf<double> cv_partial;
     DevBuf<double> es_acc;  // mlggd_error_stats: [4 + MLGGD_MAX_BETAS][D] sums of the call, allocated on first use
+    DevBuf<double> os_acc;  // mlggd_output_stats: [4][D] sums of the call, allocated on first use
+    // mlggd_set_gv: one equalisation factor per output bin (gv_rule.h).  gv_dev [D] exists from the first set on and is
+    // only read by the decoders while gv_on; gv_host [D] is what mlggd_get_gv returns.
+    bool gv_on = false;
+    DevBuf<float> gv_dev;
+    std::vector<float> gv_host;
     int chunk_frames = 0;
     float *in_bunch = nullptr;
     float *in_bunch_buf[2] = {nullptr, nullptr};  // in_bunch alternates between them when bunches are staged ahead
@@ -1982,6 +1991,55 @@ int mlggd_read_shapefactors(const char *path, int D, float fallback, float *beta
     return MLGGD_OK;
 }
 
+// ------------------------------------------------------------------ global variance equalisation (gv_rule.h)
+int mlggd_set_gv(mlggd_handle e, const float *eta) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!eta) {  // decode calls already made have enqueued their launches with the factors they saw
+        e->gv_on = false;
+        e->gv_host.clear();
+        return MLGGD_OK;
+    }
+    for (int d = 0; d < e->D; d++)
+        if (!(eta[d] > 0.0f) || !std::isfinite(eta[d]))
+            return fail(MLGGD_ERR_ARG, "eta[%d] = %g: a factor must be positive and finite", d, (double)eta[d]);
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(e->gv_dev.grow((size_t)e->D, (size_t)e->D, e->bufs, nullptr, nullptr));
+    // on the engine's stream: behind every decode already enqueued, which may still read the previous vector
+    HIPCHK(hipMemcpyAsync(e->gv_dev.p, eta, (size_t)e->D * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->gv_host.assign(eta, eta + e->D);
+    e->gv_on = true;
+    return MLGGD_OK;
+}
+
+int mlggd_get_gv(mlggd_handle e, float *eta) {
+    if (!e || !eta) return fail(MLGGD_ERR_ARG, "NULL argument");
+    for (int d = 0; d < e->D; d++) eta[d] = e->gv_on ? e->gv_host[d] : 1.0f;
+    return MLGGD_OK;
+}
+
+int mlggd_read_gv(const char *path, int D, int shared, float *eta) {
+    if (!path || !eta) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    std::string err;
+    if (!mlggd_host::parse_gv(path, D, shared != 0, eta, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    return MLGGD_OK;
+}
+
+// Host only, no device: the per-bin and the shared factor from the sums of mlggd_output_stats.
+int mlggd_gv_fit(int D, int64_t n, const double *sums, double *gv_est, double *gv_ref, float *eta, uint8_t *fitted,
+                 double *gv_est_shared, double *gv_ref_shared, float *eta_shared, int32_t *fitted_shared) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n <= 0) return fail(MLGGD_ERR_ARG, "n %lld: the fit needs at least one sample", (long long)n);
+    if (!sums) return fail(MLGGD_ERR_ARG, "sums is NULL");
+    const gv_rule::Fit s = gv_rule::fit_all(D, n, sums, gv_est, gv_ref, eta, fitted);
+    if (gv_est_shared) *gv_est_shared = s.gv_est;
+    if (gv_ref_shared) *gv_ref_shared = s.gv_ref;
+    if (eta_shared) *eta_shared = s.eta;
+    if (fitted_shared) *fitted_shared = s.fitted ? 1 : 0;
+    return MLGGD_OK;
+}
+
 int mlggd_set_cv_device_reduce(mlggd_handle e, int on) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     e->cv_device = on ? 1 : 0;
@@ -2569,10 +2627,10 @@ static int check_betas(int n_betas, const float *betas) {
             return fail(MLGGD_ERR_ARG, "betas[%d] = %g: a shape must be positive and finite", k, (double)betas[k]);
     return MLGGD_OK;
 }
-static int error_stats_state(mlggd_engine *e, const char *who) {
+static int error_stats_state(mlggd_engine *e, const char *who, const char *what = "the error model is") {
     if (e->comm || e->fake_world) return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
     if (e->cfg.dropoutflag != 0)
-        return fail(MLGGD_ERR_STATE, "%s: the error model is not available with dropoutflag = %d", who, e->cfg.dropoutflag);
+        return fail(MLGGD_ERR_STATE, "%s: %s not available with dropoutflag = %d", who, what, e->cfg.dropoutflag);
     return MLGGD_OK;
 }
 // The chunk (inputs AND targets) is resident: the CV forward per bunch, trailing partial bunch included, each
@@ -2627,6 +2685,56 @@ int mlggd_error_stats_frames(mlggd_handle e, int n_frames, int fea_context, cons
         return MLGGD_OK;
     }
     return error_stats_resident(e, n_samples, n_betas, betas, sums);
+}
+
+// ------------------------------------------------------------------ output statistics (outstats.hip.h)
+// error_stats_resident with k_out_stats in the place of k_err_stats: the CV forward per bunch, trailing partial bunch
+// included, each followed by ONE k_out_stats launch that folds the bunch into os_acc; one download, one synchronise.
+static int output_stats_resident(mlggd_engine *e, int n, double *sums) {
+    const int D = e->D;
+    const size_t n_acc = (size_t)gv_rule::kRows * D;
+    HIPCHK(e->os_acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
+    OutStatsArgs a;
+    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
+    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.acc = e->os_acc.p;
+    for (int i = 0; i < n; i += e->B) {
+        const int fb = (e->B > n - i) ? (n - i) : e->B;
+        const Bunch bn = bunch_at(e, i);
+        CHK(run_forward(e, bn, fb, false));
+        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = i == 0;
+        hipLaunchKernelGGL(k_out_stats, dim3(e->Dp / OS_DT), dim3(256), 0, e->stream, a);
+        CHK(launch_check("k_out_stats"));
+    }
+    HIPCHK(hipMemcpyAsync(sums, e->os_acc.p, n_acc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_output_stats(mlggd_handle e, int n_frames, const float *in, const float *targ, double *sums) {
+    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    CHK(check_frames(e, n_frames));
+    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
+    CHK(error_stats_state(e, "mlggd_output_stats", "the output statistics are"));
+    if (n_frames == 0) {
+        std::fill(sums, sums + (size_t)gv_rule::kRows * e->D, 0.0);
+        return MLGGD_OK;
+    }
+    CHK(mlggd_load_chunk(e, n_frames, in, targ));
+    return output_stats_resident(e, n_frames, sums);
+}
+
+int mlggd_output_stats_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                              int n_samples, const int32_t *first_frame, int targ_offset, double *sums) {
+    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
+    CHK(error_stats_state(e, "mlggd_output_stats_frames", "the output statistics are"));
+    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
+    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
+    if (n_samples == 0) {
+        std::fill(sums, sums + (size_t)gv_rule::kRows * e->D, 0.0);
+        return MLGGD_OK;
+    }
+    return output_stats_resident(e, n_samples, sums);
 }
 
 // Host only, no device: moments, ML scale and profile log-likelihood of the GGD error model from the sums of
@@ -3298,9 +3406,15 @@ int launch_analysis_seg(const SpecPlan *p, const int16_t *wave, const long long 
     return launch_check("k_lps_analysis_seg");
 }
 
+// eta (optional, with mean): the equalisation factors of gv_rule.h; without them the launch is the one it always was
 int launch_synthesis(const SpecPlan *p, const float *src, const float *mean, const float *inv, const float2 *X, int t0,
-                     int nf, float *blk, hipStream_t st, float *lps_den = nullptr) {
+                     int nf, float *blk, hipStream_t st, float *lps_den = nullptr, const float *eta = nullptr) {
     if (nf == 0) return MLGGD_OK;
+    if (eta) {
+        hipLaunchKernelGGL(k_lps_synthesis_gv, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, eta, X,
+                           t0, nf, p->d, p->win, p->tw, p->tws, kSpecFloor, blk, lps_den);
+        return launch_check("k_lps_synthesis_gv");
+    }
     hipLaunchKernelGGL(k_lps_synthesis, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, X, t0, nf,
                        p->d, p->win, p->tw, p->tws, kSpecFloor, blk, lps_den);
     return launch_check("k_lps_synthesis");
@@ -3362,17 +3476,22 @@ int check_single_device(const mlggd_engine *e, const char *who, bool no_comm) {
 // One decode chunk: n output frames read through windows of ctx rows over a stream of `rows` rows.  The idle raw set is
 // borrowed, fill(set) writes its stream and first_frame (and nat_row on a NAT engine, whose samples then read the
 // noise table `nat`), the set becomes current, the net runs and its n rows are resynthesised against X into blk from
-// frame t0 on (lps_den: the de-normalised rows, optional).  The set is marked in use until that has run.
+// frame t0 on (lps_den: the de-normalised rows, optional; eta: the equalisation factors in effect, or nullptr).  The
+// set is marked in use until that has run.
+// the factors a decode call or push applies: those of mlggd_set_gv while they are on
+const float *gv_factors(const mlggd_engine *e) { return e->gv_on ? e->gv_dev.p : nullptr; }
+
 template <typename Fill>
 int decode_chunk(mlggd_engine *e, const SpecPlan *p, int rows, int n, int ctx, const Fill &fill, const float *nat,
-                 const float *mean, const float *inv, const float2 *X, int t0, float *blk, float *lps_den) {
+                 const float *mean, const float *inv, const float *eta, const float2 *X, int t0, float *blk,
+                 float *lps_den) {
     mlggd_engine::RawSet *r;
     CHK(raw_set_acquire(e, rows, n, ctx, 0, false, &r));
     CHK(fill(r));
     raw_set_commit(e, rows, n, ctx, 0);
     if (e->nat_frames) e->nat = nat;
     CHK(forward_resident(e, n));
-    CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, t0, n, blk, e->stream, lps_den));
+    CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, t0, n, blk, e->stream, lps_den, eta));
     HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, e->stream));
     return MLGGD_OK;
 }
@@ -3623,7 +3742,7 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
     for (int a = 0; a < F; a += cap) {
         const int n = std::min(cap, F - a);
         auto fill = [&](mlggd_engine::RawSet *r) { return load_frames_device(e, r, dl, F, a, n, fea_context, mean, inv); };
-        CHK(decode_chunk(e, p, n + fea_context - 1, n, fea_context, fill, natz, mean, inv, X, a, blk, nullptr));
+        CHK(decode_chunk(e, p, n + fea_context - 1, n, fea_context, fill, natz, mean, inv, gv_factors(e), X, a, blk, nullptr));
     }
     return ola_to_host(p, blk, F, out, out_f32, st);
 }
@@ -3761,7 +3880,7 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
                                (const int *)d_utt, n_utts, a, n, r->nat_row.p);
             return launch_check("k_nat_rows_seg");
         };
-        CHK(decode_chunk(e, p, sp.rows, n, fea_context, fill, natz, mean, inv, X, a, blk, den));
+        CHK(decode_chunk(e, p, sp.rows, n, fea_context, fill, natz, mean, inv, gv_factors(e), X, a, blk, den));
     }
     hipLaunchKernelGGL(k_ola_seg, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, blk, d_foff, d_ooff, n_utts,
                        p->d, p->win, of, oi, (long long)n_out);
@@ -4148,7 +4267,7 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
                                dv.dk_off, dv.dk_slot, n_dk, d.D, a, n, sp.u0, sp.u1, ctx, mean, inv, r->feat.p, r->first.p);
             return launch_check("k_live_stream");
         };
-        CHK(decode_chunk(e, p, sp.rows, n, ctx, fill, nullptr, mean, inv, X_dec, a, blk_new, nullptr));
+        CHK(decode_chunk(e, p, sp.rows, n, ctx, fill, nullptr, mean, inv, gv_factors(e), X_dec, a, blk_new, nullptr));
     }
     if (n_emit > 0) {
         hipLaunchKernelGGL(k_live_ola, dim3((unsigned)((n_emit + 255) / 256)), dim3(256), 0, st, s->blk[c0].p, blk_new,

@@ -4,6 +4,7 @@
 //   k_lps_analysis   int16 frames -> window -> real N-point FFT in LDS -> log power rows (and the complex spectrum X)
 //   k_lps_stream     LPS rows -> (lps - mean) * inv_std, edge-replicated context stream for the forward pass
 //   k_lps_synthesis  LPS rows, or the forward pass's outputs de-normalised, + X -> noisy phase, inverse FFT, window
+//                    (k_lps_synthesis_gv: de-normalised with the equalisation factors of gv_rule.h)
 //   k_ola            overlap-add of the windowed time blocks, / sum w^2, float and saturated int16 output
 //
 // The *_seg kernels are the same steps over a packed batch of utterances (mlggd_enhance_waves): global frame g of
@@ -21,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gv_rule.h"    // gv_rule::apply
 #include "spec_rule.h"  // SpecDims
 
 #define SPEC_FRAMES 4     // frames (= wavefronts) per workgroup
@@ -181,14 +183,16 @@ __global__ void k_lps_stream_seg(const float *__restrict__ lps, const int *__res
 }
 
 // Frames [t0, t0 + nf): target LPS row r = src[(t - t0) * D + k] (de-normalised first when mean != nullptr: y / inv +
-// mean, two IEEE operations), noisy spectrum X [t][k] -> windowed time block blk [t][L].  lps_den (optional, with
-// mean): receives the de-normalised rows, [t][D].
-__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float *__restrict__ src, const float *__restrict__ mean,
-                                                                    const float *__restrict__ inv, const float2 *__restrict__ X,
-                                                                    int t0, int nf, SpecDims d, const float *__restrict__ win,
-                                                                    const float2 *__restrict__ tw,
-                                                                    const float2 *__restrict__ tws, float floor_exp,
-                                                                    float *__restrict__ blk, float *__restrict__ lps_den) {
+// mean, two IEEE operations; GV: (y * eta) / inv + mean, gv_rule::apply), noisy spectrum X [t][k] -> windowed time block
+// blk [t][L].  lps_den (optional, with mean): receives the de-normalised rows, [t][D].  The body of k_lps_synthesis
+// (GV = false: eta is never read) and of k_lps_synthesis_gv.
+template <bool GV>
+__device__ __forceinline__ void lps_synthesis_frames(const float *__restrict__ src, const float *__restrict__ mean,
+                                                     const float *__restrict__ inv, const float *__restrict__ eta,
+                                                     const float2 *__restrict__ X, int t0, int nf, SpecDims d,
+                                                     const float *__restrict__ win, const float2 *__restrict__ tw,
+                                                     const float2 *__restrict__ tws, float floor_exp,
+                                                     float *__restrict__ blk, float *__restrict__ lps_den) {
     __shared__ float s_yr[SPEC_FRAMES][SPEC_MAXM + 1], s_yi[SPEC_FRAMES][SPEC_MAXM + 1];
     __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -199,7 +203,10 @@ __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float 
     // magnitude substitution, LogSpec2Wav.c:481-494, 683-696
     for (int k = lane; k < d.D; k += 64) {
         float v = live ? src[(size_t)(live ? r : 0) * d.D + k] : 0.0f;
-        if (mean) {
+        if (GV) {  // always de-normalising: the factors belong to the net's outputs
+            v = gv_rule::apply(v, eta[k], inv[k], mean[k]);
+            if (lps_den && live) lps_den[t * d.D + k] = v;
+        } else if (mean) {
             const float q = v / inv[k];
             v = q + mean[k];
             if (lps_den && live) lps_den[t * d.D + k] = v;
@@ -240,6 +247,24 @@ __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float 
         const float v = (n & 1) ? -im[spec_pad(m)] * scale : re[spec_pad(m)] * scale;  // rifft divides by N
         blk[t * d.L + n] = v * win[n];                                                  // OLA_KIND 1: window again
     }
+}
+
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis(const float *__restrict__ src, const float *__restrict__ mean,
+                                                                    const float *__restrict__ inv, const float2 *__restrict__ X,
+                                                                    int t0, int nf, SpecDims d, const float *__restrict__ win,
+                                                                    const float2 *__restrict__ tw,
+                                                                    const float2 *__restrict__ tws, float floor_exp,
+                                                                    float *__restrict__ blk, float *__restrict__ lps_den) {
+    lps_synthesis_frames<false>(src, mean, inv, nullptr, X, t0, nf, d, win, tw, tws, floor_exp, blk, lps_den);
+}
+
+// the same with the global variance equalisation factors eta [D] of the engine (mlggd_set_gv); mean and inv are given
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis_gv(
+    const float *__restrict__ src, const float *__restrict__ mean, const float *__restrict__ inv,
+    const float *__restrict__ eta, const float2 *__restrict__ X, int t0, int nf, SpecDims d,
+    const float *__restrict__ win, const float2 *__restrict__ tw, const float2 *__restrict__ tws, float floor_exp,
+    float *__restrict__ blk, float *__restrict__ lps_den) {
+    lps_synthesis_frames<true>(src, mean, inv, eta, X, t0, nf, d, win, tw, tws, floor_exp, blk, lps_den);
 }
 
 // One thread per output sample i of F S + L - S: the frames that cover it, in frame order, then / sum w^2 (formed in

@@ -113,6 +113,14 @@ void BP_GPU::ErrorStats_frames(int n_frames, int fea_context, const float *feat,
                                    betas, sums),
           "mlggd_error_stats_frames");
 }
+void BP_GPU::OutputStats(int n, const float *in, const float *targ, double *sums) {
+    check(mlggd_output_stats(h_, n, in, targ, sums), "mlggd_output_stats");
+}
+void BP_GPU::OutputStats_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
+                                const int *first_frame, int targ_offset, double *sums) {
+    check(mlggd_output_stats_frames(h_, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset, sums),
+          "mlggd_output_stats_frames");
+}
 void BP_GPU::setShapefactors(const float *betas) { check(mlggd_set_shapefactors(h_, betas), "mlggd_set_shapefactors"); }
 void BP_GPU::returnWeights(float **weights, float **bias) {
     check(mlggd_get_weights(h_, weights, bias), "mlggd_get_weights");

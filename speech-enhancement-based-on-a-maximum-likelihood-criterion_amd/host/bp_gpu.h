@@ -36,6 +36,11 @@ class BP_GPU {
     void ErrorStats(int n_frames, const float *in, const float *targ, int n_betas, const float *betas, double *sums);
     void ErrorStats_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
                            const int *first_frame, int targ_offset, int n_betas, const float *betas, double *sums);
+    // output statistics of a CV chunk (not in the reference): sums [4][D] of y, y^2, t, t^2 per output bin, overwritten;
+    // see mlggd_output_stats.  Needs a single-device engine without dropout.
+    void OutputStats(int n_frames, const float *in, const float *targ, double *sums);
+    void OutputStats_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
+                            const int *first_frame, int targ_offset, double *sums);
     // one shape per output bin from the next step or CV call on (not in the reference; MLflag 1 only), nullptr: back
     // to `shapefactor`; see mlggd_set_shapefactors
     void setShapefactors(const float *betas);

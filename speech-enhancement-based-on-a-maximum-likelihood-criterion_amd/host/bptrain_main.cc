@@ -17,6 +17,12 @@
 // FILE (errmodel.h); one stdout line names the file and the shared beta -- the value for `shapefactor`.  The
 // command line, the log file and the weights do not change.
 //
+// Global variance (new, opt-in): with MLGGD_GVFILE=FILE rank 0 makes one more pass over the CV chunks after the error
+// model's (both may be set in one run), adds their output statistics (mlggd_output_stats: per-bin sums of y, y^2, t,
+// t^2 of the normalised outputs and targets), fits the equalisation factors per bin and shared (mlggd_gv_fit) and
+// writes FILE (gvfile.h) for the decoders' gv=FILE; one stdout line names the file and the shared factor.  The command
+// line, the log file and the weights do not change.
+//
 // Per-bin shapes (new, opt-in): with MLGGD_SHAPEFACTORS=FILE every rank reads one shape per output bin from FILE -- a
 // plain list of D numbers or the file MLGGD_ERRMODEL wrote in an earlier epoch (its best_beta column; a bin without a
 // fit takes the file's shared beta, else `shapefactor`) -- and sets it on the engine before the first chunk
@@ -49,6 +55,7 @@
 #include "bp_gpu.h"
 #include "dp_launch.h"
 #include "errmodel.h"
+#include "gvfile.h"
 #include "prefetch.h"
 #include "trainer_io.h"
 
@@ -162,6 +169,8 @@ int main(int argc, char *argv[]) {
         if (errmodel_fn && !*errmodel_fn) errmodel_fn = nullptr;
         std::vector<float> errmodel_betas;  // a bad grid ends the run here, not after the epoch
         if (errmodel_fn && rank == 0) errmodel_betas = mlggd_host::beta_grid(getenv("MLGGD_ERRMODEL_BETAS"));
+        const char *gv_fn = getenv("MLGGD_GVFILE");
+        if (gv_fn && !*gv_fn) gv_fn = nullptr;
         const char *shapes_fn = getenv("MLGGD_SHAPEFACTORS");
         if (shapes_fn && !*shapes_fn) shapes_fn = nullptr;
         std::vector<float> shapes;  // a bad file or a beta-norm run ends here, before anything is trained
@@ -362,6 +371,33 @@ int main(int argc, char *argv[]) {
                 const double shared = mlggd_host::write_error_model(errmodel_fn, D, n_total, errmodel_betas, total);
                 printf("error model: %s written, %lld CV samples, shared beta %.9g\n", errmodel_fn, (long long)n_total, shared);
                 phase("error model", t_phase);
+            }
+
+            // ---- global variance of the CV set (MLGGD_GVFILE): one more pass, nothing of it reaches the log
+            if (gv_fn && (p->dropoutflag != 0 || world > 1)) {
+                printf("global variance: MLGGD_GVFILE is not available %s; %s is not written\n",
+                       p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", gv_fn);
+            } else if (gv_fn) {
+                std::vector<double> total((size_t)4 * D, 0.0), part(total.size());
+                int64_t n_total = 0;
+                for (unsigned i = 0; i < io->cv_total_chunks; i++) {
+                    progress("global variance");
+                    int n;
+                    if (frames) {
+                        n = io->Readchunk_frames_cv((int)i);
+                        net->OutputStats_frames(p->chunk_frames[0], p->fea_context, p->frames_in[0], p->frames_targ[0], n,
+                                                p->first_frame[0], p->targ_offset, part.data());
+                    } else {
+                        n = io->Readchunk_cv((int)i);
+                        net->OutputStats(n, p->indata[0], p->targ[0], part.data());
+                    }
+                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
+                    n_total += n;
+                }
+                if (n_total == 0) throw IoError(std::string("MLGGD_GVFILE: the CV set has no samples, ") + gv_fn + " is not written");
+                const float shared = mlggd_host::write_gv_file(gv_fn, D, n_total, total);
+                printf("global variance: %s written, %lld CV samples, shared eta %.9g\n", gv_fn, (long long)n_total, (double)shared);
+                phase("global variance", t_phase);
             }
         }
         printf("all finish!\n");

@@ -10,9 +10,13 @@
 //
 //   enhance_lps wts=mlp.50.wts norm_file=train_noisy.norm in=noisy.lps out=enhanced.htk
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [scp=list of "in out" lines] [activation=sigmoid|relu] [nat=T]
+//               [gv=FILE [gv_mode=bin|shared]]
 // activation: the hidden units the net was trained with (BPtrain_Sigmoid / BPtrain_ReLU); the .wts file does not say.
 // nat=T: the net was trained noise-aware (csrc/nat_rule.h): every input row ends in the mean of the file's first T
 // normalised frames, layersizes[0] = (fea_context + 1) x the feature dimension; the .wts file does not say that either.
+// gv=FILE: global variance equalisation (csrc/gv_rule.h): output bin j of the net is multiplied by the factor FILE
+// holds for it (a plain list or the file an epoch with MLGGD_GVFILE=FILE wrote; gv_mode=shared: the file's one factor
+// for all bins) before it is de-normalised.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -33,7 +37,7 @@ using tool_io::read_htk;
 using tool_io::write_htk;
 
 int main(int argc, char **argv) {
-    std::string wts, norm_file, in, out, scp;
+    std::string wts, norm_file, in, out, scp, gv, gv_mode = "bin";
     int ctx = 7, gpu = 0, bunch = 512, act = MLGGD_ACT_SIGMOID, nat = 0;
     for (int a = 1; a < argc; a++) {
         const std::string arg(argv[a]);
@@ -50,9 +54,11 @@ int main(int argc, char **argv) {
         else if (k == "bunchsize") bunch = atoi(v.c_str());
         else if (k == "activation") act = tool_io::parse_activation(v);
         else if (k == "nat") nat = tool_io::parse_nat(v);
+        else if (k == "gv") gv = v;
+        else if (k == "gv_mode") gv_mode = v;
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
-        die("usage: enhance_lps wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] [activation=sigmoid|relu] [nat=T]");
+        die("usage: enhance_lps wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] [activation=sigmoid|relu] [nat=T] [gv=FILE [gv_mode=bin|shared]]");
     if (ctx < 1 || ctx % 2 == 0) die("fea_context must be odd");
 
     // ---- model: the trainer's .wts container (Interface.cc:484-516)
@@ -68,6 +74,7 @@ int main(int argc, char **argv) {
     tool_io::read_norm(norm_file, dim, mean, inv);
     if (D % dim) die("output dimension is not a multiple of the feature dimension");
 
+    const std::vector<float> eta = tool_io::read_gv_arg(gv, gv_mode, D);  // a bad file ends the run before the engine exists
     mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act, nat);
 
     std::vector<std::pair<std::string, std::string>> jobs;
@@ -104,7 +111,12 @@ int main(int argc, char **argv) {
         } else if (mlggd_forward_frames(h, np, ctx, stream.data(), n, first.data(), y.data()) != MLGGD_OK)
             die(std::string("mlggd_forward_frames: ") + mlggd_last_error());
         for (int t = 0; t < n; t++)
-            for (int j = 0; j < D; j++) y[(size_t)t * D + j] = y[(size_t)t * D + j] / inv[j % dim] + mean[j % dim];  // decode.m:59-61
+            for (int j = 0; j < D; j++) {  // decode.m:59-61; with gv= the factor first (csrc/gv_rule.h), one rounding each
+                const float v = y[(size_t)t * D + j];
+                const float s = eta.empty() ? v : v * eta[j];
+                const float q = s / inv[j % dim];
+                y[(size_t)t * D + j] = q + mean[j % dim];
+            }
         write_htk(job.second, y.data(), n, D);
         printf("%s -> %s (%d frames)\n", job.first.c_str(), job.second.c_str(), n);
     }

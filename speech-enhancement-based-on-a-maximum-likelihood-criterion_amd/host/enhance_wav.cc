@@ -7,7 +7,12 @@
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
 //               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu] [nat=T]
+//               [gv=FILE [gv_mode=bin|shared]]
 //
+// gv=FILE: global variance equalisation (csrc/gv_rule.h): the normalised network output of bin k is multiplied by the
+// factor FILE holds for it -- a plain list or the file an epoch with MLGGD_GVFILE=FILE wrote -- before it is
+// de-normalised, in every mode (mlggd_set_gv); gv_mode=shared takes the file's one factor for all bins.  A .wts file
+// does not say how it is to be post-filtered.  The reports are those of the equalised rows.
 // activation: the hidden units the net was trained with (BPtrain_Sigmoid / BPtrain_ReLU); the .wts file does not say.
 // nat=T: the net was trained noise-aware (csrc/nat_rule.h): its input rows end in the mean of the utterance's first T
 // normalised frames, layersizes[0] = (fea_context + 1) x bins; the .wts file does not say that either.  Not with live=.
@@ -85,11 +90,11 @@ void report(const Item &it, const float *y) {
 }
 
 int main(int argc, char **argv) {
-    std::string wts, norm_file, in, out, scp, clean, info, score = "host";
+    std::string wts, norm_file, in, out, scp, clean, info, score = "host", gv, gv_mode = "bin";
     const char *usage =
         "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
         "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu] "
-        "[nat=T]";
+        "[nat=T] [gv=FILE [gv_mode=bin|shared]]";
     int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64, act = MLGGD_ACT_SIGMOID, nat = 0;
     bool live = false, score_given = false, want_stoi = false;
     double batch_s = 300.0;
@@ -115,6 +120,8 @@ int main(int argc, char **argv) {
         else if (k == "sessions") n_slots = atoi(v.c_str());
         else if (k == "activation") act = tool_io::parse_activation(v);
         else if (k == "nat") nat = tool_io::parse_nat(v);
+        else if (k == "gv") gv = v;
+        else if (k == "gv_mode") gv_mode = v;
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
@@ -140,7 +147,9 @@ int main(int argc, char **argv) {
     if (nat == 0 && model.ls[0] != ctx * D) die("layersizes[0] is not fea_context x the output dimension");
     std::vector<float> mean, inv;
     tool_io::read_norm(norm_file, D, mean, inv);
+    const std::vector<float> eta = tool_io::read_gv_arg(gv, gv_mode, D);  // a bad file ends the run before the engine exists
     mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act, nat);
+    if (!eta.empty() && mlggd_set_gv(h, eta.data()) != MLGGD_OK) die(std::string("mlggd_set_gv: ") + mlggd_last_error());
 
     std::vector<Job> jobs;
     if (!scp.empty()) {
@@ -386,7 +395,11 @@ int main(int argc, char **argv) {
                     die(std::string("mlggd_forward_frames_nat: ") + mlggd_last_error());
             } else if (mlggd_forward_frames(h, np, ctx, stream.data(), F, first.data(), y.data()) != MLGGD_OK)
                 die(std::string("mlggd_forward_frames: ") + mlggd_last_error());
-            for (size_t i = 0; i < y.size(); i++) y[i] = y[i] / inv[i % D] + mean[i % D];
+            for (size_t i = 0; i < y.size(); i++) {  // csrc/gv_rule.h: one rounding per operation
+                const float s = eta.empty() ? y[i] : y[i] * eta[i % D];
+                const float q = s / inv[i % D];
+                y[i] = q + mean[i % D];
+            }
             report(it, y.data());
         }
     }

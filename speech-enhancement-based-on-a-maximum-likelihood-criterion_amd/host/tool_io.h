@@ -131,6 +131,17 @@ inline int parse_nat(const std::string &v) {
     return (int)t;
 }
 
+// gv=FILE [gv_mode=bin|shared] of the decoding tools: the global variance equalisation factors of the D output bins
+// (mlggd_read_gv: a plain list or the file MLGGD_GVFILE wrote); without gv= no factors (an empty vector)
+inline std::vector<float> read_gv_arg(const std::string &path, const std::string &mode, int D) {
+    if (mode != "bin" && mode != "shared") die("gv_mode=" + mode + ": must be bin or shared");
+    std::vector<float> eta;
+    if (path.empty()) return eta;
+    eta.resize(D);
+    if (mlggd_read_gv(path.c_str(), D, mode == "shared", eta.data()) != MLGGD_OK) die(std::string("gv=") + mlggd_last_error());
+    return eta;
+}
+
 inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_cache_frames = 0,
                                   int activation = MLGGD_ACT_SIGMOID, int nat_frames = 0) {
     const int L = (int)m.ls.size();
