@@ -448,6 +448,54 @@ int mlggd_get_shapefactors(mlggd_handle h, float *betas /* [D] */);
  * file. */
 int mlggd_read_shapefactors(const char *path, int D, float fallback, float *betas /* [D] */);
 
+/* ---- asymmetric GGD error model: a skew per output bin (no counterpart in the reference; csrc/asym_rule.h).  An LPS
+ * regression net over-smooths, so the error e = out - targ of a bin is skewed and a symmetric density spends its
+ * likelihood on a tail that is not there.  Per bin d, with shape beta_d, scale alpha_d and skew kappa_d > 0:
+ *   f(e) = beta / (alpha (kappa + 1/kappa) Gamma(1/beta)) exp(-(s(e) / alpha)^beta),
+ *   s(e) = kappa e (e > 0),  (-e) / kappa (e < 0),  0 (e == 0)   -- one fp32 multiplication or one fp32 division.
+ * kappa > 1 charges over-estimates more, kappa < 1 under-estimates; kappa = 1 is the GGD.  The whole loss chain carries
+ * over with |e| replaced by s(e): p = s^beta, the column sum, alpha = (beta colsum / n)^(1/beta), and the gradient
+ * s^(beta-1) beta / alpha^beta times ds/de (times kappa for e > 0, divided by kappa for e < 0, with the sign).  With a
+ * vector set every loss path (fused and MLGGD_LOSS_FUSE=0, a communicator, the emulated worlds) runs kernels of its
+ * own, k_loss_ml_asym / k_loss_err_asym / k_loss_grad_asym, and both CV log-likelihood paths use s(o - t) / alpha_d
+ * in density3 and take n sum_d logf((kappa_d + 1/kappa_d) / 2) off density1.  Two identities are exact in fp32: a
+ * vector of ones gives the bits of the engine without a vector, and for kappa a power of two the engine with 1/kappa,
+ * the negated last layer and negated targets is the exact mirror image.
+ * mlggd_set_asymmetry is ordered after every step already enqueued, takes effect from the next step or CV call and
+ * leaves the weights, the momentum buffers, the scalefactor and the shape vector alone; it composes with
+ * mlggd_set_shapefactors in either order (without a shape vector every bin has cfg.shapefactor).  kappas NULL: off,
+ * the launches of an engine that never had a vector.  A kappa that is not positive and finite is MLGGD_ERR_ARG, found
+ * before any device call, the message names the bin; MLflag != 1 is MLGGD_ERR_STATE.  In both cases the engine stays
+ * usable and unchanged.  mlggd_get_asymmetry returns the D values in effect: ones when asymmetry is off. */
+int mlggd_set_asymmetry(mlggd_handle h, const float *kappas /* [D], NULL: off */);
+int mlggd_get_asymmetry(mlggd_handle h, float *kappas /* [D] */);
+/* The sufficient statistics of that model: mlggd_error_stats with the power sums split by the sign of e and no moment
+ * rows.  sums is [2 n_betas][D] doubles: row k is P+_k[d] = sum_{e>0} pow(e, beta_k), row n_betas + k is
+ * P-_k[d] = sum_{e<0} pow(-e, beta_k), each term the fp32 value of the trainer's own power widened to double.  Same
+ * arguments, refusals, overwrite-not-accumulate rule and bit-reproducibility as mlggd_error_stats*; additive over
+ * chunks; independent of the shape and skew vectors in effect. */
+int mlggd_error_stats_signed(mlggd_handle h, int n_frames, const float *in, const float *targ, int n_betas,
+                             const float *betas, double *sums /* [2 n_betas][D] */);
+int mlggd_error_stats_signed_frames(mlggd_handle h, int n_frames, int fea_context, const float *feat,
+                                    const float *targ, int n_samples, const int32_t *first_frame, int targ_offset,
+                                    int n_betas, const float *betas, double *sums /* [2 n_betas][D] */);
+/* mlggd_asym_fit: host only, no device, everything in double.  For every bin and grid shape, from n samples per bin:
+ *   kappa = (P- / P+)^(1 / (2 (beta + 1)))                     the ML skew in closed form (asym_rule.h)
+ *   alpha^beta = (beta / n) (kappa^beta P+ + kappa^-beta P-)
+ *   loglik = n [ln beta - ln(kappa + 1/kappa) - lgamma(1/beta) - ln alpha - 1/beta]
+ * kappa, alpha, loglik are [n_betas][D]; best [D] is the argmax over the grid; loglik_shared [n_betas] sums loglik over
+ * the bins and best_shared is its argmax.  Ties go to the lower index.  A bin with P+ == 0 or P- == 0 has no fit:
+ * kappa and loglik NaN, alpha 0, best -1, and it is left out of the shared totals (best_shared -1 when no bin has a
+ * fit).  Every output pointer may be NULL.  D < 1, n < 1, a bad grid and NULL sums are MLGGD_ERR_ARG. */
+int mlggd_asym_fit(int D, int64_t n, int n_betas, const float *betas, const double *signed_sums, double *kappa,
+                   double *alpha, double *loglik, int32_t *best, double *loglik_shared, int32_t *best_shared);
+/* mlggd_read_asymmetry: host only, no device.  Reads D skews from a plain white-space separated list of exactly D
+ * numbers, or from the file MLGGD_ASYMMODEL writes: '#' lines are skipped, the rows `d p_plus p_minus alpha best_beta
+ * best_kappa ...` must be rows 0..D-1 in order and field 6 of row d is bin d's skew; a `nan` there, a bin without a
+ * fit, takes `fallback`.  The same file reads as a shape file through mlggd_read_shapefactors (field 5).  Errors as
+ * mlggd_read_shapefactors: MLGGD_ERR_ARG with "PATH line N: ..." as the message. */
+int mlggd_read_asymmetry(const char *path, int D, float fallback, float *kappas /* [D] */);
+
 /* ---- global variance equalisation (Xu, Du, Dai and Lee 2015; no counterpart in the reference).  A regression net
  * trained under MMSE or ML over-smooths: per bin the variance of its output is smaller than the clean target's.  The
  * post-filter is one factor per bin (or one for all bins) multiplied onto the NORMALISED network output before it is

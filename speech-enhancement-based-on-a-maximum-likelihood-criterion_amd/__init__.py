@@ -76,6 +76,8 @@ EXPORTS = [
     "mlggd_load_waves", "mlggd_cv_all_waves", "mlggd_set_noise", "mlggd_train_waves",
     "mlggd_load_frames_nat", "mlggd_train_frames_nat", "mlggd_cv_all_frames_nat", "mlggd_forward_frames_nat",
     "mlggd_nat_estimate", "mlggd_nat_rows", "mlggd_get_nat_frames",
+    "mlggd_set_asymmetry", "mlggd_get_asymmetry", "mlggd_error_stats_signed", "mlggd_error_stats_signed_frames",
+    "mlggd_asym_fit", "mlggd_read_asymmetry",
 ]
 MAX_BETAS = 32
 
@@ -86,10 +88,11 @@ def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "outstats.hip.h", "gv_rule.h", "mix.hip.h",
-                                             "mix_rule.h", "nat_rule.h", "devbuf.h", "devbuf_rule.h")]
+                                             "mix_rule.h", "nat_rule.h", "asym_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     srcs.append(os.path.join(_HERE, "host", "gvfile.h"))
+    srcs.append(os.path.join(_HERE, "host", "asymfile.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -185,6 +188,12 @@ def load():
     L.mlggd_set_shapefactors.argtypes = [C.c_void_p, _fp]
     L.mlggd_get_shapefactors.argtypes = [C.c_void_p, _fp]
     L.mlggd_read_shapefactors.argtypes = [C.c_char_p, C.c_int, C.c_float, _fp]
+    L.mlggd_set_asymmetry.argtypes = [C.c_void_p, _fp]
+    L.mlggd_get_asymmetry.argtypes = [C.c_void_p, _fp]
+    L.mlggd_error_stats_signed.argtypes = [C.c_void_p, C.c_int, _fp, _fp, C.c_int, _fp, _dp]
+    L.mlggd_error_stats_signed_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, C.c_int, _fp, _dp]
+    L.mlggd_asym_fit.argtypes = [C.c_int, C.c_int64, C.c_int, _fp, _dp, _dp, _dp, _dp, _ip, _dp, _ip]
+    L.mlggd_read_asymmetry.argtypes = [C.c_char_p, C.c_int, C.c_float, _fp]
     L.mlggd_output_stats.argtypes = [C.c_void_p, C.c_int, _fp, _fp, _dp]
     L.mlggd_output_stats_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, _dp]
     L.mlggd_gv_fit.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _fp, _bp, _dp, _dp, _fp, _ip]
@@ -643,6 +652,37 @@ def read_shapefactors(path, D, fallback):
     return b
 
 
+AsymFit = collections.namedtuple("AsymFit", "kappa alpha loglik best loglik_shared best_shared")
+
+
+def asym_fit(n, signed, betas):
+    """Fit of the asymmetric GGD error model to the [2 K][D] sums of BPGpu.error_stats_signed over n samples (added
+    over the chunks by the caller): an AsymFit of kappa, alpha, loglik [K][D] (the closed-form ML skew and scale and
+    the profile log-likelihood per grid shape; NaN / 0 / NaN where a bin has no fit), best [D] (grid index per bin, -1
+    without a fit), loglik_shared [K] and best_shared.  A host call: needs no device (mlggd_asym_fit)."""
+    b = _betas(betas)
+    s = np.ascontiguousarray(signed, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != 2 * b.size:
+        raise ValueError("signed must be [2 * len(betas)][D]")
+    K, D = b.size, s.shape[1]
+    _dp, _i32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
+    kappa, alpha, loglik = np.zeros((K, D)), np.zeros((K, D)), np.zeros((K, D))
+    best, shared, bs = np.zeros(D, np.int32), np.zeros(K), C.c_int32(0)
+    d = lambda a: a.ctypes.data_as(_dp)
+    _check(load().mlggd_asym_fit(D, int(n), K, _p(b), d(s), d(kappa), d(alpha), d(loglik), best.ctypes.data_as(_i32),
+                                 d(shared), C.byref(bs)))
+    return AsymFit(kappa, alpha, loglik, best, shared, bs.value)
+
+
+def read_asymmetry(path, D, fallback=1.0):
+    """[D] float32 skews from a plain list of D numbers or from the file MLGGD_ASYMMODEL writes (its best_kappa column;
+    a bin without a fit takes `fallback`).  A host call: needs no device (mlggd_read_asymmetry); a malformed file
+    raises MlggdError naming the line."""
+    k = np.empty(int(D), np.float32)
+    _check(load().mlggd_read_asymmetry(None if path is None else os.fsencode(path), int(D), float(fallback), _p(k)))
+    return k
+
+
 GvFit = collections.namedtuple("GvFit", "gv_est gv_ref eta fitted gv_est_shared gv_ref_shared eta_shared fitted_shared")
 
 
@@ -838,6 +878,45 @@ class BPGpu:
                                                first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset), b.size,
                                                _p(b), sums.ctypes.data_as(C.POINTER(C.c_double))))
         return sums
+
+    # -- the asymmetric error model: the power sums split by the sign of e (asym_fit fits them), and the skew per bin
+    def error_stats_signed(self, inp, targ, betas):
+        """[2 K][D] float64: rows 0..K-1 sum_{e>0} e^betas[k], rows K..2K-1 sum_{e<0} (-e)^betas[k] per output bin over
+        the rows of inp / targ, e = forward(inp) - targ (mlggd_error_stats_signed).  Additive over chunks."""
+        inp, targ, b = _f32(inp), _f32(targ), _betas(betas)
+        n = inp.shape[0]
+        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
+            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
+        sums = np.zeros((2 * b.size, self.D), np.float64)
+        _check(load().mlggd_error_stats_signed(self._h, n, _p(inp), _p(targ), b.size, _p(b),
+                                               sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def error_stats_signed_frames(self, feat, targ, first_frame, fea_context, targ_offset, betas):
+        """The same over a frame-stream chunk (mlggd_error_stats_signed_frames): the same bits for the same rows."""
+        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
+        b = _betas(betas)
+        sums = np.zeros((2 * b.size, self.D), np.float64)
+        _check(load().mlggd_error_stats_signed_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ),
+                                                      first.size, first.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                      int(targ_offset), b.size, _p(b),
+                                                      sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def asymmetry(self):
+        """The D skews in effect: the vector of set_asymmetry, else ones."""
+        k = np.empty(self.D, np.float32)
+        _check(load().mlggd_get_asymmetry(self._h, _p(k)))
+        return k
+
+    def set_asymmetry(self, kappas):
+        """One skew per output bin from the next step or CV call on (MLflag 1 only); None: off.  Weights, momentum,
+        the current scalefactor and the shape vector stay (mlggd_set_asymmetry)."""
+        if kappas is None:
+            _check(load().mlggd_set_asymmetry(self._h, None))
+            return
+        k = _f32(kappas, (self.D,))
+        _check(load().mlggd_set_asymmetry(self._h, _p(k)))
 
     # -- global variance equalisation: per-bin sums of y, y^2, t, t^2 over a CV chunk, formed on the device (gv_fit fits them)
     def output_stats(self, inp, targ):

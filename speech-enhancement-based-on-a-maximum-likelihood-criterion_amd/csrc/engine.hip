@@ -23,6 +23,7 @@
 #include "../../include/mlggd.h"
 #include "../host/errmodel.h"  // parse_shapefactors: one file format, one reader and one writer
 #include "../host/gvfile.h"    // parse_gv: the same for the global variance file
+#include "../host/asymfile.h"  // parse_asymmetry: the same for the asymmetric error model's file
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
@@ -214,12 +215,19 @@ struct mlggd_engine {
     bool per_bin = false;
     float *betas_dev = nullptr;
     std::vector<float> betas_host;
+    // mlggd_set_asymmetry: one skew per output bin (asym_rule.h).  kappas_dev [Dp] (pads 1.0) and asym_betas_dev [Dp]
+    // (cfg.shapefactor, pads 1.0: the shapes the _asym kernels read on an engine without a shape vector) exist from the
+    // first set on and are only read while asym is on; kappas_host [D] is what mlggd_get_asymmetry returns.
+    bool asym = false;
+    DevBuf<float> kappas_dev, asym_betas_dev;
+    std::vector<float> kappas_host;
     DevBuf<float> chunk_in, chunk_targ, chunk_out;
     // CV metrics: 0 = outputs copied back, host fp32 accumulation in the reference's order (default: it is what
     // the log lines are compared on); 1 = sums formed on the device (k_cv_reduce), nothing of size n x D leaves it
     int cv_device = 0;
     DevBuf<double> cv_partial;
     DevBuf<double> es_acc;  // mlggd_error_stats: [4 + MLGGD_MAX_BETAS][D] sums of the call, allocated on first use
+    DevBuf<double> ess_acc;  // mlggd_error_stats_signed: [2 MLGGD_MAX_BETAS][D] sums of the call, allocated on first use
     DevBuf<double> os_acc;  // mlggd_output_stats: [4][D] sums of the call, allocated on first use
     // mlggd_set_gv: one equalisation factor per output bin (gv_rule.h).  gv_dev [D] exists from the first set on and is
     // only read by the decoders while gv_on; gv_host [D] is what mlggd_get_gv returns.
@@ -1236,6 +1244,9 @@ enum ColsumSource {
 // largest dynamic LDS the loss kernels are ever launched with (bunchsize 1152, the cap mlggd_create enforces)
 constexpr size_t LOSS_LDS_MAX = (size_t)(32 * (1152 + 1) + 32) * sizeof(float);
 
+// the shapes [Dp] the _asym kernels read: the vector of mlggd_set_shapefactors, else cfg.shapefactor per unit
+static const float *asym_betas(const mlggd_engine *e) { return e->per_bin ? e->betas_dev : e->asym_betas_dev.p; }
+
 // Output-layer loss of one minibatch: BP_GPU.cu:408-423.  sa / n_stage: input-staging blocks of the NEXT
 // minibatch that ride along with the first loss launch (n_stage 0: none).
 static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, ColsumSource cs, bool first_acc,
@@ -1261,6 +1272,12 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         la.outT = e->outT; la.eT = e->eT; la.scalefactor = e->scalefactor; la.dEdXt = e->dEdXt[L - 1]; la.dEdX = e->dEdX[L - 1];
         la.first = bn.first; la.toff = e->toff;
         const size_t lds_ml = (size_t)2 * LOSS_DT * (Bp + 1) * sizeof(float);
+        if (e->asym) {  // only ever on with ML == 1 (mlggd_set_asymmetry)
+            CHK(ensure_lds(e, k_loss_ml_asym, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
+            hipLaunchKernelGGL(k_loss_ml_asym, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
+                               asym_betas(e), (const float *)e->kappas_dev.p, e->Dp / LOSS_DT, sa, n_stage);
+            return launch_check("k_loss_ml_asym");
+        }
         if (e->per_bin) {
             CHK(ensure_lds(e, k_loss_ml_bins, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
             hipLaunchKernelGGL(k_loss_ml_bins, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
@@ -1277,7 +1294,11 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
     la.B = B; la.D = e->D; la.Dp = e->Dp; la.Bp = Bp; la.beta = e->cfg.shapefactor; la.want_pow = ML == 1 ? 1 : 0;
     la.outT = e->outT; la.eT = e->eT; la.pT = e->pT;
     la.b_tiles = b_tiles; la.first = bn.first; la.toff = e->toff;
-    if (e->per_bin) {  // only ever on with ML == 1 (mlggd_set_shapefactors)
+    if (e->asym) {  // only ever on with ML == 1 (mlggd_set_asymmetry)
+        hipLaunchKernelGGL(k_loss_err_asym, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, asym_betas(e),
+                           (const float *)e->kappas_dev.p, n_loss, sa);
+        CHK(launch_check("k_loss_err_asym"));
+    } else if (e->per_bin) {  // only ever on with ML == 1 (mlggd_set_shapefactors)
         hipLaunchKernelGGL(k_loss_err_bins, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, (const float *)e->betas_dev,
                            n_loss, sa);
         CHK(launch_check("k_loss_err_bins"));
@@ -1301,6 +1322,13 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         colsum_in = e->colsum;
     }
     if (cs == CS_ACCUMULATE) return MLGGD_OK;
+    if (e->asym) {
+        CHK(ensure_lds(e, k_loss_grad_asym, LOSS_LDS_MAX));
+        hipLaunchKernelGGL(k_loss_grad_asym, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D,
+                           e->Dp, Bp, asym_betas(e), (const float *)e->kappas_dev.p, nf, inv_n, e->scalefactor,
+                           e->dEdXt[L - 1], e->dEdX[L - 1], b_tiles);
+        return launch_check("k_loss_grad_asym");
+    }
     if (e->per_bin) {
         CHK(ensure_lds(e, k_loss_grad_bins, LOSS_LDS_MAX));
         hipLaunchKernelGGL(k_loss_grad_bins, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D,
@@ -1991,6 +2019,51 @@ int mlggd_read_shapefactors(const char *path, int D, float fallback, float *beta
     return MLGGD_OK;
 }
 
+// ------------------------------------------------------------------ asymmetric error model (asym_rule.h)
+int mlggd_set_asymmetry(mlggd_handle e, const float *kappas) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!kappas) {  // steps already enqueued chose their kernels when they were enqueued
+        e->asym = false;
+        e->kappas_host.clear();
+        return MLGGD_OK;
+    }
+    if (e->cfg.MLflag != 1)
+        return fail(MLGGD_ERR_STATE, "a skew per bin needs the ML-GGD loss (MLflag 1), this engine has MLflag %d: a "
+                    "beta-norm has no density to skew", e->cfg.MLflag);
+    for (int d = 0; d < e->D; d++)
+        if (!(kappas[d] > 0.0f) || !std::isfinite(kappas[d]))
+            return fail(MLGGD_ERR_ARG, "kappas[%d] = %g: a skew must be positive and finite", d, (double)kappas[d]);
+    HIPCHK(hipSetDevice(e->device));
+    const size_t Dp = (size_t)e->Dp;
+    const bool first = !e->asym_betas_dev.p;
+    HIPCHK(e->kappas_dev.grow(Dp, Dp, e->bufs, nullptr, nullptr));
+    HIPCHK(e->asym_betas_dev.grow(Dp, Dp, e->bufs, nullptr, nullptr));
+    std::vector<float> padded(Dp, 1.0f), shapes(Dp, 1.0f);
+    std::copy(kappas, kappas + e->D, padded.begin());
+    std::fill(shapes.begin(), shapes.begin() + e->D, e->cfg.shapefactor);
+    // on the engine's stream: behind every step already enqueued, which may still read the previous vector
+    HIPCHK(hipMemcpyAsync(e->kappas_dev.p, padded.data(), Dp * 4, hipMemcpyHostToDevice, e->stream));
+    if (first) HIPCHK(hipMemcpyAsync(e->asym_betas_dev.p, shapes.data(), Dp * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->kappas_host.assign(kappas, kappas + e->D);
+    e->asym = true;
+    return MLGGD_OK;
+}
+
+int mlggd_get_asymmetry(mlggd_handle e, float *kappas) {
+    if (!e || !kappas) return fail(MLGGD_ERR_ARG, "NULL argument");
+    for (int d = 0; d < e->D; d++) kappas[d] = e->asym ? e->kappas_host[d] : 1.0f;
+    return MLGGD_OK;
+}
+
+int mlggd_read_asymmetry(const char *path, int D, float fallback, float *kappas) {
+    if (!path || !kappas) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    std::string err;
+    if (!mlggd_host::parse_asymmetry(path, D, fallback, kappas, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    return MLGGD_OK;
+}
+
 // ------------------------------------------------------------------ global variance equalisation (gv_rule.h)
 int mlggd_set_gv(mlggd_handle e, const float *eta) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
@@ -2409,10 +2482,19 @@ static int cv_accumulate(mlggd_engine *e, int n_frames, const std::function<cons
         }
         *abserr = s / D;
     }
+    // the asymmetric model (asym_rule.h): s(o - t) in the place of |t - o| in density3, and density1 loses
+    // n sum_d logf((kappa_d + 1/kappa_d) / 2), the D fp32 logarithms added in double; exactly 0 at kappa = 1
+    const float *kap = e->asym ? e->kappas_host.data() : nullptr;
+    double kterm = 0;
+    if (loglik && kap) {
+        for (int d = 0; d < D; d++) kterm += (double)asym_rule::log_norm(kap[d]);
+        kterm = kterm * n_frames;
+    }
     if (loglik && e->per_bin) {  // the same three terms with beta_d; density1 is a sum over the bins, kept in double
         const float *betas = e->betas_host.data();
         double d1 = 0;
         for (int d = 0; d < D; d++) d1 += (double)n_frames * logf(betas[d] / (2 * mlggd_gamma((float)(1.0 / betas[d]))));
+        if (kap) d1 = d1 - kterm;
         float density2 = 0, density3 = 0;
         for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
         density2 = density2 * n_frames;
@@ -2420,7 +2502,7 @@ static int cv_accumulate(mlggd_engine *e, int n_frames, const std::function<cons
             const float *t = trow(i), *o = &out[(size_t)i * D];
             for (int d = 0; d < D; d++) {
                 const float err = t[d] - o[d];
-                density3 += powf(fabsf(err) / scalefac[d], betas[d]);
+                density3 += powf((kap ? asym_rule::skewed(o[d] - t[d], kap[d]) : fabsf(err)) / scalefac[d], betas[d]);
             }
         }
         *loglik = (float)d1 - density2 - density3;
@@ -2428,13 +2510,14 @@ static int cv_accumulate(mlggd_engine *e, int n_frames, const std::function<cons
         const float beta = e->cfg.shapefactor;
         float density1, density2 = 0, density3 = 0;
         density1 = n_frames * D * logf(beta / (2 * mlggd_gamma((float)(1.0 / beta))));
+        if (kap) density1 = density1 - (float)kterm;
         for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
         density2 = density2 * n_frames;
         for (int i = 0; i < n_frames; i++) {
             const float *t = trow(i), *o = &out[(size_t)i * D];
             for (int d = 0; d < D; d++) {
                 const float err = t[d] - o[d];
-                density3 += powf(fabsf(err) / scalefac[d], beta);
+                density3 += powf((kap ? asym_rule::skewed(o[d] - t[d], kap[d]) : fabsf(err)) / scalefac[d], beta);
             }
         }
         *loglik = density1 - density2 - density3;
@@ -2461,7 +2544,11 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
         a.alpha = loglik ? e->scalefactor : nullptr;
         a.first = bn.first; a.toff = e->toff; a.b_tiles = b_tiles;
         a.partial = e->cv_partial.p + (size_t)k * tiles * 3;
-        if (loglik && e->per_bin) {
+        if (loglik && e->asym) {
+            hipLaunchKernelGGL(k_cv_reduce_asym, dim3(tiles), dim3(256), 0, e->stream, a, asym_betas(e),
+                               (const float *)e->kappas_dev.p);
+            CHK(launch_check("k_cv_reduce_asym"));
+        } else if (loglik && e->per_bin) {
             hipLaunchKernelGGL(k_cv_reduce_bins, dim3(tiles), dim3(256), 0, e->stream, a, (const float *)e->betas_dev);
             CHK(launch_check("k_cv_reduce_bins"));
         } else {
@@ -2489,6 +2576,11 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
                 const float bd = e->betas_host[d];
                 density1 += (double)n_frames * logf(bd / (2 * mlggd_gamma((float)(1.0 / bd))));
             }
+        }
+        if (e->asym) {  // minus n sum_d logf((kappa_d + 1/kappa_d) / 2), exactly 0 at kappa = 1 (asym_rule.h)
+            double kterm = 0;
+            for (int d = 0; d < D; d++) kterm += (double)asym_rule::log_norm(e->kappas_host[d]);
+            density1 = density1 - kterm * n_frames;
         }
         double density2 = 0;
         for (int u = 0; u < D; u++) density2 += logf(scalefac[u]);
@@ -2685,6 +2777,100 @@ int mlggd_error_stats_frames(mlggd_handle e, int n_frames, int fea_context, cons
         return MLGGD_OK;
     }
     return error_stats_resident(e, n_samples, n_betas, betas, sums);
+}
+
+// error_stats_resident with k_err_stats_signed in the place of k_err_stats: [2 n_betas][D], the rows of P+ then of P-.
+// It does not look at the skew or shape vector in effect: the statistics are of the errors, the grid is the call's.
+static int error_stats_signed_resident(mlggd_engine *e, int n, int n_betas, const float *betas, double *sums) {
+    const int D = e->D;
+    const size_t n_acc = (size_t)2 * MLGGD_MAX_BETAS * D;
+    HIPCHK(e->ess_acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
+    ErrStatsArgs a;
+    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
+    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = e->ess_acc.p;
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < n_betas ? betas[k] : 1.0f;
+    for (int i = 0; i < n; i += e->B) {
+        const int fb = (e->B > n - i) ? (n - i) : e->B;
+        const Bunch bn = bunch_at(e, i);
+        CHK(run_forward(e, bn, fb, false));
+        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = i == 0;
+        hipLaunchKernelGGL(k_err_stats_signed, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
+        CHK(launch_check("k_err_stats_signed"));
+    }
+    HIPCHK(hipMemcpyAsync(sums, e->ess_acc.p, (size_t)2 * n_betas * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_error_stats_signed(mlggd_handle e, int n_frames, const float *in, const float *targ, int n_betas,
+                             const float *betas, double *sums) {
+    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    CHK(check_betas(n_betas, betas));
+    CHK(check_frames(e, n_frames));
+    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
+    CHK(error_stats_state(e, "mlggd_error_stats_signed"));
+    if (n_frames == 0) {
+        std::fill(sums, sums + (size_t)2 * n_betas * e->D, 0.0);
+        return MLGGD_OK;
+    }
+    CHK(mlggd_load_chunk(e, n_frames, in, targ));
+    return error_stats_signed_resident(e, n_frames, n_betas, betas, sums);
+}
+
+int mlggd_error_stats_signed_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                                    int n_samples, const int32_t *first_frame, int targ_offset, int n_betas,
+                                    const float *betas, double *sums) {
+    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    CHK(check_betas(n_betas, betas));
+    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
+    CHK(error_stats_state(e, "mlggd_error_stats_signed_frames"));
+    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
+    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
+    if (n_samples == 0) {
+        std::fill(sums, sums + (size_t)2 * n_betas * e->D, 0.0);
+        return MLGGD_OK;
+    }
+    return error_stats_signed_resident(e, n_samples, n_betas, betas, sums);
+}
+
+// Host only, no device: the closed-form fit of the asymmetric model (asym_rule::fit) for every bin and grid shape from
+// the sums of mlggd_error_stats_signed.  Everything in double; ties go to the lower index; a bin with P+ == 0 or
+// P- == 0 at a shape has no fit there and stays out of that shape's shared total.
+int mlggd_asym_fit(int D, int64_t n, int n_betas, const float *betas, const double *signed_sums, double *kappa,
+                   double *alpha, double *loglik, int32_t *best, double *loglik_shared, int32_t *best_shared) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n <= 0) return fail(MLGGD_ERR_ARG, "n %lld: the fit needs at least one sample", (long long)n);
+    CHK(check_betas(n_betas, betas));
+    if (!signed_sums) return fail(MLGGD_ERR_ARG, "signed_sums is NULL");
+    std::vector<double> shared(n_betas, 0.0);
+    bool any = false;
+    for (int d = 0; d < D; d++) {
+        int arg = -1;
+        double top = 0.0;
+        for (int k = 0; k < n_betas; k++) {
+            const asym_rule::Fit f = asym_rule::fit(signed_sums[(size_t)k * D + d], signed_sums[(size_t)(n_betas + k) * D + d],
+                                                    (double)betas[k], (double)n);
+            if (f.fitted) {
+                shared[k] += f.loglik;
+                any = true;
+                if (arg < 0 || f.loglik > top) {
+                    arg = k;
+                    top = f.loglik;
+                }
+            }
+            if (kappa) kappa[(size_t)k * D + d] = f.kappa;
+            if (alpha) alpha[(size_t)k * D + d] = f.alpha;
+            if (loglik) loglik[(size_t)k * D + d] = f.loglik;
+        }
+        if (best) best[d] = arg;
+    }
+    int arg = -1;
+    if (any)
+        for (int k = 0; k < n_betas; k++)
+            if (arg < 0 || shared[k] > shared[arg]) arg = k;
+    if (loglik_shared) std::copy(shared.begin(), shared.end(), loglik_shared);
+    if (best_shared) *best_shared = arg;
+    return MLGGD_OK;
 }
 
 // ------------------------------------------------------------------ output statistics (outstats.hip.h)

@@ -89,3 +89,54 @@ __global__ __launch_bounds__(256) void k_err_stats(ErrStatsArgs A) {
             if (k < A.K) p[(4 + k) * D] = A.fresh ? pw[k] : p[(4 + k) * D] + pw[k];
     }
 }
+
+// The sufficient statistics of the asymmetric model (asym_rule.h; mlggd_error_stats_signed, mlggd_asym_fit): k_err_stats
+// with the power accumulators split by the sign of e and no moment sums.  For every grid shape k
+//   P+_k[d] = sum_{e > 0} pow_or_self(e, beta_k),   P-_k[d] = sum_{e < 0} pow_or_self(-e, beta_k),
+// acc [2 K][D]: the K rows of P+, then the K rows of P-.  The power is evaluated once per element at fabsf(e), which is
+// e or -e, and a select on the lane's own e sends it to one side and +0.0 to the other (adding +0.0 to a sum of
+// non-negative terms leaves its bits), so the exponent stays wave-uniform.  Same double accumulators, lane order,
+// butterfly and fresh/add rule as k_err_stats; no atomics.  A.acc is [2 K][D] here; the rest of ErrStatsArgs is as it is.
+__global__ __launch_bounds__(256) void k_err_stats_signed(ErrStatsArgs A) {
+    const int tx = threadIdx.x & 31;
+    const int d = (int)blockIdx.x * ES_DT + (int)(threadIdx.x >> 5);  // < Dp: the grid is Dp / ES_DT
+    double pp[MLGGD_MAX_BETAS], pm[MLGGD_MAX_BETAS];
+#pragma unroll
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++) pp[k] = pm[k] = 0.0;
+    if (d < A.D) {
+        const float bias = A.bias[d];
+        for (int b = tx; b < A.B; b += 32) {
+            float x = slab_sum(A.slab, (size_t)d * A.Bp + b, (size_t)A.Dp * A.Bp, A.S);
+            x = x + bias;
+            const float t = A.targ[(size_t)(A.first ? A.first[b] + A.toff : b) * A.D + d];
+            const float e = x - t;
+            const float a = fabsf(e);
+#pragma unroll
+            for (int k = 0; k < MLGGD_MAX_BETAS; k++)
+                if (k < A.K) {
+                    const double v = (double)pow_or_self(a, A.betas[k]);
+                    pp[k] += e > 0 ? v : 0.0;
+                    pm[k] += e < 0 ? v : 0.0;
+                }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++)
+        if (k < A.K) {
+#pragma unroll
+            for (int off = 16; off > 0; off >>= 1) {
+                pp[k] += __shfl_xor(pp[k], off, 64);
+                pm[k] += __shfl_xor(pm[k], off, 64);
+            }
+        }
+    if (tx == 0 && d < A.D) {
+        double *p = A.acc + d;
+        const size_t D = (size_t)A.D;
+#pragma unroll
+        for (int k = 0; k < MLGGD_MAX_BETAS; k++)
+            if (k < A.K) {
+                p[k * D] = A.fresh ? pp[k] : p[k * D] + pp[k];
+                p[(A.K + k) * D] = A.fresh ? pm[k] : p[(A.K + k) * D] + pm[k];
+            }
+    }
+}

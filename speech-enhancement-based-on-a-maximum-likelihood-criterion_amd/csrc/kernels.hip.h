@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "nat_rule.h"
+#include "asym_rule.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -2097,6 +2098,36 @@ __global__ __launch_bounds__(256) void k_loss_err_bins(LossErrArgs A, const floa
     if ((int)blockIdx.x >= n_stage) loss_err_body<true>(A, betas, (int)blockIdx.x - n_stage);
     else transpose_in_body(G, (int)blockIdx.x);
 }
+// Phase A under the asymmetric model (mlggd_set_asymmetry, asym_rule.h): k_loss_err_bins with p = s(e)^beta_d,
+// s(e) = kappa_d e for e > 0 and (-e) / kappa_d for e < 0, both read per unit from [Dp] arrays (pads 1.0).  ML only,
+// so there is no want_pow.  A body and a kernel of its own so that loss_err_body stays the code it was.
+__global__ __launch_bounds__(256) void k_loss_err_asym(LossErrArgs A, const float *__restrict__ betas,
+                                                       const float *__restrict__ kappas, int n_loss, StageArgs G) {
+    const int n_stage = (int)gridDim.x - n_loss;
+    if ((int)blockIdx.x < n_stage) {
+        transpose_in_body(G, (int)blockIdx.x);
+        return;
+    }
+    const int bid = (int)blockIdx.x - n_stage;
+    const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
+    float *__restrict__ outT = A.outT, *__restrict__ eT = A.eT, *__restrict__ pT = A.pT;
+    const int *__restrict__ first = A.first;
+    const int dt = bid / A.b_tiles, bt = bid % A.b_tiles;
+    const int d = dt * LOSS_DT + (int)(threadIdx.x >> 5), b = bt * 32 + (int)(threadIdx.x & 31);
+    const size_t o = (size_t)d * A.Bp + b;
+    float x = slab_sum(slab, o, (size_t)A.Dp * A.Bp, A.S);
+    x = x + bias[d];
+    float e = 0.0f, p = 0.0f;
+    if (b < A.B && d < A.D) {
+        e = x - targ[(size_t)(first ? first[b] + A.toff : b) * A.D + d];  // kernerror
+        p = pow_or_self(asym_rule::skewed(e, kappas[d]), betas[d]);      // s(e) in the place of |e|, then kernindex2
+    } else {
+        x = 0.0f;
+    }
+    outT[o] = x;
+    eT[o] = e;
+    pT[o] = p;
+}
 
 // Per-dimension sum over the minibatch of |e|^beta in the reference's order (kernSumcol,
 // DevFunc.cu:167-185 <- BP_GPU.cu:416: one thread per column, rows added sequentially).
@@ -2256,6 +2287,57 @@ __global__ __launch_bounds__(256) void k_loss_grad_bins(const float *__restrict_
         if (e > 0) g = pow_or_self(e, beta - 1.0f) * beta / denom[dl];
         else if (e == 0) g = 0;
         else g = -pow_or_self(-e, beta - 1.0f) * beta / denom[dl];
+        g = g * inv_n;
+    }
+    dEdXt[o] = g;
+    dEdX[(size_t)b * Dp + d] = g;
+}
+// k_loss_grad_bins under the asymmetric model (asym_rule.h): pT holds s(e)^beta_d, so the statistic, alpha and the
+// denominator are the statements they were; the gradient is the existing value at s(e) times ds/de.  s and the choice
+// between the two gradient forms are selects on the lane's own e; beta and kappa are uniform over a unit's half-wave.
+// A kernel of its own so that k_loss_grad_bins stays the code it was.
+__global__ __launch_bounds__(256) void k_loss_grad_asym(const float *__restrict__ eT, const float *__restrict__ pT,
+                                                        const float *__restrict__ colsum_in, int B, int D, int Dp,
+                                                        int Bp, const float *__restrict__ betas,
+                                                        const float *__restrict__ kappas, float nf, float inv_n,
+                                                        float *__restrict__ scalefactor, float *__restrict__ dEdXt,
+                                                        float *__restrict__ dEdX, int b_tiles) {
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    __shared__ float denom[LOSS_DT];
+    const int dt = blockIdx.x / b_tiles, bt = blockIdx.x % b_tiles;
+    const int d0 = dt * LOSS_DT;
+    const int tid = threadIdx.x;
+    {
+        float *rows = dyn, *sums = dyn + LOSS_DT * (Bp + 1);
+        if (colsum_in == nullptr) {
+            colsum_tile<LOSS_DT>(pT, d0, B, Bp, rows, sums);
+        } else {
+            if (tid < LOSS_DT) sums[tid] = colsum_in[d0 + tid];
+            __syncthreads();
+        }
+        if (tid < LOSS_DT) {
+            const int d = d0 + tid;
+            float q = 1.0f;
+            if (d < D) {
+                const float beta = betas[d];
+                const float v1 = sums[tid] / nf;            // kernDivide
+                const float v2 = v1 * beta;                 // kernVecMulNum
+                const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
+                if (bt == 0) scalefactor[d] = alpha;
+                q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
+            }
+            denom[tid] = q;
+        }
+        __syncthreads();
+    }
+    const int dl = tid >> 5, d = d0 + dl, b = bt * 32 + (tid & 31);
+    const size_t o = (size_t)d * Bp + b;
+    const float e = eT[o];
+    float g = 0.0f;
+    if (b < B && d < D) {
+        const float beta = betas[d], kappa = kappas[d];
+        const float v = pow_or_self(asym_rule::skewed(e, kappa), beta - 1.0f) * beta / denom[dl];  // kernfunc2 at s(e)
+        g = asym_rule::grad(e, v, kappa);
         g = g * inv_n;
     }
     dEdXt[o] = g;
@@ -2492,6 +2574,93 @@ __global__ __launch_bounds__(1024) void k_loss_ml_bins(LossMlArgs A, const float
         *reinterpret_cast<float4 *>(&A.dEdX[(size_t)b * Dp + d0 + h4]) = v;
     }
 }
+// k_loss_ml_bins under the asymmetric model (mlggd_set_asymmetry, asym_rule.h): the same statements in the same order
+// with s(e) = kappa_d e (e > 0), (-e) / kappa_d (e < 0) in the place of |e| and the gradient times ds/de; beta and
+// kappa come from [Dp] arrays (pads 1.0; an engine without a shape vector fills betas with cfg.shapefactor).  s and
+// the choice between the two gradient forms are selects on the lane's own e, so pow_or_self still sees a wave-uniform
+// exponent.  At kappa = 1 every intermediate is k_loss_ml_bins' value.  The LDS size, the staging blocks and the float4
+// dEdX stores are k_loss_ml's.  A kernel of its own so that k_loss_ml_bins stays the code it was.
+__global__ __launch_bounds__(1024) void k_loss_ml_asym(LossMlArgs A, const float *__restrict__ betas,
+                                                       const float *__restrict__ kappas, int n_loss, StageArgs G,
+                                                       int n_stage_tiles) {
+    const int n_stage = (int)gridDim.x - n_loss;
+    if ((int)blockIdx.x < n_stage) {
+        transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
+        return;
+    }
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    __shared__ float denom[LOSS_DT];
+    const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
+    const int *__restrict__ first = A.first;
+    const int B = A.B, D = A.D, Dp = A.Dp, Bp = A.Bp;
+    float *es = dyn, *ps = dyn + LOSS_DT * (Bp + 1);  // [8][Bp+1] each
+    const int d0 = ((int)blockIdx.x - n_stage) * LOSS_DT;
+    const int tid = threadIdx.x, dl = tid >> 7, d = d0 + dl;  // 8 units x 128 frames per pass
+    const float beta = betas[d], kappa = kappas[d];  // uniform over the unit's 128 threads, two whole waves
+    for (int b = tid & 127; b < Bp; b += 128) {
+        const size_t o = (size_t)d * Bp + b;
+        float x = slab_sum(slab, o, (size_t)Dp * Bp, A.S);
+        x = x + bias[d];
+        float e = 0.0f, p = 0.0f;
+        if (b < B && d < D) {
+            e = x - targ[(size_t)(first ? first[b] + A.toff : b) * D + d];  // kernerror
+            p = pow_or_self(asym_rule::skewed(e, kappa), beta);              // s(e) in the place of |e|, then kernindex2
+        } else {
+            x = 0.0f;
+        }
+        A.outT[o] = x;
+        A.eT[o] = e;
+        es[dl * (Bp + 1) + b] = e;
+        ps[dl * (Bp + 1) + b] = p;
+    }
+    __syncthreads();
+    if (tid < LOSS_DT) {
+        const float *col = ps + tid * (Bp + 1);
+        float s = col[0];  // kernSumcol: (*top) = (*fromp); then += in row order
+        int b = 1;
+        for (; b + 16 <= B; b += 16) {
+            float v[16];
+#pragma unroll
+            for (int u = 0; u < 16; u++) v[u] = col[b + u];
+#pragma unroll
+            for (int u = 0; u < 16; u++) s += v[u];
+        }
+        for (; b < B; b++) s += col[b];
+        float q = 1.0f;
+        if (d0 + tid < D) {
+            const float beta = betas[d0 + tid];         // the column this thread sums, not the unit of its passes
+            const float v1 = s / A.nf;                  // kernDivide
+            const float v2 = v1 * beta;                 // kernVecMulNum
+            const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
+            A.scalefactor[d0 + tid] = alpha;
+            q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
+        }
+        denom[tid] = q;
+    }
+    __syncthreads();
+    for (int b = tid & 127; b < Bp; b += 128) {
+        const float e = es[dl * (Bp + 1) + b];
+        float g = 0.0f;
+        if (b < B && d < D) {
+            const float v = pow_or_self(asym_rule::skewed(e, kappa), beta - 1.0f) * beta / denom[dl];  // kernfunc2 at s(e)
+            g = asym_rule::grad(e, v, kappa);                                 // the sign, then ds/de
+            g = g * A.inv_n;                                                  // kernVecMulNum
+        }
+        A.dEdXt[(size_t)d * Bp + b] = g;
+        es[dl * (Bp + 1) + b] = g;  // this thread's own element: the row layout leaves below, 16 bytes at a time
+    }
+    // dEdX [frame][unit]: two 16-byte stores per frame, as in k_loss_ml
+    __syncthreads();
+    for (int t = tid; t < 2 * Bp; t += 1024) {
+        const int b = t >> 1, h4 = (t & 1) * 4;
+        float4 v;
+        v.x = es[(h4 + 0) * (Bp + 1) + b];
+        v.y = es[(h4 + 1) * (Bp + 1) + b];
+        v.z = es[(h4 + 2) * (Bp + 1) + b];
+        v.w = es[(h4 + 3) * (Bp + 1) + b];
+        *reinterpret_cast<float4 *>(&A.dEdX[(size_t)b * Dp + d0 + h4]) = v;
+    }
+}
 
 // Forward-only output (cv_bunch_single, BP_GPU.cu:442-512): out[b][d] = bias + sum_s slab,
 // compact row-major [B][D] for the D2H copy.
@@ -2605,6 +2774,54 @@ __global__ __launch_bounds__(256) void k_cv_reduce_bins(CvArgs A, const float *_
             sq += (double)((x - t) * (x - t));   // BP_GPU.cu:211
             ab += (double)fabsf(x - t);           // BP_GPU.cu:246
             if (A.alpha) ll += (double)pow_or_self(fabsf(t - x) / A.alpha[d], betas[d]);  // BP_GPU.cu:295-296
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sq += __shfl_down(sq, off, 64);
+        ab += __shfl_down(ab, off, 64);
+        ll += __shfl_down(ll, off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[wave][0] = sq;
+        red[wave][1] = ab;
+        red[wave][2] = ll;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int j = threadIdx.x;
+        A.partial[(size_t)blockIdx.x * 3 + j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
+    }
+}
+
+// k_cv_reduce_bins under the asymmetric model (asym_rule.h): s(o - t) / alpha_d in the place of |t - o| / alpha_d in the
+// likelihood term, kappa_d from kappas [Dp]; the two shape-free sums are the statements they were.  A kernel of its
+// own so that k_cv_reduce_bins stays the code it was.
+__global__ __launch_bounds__(256) void k_cv_reduce_asym(CvArgs A, const float *__restrict__ betas,
+                                                        const float *__restrict__ kappas) {
+    __shared__ float tt[32][33];
+    __shared__ double red[4][3];
+    const int dt = blockIdx.x / A.b_tiles, bt = blockIdx.x % A.b_tiles;
+    const int d0 = dt * 32, b0 = bt * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int b = b0 + ty + 8 * q, d = d0 + tx;
+        tt[ty + 8 * q][tx] = (b < A.B && d < A.D) ? A.targ[(size_t)(A.first ? A.first[b] + A.toff : b) * A.D + d] : 0.0f;
+    }
+    __syncthreads();
+    double sq = 0.0, ab = 0.0, ll = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const int dl = ty + 8 * q, d = d0 + dl, b = b0 + tx;
+        if (b < A.B && d < A.D) {
+            float x = slab_sum(A.slab, (size_t)d * A.Bp + b, (size_t)A.Dp * A.Bp, A.S);
+            x = x + A.bias[d];
+            const float t = tt[tx][dl];
+            sq += (double)((x - t) * (x - t));   // BP_GPU.cu:211
+            ab += (double)fabsf(x - t);           // BP_GPU.cu:246
+            if (A.alpha) ll += (double)pow_or_self(asym_rule::skewed(x - t, kappas[d]) / A.alpha[d], betas[d]);
         }
     }
 #pragma unroll

@@ -113,6 +113,17 @@ void BP_GPU::ErrorStats_frames(int n_frames, int fea_context, const float *feat,
                                    betas, sums),
           "mlggd_error_stats_frames");
 }
+void BP_GPU::ErrorStatsSigned(int n, const float *in, const float *targ, int n_betas, const float *betas, double *sums) {
+    check(mlggd_error_stats_signed(h_, n, in, targ, n_betas, betas, sums), "mlggd_error_stats_signed");
+}
+void BP_GPU::ErrorStatsSigned_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
+                                     const int *first_frame, int targ_offset, int n_betas, const float *betas,
+                                     double *sums) {
+    check(mlggd_error_stats_signed_frames(h_, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset,
+                                          n_betas, betas, sums),
+          "mlggd_error_stats_signed_frames");
+}
+void BP_GPU::setAsymmetry(const float *kappas) { check(mlggd_set_asymmetry(h_, kappas), "mlggd_set_asymmetry"); }
 void BP_GPU::OutputStats(int n, const float *in, const float *targ, double *sums) {
     check(mlggd_output_stats(h_, n, in, targ, sums), "mlggd_output_stats");
 }

@@ -44,6 +44,12 @@ class BP_GPU {
     // one shape per output bin from the next step or CV call on (not in the reference; MLflag 1 only), nullptr: back
     // to `shapefactor`; see mlggd_set_shapefactors
     void setShapefactors(const float *betas);
+    // the asymmetric error model (not in the reference; MLflag 1 only): one skew per output bin from the next step or
+    // CV call on, nullptr: off (mlggd_set_asymmetry); its sufficient statistics [2 n_betas][D] of a CV chunk
+    void setAsymmetry(const float *kappas);
+    void ErrorStatsSigned(int n_frames, const float *in, const float *targ, int n_betas, const float *betas, double *sums);
+    void ErrorStatsSigned_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
+                                 const int *first_frame, int targ_offset, int n_betas, const float *betas, double *sums);
     void returnWeights(float **weights, float **bias);
     float Gamma(float x) { return mlggd_gamma(x); }
     // data parallel (not in the reference): join an RCCL communicator of `world` ranks

@@ -34,6 +34,14 @@
 // any other name sigmoid ones, so a finetune.pl edited only in its $exe line trains a ReLU net.  Any other value ends
 // the run before a file or a device is opened.  The banner line names the choice; the log file does not change.
 //
+// Asymmetric error model (new, opt-in; asymfile.h): with MLGGD_ASYMMODEL=FILE rank 0 makes one more pass over the CV
+// chunks after the epoch (mlggd_error_stats_signed over the grid of MLGGD_ERRMODEL_BETAS, added, mlggd_asym_fit) and
+// writes a shape and a skew per bin to FILE; the file reads as a shape file too.  With MLGGD_ASYMMETRY=FILE every
+// rank reads one skew per output bin from FILE -- a plain list of D numbers or that file (its best_kappa column; a bin
+// without a fit takes 1) -- and sets it on the engine before the first chunk (mlggd_set_asymmetry); one stderr line
+// names the file and the minimum, maximum and mean skew.  Needs MLflag=1.  One fit feeds
+// MLGGD_SHAPEFACTORS=fit.txt MLGGD_ASYMMETRY=fit.txt in the next epoch.
+//
 // Data parallel (new): when WORLD_SIZE > 1 (torchrun-style env: RANK,
 // LOCAL_RANK, WORLD_SIZE; MLGGD_ID_FILE names a file on a shared filesystem used to hand the
 // RCCL unique id from rank 0 to the others) every rank reads the same chunks with the same
@@ -55,6 +63,7 @@
 #include "bp_gpu.h"
 #include "dp_launch.h"
 #include "errmodel.h"
+#include "asymfile.h"
 #include "gvfile.h"
 #include "prefetch.h"
 #include "trainer_io.h"
@@ -183,6 +192,22 @@ int main(int argc, char *argv[]) {
             if (!mlggd_host::parse_shapefactors(shapes_fn, (int)shapes.size(), p->shapefactor, shapes.data(), &why))
                 throw IoError("MLGGD_SHAPEFACTORS: " + why);
         }
+        const char *asymmodel_fn = getenv("MLGGD_ASYMMODEL");
+        if (asymmodel_fn && !*asymmodel_fn) asymmodel_fn = nullptr;
+        std::vector<float> asymmodel_betas;  // a bad grid ends the run here, not after the epoch
+        if (asymmodel_fn && rank == 0) asymmodel_betas = mlggd_host::beta_grid(getenv("MLGGD_ERRMODEL_BETAS"));
+        const char *asym_fn = getenv("MLGGD_ASYMMETRY");
+        if (asym_fn && !*asym_fn) asym_fn = nullptr;
+        std::vector<float> skews;  // a bad file or a beta-norm run ends here, before anything is trained
+        if (asym_fn) {
+            if (p->MLflag != 1)
+                throw IoError(std::string("MLGGD_ASYMMETRY=") + asym_fn + ": a skew per bin needs MLflag=1, this run has MLflag=" +
+                              std::to_string(p->MLflag));
+            skews.resize(p->layersizes[io->numlayers - 1]);
+            std::string why;
+            if (!mlggd_host::parse_asymmetry(asym_fn, (int)skews.size(), 1.0f, skews.data(), &why))
+                throw IoError("MLGGD_ASYMMETRY: " + why);
+        }
         // ---- train (BPtrain.cc:81-102).  The chunk plan and the fetch thread only touch host state, so the
         // first chunk is read while the engine initialises HIP and uploads the weights (the reference creates
         // BP_GPU first, BPtrain.cc:77-78, and reads the first chunk afterwards).
@@ -254,6 +279,18 @@ int main(int argc, char *argv[]) {
             }
             fprintf(stderr, "shape factors: %s, %zu bins, beta min %.9g max %.9g mean %.9g\n", shapes_fn, shapes.size(),
                     (double)lo, (double)hi, sum / (double)shapes.size());
+        }
+        if (asym_fn) {
+            net->setAsymmetry(skews.data());
+            float lo = skews[0], hi = skews[0];
+            double sum = 0;
+            for (float k : skews) {
+                lo = k < lo ? k : lo;
+                hi = k > hi ? k : hi;
+                sum += k;
+            }
+            fprintf(stderr, "asymmetry: %s, %zu bins, kappa min %.9g max %.9g mean %.9g\n", asym_fn, skews.size(),
+                    (double)lo, (double)hi, sum / (double)skews.size());
         }
         phase("engine (HIP init, upload)", t_phase);
         const int K0 = p->layersizes[0], D = p->layersizes[io->numlayers - 1], B = p->bunchsize;
@@ -371,6 +408,36 @@ int main(int argc, char *argv[]) {
                 const double shared = mlggd_host::write_error_model(errmodel_fn, D, n_total, errmodel_betas, total);
                 printf("error model: %s written, %lld CV samples, shared beta %.9g\n", errmodel_fn, (long long)n_total, shared);
                 phase("error model", t_phase);
+            }
+
+            // ---- asymmetric error model of the CV set (MLGGD_ASYMMODEL): one more pass, nothing of it reaches the log
+            if (asymmodel_fn && (p->dropoutflag != 0 || world > 1)) {
+                printf("asymmetric error model: not available %s; %s is not written\n",
+                       p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", asymmodel_fn);
+            } else if (asymmodel_fn) {
+                const int K = (int)asymmodel_betas.size();
+                std::vector<double> total((size_t)2 * K * D, 0.0), part(total.size());
+                int64_t n_total = 0;
+                for (unsigned i = 0; i < io->cv_total_chunks; i++) {
+                    progress("asymmetric error model");
+                    int n;
+                    if (frames) {
+                        n = io->Readchunk_frames_cv((int)i);
+                        net->ErrorStatsSigned_frames(p->chunk_frames[0], p->fea_context, p->frames_in[0], p->frames_targ[0], n,
+                                                     p->first_frame[0], p->targ_offset, K, asymmodel_betas.data(), part.data());
+                    } else {
+                        n = io->Readchunk_cv((int)i);
+                        net->ErrorStatsSigned(n, p->indata[0], p->targ[0], K, asymmodel_betas.data(), part.data());
+                    }
+                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
+                    n_total += n;
+                }
+                if (n_total == 0)
+                    throw IoError(std::string("MLGGD_ASYMMODEL: the CV set has no samples, ") + asymmodel_fn + " is not written");
+                const double shared = mlggd_host::write_asym_model(asymmodel_fn, D, n_total, asymmodel_betas, total);
+                printf("asymmetric error model: %s written, %lld CV samples, shared beta %.9g\n", asymmodel_fn,
+                       (long long)n_total, shared);
+                phase("asymmetric error model", t_phase);
             }
 
             // ---- global variance of the CV set (MLGGD_GVFILE): one more pass, nothing of it reaches the log
