@@ -44,6 +44,11 @@ enum { MLGGD_ACT_SIGMOID = 0, MLGGD_ACT_RELU = 1 };
 
 typedef struct mlggd_engine *mlggd_handle;
 
+/* One int32 slot of mlggd_config under a name of its own: the struct ends in `reserved[5]` as it always did, and a
+ * reserved slot that takes a meaning is reached under its name through an anonymous union (C11, C++) with that array,
+ * so that code which fills or checks `reserved` keeps compiling and the layout cannot move. */
+#define MLGGD_CONFIG_SLOT(name) int32_t name
+
 /* Constructor arguments of BP_GPU (BP_GPU.h:48-49, BP_GPU.cu:9-11), same meaning. */
 typedef struct mlggd_config {
     int32_t struct_size;     /* = sizeof(mlggd_config), ABI guard */
@@ -64,7 +69,12 @@ typedef struct mlggd_config {
     int32_t activation;      /* hidden units: MLGGD_ACT_SIGMOID (0, the default of a zeroed struct) or MLGGD_ACT_RELU */
     int32_t nat_frames;      /* noise-aware training: 0 (a zeroed struct) = off; T >= 1: every input row ends in its utterance's
                               * noise row over the first T frames, layersizes[0] = (fea_context + 1) * D; < 0: MLGGD_ERR_ARG */
-    int32_t reserved[5];
+    union {                  /* the five reserved slots stay one array; a slot that takes a meaning is also a named member */
+        MLGGD_CONFIG_SLOT(mask_bins); /* = reserved[0].  Multi-objective net: 0 (a zeroed struct) = off; M >= 1: the last layer
+                              * has 2 * M units, the first M the clean LPS, the last M a ratio mask (mlggd_set_mask); < 0 or
+                              * another width: MLGGD_ERR_ARG */
+        int32_t reserved[5];
+    };
 } mlggd_config;
 
 /* ---- lifetime: BP_GPU::BP_GPU / ~BP_GPU (BP_GPU.cu:9-150) ---- */
@@ -548,6 +558,41 @@ int mlggd_get_gv(mlggd_handle h, float *eta /* [D]; ones when off */);
  * is not positive and finite and a file that cannot be read are MLGGD_ERR_ARG with "PATH line N: ..." as the
  * message; a NULL pointer and D < 1 are MLGGD_ERR_ARG too. */
 int mlggd_read_gv(const char *path, int D, int shared, float *eta /* [D] */);
+
+/* ---- multi-objective learning with mask-based post-processing (the regression-DNN recipe of Xu, Du, Dai and Lee; no
+ * counterpart in the reference).  An engine created with mlggd_config.mask_bins = M >= 1 has 2 M outputs per frame:
+ * the clean LPS and a ratio mask.  The rule is csrc/mask_rule.h; M must be the bin count D of the rate a wave entry is
+ * called with.  All fp32, one IEEE operation per step, nothing contracted.
+ *
+ * Targets.  mlggd_load_waves, mlggd_cv_all_waves and mlggd_train_waves on a mask engine form target rows [clean LPS
+ * normalised as before | t], t = scale * min(1, exp_det(0.5f * (c - y))) from the UN-normalised clean and noisy LPS c,
+ * y: the clean-to-noisy magnitude ratio capped at 1, not z-normalised; exp_det is the kernels' IEEE-only exponential
+ * ("exp_det" of mlggd_debug_math).  scale is the engine's (mlggd_set_mask).  mlggd_mask_targets runs the same device
+ * arithmetic on n_frames given rows of D bins (out [n_frames][D]) for callers who build frame targets themselves; the
+ * frame entries (mlggd_train_frames, ...) are generic in the output width and take such 2 M-wide rows as they are.
+ * Under MMSE the mask half weighs scale^2 against the LPS half; under ML-GGD every bin has its own alpha and
+ * mlggd_set_shapefactors can give the mask half beta = 2.  mlggd_cv_all* sum over all 2 M outputs.
+ *
+ * Decoding.  mlggd_enhance_wave, _waves, _scored and _scored_stoi take a mask engine as they are.  With o the 2 D
+ * outputs of a frame, x the de-normalised estimate of bin k exactly as on an engine without a mask (o[k] / inv + mean,
+ * or with the factors of mlggd_set_gv, of whose 2 D values the first D are read), n the noisy LPS of that frame and bin:
+ *   m = o[D + k] / scale      v = m > hi ? n : (m >= lo ? 0.5f * (n + x) : x)          a NaN mask takes x
+ * and v takes the place of x everywhere: the magnitudes, lps_out, the scores.  MLGGD_MASK_OFF: v = x, the mask half is
+ * ignored.  A new engine has MLGGD_MASK_SELECT, lo 0.25, hi 0.75, scale 1: a choice, not a measured optimum.
+ * mlggd_set_mask takes effect from the next call on; lo > hi, a value that is not finite, scale <= 0 and another mode
+ * are MLGGD_ERR_ARG, any call on an engine without mask_bins is MLGGD_ERR_STATE, and the engine stays unchanged.
+ * mlggd_live_open on a mask engine is MLGGD_ERR_STATE (a live group would need the noisy rows of the frames it
+ * decodes in a second ring), and a wave entry at a rate whose D != mask_bins is MLGGD_ERR_ARG.
+ * mlggd_mask_select: host only, no device; out[i] = the post-filter of (noisy_lps[i], lps[i], m = mask[i]) over n rows
+ * of D values, straight from the header: the float32 statement tests and users compare against. */
+enum { MLGGD_MASK_OFF = 0, MLGGD_MASK_SELECT = 1 };
+int mlggd_set_mask(mlggd_handle h, int mode, float lo, float hi, float scale);
+int mlggd_get_mask(mlggd_handle h, int *mode, float *lo, float *hi, float *scale); /* every pointer optional */
+int mlggd_get_mask_bins(mlggd_handle h, int *mask_bins); /* the mask_bins the engine was created with */
+int mlggd_mask_targets(int device, int D, int64_t n_frames, const float *noisy_lps, const float *clean_lps, float scale,
+                       float *out /* [n_frames][D] */);
+int mlggd_mask_select(int D, int64_t n, const float *noisy_lps, const float *lps, const float *mask, float lo, float hi,
+                      float *out /* [n][D] */);
 int mlggd_set_lrate(mlggd_handle h, float lrate);
 int mlggd_get_activation(mlggd_handle h, int *act); /* MLGGD_ACT_* the engine was created with */
 /* CV metrics: on = the three sums are formed on the device (per-tile partials in double, combined

@@ -26,14 +26,20 @@ class MlggdError(RuntimeError):
     pass
 
 
+class _ConfigSlots(C.Union):
+    """the five reserved slots of mlggd_config, and the names of those that have taken a meaning (include/mlggd.h)"""
+    _fields_ = [("mask_bins", C.c_int32), ("reserved", C.c_int32 * 5)]  # mask_bins = reserved[0]
+
+
 class _Config(C.Structure):
+    _anonymous_ = ("_slots",)
     _fields_ = [
         ("struct_size", C.c_int32), ("random_seed", C.c_int32), ("device", C.c_int32),
         ("numlayers", C.c_int32), ("layersizes", C.c_int32 * MAXLAYER), ("bunchsize", C.c_int32),
         ("lrate", C.c_float), ("momentum", C.c_float), ("weightcost", C.c_float),
         ("shapefactor", C.c_float), ("MLflag", C.c_int32), ("dropoutflag", C.c_int32),
         ("visible_omit", C.c_float), ("hid_omit", C.c_float), ("max_cache_frames", C.c_int32),
-        ("activation", C.c_int32), ("nat_frames", C.c_int32), ("reserved", C.c_int32 * 5),
+        ("activation", C.c_int32), ("nat_frames", C.c_int32), ("_slots", _ConfigSlots),
     ]
 
 
@@ -76,6 +82,7 @@ EXPORTS = [
     "mlggd_load_waves", "mlggd_cv_all_waves", "mlggd_set_noise", "mlggd_train_waves",
     "mlggd_load_frames_nat", "mlggd_train_frames_nat", "mlggd_cv_all_frames_nat", "mlggd_forward_frames_nat",
     "mlggd_nat_estimate", "mlggd_nat_rows", "mlggd_get_nat_frames",
+    "mlggd_set_mask", "mlggd_get_mask", "mlggd_get_mask_bins", "mlggd_mask_targets", "mlggd_mask_select",
     "mlggd_set_asymmetry", "mlggd_get_asymmetry", "mlggd_error_stats_signed", "mlggd_error_stats_signed_frames",
     "mlggd_asym_fit", "mlggd_read_asymmetry",
 ]
@@ -87,7 +94,7 @@ _lib = None
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
-                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "outstats.hip.h", "gv_rule.h", "mix.hip.h",
+                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "outstats.hip.h", "gv_rule.h", "mask_rule.h", "mask.hip.h", "mix.hip.h",
                                              "mix_rule.h", "nat_rule.h", "asym_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
@@ -216,6 +223,11 @@ def load():
     L.mlggd_nat_estimate.argtypes = [C.c_int, C.c_int, _ip, _fp, C.c_int, _fp]
     L.mlggd_nat_rows.argtypes = [C.c_int, _ip, C.c_int, _ip, _ip]
     L.mlggd_get_nat_frames.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.mlggd_set_mask.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    L.mlggd_get_mask.argtypes = [C.c_void_p, C.POINTER(C.c_int), _fp, _fp, _fp]
+    L.mlggd_get_mask_bins.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.mlggd_mask_targets.argtypes = [C.c_int, C.c_int, C.c_int64, _fp, _fp, C.c_float, _fp]
+    L.mlggd_mask_select.argtypes = [C.c_int, C.c_int64, _fp, _fp, _fp, C.c_float, C.c_float, _fp]
     _lib = L
     return L
 
@@ -713,6 +725,40 @@ def read_gv(path, D, shared=False):
     return e
 
 
+MASK_MODES = ("off", "select")  # MLGGD_MASK_OFF = 0, MLGGD_MASK_SELECT = 1 (include/mlggd.h)
+Mask = collections.namedtuple("Mask", "mode lo hi scale")
+
+
+def mask_mode_code(mode):
+    if mode not in MASK_MODES:
+        raise ValueError("mask mode %r: must be one of %s" % (mode, ", ".join(MASK_MODES)))
+    return MASK_MODES.index(mode)
+
+
+def mask_targets(noisy_lps, clean_lps, scale=1.0, device=0):
+    """The mask half of a mask engine's target rows (csrc/mask_rule.h) from UN-normalised LPS rows [n][D]:
+    scale * min(1, exp_det(0.5 * (clean - noisy))) in float32, the arithmetic train_waves runs, on the device
+    (mlggd_mask_targets)."""
+    n, c = _f32(noisy_lps), _f32(clean_lps)
+    if n.ndim != 2 or n.shape != c.shape or n.shape[1] < 1:
+        raise ValueError("noisy_lps and clean_lps must both be [n][D]")
+    out = np.empty(n.shape, np.float32)
+    _check(load().mlggd_mask_targets(int(device), n.shape[1], n.shape[0], _p(n), _p(c), float(scale), _p(out)))
+    return out
+
+
+def mask_select(noisy_lps, lps, mask, lo, hi):
+    """The mask post-filter on rows [n][D]: mask > hi takes the noisy LPS, lo <= mask <= hi the mean of the noisy LPS and
+    the estimate lps, else (a NaN included) the estimate.  A host call: needs no device (mlggd_mask_select), the float32
+    statement of csrc/mask_rule.h."""
+    n, x, m = _f32(noisy_lps), _f32(lps), _f32(mask)
+    if n.ndim != 2 or n.shape != x.shape or n.shape != m.shape or n.shape[1] < 1:
+        raise ValueError("noisy_lps, lps and mask must all be [n][D]")
+    out = np.empty(n.shape, np.float32)
+    _check(load().mlggd_mask_select(n.shape[1], n.shape[0], _p(n), _p(x), _p(m), float(lo), float(hi), _p(out)))
+    return out
+
+
 def comm_unique_id():
     buf = (C.c_char * UNIQUE_ID_BYTES)()
     _check(load().mlggd_comm_unique_id(buf))
@@ -724,7 +770,7 @@ class BPGpu:
 
     def __init__(self, random_seed, gpu, layersizes, bunchsize, lrate, momentum, weightcost, weights, bias,
                  shapefactor, MLflag, dropoutflag=0, visible_omit=0.0, hid_omit=0.0, max_cache_frames=0, activation="sigmoid",
-                 nat_frames=0):
+                 nat_frames=0, mask_bins=0):
         self._h = None
         act = activation_code(activation)  # hidden units: "sigmoid" (the reference's BPtrain_Sigmoid) or "relu"
         self._lives = []
@@ -755,6 +801,7 @@ class BPGpu:
         cfg.max_cache_frames = int(max_cache_frames)
         cfg.activation = act
         cfg.nat_frames = int(nat_frames)  # noise-aware training: every input row ends in its utterance's noise row
+        cfg.mask_bins = int(mask_bins)  # multi-objective net: 2 * mask_bins outputs, the clean LPS and a ratio mask
         h = C.c_void_p()
         rc = load().mlggd_create(C.byref(cfg), _ptr_array(ws), _ptr_array(bs), C.byref(h))
         if rc != 0:
@@ -777,6 +824,26 @@ class BPGpu:
         n = C.c_int()
         _check(load().mlggd_get_nat_frames(self._h, C.byref(n)))
         return n.value
+
+    @property
+    def mask_bins(self):
+        """0, or the M of a multi-objective net: 2 M outputs, the clean LPS and a ratio mask (mlggd_get_mask_bins)."""
+        n = C.c_int()
+        _check(load().mlggd_get_mask_bins(self._h, C.byref(n)))
+        return n.value
+
+    def set_mask(self, mode="select", lo=0.25, hi=0.75, scale=1.0):
+        """The mask post-filter of a mask engine's decoders and the scale of its mask targets (csrc/mask_rule.h,
+        mlggd_set_mask): "select" lets mask / scale choose per bin between the noisy LPS (> hi), the mean of noisy
+        LPS and estimate (lo .. hi) and the estimate; "off" decodes the LPS half alone.  The defaults are a choice,
+        not a measured optimum."""
+        _check(load().mlggd_set_mask(self._h, mask_mode_code(mode), float(lo), float(hi), float(scale)))
+
+    def mask(self):
+        """Mask(mode, lo, hi, scale) in effect (mlggd_get_mask)."""
+        m, lo, hi, s = C.c_int(), C.c_float(), C.c_float(), C.c_float()
+        _check(load().mlggd_get_mask(self._h, C.byref(m), C.byref(lo), C.byref(hi), C.byref(s)))
+        return Mask(MASK_MODES[m.value], lo.value, hi.value, s.value)
 
     # -- lifetime
     def close(self):

@@ -34,6 +34,7 @@
 #include "errstats.hip.h"
 #include "outstats.hip.h"
 #include "gv_rule.h"
+#include "mask_rule.h"
 #include "mix.hip.h"
 #include "mix_rule.h"
 #include "nat_rule.h"
@@ -375,6 +376,13 @@ struct mlggd_engine {
     std::vector<DwpTable> dwp_tables;
     std::vector<void *> allocs;
     std::vector<const void *> lds_attr_done;  // kernels whose dynamic-LDS limit has been raised on this device
+
+    // a mask engine (mlggd_config.mask_bins = M >= 1, mask_rule.h): D = 2 M outputs, LPS half first.  The scale is read
+    // where targets are formed from waves and where a decoder post-filters; mode and thresholds by the decoders alone.
+    // Behind everything else: the members the training step reads keep their offsets.
+    int mask_bins = 0;
+    int mask_mode = mask_rule::kSelect;
+    float mask_lo = mask_rule::kLo, mask_hi = mask_rule::kHi, mask_scale = mask_rule::kScale;
 };
 
 // buffer for the selected launch, nullptr otherwise; one-shot
@@ -1785,6 +1793,10 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     if (cfg->nat_frames < 0) return fail(MLGGD_ERR_ARG, "nat_frames %d < 0", cfg->nat_frames);
     for (int i = 0; i < cfg->numlayers; i++)
         if (cfg->layersizes[i] < 1) return fail(MLGGD_ERR_ARG, "layersizes[%d] = %d", i, cfg->layersizes[i]);
+    if (cfg->mask_bins < 0) return fail(MLGGD_ERR_ARG, "mask_bins %d < 0", cfg->mask_bins);
+    if (cfg->mask_bins > 0 && (long long)cfg->layersizes[cfg->numlayers - 1] != 2ll * cfg->mask_bins)
+        return fail(MLGGD_ERR_ARG, "mask_bins %d: the last layer must have 2 x %d units (LPS and mask), not %d",
+                    cfg->mask_bins, cfg->mask_bins, cfg->layersizes[cfg->numlayers - 1]);
     for (int i = 1; i < cfg->numlayers; i++) {
         // the kernels address a weight matrix with 32-bit byte offsets into one buffer resource
         const long long bytes = 4ll * ceil32(cfg->layersizes[i - 1]) * ceil32(cfg->layersizes[i]);
@@ -1816,6 +1828,7 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     e->D = e->ls[e->L - 1];
     e->Dp = e->lsp[e->L - 1];
     e->nat_frames = cfg->nat_frames;
+    e->mask_bins = cfg->mask_bins;
     if (const char *v = getenv("MLGGD_FWD_NW")) e->fwd_nw = atoi(v);
     if (const char *v = getenv("MLGGD_WAVES_LOOKUP")) e->ww.lookup_table = !strcmp(v, "table");
     if (const char *v = getenv("MLGGD_DX_NW")) e->dx_nw = atoi(v);
@@ -2088,6 +2101,49 @@ int mlggd_set_gv(mlggd_handle e, const float *eta) {
 int mlggd_get_gv(mlggd_handle e, float *eta) {
     if (!e || !eta) return fail(MLGGD_ERR_ARG, "NULL argument");
     for (int d = 0; d < e->D; d++) eta[d] = e->gv_on ? e->gv_host[d] : 1.0f;
+    return MLGGD_OK;
+}
+
+// ------------------------------------------------------------------ mask post-filter (mask_rule.h)
+int mlggd_set_mask(mlggd_handle e, int mode, float lo, float hi, float scale) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!e->mask_bins) return fail(MLGGD_ERR_STATE, "mlggd_set_mask: the engine was created without mask_bins");
+    if (mode != MLGGD_MASK_OFF && mode != MLGGD_MASK_SELECT)
+        return fail(MLGGD_ERR_ARG, "mask mode %d: must be %d (off) or %d (select)", mode, MLGGD_MASK_OFF, MLGGD_MASK_SELECT);
+    if (!mask_rule::valid(mode, lo, hi, scale))
+        return fail(MLGGD_ERR_ARG, "mask lo %g, hi %g, scale %g: finite values with lo <= hi and scale > 0 are required",
+                    (double)lo, (double)hi, (double)scale);
+    // kernel arguments of the launches to come: those already enqueued carry the values they were launched with
+    e->mask_mode = mode, e->mask_lo = lo, e->mask_hi = hi, e->mask_scale = scale;
+    return MLGGD_OK;
+}
+
+int mlggd_get_mask(mlggd_handle e, int *mode, float *lo, float *hi, float *scale) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!e->mask_bins) return fail(MLGGD_ERR_STATE, "mlggd_get_mask: the engine was created without mask_bins");
+    if (mode) *mode = e->mask_mode;
+    if (lo) *lo = e->mask_lo;
+    if (hi) *hi = e->mask_hi;
+    if (scale) *scale = e->mask_scale;
+    return MLGGD_OK;
+}
+
+int mlggd_get_mask_bins(mlggd_handle e, int *mask_bins) {
+    if (!e || !mask_bins) return fail(MLGGD_ERR_ARG, "NULL argument");
+    *mask_bins = e->mask_bins;
+    return MLGGD_OK;
+}
+
+// Host only, no device: the post-filter on given rows, straight from the header.
+int mlggd_mask_select(int D, int64_t n, const float *noisy_lps, const float *lps, const float *mask, float lo, float hi,
+                      float *out) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n < 0) return fail(MLGGD_ERR_ARG, "n %lld < 0", (long long)n);
+    if (!mask_rule::valid(mask_rule::kSelect, lo, hi, 1.0f))
+        return fail(MLGGD_ERR_ARG, "mask lo %g, hi %g: finite values with lo <= hi are required", (double)lo, (double)hi);
+    if (n == 0) return MLGGD_OK;
+    if (!noisy_lps || !lps || !mask || !out) return fail(MLGGD_ERR_ARG, "noisy_lps/lps/mask/out is NULL");
+    mask_rule::select_rows(D, (size_t)n, noisy_lps, lps, mask, lo, hi, out);
     return MLGGD_OK;
 }
 
@@ -3594,8 +3650,19 @@ int launch_analysis_seg(const SpecPlan *p, const int16_t *wave, const long long 
 
 // eta (optional, with mean): the equalisation factors of gv_rule.h; without them the launch is the one it always was
 int launch_synthesis(const SpecPlan *p, const float *src, const float *mean, const float *inv, const float2 *X, int t0,
-                     int nf, float *blk, hipStream_t st, float *lps_den = nullptr, const float *eta = nullptr) {
+                     int nf, float *blk, hipStream_t st, float *lps_den = nullptr, const float *eta = nullptr,
+                     const MaskArgs *mk = nullptr) {
     if (nf == 0) return MLGGD_OK;
+    if (mk) {  // a mask engine: src rows of 2 D outputs, post-filtered against the noisy rows (mask_rule.h)
+        if (eta) {
+            hipLaunchKernelGGL(k_lps_synthesis_mask_gv, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv,
+                               eta, X, t0, nf, p->d, p->win, p->tw, p->tws, kSpecFloor, blk, lps_den, *mk);
+            return launch_check("k_lps_synthesis_mask_gv");
+        }
+        hipLaunchKernelGGL(k_lps_synthesis_mask, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, X, t0,
+                           nf, p->d, p->win, p->tw, p->tws, kSpecFloor, blk, lps_den, *mk);
+        return launch_check("k_lps_synthesis_mask");
+    }
     if (eta) {
         hipLaunchKernelGGL(k_lps_synthesis_gv, dim3(spec_grid(nf)), dim3(64 * SPEC_FRAMES), 0, st, src, mean, inv, eta, X,
                            t0, nf, p->d, p->win, p->tw, p->tws, kSpecFloor, blk, lps_den);
@@ -3642,11 +3709,15 @@ int check_wave_engine(const mlggd_engine *e, int fs_khz, int ctx, bool decoding,
     CHK(spec_dims(fs_khz, d));
     if (decoding && (ctx < 1 || ctx % 2 == 0)) return fail(MLGGD_ERR_ARG, "fea_context %d must be odd", ctx);
     if (ctx < 1) return fail(MLGGD_ERR_ARG, "fea_context %d < 1", ctx);
+    // a mask engine puts out the frame's D bins twice, LPS then mask: the rate must be the one it was created for
+    if (e->mask_bins && e->mask_bins != d->D)
+        return fail(MLGGD_ERR_ARG, "mask_bins %d != %d bins at %d kHz", e->mask_bins, d->D, fs_khz);
     if (e->nat_frames > 0 && ((long long)ctx + 1) * d->D != e->K0)
         return fail(MLGGD_ERR_ARG, "(fea_context %d + 1) x %d bins != layersizes[0] = %d (nat_frames = %d)", ctx, d->D,
                     e->K0, e->nat_frames);
     if (e->nat_frames == 0 && (long long)ctx * d->D != e->K0)
         return fail(MLGGD_ERR_ARG, "fea_context %d x %d bins != layersizes[0] = %d", ctx, d->D, e->K0);
+    if (e->mask_bins) return MLGGD_OK;  // its last layer is 2 mask_bins wide (mlggd_create)
     if (e->D != d->D) return fail(MLGGD_ERR_ARG, "output dimension %d != %d bins at %d kHz", e->D, d->D, fs_khz);
     return MLGGD_OK;
 }
@@ -3667,17 +3738,24 @@ int check_single_device(const mlggd_engine *e, const char *who, bool no_comm) {
 // the factors a decode call or push applies: those of mlggd_set_gv while they are on
 const float *gv_factors(const mlggd_engine *e) { return e->gv_on ? e->gv_dev.p : nullptr; }
 
+// noisy_lps: the analysis' un-normalised rows of the whole call, indexed like X by the packed frame; read on a mask
+// engine only, whose post-filter chooses between them and the estimate
 template <typename Fill>
 int decode_chunk(mlggd_engine *e, const SpecPlan *p, int rows, int n, int ctx, const Fill &fill, const float *nat,
                  const float *mean, const float *inv, const float *eta, const float2 *X, int t0, float *blk,
-                 float *lps_den) {
+                 float *lps_den, const float *noisy_lps) {
     mlggd_engine::RawSet *r;
     CHK(raw_set_acquire(e, rows, n, ctx, 0, false, &r));
     CHK(fill(r));
     raw_set_commit(e, rows, n, ctx, 0);
     if (e->nat_frames) e->nat = nat;
     CHK(forward_resident(e, n));
-    CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, t0, n, blk, e->stream, lps_den, eta));
+    if (e->mask_bins) {
+        const MaskArgs mk = {noisy_lps, e->mask_lo, e->mask_hi, e->mask_scale, e->mask_mode};
+        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, t0, n, blk, e->stream, lps_den, eta, &mk));
+    } else {
+        CHK(launch_synthesis(p, e->chunk_out.p, mean, inv, X, t0, n, blk, e->stream, lps_den, eta));
+    }
     HIPCHK(hipEventRecord(e->raw[e->raw_cur].last_use, e->stream));
     return MLGGD_OK;
 }
@@ -3928,7 +4006,7 @@ int mlggd_enhance_wave(mlggd_handle e, int fs_khz, int fea_context, const float 
     for (int a = 0; a < F; a += cap) {
         const int n = std::min(cap, F - a);
         auto fill = [&](mlggd_engine::RawSet *r) { return load_frames_device(e, r, dl, F, a, n, fea_context, mean, inv); };
-        CHK(decode_chunk(e, p, n + fea_context - 1, n, fea_context, fill, natz, mean, inv, gv_factors(e), X, a, blk, nullptr));
+        CHK(decode_chunk(e, p, n + fea_context - 1, n, fea_context, fill, natz, mean, inv, gv_factors(e), X, a, blk, nullptr, dl));
     }
     return ola_to_host(p, blk, F, out, out_f32, st);
 }
@@ -4066,7 +4144,7 @@ static int enhance_waves_run(mlggd_handle e, const char *who, int fs_khz, int fe
                                (const int *)d_utt, n_utts, a, n, r->nat_row.p);
             return launch_check("k_nat_rows_seg");
         };
-        CHK(decode_chunk(e, p, sp.rows, n, fea_context, fill, natz, mean, inv, gv_factors(e), X, a, blk, den));
+        CHK(decode_chunk(e, p, sp.rows, n, fea_context, fill, natz, mean, inv, gv_factors(e), X, a, blk, den, dl));
     }
     hipLaunchKernelGGL(k_ola_seg, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, blk, d_foff, d_ooff, n_utts,
                        p->d, p->win, of, oi, (long long)n_out);
@@ -4310,6 +4388,8 @@ int mlggd_live_open(mlggd_handle e, int fs_khz, int fea_context, const float *no
     *out = nullptr;
     if (e->nat_frames > 0)  // a session would have to hold its output back until nat_frames frames have arrived
         return fail(MLGGD_ERR_STATE, "mlggd_live_open: live decoding of an engine with nat_frames = %d is not built", e->nat_frames);
+    if (e->mask_bins > 0)  // the post-filter reads the noisy LPS of the decoded frames: a second gathered ring
+        return fail(MLGGD_ERR_STATE, "mlggd_live_open: live decoding of an engine with mask_bins = %d is not built", e->mask_bins);
     int L, S;
     RULE(live_rule::check_group(fs_khz, fea_context, n_sessions, &L, &S, RULE_MSG));
     SpecDims d;
@@ -4453,7 +4533,7 @@ int mlggd_live_push(mlggd_live_handle s, const int16_t *samples, const int64_t *
                                dv.dk_off, dv.dk_slot, n_dk, d.D, a, n, sp.u0, sp.u1, ctx, mean, inv, r->feat.p, r->first.p);
             return launch_check("k_live_stream");
         };
-        CHK(decode_chunk(e, p, sp.rows, n, ctx, fill, nullptr, mean, inv, gv_factors(e), X_dec, a, blk_new, nullptr));
+        CHK(decode_chunk(e, p, sp.rows, n, ctx, fill, nullptr, mean, inv, gv_factors(e), X_dec, a, blk_new, nullptr, nullptr));
     }
     if (n_emit > 0) {
         hipLaunchKernelGGL(k_live_ola, dim3((unsigned)((n_emit + 255) / 256)), dim3(256), 0, st, s->blk[c0].p, blk_new,
@@ -4598,9 +4678,16 @@ int wave_pair_load(mlggd_engine *e, const SpecDims &d, int fs_khz, int ctx, cons
     HIPCHK(hipMemcpyAsync(r->first.p, first_frame, (size_t)n_samples * sizeof(int), hipMemcpyHostToDevice, st));
     for (int k = 0; k < 2; k++)  // the spectrum itself is not wanted here: X = nullptr
         CHK(launch_analysis_seg(p, k ? d_clean : d_noisy, d_woff, d_foff, nullptr, nc, FT, k ? lpsC : lpsN, nullptr, st));
-    hipLaunchKernelGGL(k_lps_norm_pair, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN, (const float *)lpsC,
-                       d.D, (const float *)norm, (const float *)(norm + d.D), r->feat.p, r->targ.p);
-    CHK(launch_check("k_lps_norm_pair"));
+    if (e->mask_bins) {  // targ rows of 2 D floats: [normalised clean LPS | ratio mask]
+        hipLaunchKernelGGL(k_lps_norm_pair_mask, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN,
+                           (const float *)lpsC, d.D, (const float *)norm, (const float *)(norm + d.D), e->mask_scale,
+                           r->feat.p, r->targ.p);
+        CHK(launch_check("k_lps_norm_pair_mask"));
+    } else {
+        hipLaunchKernelGGL(k_lps_norm_pair, dim3((unsigned)FT), dim3(256), 0, st, (const float *)lpsN, (const float *)lpsC,
+                           d.D, (const float *)norm, (const float *)(norm + d.D), r->feat.p, r->targ.p);
+        CHK(launch_check("k_lps_norm_pair"));
+    }
     if (e->nat_frames) {  // the noise rows from the normalised noisy rows, over the utterances that have frames
         CHK(launch_nat_estimate(e, r->feat.p, d_foff, nc, d.D, nullptr, nullptr, r->nat.p));
         t.h_nat_row.resize((size_t)n_samples);
@@ -4723,6 +4810,31 @@ int mlggd_lps_stats(int device, int fs_khz, int n_utts, const int16_t *wave, con
                        (const double *)part, chunks, 2 * d.D, ds);
     CHK(launch_check("k_lps_colfold"));
     HIPCHK(hipMemcpy(sums, ds, (size_t)2 * d.D * sizeof(double), hipMemcpyDeviceToHost));
+    return MLGGD_OK;
+}
+
+// the mask half of a mask engine's target rows from given un-normalised LPS rows: the device arithmetic of
+// k_lps_norm_pair_mask, for users who build frame targets themselves
+int mlggd_mask_targets(int device, int D, int64_t n_frames, const float *noisy_lps, const float *clean_lps, float scale,
+                       float *out) {
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    if (n_frames < 0) return fail(MLGGD_ERR_ARG, "n_frames %lld < 0", (long long)n_frames);
+    if (!(scale > 0.0f) || !std::isfinite(scale))
+        return fail(MLGGD_ERR_ARG, "scale %g: must be positive and finite", (double)scale);
+    if (n_frames == 0) return MLGGD_OK;
+    if (!noisy_lps || !clean_lps || !out) return fail(MLGGD_ERR_ARG, "noisy_lps/clean_lps/out is NULL");
+    const size_t n = (size_t)n_frames * (size_t)D;
+    if ((n + 255) / 256 > (size_t)INT32_MAX) return fail(MLGGD_ERR_ARG, "n_frames %lld x %d bins is too large", (long long)n_frames, D);
+    HIPCHK(hipSetDevice(device));
+    DevBufs b;
+    float *dn = nullptr, *dc = nullptr, *dt = nullptr;
+    CHK(b.upload(&dn, noisy_lps, n));
+    CHK(b.upload(&dc, clean_lps, n));
+    CHK(b.alloc(&dt, n));
+    hipLaunchKernelGGL(k_mask_targets, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, (const float *)dn,
+                       (const float *)dc, n, scale, dt);
+    CHK(launch_check("k_mask_targets"));
+    HIPCHK(hipMemcpy(out, dt, n * sizeof(float), hipMemcpyDeviceToHost));
     return MLGGD_OK;
 }
 
@@ -4860,3 +4972,6 @@ int mlggd_train_waves(mlggd_handle e, int fs_khz, int fea_context, const float *
 }
 
 }  // extern "C"
+
+// the mask engine's kernels (declared in spectral.hip.h and mix.hip.h)
+#include "mask.hip.h"

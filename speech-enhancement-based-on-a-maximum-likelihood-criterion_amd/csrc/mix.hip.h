@@ -5,6 +5,8 @@
 //   k_mix_energy     Ec = sum clean^2, En = sum noise^2 per utterance, exact 64-bit integers
 //   k_mix_apply      gain from (Ec, En, r), noisy = sat16(rint(clean + gain * noise)), gain[u], clipped[u]
 //   k_lps_norm_pair  (lpsN - mean) * inv_std and (lpsC - mean) * inv_std into the raw set's feat / targ
+//   k_lps_norm_pair_mask  the same for a mask engine: targ rows are [normalised clean LPS | ratio mask], mask_rule.h
+//   k_mask_targets   the mask half alone from given rows (mlggd_mask_targets)
 //   k_lps_colstats   per bin sum x and sum x^2 in double over a fixed number of rows; k_lps_colfold adds the partials
 //
 // The cut of the two mixing kernels: the host cuts every utterance into blocks of mix_rule::kBlock consecutive samples
@@ -25,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mask_rule.h"
 #include "mix_rule.h"
 
 constexpr int MIX_THREADS = 256;
@@ -158,6 +161,14 @@ __global__ void k_lps_norm_pair(const float *__restrict__ lpsN, const float *__r
         targ[row + k] = c * s;
     }
 }
+
+// The same for a mask engine (mask_rule.h): targ is [F][2 D], row f = [(lpsC - mean) * inv | s * min(1, exp_det(0.5
+// (lpsC - lpsN)))]; and the mask half alone on n given values.  Defined in mask.hip.h.
+__global__ void k_lps_norm_pair_mask(const float *__restrict__ lpsN, const float *__restrict__ lpsC, int D,
+                                     const float *__restrict__ mean, const float *__restrict__ inv, float scale,
+                                     float *__restrict__ feat, float *__restrict__ targ);
+__global__ void k_mask_targets(const float *__restrict__ noisy, const float *__restrict__ clean, size_t n, float scale,
+                               float *__restrict__ out);
 
 // Per bin the sums of x and x^2 in double over rows [chunk CS_ROWS, (chunk + 1) CS_ROWS) of the packed LPS rows
 // [F][D]: the cut of k_err_stats, a half-wave per bin, lane j adding rows j, j + 32, ... in that order, an xor

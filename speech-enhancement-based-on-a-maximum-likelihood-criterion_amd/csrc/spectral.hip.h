@@ -4,7 +4,8 @@
 //   k_lps_analysis   int16 frames -> window -> real N-point FFT in LDS -> log power rows (and the complex spectrum X)
 //   k_lps_stream     LPS rows -> (lps - mean) * inv_std, edge-replicated context stream for the forward pass
 //   k_lps_synthesis  LPS rows, or the forward pass's outputs de-normalised, + X -> noisy phase, inverse FFT, window
-//                    (k_lps_synthesis_gv: de-normalised with the equalisation factors of gv_rule.h)
+//                    (k_lps_synthesis_gv: de-normalised with the equalisation factors of gv_rule.h;
+//                    k_lps_synthesis_mask / _mask_gv: a mask engine's rows, post-filtered by mask_rule.h)
 //   k_ola            overlap-add of the windowed time blocks, / sum w^2, float and saturated int16 output
 //
 // The *_seg kernels are the same steps over a packed batch of utterances (mlggd_enhance_waves): global frame g of
@@ -23,6 +24,7 @@
 #include <stdint.h>
 
 #include "gv_rule.h"    // gv_rule::apply
+#include "mask_rule.h"  // mask_rule::select
 #include "spec_rule.h"  // SpecDims
 
 #define SPEC_FRAMES 4     // frames (= wavefronts) per workgroup
@@ -186,13 +188,24 @@ __global__ void k_lps_stream_seg(const float *__restrict__ lps, const int *__res
 // mean, two IEEE operations; GV: (y * eta) / inv + mean, gv_rule::apply), noisy spectrum X [t][k] -> windowed time block
 // blk [t][L].  lps_den (optional, with mean): receives the de-normalised rows, [t][D].  The body of k_lps_synthesis
 // (GV = false: eta is never read) and of k_lps_synthesis_gv.
-template <bool GV>
+// MASK (k_lps_synthesis_mask, _mask_gv; mean and inv are given): src holds the 2 D outputs of a mask engine per frame,
+// LPS half first.  Two frame indices: the output rows of a chunk are chunk-local, row r of src; X, lps_den AND the
+// noisy LPS rows `noisy` [t][D] of the analysis are indexed by the packed frame t = t0 + r.  The de-normalised
+// estimate x is formed as without a mask and v = mask_rule::select(noisy, x, src[r][D + k], ...) takes its place
+// (mode off: v = x and neither the mask half nor the noisy rows are read).  MaskArgs is empty for the other kernels.
+struct MaskArgs {
+    const float *noisy;  // [t][D] un-normalised noisy LPS
+    float lo, hi, scale;
+    int mode;  // mask_rule::kOff / kSelect
+};
+template <bool GV, bool MASK = false>
 __device__ __forceinline__ void lps_synthesis_frames(const float *__restrict__ src, const float *__restrict__ mean,
                                                      const float *__restrict__ inv, const float *__restrict__ eta,
                                                      const float2 *__restrict__ X, int t0, int nf, SpecDims d,
                                                      const float *__restrict__ win, const float2 *__restrict__ tw,
                                                      const float2 *__restrict__ tws, float floor_exp,
-                                                     float *__restrict__ blk, float *__restrict__ lps_den) {
+                                                     float *__restrict__ blk, float *__restrict__ lps_den,
+                                                     const MaskArgs mk = MaskArgs{nullptr, 0.0f, 0.0f, 0.0f, 0}) {
     __shared__ float s_yr[SPEC_FRAMES][SPEC_MAXM + 1], s_yi[SPEC_FRAMES][SPEC_MAXM + 1];
     __shared__ float s_re[SPEC_FRAMES][SPEC_ROW], s_im[SPEC_FRAMES][SPEC_ROW];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -202,8 +215,19 @@ __device__ __forceinline__ void lps_synthesis_frames(const float *__restrict__ s
     float *yr = s_yr[wv], *yi = s_yi[wv], *re = s_re[wv], *im = s_im[wv];
     // magnitude substitution, LogSpec2Wav.c:481-494, 683-696
     for (int k = lane; k < d.D; k += 64) {
-        float v = live ? src[(size_t)(live ? r : 0) * d.D + k] : 0.0f;
-        if (GV) {  // always de-normalising: the factors belong to the net's outputs
+        float v = live ? src[(size_t)(live ? r : 0) * (MASK ? 2 * d.D : d.D) + k] : 0.0f;
+        if (MASK) {
+            if (GV) {
+                v = gv_rule::apply(v, eta[k], inv[k], mean[k]);
+            } else {
+                const float q = v / inv[k];
+                v = q + mean[k];
+            }
+            if (live && mk.mode == mask_rule::kSelect)
+                v = mask_rule::select(mk.noisy[t * d.D + k], v, src[(size_t)r * (2 * d.D) + d.D + k], mk.scale, mk.lo,
+                                      mk.hi);
+            if (lps_den && live) lps_den[t * d.D + k] = v;
+        } else if (GV) {  // always de-normalising: the factors belong to the net's outputs
             v = gv_rule::apply(v, eta[k], inv[k], mean[k]);
             if (lps_den && live) lps_den[t * d.D + k] = v;
         } else if (mean) {
@@ -266,6 +290,19 @@ __global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis_gv(
     float *__restrict__ blk, float *__restrict__ lps_den) {
     lps_synthesis_frames<true>(src, mean, inv, eta, X, t0, nf, d, win, tw, tws, floor_exp, blk, lps_den);
 }
+
+// a mask engine's decode: src rows of 2 D outputs, the post-filter of mask_rule.h (MaskArgs above), without and with
+// the equalisation factors eta, of which the first D are read.  Defined in mask.hip.h.
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis_mask(
+    const float *__restrict__ src, const float *__restrict__ mean, const float *__restrict__ inv,
+    const float2 *__restrict__ X, int t0, int nf, SpecDims d, const float *__restrict__ win,
+    const float2 *__restrict__ tw, const float2 *__restrict__ tws, float floor_exp, float *__restrict__ blk,
+    float *__restrict__ lps_den, MaskArgs mk);
+__global__ void __launch_bounds__(64 * SPEC_FRAMES) k_lps_synthesis_mask_gv(
+    const float *__restrict__ src, const float *__restrict__ mean, const float *__restrict__ inv,
+    const float *__restrict__ eta, const float2 *__restrict__ X, int t0, int nf, SpecDims d,
+    const float *__restrict__ win, const float2 *__restrict__ tw, const float2 *__restrict__ tws, float floor_exp,
+    float *__restrict__ blk, float *__restrict__ lps_den, MaskArgs mk);
 
 // One thread per output sample i of F S + L - S: the frames that cover it, in frame order, then / sum w^2 (formed in
 // the same order, LogSpec2Wav.c:799-826).  int16 out = trunc toward zero, saturated.

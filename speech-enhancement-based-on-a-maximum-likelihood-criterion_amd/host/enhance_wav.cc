@@ -7,8 +7,14 @@
 //   enhance_wav wts=mlp.wts norm_file=train_noisy.norm (in=noisy.wav out=enhanced.wav | scp=LIST)
 //               [fea_context=7] [gpu_used=0] [bunchsize=512] [batch_s=300] [clean=clean.wav info=info.txt]
 //               [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu] [nat=T]
-//               [gv=FILE [gv_mode=bin|shared]]
+//               [gv=FILE [gv_mode=bin|shared]] [mask=select|off [mask_lo=0.25] [mask_hi=0.75] [mask_scale=1]]
 //
+// mask=: the net is a multi-objective one (csrc/mask_rule.h): its last layer has 2 x bins units, the clean LPS and a
+// ratio mask trained with scale mask_scale; the .wts file does not say how it was trained.  select: per bin the mask
+// divided by mask_scale picks the noisy LPS (> mask_hi), the mean of noisy LPS and estimate (mask_lo .. mask_hi) or the
+// estimate; off: the LPS half alone is decoded.  The defaults are a choice, not a measured optimum.  In every mode but
+// live=; the reports are those of the post-filtered rows; gv= still holds one factor per bin.  Without mask= a net
+// whose last layer is 2 x bins wide is refused like any other net of the wrong width.
 // gv=FILE: global variance equalisation (csrc/gv_rule.h): the normalised network output of bin k is multiplied by the
 // factor FILE holds for it -- a plain list or the file an epoch with MLGGD_GVFILE=FILE wrote -- before it is
 // de-normalised, in every mode (mlggd_set_gv); gv_mode=shared takes the file's one factor for all bins.  A .wts file
@@ -94,7 +100,8 @@ int main(int argc, char **argv) {
     const char *usage =
         "usage: enhance_wav wts=F norm_file=F (in=F out=F | scp=LIST) [fea_context=7] [gpu_used=0] [bunchsize=512] "
         "[batch_s=300] [clean=F info=F] [score=host|device [stoi=1]] [live=BLOCK [sessions=64]] [activation=sigmoid|relu] "
-        "[nat=T] [gv=FILE [gv_mode=bin|shared]]";
+        "[nat=T] [gv=FILE [gv_mode=bin|shared]] [mask=select|off [mask_lo=0.25] [mask_hi=0.75] [mask_scale=1]]";
+    tool_io::MaskArg mask;
     int ctx = 7, gpu = 0, bunch = 512, live_block = 0, n_slots = 64, act = MLGGD_ACT_SIGMOID, nat = 0;
     bool live = false, score_given = false, want_stoi = false;
     double batch_s = 300.0;
@@ -122,6 +129,10 @@ int main(int argc, char **argv) {
         else if (k == "nat") nat = tool_io::parse_nat(v);
         else if (k == "gv") gv = v;
         else if (k == "gv_mode") gv_mode = v;
+        else if (k == "mask") mask.mode = tool_io::parse_mask_mode(v), mask.given = true;
+        else if (k == "mask_lo") mask.lo = tool_io::parse_mask_value(k, v);
+        else if (k == "mask_hi") mask.hi = tool_io::parse_mask_value(k, v);
+        else if (k == "mask_scale") mask.scale = tool_io::parse_mask_value(k, v);
         else die("unknown argument " + k);
     }
     if (wts.empty() || norm_file.empty() || (scp.empty() && (in.empty() || out.empty())))
@@ -139,16 +150,23 @@ int main(int argc, char **argv) {
         if (live_block < 1) die("live= must be a block of at least one sample");
         if (n_slots < 1) die("sessions= must be at least 1");
         if (nat > 0) die("live= and nat= do not go together: a live session of a noise-aware net is not built");
+        if (mask.given) die("live= and mask= do not go together: a live session of a mask net is not built");
     }
 
     const tool_io::Model model = tool_io::read_wts(wts);
-    const int D = model.ls.back();
+    if (mask.given && model.ls.back() % 2 != 0) die("mask=: the last layer is not 2 x the bins (LPS and mask)");
+    const int D = mask.given ? model.ls.back() / 2 : model.ls.back();  // the bins of a frame
     if (nat > 0 && model.ls[0] != (ctx + 1) * D) die("layersizes[0] is not (fea_context + 1) x the output dimension (nat=)");
     if (nat == 0 && model.ls[0] != ctx * D) die("layersizes[0] is not fea_context x the output dimension");
     std::vector<float> mean, inv;
     tool_io::read_norm(norm_file, D, mean, inv);
-    const std::vector<float> eta = tool_io::read_gv_arg(gv, gv_mode, D);  // a bad file ends the run before the engine exists
-    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act, nat);
+    std::vector<float> eta = tool_io::read_gv_arg(gv, gv_mode, D);  // a bad file ends the run before the engine exists
+    mlggd_handle h = tool_io::create_engine(model, gpu, bunch, 0, act, nat, mask.given ? D : 0);
+    if (mask.given) {
+        if (mlggd_set_mask(h, mask.mode, mask.lo, mask.hi, mask.scale) != MLGGD_OK)
+            die(std::string("mlggd_set_mask: ") + mlggd_last_error());
+        if (!eta.empty()) eta.resize((size_t)2 * D, 1.0f);  // one factor per output; the decoders read the LPS half's
+    }
     if (!eta.empty() && mlggd_set_gv(h, eta.data()) != MLGGD_OK) die(std::string("mlggd_set_gv: ") + mlggd_last_error());
 
     std::vector<Job> jobs;
@@ -356,7 +374,8 @@ int main(int argc, char **argv) {
         if (noisy.size() < (size_t)L) die_in_order(job.in + ": shorter than one frame");
         const int F = it.F = (int)((noisy.size() - (L - S)) / S);
         if (on_device && !job.clean.empty()) it.clean = read_clean(it, &it.Fm, die_in_order);
-        if (batched || on_device) {
+        // (a mask net with a host report: the post-filtered rows come from the batch entry, as a batch of one)
+        if (batched || on_device || (mask.given && !job.clean.empty())) {
             if (!pend.empty() && pend[0].rate != rate) flush();
             pend_samples += noisy.size();
             pend.push_back(std::move(it));

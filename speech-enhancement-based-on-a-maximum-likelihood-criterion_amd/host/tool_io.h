@@ -142,8 +142,26 @@ inline std::vector<float> read_gv_arg(const std::string &path, const std::string
     return eta;
 }
 
+// mask=select|off [mask_lo=] [mask_hi=] [mask_scale=] of enhance_wav: the net is a multi-objective one (csrc/mask_rule.h)
+struct MaskArg {
+    bool given = false;  // mask= was on the command line: the last layer holds the LPS and the mask
+    int mode = MLGGD_MASK_SELECT;
+    float lo = 0.25f, hi = 0.75f, scale = 1.0f;
+};
+inline int parse_mask_mode(const std::string &v) {
+    if (v == "select") return MLGGD_MASK_SELECT;
+    if (v == "off") return MLGGD_MASK_OFF;
+    die("mask=" + v + ": must be select or off");
+}
+inline float parse_mask_value(const std::string &k, const std::string &v) {
+    char *end = nullptr;
+    const float x = strtof(v.c_str(), &end);
+    if (v.empty() || *end) die(k + "=" + v + ": must be a number");
+    return x;
+}
+
 inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_cache_frames = 0,
-                                  int activation = MLGGD_ACT_SIGMOID, int nat_frames = 0) {
+                                  int activation = MLGGD_ACT_SIGMOID, int nat_frames = 0, int mask_bins = 0) {
     const int L = (int)m.ls.size();
     mlggd_config cfg;
     memset(&cfg, 0, sizeof(cfg));
@@ -156,6 +174,7 @@ inline mlggd_handle create_engine(const Model &m, int gpu, int bunch, int max_ca
     cfg.max_cache_frames = max_cache_frames;
     cfg.activation = activation;
     cfg.nat_frames = nat_frames;
+    cfg.mask_bins = mask_bins;
     std::vector<const float *> wp(L, nullptr), bp(L, nullptr);
     for (int l = 1; l < L; l++) { wp[l] = m.W[l].data(); bp[l] = m.B[l].data(); }
     mlggd_handle h = nullptr;
