@@ -1252,14 +1252,48 @@ enum ColsumSource {
 // largest dynamic LDS the loss kernels are ever launched with (bunchsize 1152, the cap mlggd_create enforces)
 constexpr size_t LOSS_LDS_MAX = (size_t)(32 * (1152 + 1) + 32) * sizeof(float);
 
-// the shapes [Dp] the _asym kernels read: the vector of mlggd_set_shapefactors, else cfg.shapefactor per unit
-static const float *asym_betas(const mlggd_engine *e) { return e->per_bin ? e->betas_dev : e->asym_betas_dev.p; }
+// The error model in effect (ErrModel, kernels.hip.h) and the [Dp] device arrays its kernels read, nullptr where the
+// model has none: the one place that knows.  Both vectors are only ever set with MLflag == 1.  EM_ASYM's shapes are the
+// vector of mlggd_set_shapefactors, else cfg.shapefactor per unit.
+struct ErrModelInUse {
+    ErrModel model;
+    const float *betas, *kappas;
+};
+static ErrModelInUse err_model(const mlggd_engine *e) {
+    if (e->asym) return {EM_ASYM, e->per_bin ? e->betas_dev : e->asym_betas_dev.p, e->kappas_dev.p};
+    if (e->per_bin) return {EM_BINS, e->betas_dev, nullptr};
+    return {EM_SHARED, nullptr, nullptr};
+}
+// One launch of a loss-family kernel: the dynamic-LDS attribute of the kernel actually launched (lds_attr 0: it needs
+// none), the launch on the engine's stream, its check.
+template <typename F, typename... Args>
+static int launch_loss(mlggd_engine *e, const char *name, F kernel, dim3 grid, dim3 block, size_t lds_attr, size_t lds,
+                       Args... args) {
+    if (lds_attr) CHK(ensure_lds(e, kernel, lds_attr));
+    hipLaunchKernelGGL(kernel, grid, block, lds, e->stream, args...);
+    return launch_check(name);
+}
+
+// The walk of the resident chunk (inputs AND targets) that every CV-side pass makes, the bunch loop of CrossValid*
+// (BP_GPU.cu:202-216): the CV forward per bunch, the trailing partial bunch INCLUDED, each followed by
+// fold(bunch, its frames, its index), which launches what consumes the bunch's output slabs.
+template <typename Fold>
+static int walk_bunches(mlggd_engine *e, int n, Fold fold) {
+    for (int i = 0, k = 0; i < n; i += e->B, k++) {
+        const int fb = (e->B > n - i) ? (n - i) : e->B;
+        const Bunch bn = bunch_at(e, i);
+        CHK(run_forward(e, bn, fb, false));
+        CHK(fold(bn, fb, k));
+    }
+    return MLGGD_OK;
+}
 
 // Output-layer loss of one minibatch: BP_GPU.cu:408-423.  sa / n_stage: input-staging blocks of the NEXT
 // minibatch that ride along with the first loss launch (n_stage 0: none).
 static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, ColsumSource cs, bool first_acc,
                     const StageArgs &sa, int n_stage) {
     const int L = e->L, B = e->B, Bp = e->Bp, b_tiles = Bp / 32, ML = e->cfg.MLflag;
+    const ErrModelInUse em = err_model(e);
     ProfScope ps(e, KC_LOSS, 0);
     const size_t lds_grad = (size_t)(LOSS_DT * (Bp + 1) + LOSS_DT) * sizeof(float);  // k_loss_grad: LOSS_DT columns
     const int n_loss = (e->Dp / LOSS_DT) * b_tiles;  // 8 (d) x 32 (b) elements per loss workgroup, one per thread
@@ -1280,39 +1314,35 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         la.outT = e->outT; la.eT = e->eT; la.scalefactor = e->scalefactor; la.dEdXt = e->dEdXt[L - 1]; la.dEdX = e->dEdX[L - 1];
         la.first = bn.first; la.toff = e->toff;
         const size_t lds_ml = (size_t)2 * LOSS_DT * (Bp + 1) * sizeof(float);
-        if (e->asym) {  // only ever on with ML == 1 (mlggd_set_asymmetry)
-            CHK(ensure_lds(e, k_loss_ml_asym, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
-            hipLaunchKernelGGL(k_loss_ml_asym, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
-                               asym_betas(e), (const float *)e->kappas_dev.p, e->Dp / LOSS_DT, sa, n_stage);
-            return launch_check("k_loss_ml_asym");
+        const size_t lds_ml_max = (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float);
+        const int n_ml = e->Dp / LOSS_DT;
+        const dim3 grid(n_ml + (n_stage + 3) / 4), block(1024);
+        switch (em.model) {
+        case EM_ASYM:
+            return launch_loss(e, "k_loss_ml_asym", k_loss_ml_asym, grid, block, lds_ml_max, lds_ml, la, em.betas, em.kappas,
+                               n_ml, sa, n_stage);
+        case EM_BINS:
+            return launch_loss(e, "k_loss_ml_bins", k_loss_ml_bins, grid, block, lds_ml_max, lds_ml, la, em.betas, n_ml, sa,
+                               n_stage);
+        default:
+            return launch_loss(e, "k_loss_ml", k_loss_ml, grid, block, lds_ml_max, lds_ml, la, n_ml, sa, n_stage);
         }
-        if (e->per_bin) {
-            CHK(ensure_lds(e, k_loss_ml_bins, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
-            hipLaunchKernelGGL(k_loss_ml_bins, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
-                               (const float *)e->betas_dev, e->Dp / LOSS_DT, sa, n_stage);
-            return launch_check("k_loss_ml_bins");
-        }
-        CHK(ensure_lds(e, k_loss_ml, (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float)));
-        hipLaunchKernelGGL(k_loss_ml, dim3(e->Dp / LOSS_DT + (n_stage + 3) / 4), dim3(1024), lds_ml, e->stream, la,
-                           e->Dp / LOSS_DT, sa, n_stage);
-        return launch_check("k_loss_ml");
     }
     LossErrArgs la;
     la.slab = e->slab; la.S = e->S_out; la.bias = e->bias[L - 1]; la.targ = bn.targ;
     la.B = B; la.D = e->D; la.Dp = e->Dp; la.Bp = Bp; la.beta = e->cfg.shapefactor; la.want_pow = ML == 1 ? 1 : 0;
     la.outT = e->outT; la.eT = e->eT; la.pT = e->pT;
     la.b_tiles = b_tiles; la.first = bn.first; la.toff = e->toff;
-    if (e->asym) {  // only ever on with ML == 1 (mlggd_set_asymmetry)
-        hipLaunchKernelGGL(k_loss_err_asym, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, asym_betas(e),
-                           (const float *)e->kappas_dev.p, n_loss, sa);
-        CHK(launch_check("k_loss_err_asym"));
-    } else if (e->per_bin) {  // only ever on with ML == 1 (mlggd_set_shapefactors)
-        hipLaunchKernelGGL(k_loss_err_bins, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, (const float *)e->betas_dev,
-                           n_loss, sa);
-        CHK(launch_check("k_loss_err_bins"));
-    } else {
-        hipLaunchKernelGGL(k_loss_err, dim3(n_loss + n_stage), dim3(256), 0, e->stream, la, n_loss, sa);
-        CHK(launch_check("k_loss_err"));
+    const dim3 grid_err(n_loss + n_stage), grid(n_loss), block(256);
+    switch (em.model) {
+    case EM_ASYM:
+        CHK(launch_loss(e, "k_loss_err_asym", k_loss_err_asym, grid_err, block, 0, 0, la, em.betas, em.kappas, n_loss, sa));
+        break;
+    case EM_BINS:
+        CHK(launch_loss(e, "k_loss_err_bins", k_loss_err_bins, grid_err, block, 0, 0, la, em.betas, n_loss, sa));
+        break;
+    default:
+        CHK(launch_loss(e, "k_loss_err", k_loss_err, grid_err, block, 0, 0, la, n_loss, sa));
     }
     const float *colsum_in = nullptr;
     if (ML == 1 && cs == CS_GIVEN) {
@@ -1330,24 +1360,18 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         colsum_in = e->colsum;
     }
     if (cs == CS_ACCUMULATE) return MLGGD_OK;
-    if (e->asym) {
-        CHK(ensure_lds(e, k_loss_grad_asym, LOSS_LDS_MAX));
-        hipLaunchKernelGGL(k_loss_grad_asym, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D,
-                           e->Dp, Bp, asym_betas(e), (const float *)e->kappas_dev.p, nf, inv_n, e->scalefactor,
-                           e->dEdXt[L - 1], e->dEdX[L - 1], b_tiles);
-        return launch_check("k_loss_grad_asym");
+    float *const dEdXt = e->dEdXt[L - 1], *const dEdX = e->dEdX[L - 1];
+    switch (em.model) {
+    case EM_ASYM:
+        return launch_loss(e, "k_loss_grad_asym", k_loss_grad_asym, grid, block, LOSS_LDS_MAX, lds_grad, e->eT, e->pT,
+                           colsum_in, B, e->D, e->Dp, Bp, em.betas, em.kappas, nf, inv_n, e->scalefactor, dEdXt, dEdX, b_tiles);
+    case EM_BINS:
+        return launch_loss(e, "k_loss_grad_bins", k_loss_grad_bins, grid, block, LOSS_LDS_MAX, lds_grad, e->eT, e->pT,
+                           colsum_in, B, e->D, e->Dp, Bp, em.betas, nf, inv_n, e->scalefactor, dEdXt, dEdX, b_tiles);
+    default:
+        return launch_loss(e, "k_loss_grad", k_loss_grad, grid, block, LOSS_LDS_MAX, lds_grad, e->eT, e->pT, colsum_in, B,
+                           e->D, e->Dp, Bp, e->cfg.shapefactor, ML, nf, inv_n, e->scalefactor, dEdXt, dEdX, b_tiles);
     }
-    if (e->per_bin) {
-        CHK(ensure_lds(e, k_loss_grad_bins, LOSS_LDS_MAX));
-        hipLaunchKernelGGL(k_loss_grad_bins, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D,
-                           e->Dp, Bp, (const float *)e->betas_dev, nf, inv_n, e->scalefactor, e->dEdXt[L - 1],
-                           e->dEdX[L - 1], b_tiles);
-        return launch_check("k_loss_grad_bins");
-    }
-    CHK(ensure_lds(e, k_loss_grad, LOSS_LDS_MAX));
-    hipLaunchKernelGGL(k_loss_grad, dim3(n_loss), dim3(256), lds_grad, e->stream, e->eT, e->pT, colsum_in, B, e->D, e->Dp, Bp,
-                       e->cfg.shapefactor, ML, nf, inv_n, e->scalefactor, e->dEdXt[L - 1], e->dEdX[L - 1], b_tiles);
-    return launch_check("k_loss_grad");
 }
 
 // dEdX_{l-1} from dEdX_l and the OLD W_l (+ the derivative of layer l-1's activation): BP_GPU.cu:402,430
@@ -2589,29 +2613,21 @@ static int cv_device_reduce(mlggd_engine *e, int n_frames, float *sqerr, float *
     const int nb = (n_frames + e->B - 1) / e->B;
     const size_t need = (size_t)(nb > 0 ? nb : 1) * tiles * 3;
     HIPCHK(e->cv_partial.grow(need, need, e->bufs, nullptr, nullptr));
-    // bunch loop of CrossValid*, BP_GPU.cu:202-216: INCLUDES the trailing partial bunch
-    for (int i = 0, k = 0; i < n_frames; i += e->B, k++) {
-        const int fb = (e->B > n_frames - i) ? (n_frames - i) : e->B;
-        const Bunch bn = bunch_at(e, i);
-        CHK(run_forward(e, bn, fb, false));
-        CvArgs a;
-        a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1]; a.targ = bn.targ;
-        a.B = fb; a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.beta = e->cfg.shapefactor;
-        a.alpha = loglik ? e->scalefactor : nullptr;
-        a.first = bn.first; a.toff = e->toff; a.b_tiles = b_tiles;
+    const ErrModelInUse em = err_model(e);
+    CvArgs a;
+    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
+    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.beta = e->cfg.shapefactor;
+    a.alpha = loglik ? e->scalefactor : nullptr;
+    a.toff = e->toff; a.b_tiles = b_tiles;
+    CHK(walk_bunches(e, n_frames, [&](const Bunch &bn, int fb, int k) {
+        a.targ = bn.targ; a.first = bn.first; a.B = fb;
         a.partial = e->cv_partial.p + (size_t)k * tiles * 3;
-        if (loglik && e->asym) {
-            hipLaunchKernelGGL(k_cv_reduce_asym, dim3(tiles), dim3(256), 0, e->stream, a, asym_betas(e),
-                               (const float *)e->kappas_dev.p);
-            CHK(launch_check("k_cv_reduce_asym"));
-        } else if (loglik && e->per_bin) {
-            hipLaunchKernelGGL(k_cv_reduce_bins, dim3(tiles), dim3(256), 0, e->stream, a, (const float *)e->betas_dev);
-            CHK(launch_check("k_cv_reduce_bins"));
-        } else {
-            hipLaunchKernelGGL(k_cv_reduce, dim3(tiles), dim3(256), 0, e->stream, a);
-            CHK(launch_check("k_cv_reduce"));
+        switch (loglik ? em.model : EM_SHARED) {  // the models differ in the likelihood term only
+        case EM_ASYM: return launch_loss(e, "k_cv_reduce_asym", k_cv_reduce_asym, dim3(tiles), dim3(256), 0, 0, a, em.betas, em.kappas);
+        case EM_BINS: return launch_loss(e, "k_cv_reduce_bins", k_cv_reduce_bins, dim3(tiles), dim3(256), 0, 0, a, em.betas);
+        default: return launch_loss(e, "k_cv_reduce", k_cv_reduce, dim3(tiles), dim3(256), 0, 0, a);
         }
-    }
+    }));
     std::vector<double> part((size_t)nb * tiles * 3);
     std::vector<float> scalefac(D);
     if (nb > 0)
@@ -2781,25 +2797,25 @@ static int error_stats_state(mlggd_engine *e, const char *who, const char *what 
         return fail(MLGGD_ERR_STATE, "%s: %s not available with dropoutflag = %d", who, what, e->cfg.dropoutflag);
     return MLGGD_OK;
 }
-// The chunk (inputs AND targets) is resident: the CV forward per bunch, trailing partial bunch included, each
-// followed by ONE k_err_stats launch that folds the bunch into es_acc; one download and one synchronise.
-static int error_stats_resident(mlggd_engine *e, int n, int n_betas, const float *betas, double *sums) {
-    const int D = e->D, rows = 4 + n_betas;
-    const size_t n_acc = (size_t)(4 + MLGGD_MAX_BETAS) * D;
-    HIPCHK(e->es_acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
+// The error statistics of the resident chunk: ONE launch per bunch folds it into the accumulator (fresh: the first
+// bunch overwrites); one download and one synchronise.  by_sign false: k_err_stats into es_acc, [4 + n_betas][D];
+// true: k_err_stats_signed into ess_acc, [2 n_betas][D], the rows of P+ then of P-.  Neither looks at the skew or
+// shape vector in effect: the statistics are of the errors, the grid is the call's.
+static int error_stats_resident(mlggd_engine *e, int n, int n_betas, const float *betas, bool by_sign, double *sums) {
+    const int D = e->D, rows = by_sign ? 2 * n_betas : 4 + n_betas;
+    const size_t n_acc = (size_t)(by_sign ? 2 * MLGGD_MAX_BETAS : 4 + MLGGD_MAX_BETAS) * D;
+    DevBuf<double> &acc = by_sign ? e->ess_acc : e->es_acc;
+    HIPCHK(acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
     ErrStatsArgs a;
     a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
-    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = e->es_acc.p;
+    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = acc.p;
     for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < n_betas ? betas[k] : 1.0f;
-    for (int i = 0; i < n; i += e->B) {
-        const int fb = (e->B > n - i) ? (n - i) : e->B;
-        const Bunch bn = bunch_at(e, i);
-        CHK(run_forward(e, bn, fb, false));
-        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = i == 0;
-        hipLaunchKernelGGL(k_err_stats, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
-        CHK(launch_check("k_err_stats"));
-    }
-    HIPCHK(hipMemcpyAsync(sums, e->es_acc.p, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    CHK(walk_bunches(e, n, [&](const Bunch &bn, int fb, int k) {
+        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = k == 0;
+        hipLaunchKernelGGL(by_sign ? k_err_stats_signed : k_err_stats, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
+        return launch_check(by_sign ? "k_err_stats_signed" : "k_err_stats");
+    }));
+    HIPCHK(hipMemcpyAsync(sums, acc.p, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }
@@ -2816,7 +2832,7 @@ int mlggd_error_stats(mlggd_handle e, int n_frames, const float *in, const float
         return MLGGD_OK;
     }
     CHK(mlggd_load_chunk(e, n_frames, in, targ));
-    return error_stats_resident(e, n_frames, n_betas, betas, sums);
+    return error_stats_resident(e, n_frames, n_betas, betas, false, sums);
 }
 
 int mlggd_error_stats_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
@@ -2832,30 +2848,7 @@ int mlggd_error_stats_frames(mlggd_handle e, int n_frames, int fea_context, cons
         std::fill(sums, sums + (size_t)(4 + n_betas) * e->D, 0.0);
         return MLGGD_OK;
     }
-    return error_stats_resident(e, n_samples, n_betas, betas, sums);
-}
-
-// error_stats_resident with k_err_stats_signed in the place of k_err_stats: [2 n_betas][D], the rows of P+ then of P-.
-// It does not look at the skew or shape vector in effect: the statistics are of the errors, the grid is the call's.
-static int error_stats_signed_resident(mlggd_engine *e, int n, int n_betas, const float *betas, double *sums) {
-    const int D = e->D;
-    const size_t n_acc = (size_t)2 * MLGGD_MAX_BETAS * D;
-    HIPCHK(e->ess_acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
-    ErrStatsArgs a;
-    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
-    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = e->ess_acc.p;
-    for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < n_betas ? betas[k] : 1.0f;
-    for (int i = 0; i < n; i += e->B) {
-        const int fb = (e->B > n - i) ? (n - i) : e->B;
-        const Bunch bn = bunch_at(e, i);
-        CHK(run_forward(e, bn, fb, false));
-        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = i == 0;
-        hipLaunchKernelGGL(k_err_stats_signed, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
-        CHK(launch_check("k_err_stats_signed"));
-    }
-    HIPCHK(hipMemcpyAsync(sums, e->ess_acc.p, (size_t)2 * n_betas * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return MLGGD_OK;
+    return error_stats_resident(e, n_samples, n_betas, betas, false, sums);
 }
 
 int mlggd_error_stats_signed(mlggd_handle e, int n_frames, const float *in, const float *targ, int n_betas,
@@ -2870,7 +2863,7 @@ int mlggd_error_stats_signed(mlggd_handle e, int n_frames, const float *in, cons
         return MLGGD_OK;
     }
     CHK(mlggd_load_chunk(e, n_frames, in, targ));
-    return error_stats_signed_resident(e, n_frames, n_betas, betas, sums);
+    return error_stats_resident(e, n_frames, n_betas, betas, true, sums);
 }
 
 int mlggd_error_stats_signed_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
@@ -2886,7 +2879,7 @@ int mlggd_error_stats_signed_frames(mlggd_handle e, int n_frames, int fea_contex
         std::fill(sums, sums + (size_t)2 * n_betas * e->D, 0.0);
         return MLGGD_OK;
     }
-    return error_stats_signed_resident(e, n_samples, n_betas, betas, sums);
+    return error_stats_resident(e, n_samples, n_betas, betas, true, sums);
 }
 
 // Host only, no device: the closed-form fit of the asymmetric model (asym_rule::fit) for every bin and grid shape from
@@ -2939,14 +2932,11 @@ static int output_stats_resident(mlggd_engine *e, int n, double *sums) {
     OutStatsArgs a;
     a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
     a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.acc = e->os_acc.p;
-    for (int i = 0; i < n; i += e->B) {
-        const int fb = (e->B > n - i) ? (n - i) : e->B;
-        const Bunch bn = bunch_at(e, i);
-        CHK(run_forward(e, bn, fb, false));
-        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = i == 0;
+    CHK(walk_bunches(e, n, [&](const Bunch &bn, int fb, int k) {
+        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = k == 0;
         hipLaunchKernelGGL(k_out_stats, dim3(e->Dp / OS_DT), dim3(256), 0, e->stream, a);
-        CHK(launch_check("k_out_stats"));
-    }
+        return launch_check("k_out_stats");
+    }));
     HIPCHK(hipMemcpyAsync(sums, e->os_acc.p, n_acc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;

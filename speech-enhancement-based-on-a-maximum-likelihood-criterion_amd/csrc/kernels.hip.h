@@ -2059,10 +2059,26 @@ struct LossErrArgs {
     const int *first;
     int toff;
 };
-// PER_BIN: the shape is read per output unit from betas [Dp] (pads 1.0, mlggd_set_shapefactors) instead of A.beta;
-// the scalar instantiation is the body as it always was.
-template <bool PER_BIN>
+// The error model of the output-layer loss, a compile-time tag.  The families below (loss_err, loss_grad, loss_ml,
+// cv_reduce) are ONE body each, instantiated per model, and the models substitute exactly three things:
+//   EM_SHARED  the reference's scalar shape: beta is the argument struct's (A.beta), the magnitude of an error is
+//              fabsf(e), the gradient takes its sign from the three-way if of kernfunc2;
+//   EM_BINS    a shape per output unit (mlggd_set_shapefactors): beta_d from betas [Dp] (pads 1.0), the rest as EM_SHARED;
+//   EM_ASYM    a shape and a skew per unit (mlggd_set_asymmetry, asym_rule.h): beta_d as EM_BINS (an engine without a
+//              shape vector fills betas with cfg.shapefactor), kappa_d from kappas [Dp] (pads 1.0), the magnitude is
+//              s(e) = kappa_d e (e > 0), (-e) / kappa_d (e < 0), and the gradient is the existing value at s(e) times
+//              ds/de (asym_rule::grad).  s and the choice between the two gradient forms are selects on the lane's
+//              own e; beta and kappa are uniform over a unit's lanes, so pow_or_self's branches stay uniform.  At
+//              kappa = 1 every intermediate is EM_BINS' value.  ML only: there is no want_pow and no MLflag.
+// A model's pointers are nullptr where it does not read them.  Every other statement -- slab sum, target gather,
+// kernSumcol's order, alpha and alpha^beta, LDS layout, stores, reductions -- is the same text for all three.
+enum ErrModel { EM_SHARED, EM_BINS, EM_ASYM };
+// Phase A is the one family whose EM_ASYM instantiation of a shared body does not compile to the code its own kernel
+// has (the target row's 64-bit index costs five more integer instructions, profiles/loss_family_isa.txt), so
+// k_loss_err_asym below keeps its own text and this body serves EM_SHARED and EM_BINS.
+template <int EM>
 __device__ __forceinline__ void loss_err_body(const LossErrArgs &A, const float *__restrict__ betas, const int bid) {
+    static_assert(EM != EM_ASYM, "k_loss_err_asym has its own text");
     const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
     float *__restrict__ outT = A.outT, *__restrict__ eT = A.eT, *__restrict__ pT = A.pT;
     const int *__restrict__ first = A.first;
@@ -2076,7 +2092,7 @@ __device__ __forceinline__ void loss_err_body(const LossErrArgs &A, const float 
     float e = 0.0f, p = 0.0f;
     if (b < A.B && d < A.D) {
         e = x - targ[(size_t)(first ? first[b] + A.toff : b) * A.D + d];  // kernerror
-        if (A.want_pow) p = pow_or_self(fabsf(e), PER_BIN ? betas[d] : A.beta);  // kernabsolutevalus + kernindex2
+        if (A.want_pow) p = pow_or_self(fabsf(e), EM == EM_SHARED ? A.beta : betas[d]);  // kernabsolutevalus + kernindex2
     } else {
         x = 0.0f;
     }
@@ -2089,18 +2105,16 @@ __device__ __forceinline__ void loss_err_body(const LossErrArgs &A, const float 
 // blocks ride along on the idle ones instead of costing a launch of their own.
 __global__ __launch_bounds__(256) void k_loss_err(LossErrArgs A, int n_loss, StageArgs G) {
     const int n_stage = (int)gridDim.x - n_loss;  // staging blocks first: they are the longer ones
-    if ((int)blockIdx.x >= n_stage) loss_err_body<false>(A, nullptr, (int)blockIdx.x - n_stage);
+    if ((int)blockIdx.x >= n_stage) loss_err_body<EM_SHARED>(A, nullptr, (int)blockIdx.x - n_stage);
     else transpose_in_body(G, (int)blockIdx.x);
 }
 __global__ __launch_bounds__(256) void k_loss_err_bins(LossErrArgs A, const float *__restrict__ betas, int n_loss,
                                                        StageArgs G) {
     const int n_stage = (int)gridDim.x - n_loss;
-    if ((int)blockIdx.x >= n_stage) loss_err_body<true>(A, betas, (int)blockIdx.x - n_stage);
+    if ((int)blockIdx.x >= n_stage) loss_err_body<EM_BINS>(A, betas, (int)blockIdx.x - n_stage);
     else transpose_in_body(G, (int)blockIdx.x);
 }
-// Phase A under the asymmetric model (mlggd_set_asymmetry, asym_rule.h): k_loss_err_bins with p = s(e)^beta_d,
-// s(e) = kappa_d e for e > 0 and (-e) / kappa_d for e < 0, both read per unit from [Dp] arrays (pads 1.0).  ML only,
-// so there is no want_pow.  A body and a kernel of its own so that loss_err_body stays the code it was.
+// EM_ASYM: p = s(e)^beta_d; ML only, so there is no want_pow.
 __global__ __launch_bounds__(256) void k_loss_err_asym(LossErrArgs A, const float *__restrict__ betas,
                                                        const float *__restrict__ kappas, int n_loss, StageArgs G) {
     const int n_stage = (int)gridDim.x - n_loss;
@@ -2191,17 +2205,21 @@ __global__ __launch_bounds__(256) void k_colsum(const float *__restrict__ pT, in
 // otherwise colsum_in is the GLOBAL minibatch sum (all-reduced).  nf = global minibatch size.
 // One workgroup per 8(d) x 32(b) tile; writes dEdXt and dEdX.  Dynamic LDS: 8*(Bp+1)+8 floats.
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_loss_grad(const float *__restrict__ eT, const float *__restrict__ pT,
-                                                   const float *__restrict__ colsum_in, int B, int D, int Dp, int Bp,
-                                                   float beta, int MLflag, float nf, float inv_n,
-                                                   float *__restrict__ scalefactor, float *__restrict__ dEdXt,
-                                                   float *__restrict__ dEdX, int b_tiles) {
+// beta and MLflag are read under EM_SHARED only: the other two models are ML by construction.
+template <int EM>
+__device__ __forceinline__ void loss_grad_body(const float *__restrict__ eT, const float *__restrict__ pT,
+                                               const float *__restrict__ colsum_in, int B, int D, int Dp, int Bp,
+                                               float beta_shared, const float *__restrict__ betas,
+                                               const float *__restrict__ kappas, int MLflag, float nf, float inv_n,
+                                               float *__restrict__ scalefactor, float *__restrict__ dEdXt,
+                                               float *__restrict__ dEdX, int b_tiles) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ float denom[LOSS_DT];
+    const bool ml = EM != EM_SHARED || MLflag == 1;
     const int dt = blockIdx.x / b_tiles, bt = blockIdx.x % b_tiles;
     const int d0 = dt * LOSS_DT;
     const int tid = threadIdx.x;
-    if (MLflag == 1) {
+    if (ml) {
         float *rows = dyn, *sums = dyn + LOSS_DT * (Bp + 1);
         if (colsum_in == nullptr) {
             colsum_tile<LOSS_DT>(pT, d0, B, Bp, rows, sums);
@@ -2213,6 +2231,7 @@ __global__ __launch_bounds__(256) void k_loss_grad(const float *__restrict__ eT,
             const int d = d0 + tid;
             float q = 1.0f;
             if (d < D) {
+                const float beta = EM == EM_SHARED ? beta_shared : betas[d];
                 const float v1 = sums[tid] / nf;            // kernDivide
                 const float v2 = v1 * beta;                 // kernVecMulNum
                 const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
@@ -2228,7 +2247,12 @@ __global__ __launch_bounds__(256) void k_loss_grad(const float *__restrict__ eT,
     const float e = eT[o];
     float g = 0.0f;
     if (b < B && d < D) {
-        if (MLflag == 1) {
+        const float beta = EM == EM_SHARED ? beta_shared : betas[d];
+        if (EM == EM_ASYM) {
+            const float kappa = kappas[d];
+            const float v = pow_or_self(asym_rule::skewed(e, kappa), beta - 1.0f) * beta / denom[dl];  // kernfunc2 at s(e)
+            g = asym_rule::grad(e, v, kappa);
+        } else if (ml) {
             if (e > 0) g = pow_or_self(e, beta - 1.0f) * beta / denom[dl];
             else if (e == 0) g = 0;
             else g = -pow_or_self(-e, beta - 1.0f) * beta / denom[dl];
@@ -2242,106 +2266,30 @@ __global__ __launch_bounds__(256) void k_loss_grad(const float *__restrict__ eT,
     dEdXt[o] = g;
     dEdX[(size_t)b * Dp + d] = g;
 }
-// The ML-GGD gradient with a shape per output unit (mlggd_set_shapefactors): k_loss_grad's MLflag == 1 branch, every
-// expression and its order unchanged, with beta read from betas [Dp] (pads 1.0) for the thread's own unit.  A kernel
-// of its own so that k_loss_grad stays the code it was.
+__global__ __launch_bounds__(256) void k_loss_grad(const float *__restrict__ eT, const float *__restrict__ pT,
+                                                   const float *__restrict__ colsum_in, int B, int D, int Dp, int Bp,
+                                                   float beta, int MLflag, float nf, float inv_n,
+                                                   float *__restrict__ scalefactor, float *__restrict__ dEdXt,
+                                                   float *__restrict__ dEdX, int b_tiles) {
+    loss_grad_body<EM_SHARED>(eT, pT, colsum_in, B, D, Dp, Bp, beta, nullptr, nullptr, MLflag, nf, inv_n, scalefactor,
+                              dEdXt, dEdX, b_tiles);
+}
 __global__ __launch_bounds__(256) void k_loss_grad_bins(const float *__restrict__ eT, const float *__restrict__ pT,
                                                         const float *__restrict__ colsum_in, int B, int D, int Dp,
                                                         int Bp, const float *__restrict__ betas, float nf, float inv_n,
                                                         float *__restrict__ scalefactor, float *__restrict__ dEdXt,
                                                         float *__restrict__ dEdX, int b_tiles) {
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ float denom[LOSS_DT];
-    const int dt = blockIdx.x / b_tiles, bt = blockIdx.x % b_tiles;
-    const int d0 = dt * LOSS_DT;
-    const int tid = threadIdx.x;
-    {
-        float *rows = dyn, *sums = dyn + LOSS_DT * (Bp + 1);
-        if (colsum_in == nullptr) {
-            colsum_tile<LOSS_DT>(pT, d0, B, Bp, rows, sums);
-        } else {
-            if (tid < LOSS_DT) sums[tid] = colsum_in[d0 + tid];
-            __syncthreads();
-        }
-        if (tid < LOSS_DT) {
-            const int d = d0 + tid;
-            float q = 1.0f;
-            if (d < D) {
-                const float beta = betas[d];
-                const float v1 = sums[tid] / nf;            // kernDivide
-                const float v2 = v1 * beta;                 // kernVecMulNum
-                const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
-                if (bt == 0) scalefactor[d] = alpha;
-                q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
-            }
-            denom[tid] = q;
-        }
-        __syncthreads();
-    }
-    const int dl = tid >> 5, d = d0 + dl, b = bt * 32 + (tid & 31);
-    const size_t o = (size_t)d * Bp + b;
-    const float e = eT[o];
-    float g = 0.0f;
-    if (b < B && d < D) {
-        const float beta = betas[d];
-        if (e > 0) g = pow_or_self(e, beta - 1.0f) * beta / denom[dl];
-        else if (e == 0) g = 0;
-        else g = -pow_or_self(-e, beta - 1.0f) * beta / denom[dl];
-        g = g * inv_n;
-    }
-    dEdXt[o] = g;
-    dEdX[(size_t)b * Dp + d] = g;
+    loss_grad_body<EM_BINS>(eT, pT, colsum_in, B, D, Dp, Bp, 0.0f, betas, nullptr, 1, nf, inv_n, scalefactor, dEdXt, dEdX,
+                            b_tiles);
 }
-// k_loss_grad_bins under the asymmetric model (asym_rule.h): pT holds s(e)^beta_d, so the statistic, alpha and the
-// denominator are the statements they were; the gradient is the existing value at s(e) times ds/de.  s and the choice
-// between the two gradient forms are selects on the lane's own e; beta and kappa are uniform over a unit's half-wave.
-// A kernel of its own so that k_loss_grad_bins stays the code it was.
 __global__ __launch_bounds__(256) void k_loss_grad_asym(const float *__restrict__ eT, const float *__restrict__ pT,
                                                         const float *__restrict__ colsum_in, int B, int D, int Dp,
                                                         int Bp, const float *__restrict__ betas,
                                                         const float *__restrict__ kappas, float nf, float inv_n,
                                                         float *__restrict__ scalefactor, float *__restrict__ dEdXt,
                                                         float *__restrict__ dEdX, int b_tiles) {
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ float denom[LOSS_DT];
-    const int dt = blockIdx.x / b_tiles, bt = blockIdx.x % b_tiles;
-    const int d0 = dt * LOSS_DT;
-    const int tid = threadIdx.x;
-    {
-        float *rows = dyn, *sums = dyn + LOSS_DT * (Bp + 1);
-        if (colsum_in == nullptr) {
-            colsum_tile<LOSS_DT>(pT, d0, B, Bp, rows, sums);
-        } else {
-            if (tid < LOSS_DT) sums[tid] = colsum_in[d0 + tid];
-            __syncthreads();
-        }
-        if (tid < LOSS_DT) {
-            const int d = d0 + tid;
-            float q = 1.0f;
-            if (d < D) {
-                const float beta = betas[d];
-                const float v1 = sums[tid] / nf;            // kernDivide
-                const float v2 = v1 * beta;                 // kernVecMulNum
-                const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
-                if (bt == 0) scalefactor[d] = alpha;
-                q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
-            }
-            denom[tid] = q;
-        }
-        __syncthreads();
-    }
-    const int dl = tid >> 5, d = d0 + dl, b = bt * 32 + (tid & 31);
-    const size_t o = (size_t)d * Bp + b;
-    const float e = eT[o];
-    float g = 0.0f;
-    if (b < B && d < D) {
-        const float beta = betas[d], kappa = kappas[d];
-        const float v = pow_or_self(asym_rule::skewed(e, kappa), beta - 1.0f) * beta / denom[dl];  // kernfunc2 at s(e)
-        g = asym_rule::grad(e, v, kappa);
-        g = g * inv_n;
-    }
-    dEdXt[o] = g;
-    dEdX[(size_t)b * Dp + d] = g;
+    loss_grad_body<EM_ASYM>(eT, pT, colsum_in, B, D, Dp, Bp, 0.0f, betas, kappas, 1, nf, inv_n, scalefactor, dEdXt, dEdX,
+                            b_tiles);
 }
 
 // MLflag != 1 needs no statistic over the minibatch, so phases A and B collapse into one
@@ -2410,21 +2358,20 @@ struct LossMlArgs {
     const int *first;
     int toff;
 };
-__global__ __launch_bounds__(1024) void k_loss_ml(LossMlArgs A, int n_loss, StageArgs G, int n_stage_tiles) {
-    const int n_stage = (int)gridDim.x - n_loss;
-    if ((int)blockIdx.x < n_stage) {
-        transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
-        return;
-    }
+// wg: the loss workgroup, staging blocks not counted
+template <int EM>
+__device__ __forceinline__ void loss_ml_body(const LossMlArgs &A, const float *__restrict__ betas,
+                                             const float *__restrict__ kappas, const int wg) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ float denom[LOSS_DT];
     const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
     const int *__restrict__ first = A.first;
     const int B = A.B, D = A.D, Dp = A.Dp, Bp = A.Bp;
-    const float beta = A.beta;
     float *es = dyn, *ps = dyn + LOSS_DT * (Bp + 1);  // [8][Bp+1] each
-    const int d0 = ((int)blockIdx.x - n_stage) * LOSS_DT;
+    const int d0 = wg * LOSS_DT;
     const int tid = threadIdx.x, dl = tid >> 7, d = d0 + dl;  // 8 units x 128 frames per pass
+    // uniform over the unit's 128 threads, two whole waves: pow_or_self's branches stay wave-uniform
+    const float beta = EM == EM_SHARED ? A.beta : betas[d], kappa = EM == EM_ASYM ? kappas[d] : 1.0f;
     for (int b = tid & 127; b < Bp; b += 128) {
         const size_t o = (size_t)d * Bp + b;
         float x = slab_sum(slab, o, (size_t)Dp * Bp, A.S);
@@ -2432,7 +2379,7 @@ __global__ __launch_bounds__(1024) void k_loss_ml(LossMlArgs A, int n_loss, Stag
         float e = 0.0f, p = 0.0f;
         if (b < B && d < D) {
             e = x - targ[(size_t)(first ? first[b] + A.toff : b) * D + d];  // kernerror
-            p = pow_or_self(fabsf(e), beta);                                  // kernabsolutevalus + kernindex2
+            p = pow_or_self(EM == EM_ASYM ? asym_rule::skewed(e, kappa) : fabsf(e), beta);  // kernabsolutevalus + kernindex2
         } else {
             x = 0.0f;
         }
@@ -2456,6 +2403,7 @@ __global__ __launch_bounds__(1024) void k_loss_ml(LossMlArgs A, int n_loss, Stag
         for (; b < B; b++) s += col[b];
         float q = 1.0f;
         if (d0 + tid < D) {
+            const float beta = EM == EM_SHARED ? A.beta : betas[d0 + tid];  // the column this thread sums, not the unit of its passes
             const float v1 = s / A.nf;                  // kernDivide
             const float v2 = v1 * beta;                 // kernVecMulNum
             const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
@@ -2469,9 +2417,14 @@ __global__ __launch_bounds__(1024) void k_loss_ml(LossMlArgs A, int n_loss, Stag
         const float e = es[dl * (Bp + 1) + b];
         float g = 0.0f;
         if (b < B && d < D) {
-            if (e > 0) g = pow_or_self(e, beta - 1.0f) * beta / denom[dl];  // kernfunc2
-            else if (e == 0) g = 0;
-            else g = -pow_or_self(-e, beta - 1.0f) * beta / denom[dl];
+            if (EM == EM_ASYM) {
+                const float v = pow_or_self(asym_rule::skewed(e, kappa), beta - 1.0f) * beta / denom[dl];
+                g = asym_rule::grad(e, v, kappa);
+            } else {
+                if (e > 0) g = pow_or_self(e, beta - 1.0f) * beta / denom[dl];
+                else if (e == 0) g = 0;
+                else g = -pow_or_self(-e, beta - 1.0f) * beta / denom[dl];
+            }
             g = g * A.inv_n;                                                  // kernVecMulNum
         }
         A.dEdXt[(size_t)d * Bp + b] = g;
@@ -2490,8 +2443,14 @@ __global__ __launch_bounds__(1024) void k_loss_ml(LossMlArgs A, int n_loss, Stag
         *reinterpret_cast<float4 *>(&A.dEdX[(size_t)b * Dp + d0 + h4]) = v;
     }
 }
-// k_loss_ml with a shape per output unit (mlggd_set_shapefactors): the same statements in the same order, beta read
-// from betas [Dp] (pads 1.0) instead of A.beta.  A kernel of its own so that k_loss_ml stays the code it was.
+__global__ __launch_bounds__(1024) void k_loss_ml(LossMlArgs A, int n_loss, StageArgs G, int n_stage_tiles) {
+    const int n_stage = (int)gridDim.x - n_loss;
+    if ((int)blockIdx.x < n_stage) {
+        transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
+        return;
+    }
+    loss_ml_body<EM_SHARED>(A, nullptr, nullptr, (int)blockIdx.x - n_stage);
+}
 __global__ __launch_bounds__(1024) void k_loss_ml_bins(LossMlArgs A, const float *__restrict__ betas, int n_loss,
                                                        StageArgs G, int n_stage_tiles) {
     const int n_stage = (int)gridDim.x - n_loss;
@@ -2499,87 +2458,8 @@ __global__ __launch_bounds__(1024) void k_loss_ml_bins(LossMlArgs A, const float
         transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
         return;
     }
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ float denom[LOSS_DT];
-    const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
-    const int *__restrict__ first = A.first;
-    const int B = A.B, D = A.D, Dp = A.Dp, Bp = A.Bp;
-    float *es = dyn, *ps = dyn + LOSS_DT * (Bp + 1);  // [8][Bp+1] each
-    const int d0 = ((int)blockIdx.x - n_stage) * LOSS_DT;
-    const int tid = threadIdx.x, dl = tid >> 7, d = d0 + dl;  // 8 units x 128 frames per pass
-    const float beta = betas[d];  // uniform over the unit's 128 threads, two whole waves: pow_or_self's branches stay wave-uniform
-    for (int b = tid & 127; b < Bp; b += 128) {
-        const size_t o = (size_t)d * Bp + b;
-        float x = slab_sum(slab, o, (size_t)Dp * Bp, A.S);
-        x = x + bias[d];
-        float e = 0.0f, p = 0.0f;
-        if (b < B && d < D) {
-            e = x - targ[(size_t)(first ? first[b] + A.toff : b) * D + d];  // kernerror
-            p = pow_or_self(fabsf(e), beta);                                  // kernabsolutevalus + kernindex2
-        } else {
-            x = 0.0f;
-        }
-        A.outT[o] = x;
-        A.eT[o] = e;
-        es[dl * (Bp + 1) + b] = e;
-        ps[dl * (Bp + 1) + b] = p;
-    }
-    __syncthreads();
-    if (tid < LOSS_DT) {
-        const float *col = ps + tid * (Bp + 1);
-        float s = col[0];  // kernSumcol: (*top) = (*fromp); then += in row order
-        int b = 1;
-        for (; b + 16 <= B; b += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = col[b + u];
-#pragma unroll
-            for (int u = 0; u < 16; u++) s += v[u];
-        }
-        for (; b < B; b++) s += col[b];
-        float q = 1.0f;
-        if (d0 + tid < D) {
-            const float beta = betas[d0 + tid];         // the column this thread sums, not the unit of its passes
-            const float v1 = s / A.nf;                  // kernDivide
-            const float v2 = v1 * beta;                 // kernVecMulNum
-            const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
-            A.scalefactor[d0 + tid] = alpha;
-            q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
-        }
-        denom[tid] = q;
-    }
-    __syncthreads();
-    for (int b = tid & 127; b < Bp; b += 128) {
-        const float e = es[dl * (Bp + 1) + b];
-        float g = 0.0f;
-        if (b < B && d < D) {
-            if (e > 0) g = pow_or_self(e, beta - 1.0f) * beta / denom[dl];  // kernfunc2
-            else if (e == 0) g = 0;
-            else g = -pow_or_self(-e, beta - 1.0f) * beta / denom[dl];
-            g = g * A.inv_n;                                                  // kernVecMulNum
-        }
-        A.dEdXt[(size_t)d * Bp + b] = g;
-        es[dl * (Bp + 1) + b] = g;  // this thread's own element: the row layout leaves below, 16 bytes at a time
-    }
-    // dEdX [frame][unit]: a frame's 8 units of this workgroup are 32 contiguous bytes -- two 16-byte stores per frame
-    // (2 * Bp per workgroup) instead of eight 4-byte stores each into a line of its own (8 * Bp)
-    __syncthreads();
-    for (int t = tid; t < 2 * Bp; t += 1024) {
-        const int b = t >> 1, h4 = (t & 1) * 4;
-        float4 v;
-        v.x = es[(h4 + 0) * (Bp + 1) + b];
-        v.y = es[(h4 + 1) * (Bp + 1) + b];
-        v.z = es[(h4 + 2) * (Bp + 1) + b];
-        v.w = es[(h4 + 3) * (Bp + 1) + b];
-        *reinterpret_cast<float4 *>(&A.dEdX[(size_t)b * Dp + d0 + h4]) = v;
-    }
+    loss_ml_body<EM_BINS>(A, betas, nullptr, (int)blockIdx.x - n_stage);
 }
-// k_loss_ml_bins under the asymmetric model (mlggd_set_asymmetry, asym_rule.h): the same statements in the same order
-// with s(e) = kappa_d e (e > 0), (-e) / kappa_d (e < 0) in the place of |e| and the gradient times ds/de; beta and
-// kappa come from [Dp] arrays (pads 1.0; an engine without a shape vector fills betas with cfg.shapefactor).  s and
-// the choice between the two gradient forms are selects on the lane's own e, so pow_or_self still sees a wave-uniform
-// exponent.  At kappa = 1 every intermediate is k_loss_ml_bins' value.  The LDS size, the staging blocks and the float4
-// dEdX stores are k_loss_ml's.  A kernel of its own so that k_loss_ml_bins stays the code it was.
 __global__ __launch_bounds__(1024) void k_loss_ml_asym(LossMlArgs A, const float *__restrict__ betas,
                                                        const float *__restrict__ kappas, int n_loss, StageArgs G,
                                                        int n_stage_tiles) {
@@ -2588,78 +2468,7 @@ __global__ __launch_bounds__(1024) void k_loss_ml_asym(LossMlArgs A, const float
         transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
         return;
     }
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ float denom[LOSS_DT];
-    const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
-    const int *__restrict__ first = A.first;
-    const int B = A.B, D = A.D, Dp = A.Dp, Bp = A.Bp;
-    float *es = dyn, *ps = dyn + LOSS_DT * (Bp + 1);  // [8][Bp+1] each
-    const int d0 = ((int)blockIdx.x - n_stage) * LOSS_DT;
-    const int tid = threadIdx.x, dl = tid >> 7, d = d0 + dl;  // 8 units x 128 frames per pass
-    const float beta = betas[d], kappa = kappas[d];  // uniform over the unit's 128 threads, two whole waves
-    for (int b = tid & 127; b < Bp; b += 128) {
-        const size_t o = (size_t)d * Bp + b;
-        float x = slab_sum(slab, o, (size_t)Dp * Bp, A.S);
-        x = x + bias[d];
-        float e = 0.0f, p = 0.0f;
-        if (b < B && d < D) {
-            e = x - targ[(size_t)(first ? first[b] + A.toff : b) * D + d];  // kernerror
-            p = pow_or_self(asym_rule::skewed(e, kappa), beta);              // s(e) in the place of |e|, then kernindex2
-        } else {
-            x = 0.0f;
-        }
-        A.outT[o] = x;
-        A.eT[o] = e;
-        es[dl * (Bp + 1) + b] = e;
-        ps[dl * (Bp + 1) + b] = p;
-    }
-    __syncthreads();
-    if (tid < LOSS_DT) {
-        const float *col = ps + tid * (Bp + 1);
-        float s = col[0];  // kernSumcol: (*top) = (*fromp); then += in row order
-        int b = 1;
-        for (; b + 16 <= B; b += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; u++) v[u] = col[b + u];
-#pragma unroll
-            for (int u = 0; u < 16; u++) s += v[u];
-        }
-        for (; b < B; b++) s += col[b];
-        float q = 1.0f;
-        if (d0 + tid < D) {
-            const float beta = betas[d0 + tid];         // the column this thread sums, not the unit of its passes
-            const float v1 = s / A.nf;                  // kernDivide
-            const float v2 = v1 * beta;                 // kernVecMulNum
-            const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
-            A.scalefactor[d0 + tid] = alpha;
-            q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
-        }
-        denom[tid] = q;
-    }
-    __syncthreads();
-    for (int b = tid & 127; b < Bp; b += 128) {
-        const float e = es[dl * (Bp + 1) + b];
-        float g = 0.0f;
-        if (b < B && d < D) {
-            const float v = pow_or_self(asym_rule::skewed(e, kappa), beta - 1.0f) * beta / denom[dl];  // kernfunc2 at s(e)
-            g = asym_rule::grad(e, v, kappa);                                 // the sign, then ds/de
-            g = g * A.inv_n;                                                  // kernVecMulNum
-        }
-        A.dEdXt[(size_t)d * Bp + b] = g;
-        es[dl * (Bp + 1) + b] = g;  // this thread's own element: the row layout leaves below, 16 bytes at a time
-    }
-    // dEdX [frame][unit]: two 16-byte stores per frame, as in k_loss_ml
-    __syncthreads();
-    for (int t = tid; t < 2 * Bp; t += 1024) {
-        const int b = t >> 1, h4 = (t & 1) * 4;
-        float4 v;
-        v.x = es[(h4 + 0) * (Bp + 1) + b];
-        v.y = es[(h4 + 1) * (Bp + 1) + b];
-        v.z = es[(h4 + 2) * (Bp + 1) + b];
-        v.w = es[(h4 + 3) * (Bp + 1) + b];
-        *reinterpret_cast<float4 *>(&A.dEdX[(size_t)b * Dp + d0 + h4]) = v;
-    }
+    loss_ml_body<EM_ASYM>(A, betas, kappas, (int)blockIdx.x - n_stage);
 }
 
 // Forward-only output (cv_bunch_single, BP_GPU.cu:442-512): out[b][d] = bias + sum_s slab,
@@ -2706,7 +2515,11 @@ struct CvArgs {
     int toff, b_tiles;
     double *partial;     // [tiles][3] of this bunch
 };
-__global__ __launch_bounds__(256) void k_cv_reduce(CvArgs A) {
+// The models differ in the likelihood term only (A.beta is read under EM_SHARED alone): |t - o| / alpha_d, under
+// EM_ASYM s(o - t) / alpha_d; the two shape-free sums are the same statements.
+template <int EM>
+__device__ __forceinline__ void cv_reduce_body(const CvArgs A, const float *__restrict__ betas,
+                                               const float *__restrict__ kappas) {
     __shared__ float tt[32][33];
     __shared__ double red[4][3];
     const int dt = blockIdx.x / A.b_tiles, bt = blockIdx.x % A.b_tiles;
@@ -2728,7 +2541,9 @@ __global__ __launch_bounds__(256) void k_cv_reduce(CvArgs A) {
             const float t = tt[tx][dl];
             sq += (double)((x - t) * (x - t));   // BP_GPU.cu:211
             ab += (double)fabsf(x - t);           // BP_GPU.cu:246
-            if (A.alpha) ll += (double)pow_or_self(fabsf(t - x) / A.alpha[d], A.beta);  // BP_GPU.cu:295-296
+            if (A.alpha)                          // BP_GPU.cu:295-296
+                ll += (double)pow_or_self((EM == EM_ASYM ? asym_rule::skewed(x - t, kappas[d]) : fabsf(t - x)) / A.alpha[d],
+                                          EM == EM_SHARED ? A.beta : betas[d]);
         }
     }
 #pragma unroll
@@ -2749,98 +2564,13 @@ __global__ __launch_bounds__(256) void k_cv_reduce(CvArgs A) {
         A.partial[(size_t)blockIdx.x * 3 + j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
     }
 }
-// k_cv_reduce with beta_d from betas [Dp] in the likelihood term (A.beta is not read); a kernel of its own so that
-// k_cv_reduce stays the code it was.
+__global__ __launch_bounds__(256) void k_cv_reduce(CvArgs A) { cv_reduce_body<EM_SHARED>(A, nullptr, nullptr); }
 __global__ __launch_bounds__(256) void k_cv_reduce_bins(CvArgs A, const float *__restrict__ betas) {
-    __shared__ float tt[32][33];
-    __shared__ double red[4][3];
-    const int dt = blockIdx.x / A.b_tiles, bt = blockIdx.x % A.b_tiles;
-    const int d0 = dt * 32, b0 = bt * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int b = b0 + ty + 8 * q, d = d0 + tx;
-        tt[ty + 8 * q][tx] = (b < A.B && d < A.D) ? A.targ[(size_t)(A.first ? A.first[b] + A.toff : b) * A.D + d] : 0.0f;
-    }
-    __syncthreads();
-    double sq = 0.0, ab = 0.0, ll = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int dl = ty + 8 * q, d = d0 + dl, b = b0 + tx;
-        if (b < A.B && d < A.D) {
-            float x = slab_sum(A.slab, (size_t)d * A.Bp + b, (size_t)A.Dp * A.Bp, A.S);
-            x = x + A.bias[d];
-            const float t = tt[tx][dl];
-            sq += (double)((x - t) * (x - t));   // BP_GPU.cu:211
-            ab += (double)fabsf(x - t);           // BP_GPU.cu:246
-            if (A.alpha) ll += (double)pow_or_self(fabsf(t - x) / A.alpha[d], betas[d]);  // BP_GPU.cu:295-296
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sq += __shfl_down(sq, off, 64);
-        ab += __shfl_down(ab, off, 64);
-        ll += __shfl_down(ll, off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[wave][0] = sq;
-        red[wave][1] = ab;
-        red[wave][2] = ll;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int j = threadIdx.x;
-        A.partial[(size_t)blockIdx.x * 3 + j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-    }
+    cv_reduce_body<EM_BINS>(A, betas, nullptr);
 }
-
-// k_cv_reduce_bins under the asymmetric model (asym_rule.h): s(o - t) / alpha_d in the place of |t - o| / alpha_d in the
-// likelihood term, kappa_d from kappas [Dp]; the two shape-free sums are the statements they were.  A kernel of its
-// own so that k_cv_reduce_bins stays the code it was.
 __global__ __launch_bounds__(256) void k_cv_reduce_asym(CvArgs A, const float *__restrict__ betas,
                                                         const float *__restrict__ kappas) {
-    __shared__ float tt[32][33];
-    __shared__ double red[4][3];
-    const int dt = blockIdx.x / A.b_tiles, bt = blockIdx.x % A.b_tiles;
-    const int d0 = dt * 32, b0 = bt * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int b = b0 + ty + 8 * q, d = d0 + tx;
-        tt[ty + 8 * q][tx] = (b < A.B && d < A.D) ? A.targ[(size_t)(A.first ? A.first[b] + A.toff : b) * A.D + d] : 0.0f;
-    }
-    __syncthreads();
-    double sq = 0.0, ab = 0.0, ll = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int dl = ty + 8 * q, d = d0 + dl, b = b0 + tx;
-        if (b < A.B && d < A.D) {
-            float x = slab_sum(A.slab, (size_t)d * A.Bp + b, (size_t)A.Dp * A.Bp, A.S);
-            x = x + A.bias[d];
-            const float t = tt[tx][dl];
-            sq += (double)((x - t) * (x - t));   // BP_GPU.cu:211
-            ab += (double)fabsf(x - t);           // BP_GPU.cu:246
-            if (A.alpha) ll += (double)pow_or_self(asym_rule::skewed(x - t, kappas[d]) / A.alpha[d], betas[d]);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        sq += __shfl_down(sq, off, 64);
-        ab += __shfl_down(ab, off, 64);
-        ll += __shfl_down(ll, off, 64);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[wave][0] = sq;
-        red[wave][1] = ab;
-        red[wave][2] = ll;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int j = threadIdx.x;
-        A.partial[(size_t)blockIdx.x * 3 + j] = ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-    }
+    cv_reduce_body<EM_ASYM>(A, betas, kappas);
 }
 
 // Dropout on the transposed activations (kernDropout, DevFunc.cu:26-34 <- BP_GPU.cu:344-355):
