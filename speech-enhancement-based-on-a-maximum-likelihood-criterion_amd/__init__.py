@@ -94,12 +94,13 @@ _lib = None
 def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
-                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "errstats.hip.h", "outstats.hip.h", "gv_rule.h", "mask_rule.h", "mask.hip.h", "mix.hip.h",
+                                             "live_rule.h", "stoi.hip.h", "stoi_rule.h", "colstats.hip.h", "gv_rule.h", "mask_rule.h", "mask.hip.h", "mix.hip.h",
                                              "mix_rule.h", "nat_rule.h", "asym_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     srcs.append(os.path.join(_HERE, "host", "gvfile.h"))
     srcs.append(os.path.join(_HERE, "host", "asymfile.h"))
+    srcs.append(os.path.join(_HERE, "host", "binfile.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
     if force or stale:
@@ -923,52 +924,51 @@ class BPGpu:
                                           C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    # -- the column statistics of a CV chunk, both chunk forms: fn one of the six C entries, rows(K) the rows of its
+    # sums for a grid of K shapes, betas None where the entry has no grid
+    def _col_stats(self, fn, rows, inp, targ, betas=None):
+        inp, targ = _f32(inp), _f32(targ)
+        b = None if betas is None else _betas(betas)
+        grid = () if b is None else (b.size, _p(b))
+        n = inp.shape[0]
+        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
+            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
+        sums = np.zeros((rows(0 if b is None else b.size), self.D), np.float64)
+        _check(fn(self._h, n, _p(inp), _p(targ), *grid,
+                  sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
+    def _col_stats_frames(self, fn, rows, feat, targ, first_frame, fea_context, targ_offset, betas=None):
+        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
+        b = None if betas is None else _betas(betas)
+        grid = () if b is None else (b.size, _p(b))
+        sums = np.zeros((rows(0 if b is None else b.size), self.D), np.float64)
+        _check(fn(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
+                  first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset),
+                  *grid, sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return sums
+
     # -- the GGD error model: per-bin sums of e^1..4 and |e|^beta over a CV chunk, formed on the device (ggd_fit fits them)
     def error_stats(self, inp, targ, betas):
         """[4 + K][D] float64: sum e, e^2, e^3, e^4 and sum |e|^betas[k] per output bin over the rows of inp / targ,
         e = forward(inp) - targ (mlggd_error_stats).  Additive over chunks."""
-        inp, targ, b = _f32(inp), _f32(targ), _betas(betas)
-        n = inp.shape[0]
-        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
-            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
-        sums = np.zeros((4 + b.size, self.D), np.float64)
-        _check(load().mlggd_error_stats(self._h, n, _p(inp), _p(targ), b.size, _p(b),
-                                        sums.ctypes.data_as(C.POINTER(C.c_double))))
-        return sums
+        return self._col_stats(load().mlggd_error_stats, lambda K: 4 + K, inp, targ, betas)
 
     def error_stats_frames(self, feat, targ, first_frame, fea_context, targ_offset, betas):
         """The same over a frame-stream chunk (mlggd_error_stats_frames): the same bits for the same rows."""
-        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
-        b = _betas(betas)
-        sums = np.zeros((4 + b.size, self.D), np.float64)
-        _check(load().mlggd_error_stats_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
-                                               first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset), b.size,
-                                               _p(b), sums.ctypes.data_as(C.POINTER(C.c_double))))
-        return sums
+        return self._col_stats_frames(load().mlggd_error_stats_frames, lambda K: 4 + K, feat, targ, first_frame, fea_context,
+                                      targ_offset, betas)
 
     # -- the asymmetric error model: the power sums split by the sign of e (asym_fit fits them), and the skew per bin
     def error_stats_signed(self, inp, targ, betas):
         """[2 K][D] float64: rows 0..K-1 sum_{e>0} e^betas[k], rows K..2K-1 sum_{e<0} (-e)^betas[k] per output bin over
         the rows of inp / targ, e = forward(inp) - targ (mlggd_error_stats_signed).  Additive over chunks."""
-        inp, targ, b = _f32(inp), _f32(targ), _betas(betas)
-        n = inp.shape[0]
-        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
-            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
-        sums = np.zeros((2 * b.size, self.D), np.float64)
-        _check(load().mlggd_error_stats_signed(self._h, n, _p(inp), _p(targ), b.size, _p(b),
-                                               sums.ctypes.data_as(C.POINTER(C.c_double))))
-        return sums
+        return self._col_stats(load().mlggd_error_stats_signed, lambda K: 2 * K, inp, targ, betas)
 
     def error_stats_signed_frames(self, feat, targ, first_frame, fea_context, targ_offset, betas):
         """The same over a frame-stream chunk (mlggd_error_stats_signed_frames): the same bits for the same rows."""
-        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
-        b = _betas(betas)
-        sums = np.zeros((2 * b.size, self.D), np.float64)
-        _check(load().mlggd_error_stats_signed_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ),
-                                                      first.size, first.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                      int(targ_offset), b.size, _p(b),
-                                                      sums.ctypes.data_as(C.POINTER(C.c_double))))
-        return sums
+        return self._col_stats_frames(load().mlggd_error_stats_signed_frames, lambda K: 2 * K, feat, targ, first_frame,
+                                      fea_context, targ_offset, betas)
 
     def asymmetry(self):
         """The D skews in effect: the vector of set_asymmetry, else ones."""
@@ -989,22 +989,12 @@ class BPGpu:
     def output_stats(self, inp, targ):
         """[4][D] float64: sum y, y^2, t, t^2 per output bin over the rows of inp / targ, y = forward(inp)
         (mlggd_output_stats).  Additive over chunks."""
-        inp, targ = _f32(inp), _f32(targ)
-        n = inp.shape[0]
-        if inp.shape != (n, self.K0) or targ.shape != (n, self.D):
-            raise ValueError("in must be [n][%d] and targ [n][%d]" % (self.K0, self.D))
-        sums = np.zeros((4, self.D), np.float64)
-        _check(load().mlggd_output_stats(self._h, n, _p(inp), _p(targ), sums.ctypes.data_as(C.POINTER(C.c_double))))
-        return sums
+        return self._col_stats(load().mlggd_output_stats, lambda K: 4, inp, targ)
 
     def output_stats_frames(self, feat, targ, first_frame, fea_context, targ_offset):
         """The same over a frame-stream chunk (mlggd_output_stats_frames): the same bits for the same rows."""
-        feat, targ, first = self._frames_args(feat, targ, first_frame, fea_context)
-        sums = np.zeros((4, self.D), np.float64)
-        _check(load().mlggd_output_stats_frames(self._h, feat.shape[0], int(fea_context), _p(feat), _p(targ), first.size,
-                                                first.ctypes.data_as(C.POINTER(C.c_int32)), int(targ_offset),
-                                                sums.ctypes.data_as(C.POINTER(C.c_double))))
-        return sums
+        return self._col_stats_frames(load().mlggd_output_stats_frames, lambda K: 4, feat, targ, first_frame, fea_context,
+                                      targ_offset)
 
     def forward_frames(self, feat, first_frame, fea_context):
         feat, _, first = self._frames_args(feat, None, first_frame, fea_context)

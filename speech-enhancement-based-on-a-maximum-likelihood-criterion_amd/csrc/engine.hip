@@ -31,8 +31,7 @@
 #include "stoi_rule.h"
 #include "live.hip.h"
 #include "live_rule.h"
-#include "errstats.hip.h"
-#include "outstats.hip.h"
+#include "colstats.hip.h"
 #include "gv_rule.h"
 #include "mask_rule.h"
 #include "mix.hip.h"
@@ -1285,6 +1284,25 @@ static int walk_bunches(mlggd_engine *e, int n, Fold fold) {
         CHK(run_forward(e, bn, fb, false));
         CHK(fold(bn, fb, k));
     }
+    return MLGGD_OK;
+}
+
+// The column statistics of the resident chunk (colstats.hip.h): walk_bunches with ONE launch of `kernel` per bunch,
+// which folds the bunch into `acc` (n_acc doubles, allocated on first use; fresh: the first bunch overwrites); one
+// download of `rows` rows and one synchronise.
+template <class Args>
+static int col_stats_resident(mlggd_engine *e, int n, DevBuf<double> &acc, size_t n_acc, int rows, void (*kernel)(Args),
+                              const char *name, Args a, double *sums) {
+    HIPCHK(acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
+    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
+    a.D = e->D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.acc = acc.p;
+    CHK(walk_bunches(e, n, [&](const Bunch &bn, int fb, int k) {
+        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = k == 0;
+        hipLaunchKernelGGL(kernel, dim3(e->Dp / COLSTATS_DT), dim3(256), 0, e->stream, a);
+        return launch_check(name);
+    }));
+    HIPCHK(hipMemcpyAsync(sums, acc.p, (size_t)rows * e->D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
     return MLGGD_OK;
 }
 
@@ -2781,7 +2799,7 @@ int mlggd_forward_frames(mlggd_handle e, int n_frames, int fea_context, const fl
     return forward_to_host(e, n_samples, out);
 }
 
-// ------------------------------------------------------------------ error model (errstats.hip.h)
+// ------------------------------------------------------------------ column statistics (colstats.hip.h)
 static int check_betas(int n_betas, const float *betas) {
     if (n_betas < 1 || n_betas > MLGGD_MAX_BETAS)
         return fail(MLGGD_ERR_ARG, "n_betas %d not in 1..%d", n_betas, MLGGD_MAX_BETAS);
@@ -2791,95 +2809,94 @@ static int check_betas(int n_betas, const float *betas) {
             return fail(MLGGD_ERR_ARG, "betas[%d] = %g: a shape must be positive and finite", k, (double)betas[k]);
     return MLGGD_OK;
 }
-static int error_stats_state(mlggd_engine *e, const char *who, const char *what = "the error model is") {
+static int error_stats_state(mlggd_engine *e, const char *who, const char *what) {
     if (e->comm || e->fake_world) return fail(MLGGD_ERR_STATE, "%s runs on a single-device engine", who);
     if (e->cfg.dropoutflag != 0)
         return fail(MLGGD_ERR_STATE, "%s: %s not available with dropoutflag = %d", who, what, e->cfg.dropoutflag);
     return MLGGD_OK;
 }
-// The error statistics of the resident chunk: ONE launch per bunch folds it into the accumulator (fresh: the first
-// bunch overwrites); one download and one synchronise.  by_sign false: k_err_stats into es_acc, [4 + n_betas][D];
-// true: k_err_stats_signed into ess_acc, [2 n_betas][D], the rows of P+ then of P-.  Neither looks at the skew or
-// shape vector in effect: the statistics are of the errors, the grid is the call's.
-static int error_stats_resident(mlggd_engine *e, int n, int n_betas, const float *betas, bool by_sign, double *sums) {
-    const int D = e->D, rows = by_sign ? 2 * n_betas : 4 + n_betas;
-    const size_t n_acc = (size_t)(by_sign ? 2 * MLGGD_MAX_BETAS : 4 + MLGGD_MAX_BETAS) * D;
-    DevBuf<double> &acc = by_sign ? e->ess_acc : e->es_acc;
-    HIPCHK(acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
+// One call of the three statistics: which terms, the call's grid (none for the output statistics) and where the sums
+// go.  None of them looks at the skew or shape vector in effect: the statistics are of the errors, the grid is the call's.
+enum ColStatsKind { COLSTATS_ERR, COLSTATS_ERR_SIGNED, COLSTATS_OUT };
+struct ColStatsCall {
+    ColStatsKind kind;
+    int n_betas;
+    const float *betas;
+    double *sums;  // [rows()][D]
+    bool grid() const { return kind != COLSTATS_OUT; }
+    int rows(int K) const { return kind == COLSTATS_ERR ? 4 + K : kind == COLSTATS_ERR_SIGNED ? 2 * K : gv_rule::kRows; }
+    int rows() const { return rows(n_betas); }
+    const char *what() const { return grid() ? "the error model is" : "the output statistics are"; }
+};
+// k_err_stats into es_acc, [4 + n_betas][D]; k_err_stats_signed into ess_acc, [2 n_betas][D], the rows of P+ then of
+// P-; k_out_stats into os_acc, [4][D].  The error accumulators are sized for the largest grid.
+static int col_stats_run(mlggd_engine *e, int n, const ColStatsCall &c) {
+    const size_t n_acc = (size_t)c.rows(MLGGD_MAX_BETAS) * e->D;
+    if (c.kind == COLSTATS_OUT)
+        return col_stats_resident(e, n, e->os_acc, n_acc, c.rows(), k_out_stats, "k_out_stats", OutStatsArgs(), c.sums);
     ErrStatsArgs a;
-    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
-    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.K = n_betas; a.acc = acc.p;
-    for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < n_betas ? betas[k] : 1.0f;
-    CHK(walk_bunches(e, n, [&](const Bunch &bn, int fb, int k) {
-        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = k == 0;
-        hipLaunchKernelGGL(by_sign ? k_err_stats_signed : k_err_stats, dim3(e->Dp / ES_DT), dim3(256), 0, e->stream, a);
-        return launch_check(by_sign ? "k_err_stats_signed" : "k_err_stats");
-    }));
-    HIPCHK(hipMemcpyAsync(sums, acc.p, (size_t)rows * D * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
+    a.K = c.n_betas;
+    for (int k = 0; k < MLGGD_MAX_BETAS; k++) a.betas[k] = k < c.n_betas ? c.betas[k] : 1.0f;
+    return c.kind == COLSTATS_ERR_SIGNED
+               ? col_stats_resident(e, n, e->ess_acc, n_acc, c.rows(), k_err_stats_signed, "k_err_stats_signed", a, c.sums)
+               : col_stats_resident(e, n, e->es_acc, n_acc, c.rows(), k_err_stats, "k_err_stats", a, c.sums);
+}
+static int col_stats_zero(mlggd_engine *e, const ColStatsCall &c) {
+    std::fill(c.sums, c.sums + (size_t)c.rows() * e->D, 0.0);
     return MLGGD_OK;
+}
+// The two forms of the six entries.  The order of the checks decides which error wins and is the entries' contract.
+static int col_stats_chunk(mlggd_engine *e, const char *who, const ColStatsCall &c, int n_frames, const float *in,
+                           const float *targ) {
+    if (!e || !c.sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    if (c.grid()) CHK(check_betas(c.n_betas, c.betas));
+    CHK(check_frames(e, n_frames));
+    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
+    CHK(error_stats_state(e, who, c.what()));
+    if (n_frames == 0) return col_stats_zero(e, c);
+    CHK(mlggd_load_chunk(e, n_frames, in, targ));
+    return col_stats_run(e, n_frames, c);
+}
+static int col_stats_frames(mlggd_engine *e, const char *who, const ColStatsCall &c, int n_frames, int fea_context,
+                            const float *feat, const float *targ, int n_samples, const int32_t *first_frame,
+                            int targ_offset) {
+    if (!e || !c.sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
+    if (c.grid()) CHK(check_betas(c.n_betas, c.betas));
+    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
+    CHK(error_stats_state(e, who, c.what()));
+    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
+    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
+    if (n_samples == 0) return col_stats_zero(e, c);
+    return col_stats_run(e, n_samples, c);
 }
 
 int mlggd_error_stats(mlggd_handle e, int n_frames, const float *in, const float *targ, int n_betas,
                       const float *betas, double *sums) {
-    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
-    CHK(check_betas(n_betas, betas));
-    CHK(check_frames(e, n_frames));
-    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
-    CHK(error_stats_state(e, "mlggd_error_stats"));
-    if (n_frames == 0) {
-        std::fill(sums, sums + (size_t)(4 + n_betas) * e->D, 0.0);
-        return MLGGD_OK;
-    }
-    CHK(mlggd_load_chunk(e, n_frames, in, targ));
-    return error_stats_resident(e, n_frames, n_betas, betas, false, sums);
+    return col_stats_chunk(e, "mlggd_error_stats", {COLSTATS_ERR, n_betas, betas, sums}, n_frames, in, targ);
 }
-
 int mlggd_error_stats_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
                              int n_samples, const int32_t *first_frame, int targ_offset, int n_betas,
                              const float *betas, double *sums) {
-    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
-    CHK(check_betas(n_betas, betas));
-    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
-    CHK(error_stats_state(e, "mlggd_error_stats_frames"));
-    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
-    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
-    if (n_samples == 0) {
-        std::fill(sums, sums + (size_t)(4 + n_betas) * e->D, 0.0);
-        return MLGGD_OK;
-    }
-    return error_stats_resident(e, n_samples, n_betas, betas, false, sums);
+    return col_stats_frames(e, "mlggd_error_stats_frames", {COLSTATS_ERR, n_betas, betas, sums}, n_frames, fea_context, feat,
+                            targ, n_samples, first_frame, targ_offset);
 }
-
 int mlggd_error_stats_signed(mlggd_handle e, int n_frames, const float *in, const float *targ, int n_betas,
                              const float *betas, double *sums) {
-    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
-    CHK(check_betas(n_betas, betas));
-    CHK(check_frames(e, n_frames));
-    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
-    CHK(error_stats_state(e, "mlggd_error_stats_signed"));
-    if (n_frames == 0) {
-        std::fill(sums, sums + (size_t)2 * n_betas * e->D, 0.0);
-        return MLGGD_OK;
-    }
-    CHK(mlggd_load_chunk(e, n_frames, in, targ));
-    return error_stats_resident(e, n_frames, n_betas, betas, true, sums);
+    return col_stats_chunk(e, "mlggd_error_stats_signed", {COLSTATS_ERR_SIGNED, n_betas, betas, sums}, n_frames, in, targ);
 }
-
 int mlggd_error_stats_signed_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
                                     int n_samples, const int32_t *first_frame, int targ_offset, int n_betas,
                                     const float *betas, double *sums) {
-    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
-    CHK(check_betas(n_betas, betas));
-    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
-    CHK(error_stats_state(e, "mlggd_error_stats_signed_frames"));
-    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
-    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
-    if (n_samples == 0) {
-        std::fill(sums, sums + (size_t)2 * n_betas * e->D, 0.0);
-        return MLGGD_OK;
-    }
-    return error_stats_resident(e, n_samples, n_betas, betas, true, sums);
+    return col_stats_frames(e, "mlggd_error_stats_signed_frames", {COLSTATS_ERR_SIGNED, n_betas, betas, sums}, n_frames,
+                            fea_context, feat, targ, n_samples, first_frame, targ_offset);
+}
+int mlggd_output_stats(mlggd_handle e, int n_frames, const float *in, const float *targ, double *sums) {
+    return col_stats_chunk(e, "mlggd_output_stats", {COLSTATS_OUT, 0, nullptr, sums}, n_frames, in, targ);
+}
+int mlggd_output_stats_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
+                              int n_samples, const int32_t *first_frame, int targ_offset, double *sums) {
+    return col_stats_frames(e, "mlggd_output_stats_frames", {COLSTATS_OUT, 0, nullptr, sums}, n_frames, fea_context, feat,
+                            targ, n_samples, first_frame, targ_offset);
 }
 
 // Host only, no device: the closed-form fit of the asymmetric model (asym_rule::fit) for every bin and grid shape from
@@ -2920,53 +2937,6 @@ int mlggd_asym_fit(int D, int64_t n, int n_betas, const float *betas, const doub
     if (loglik_shared) std::copy(shared.begin(), shared.end(), loglik_shared);
     if (best_shared) *best_shared = arg;
     return MLGGD_OK;
-}
-
-// ------------------------------------------------------------------ output statistics (outstats.hip.h)
-// error_stats_resident with k_out_stats in the place of k_err_stats: the CV forward per bunch, trailing partial bunch
-// included, each followed by ONE k_out_stats launch that folds the bunch into os_acc; one download, one synchronise.
-static int output_stats_resident(mlggd_engine *e, int n, double *sums) {
-    const int D = e->D;
-    const size_t n_acc = (size_t)gv_rule::kRows * D;
-    HIPCHK(e->os_acc.grow(n_acc, n_acc, e->bufs, nullptr, nullptr));
-    OutStatsArgs a;
-    a.slab = e->slab; a.S = e->S_out; a.bias = e->bias[e->L - 1];
-    a.D = D; a.Dp = e->Dp; a.Bp = e->Bp; a.toff = e->toff; a.acc = e->os_acc.p;
-    CHK(walk_bunches(e, n, [&](const Bunch &bn, int fb, int k) {
-        a.targ = bn.targ; a.first = bn.first; a.B = fb; a.fresh = k == 0;
-        hipLaunchKernelGGL(k_out_stats, dim3(e->Dp / OS_DT), dim3(256), 0, e->stream, a);
-        return launch_check("k_out_stats");
-    }));
-    HIPCHK(hipMemcpyAsync(sums, e->os_acc.p, n_acc * sizeof(double), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return MLGGD_OK;
-}
-
-int mlggd_output_stats(mlggd_handle e, int n_frames, const float *in, const float *targ, double *sums) {
-    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
-    CHK(check_frames(e, n_frames));
-    if (n_frames > 0 && (!in || !targ)) return fail(MLGGD_ERR_ARG, "in/targ is NULL");
-    CHK(error_stats_state(e, "mlggd_output_stats", "the output statistics are"));
-    if (n_frames == 0) {
-        std::fill(sums, sums + (size_t)gv_rule::kRows * e->D, 0.0);
-        return MLGGD_OK;
-    }
-    CHK(mlggd_load_chunk(e, n_frames, in, targ));
-    return output_stats_resident(e, n_frames, sums);
-}
-
-int mlggd_output_stats_frames(mlggd_handle e, int n_frames, int fea_context, const float *feat, const float *targ,
-                              int n_samples, const int32_t *first_frame, int targ_offset, double *sums) {
-    if (!e || !sums) return fail(MLGGD_ERR_ARG, "NULL handle / sums");
-    if (n_samples > 0 && !targ) return fail(MLGGD_ERR_ARG, "targ is NULL");
-    CHK(error_stats_state(e, "mlggd_output_stats_frames", "the output statistics are"));
-    // the remaining shape checks are mlggd_load_frames' own, all made before its first device call
-    CHK(mlggd_load_frames(e, n_frames, fea_context, feat, targ, n_samples, first_frame, targ_offset));
-    if (n_samples == 0) {
-        std::fill(sums, sums + (size_t)gv_rule::kRows * e->D, 0.0);
-        return MLGGD_OK;
-    }
-    return output_stats_resident(e, n_samples, sums);
 }
 
 // Host only, no device: moments, ML scale and profile log-likelihood of the GGD error model from the sums of

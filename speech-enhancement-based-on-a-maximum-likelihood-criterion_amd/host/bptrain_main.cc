@@ -382,90 +382,62 @@ int main(int argc, char *argv[]) {
             if (io->fp_log) fflush(io->fp_log);
             phase("cross validation", t_phase);
 
-            // ---- error model of the CV set (MLGGD_ERRMODEL): a second pass, nothing of it reaches the log
-            if (errmodel_fn && (p->dropoutflag != 0 || world > 1)) {
-                printf("error model: not available %s; %s is not written\n",
-                       p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", errmodel_fn);
-            } else if (errmodel_fn) {
-                const int K = (int)errmodel_betas.size();
-                std::vector<double> total((size_t)(4 + K) * D, 0.0), part(total.size());
+            // ---- the per-bin models of the CV set: one more pass over the CV chunks each, nothing of it reaches the log.
+            // `stats` folds the chunk Readchunk*_cv left in the buffers into part ([rows][D], both chunk forms), the
+            // parts are added, and `write` fits the total over n samples, writes `fn` and returns the shared value.
+            auto cv_stats_pass = [&](const char *label, const char *var, const char *unavailable, const char *shared_what,
+                                     const char *fn, size_t rows, auto stats, auto write) {
+                if (!fn) return;
+                if (p->dropoutflag != 0 || world > 1) {
+                    printf("%s: %s %s; %s is not written\n", label, unavailable,
+                           p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", fn);
+                    return;
+                }
+                std::vector<double> total(rows * D, 0.0), part(total.size());
                 int64_t n_total = 0;
                 for (unsigned i = 0; i < io->cv_total_chunks; i++) {
-                    progress("error model");
-                    int n;
-                    if (frames) {
-                        n = io->Readchunk_frames_cv((int)i);
+                    progress(label);
+                    const int n = frames ? io->Readchunk_frames_cv((int)i) : io->Readchunk_cv((int)i);
+                    stats(n, part.data());
+                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
+                    n_total += n;
+                }
+                if (n_total == 0) throw IoError(std::string(var) + ": the CV set has no samples, " + fn + " is not written");
+                const double shared = write(n_total, total);
+                printf("%s: %s written, %lld CV samples, %s %.9g\n", label, fn, (long long)n_total, shared_what, shared);
+                phase(label, t_phase);
+            };
+            const int Ke = (int)errmodel_betas.size(), Ka = (int)asymmodel_betas.size();
+            cv_stats_pass("error model", "MLGGD_ERRMODEL", "not available", "shared beta", errmodel_fn, 4 + Ke,
+                [&](int n, double *part) {
+                    if (frames)
                         net->ErrorStats_frames(p->chunk_frames[0], p->fea_context, p->frames_in[0], p->frames_targ[0], n,
-                                               p->first_frame[0], p->targ_offset, K, errmodel_betas.data(), part.data());
-                    } else {
-                        n = io->Readchunk_cv((int)i);
-                        net->ErrorStats(n, p->indata[0], p->targ[0], K, errmodel_betas.data(), part.data());
-                    }
-                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
-                    n_total += n;
-                }
-                if (n_total == 0) throw IoError(std::string("MLGGD_ERRMODEL: the CV set has no samples, ") + errmodel_fn + " is not written");
-                const double shared = mlggd_host::write_error_model(errmodel_fn, D, n_total, errmodel_betas, total);
-                printf("error model: %s written, %lld CV samples, shared beta %.9g\n", errmodel_fn, (long long)n_total, shared);
-                phase("error model", t_phase);
-            }
-
-            // ---- asymmetric error model of the CV set (MLGGD_ASYMMODEL): one more pass, nothing of it reaches the log
-            if (asymmodel_fn && (p->dropoutflag != 0 || world > 1)) {
-                printf("asymmetric error model: not available %s; %s is not written\n",
-                       p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", asymmodel_fn);
-            } else if (asymmodel_fn) {
-                const int K = (int)asymmodel_betas.size();
-                std::vector<double> total((size_t)2 * K * D, 0.0), part(total.size());
-                int64_t n_total = 0;
-                for (unsigned i = 0; i < io->cv_total_chunks; i++) {
-                    progress("asymmetric error model");
-                    int n;
-                    if (frames) {
-                        n = io->Readchunk_frames_cv((int)i);
+                                               p->first_frame[0], p->targ_offset, Ke, errmodel_betas.data(), part);
+                    else net->ErrorStats(n, p->indata[0], p->targ[0], Ke, errmodel_betas.data(), part);
+                },
+                [&](int64_t n, const std::vector<double> &total) {
+                    return mlggd_host::write_error_model(errmodel_fn, D, n, errmodel_betas, total);
+                });
+            cv_stats_pass("asymmetric error model", "MLGGD_ASYMMODEL", "not available", "shared beta", asymmodel_fn, 2 * Ka,
+                [&](int n, double *part) {
+                    if (frames)
                         net->ErrorStatsSigned_frames(p->chunk_frames[0], p->fea_context, p->frames_in[0], p->frames_targ[0], n,
-                                                     p->first_frame[0], p->targ_offset, K, asymmodel_betas.data(), part.data());
-                    } else {
-                        n = io->Readchunk_cv((int)i);
-                        net->ErrorStatsSigned(n, p->indata[0], p->targ[0], K, asymmodel_betas.data(), part.data());
-                    }
-                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
-                    n_total += n;
-                }
-                if (n_total == 0)
-                    throw IoError(std::string("MLGGD_ASYMMODEL: the CV set has no samples, ") + asymmodel_fn + " is not written");
-                const double shared = mlggd_host::write_asym_model(asymmodel_fn, D, n_total, asymmodel_betas, total);
-                printf("asymmetric error model: %s written, %lld CV samples, shared beta %.9g\n", asymmodel_fn,
-                       (long long)n_total, shared);
-                phase("asymmetric error model", t_phase);
-            }
-
-            // ---- global variance of the CV set (MLGGD_GVFILE): one more pass, nothing of it reaches the log
-            if (gv_fn && (p->dropoutflag != 0 || world > 1)) {
-                printf("global variance: MLGGD_GVFILE is not available %s; %s is not written\n",
-                       p->dropoutflag != 0 ? "with dropoutflag != 0" : "on a data-parallel run", gv_fn);
-            } else if (gv_fn) {
-                std::vector<double> total((size_t)4 * D, 0.0), part(total.size());
-                int64_t n_total = 0;
-                for (unsigned i = 0; i < io->cv_total_chunks; i++) {
-                    progress("global variance");
-                    int n;
-                    if (frames) {
-                        n = io->Readchunk_frames_cv((int)i);
+                                                     p->first_frame[0], p->targ_offset, Ka, asymmodel_betas.data(), part);
+                    else net->ErrorStatsSigned(n, p->indata[0], p->targ[0], Ka, asymmodel_betas.data(), part);
+                },
+                [&](int64_t n, const std::vector<double> &total) {
+                    return mlggd_host::write_asym_model(asymmodel_fn, D, n, asymmodel_betas, total);
+                });
+            cv_stats_pass("global variance", "MLGGD_GVFILE", "MLGGD_GVFILE is not available", "shared eta", gv_fn, 4,
+                [&](int n, double *part) {
+                    if (frames)
                         net->OutputStats_frames(p->chunk_frames[0], p->fea_context, p->frames_in[0], p->frames_targ[0], n,
-                                                p->first_frame[0], p->targ_offset, part.data());
-                    } else {
-                        n = io->Readchunk_cv((int)i);
-                        net->OutputStats(n, p->indata[0], p->targ[0], part.data());
-                    }
-                    for (size_t j = 0; j < total.size(); j++) total[j] += part[j];
-                    n_total += n;
-                }
-                if (n_total == 0) throw IoError(std::string("MLGGD_GVFILE: the CV set has no samples, ") + gv_fn + " is not written");
-                const float shared = mlggd_host::write_gv_file(gv_fn, D, n_total, total);
-                printf("global variance: %s written, %lld CV samples, shared eta %.9g\n", gv_fn, (long long)n_total, (double)shared);
-                phase("global variance", t_phase);
-            }
+                                                p->first_frame[0], p->targ_offset, part);
+                    else net->OutputStats(n, p->indata[0], p->targ[0], part);
+                },
+                [&](int64_t n, const std::vector<double> &total) {
+                    return (double)mlggd_host::write_gv_file(gv_fn, D, n, total);
+                });
         }
         printf("all finish!\n");
         g_progress = -1000000;  // the watchdog leaves

@@ -1,18 +1,18 @@
 // errmodel.h -- the trainer's opt-in error-model report (MLGGD_ERRMODEL=FILE, bptrain_main.cc): the shape grid of
 // MLGGD_ERRMODEL_BETAS and the text file written from the CV set's error statistics (mlggd_error_stats over every CV
-// chunk, added, then mlggd_ggd_fit), and the reader of that file for MLGGD_SHAPEFACTORS=FILE (parse_shapefactors,
-// also behind mlggd_read_shapefactors).  Not in the reference: the 28-key command line and the log file do not change.
+// chunk, added, then mlggd_ggd_fit).  The reader of that file for MLGGD_SHAPEFACTORS=FILE, parse_shapefactors (also
+// behind mlggd_read_shapefactors), is in binfile.h with its two siblings.  Not in the reference: the 28-key command
+// line and the log file do not change.
 #pragma once
-#include <cctype>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/mlggd.h"
+#include "binfile.h"
 
 namespace mlggd_host {
 
@@ -65,121 +65,6 @@ inline double write_error_model(const std::string &path, int D, int64_t n, const
                 bs >= 0 ? alpha[(size_t)bs * D + d] : 0.0);
     if (fclose(fp) != 0) throw std::runtime_error("MLGGD_ERRMODEL: cannot write " + path);
     return shared_beta;
-}
-
-// The way back (MLGGD_SHAPEFACTORS=FILE, mlggd_read_shapefactors): one shape per output bin from either
-//   - a plain list: exactly D numbers separated by white space, any number per line, or
-//   - the file write_error_model writes: '#' lines are skipped (a finite '# shared_beta' is remembered), the data rows
-//     must be rows 0..D-1 in order and field 5 of row d, best_beta, is bin d's shape.  A 'nan' there marks a bin
-//     without a fit; it takes the file's shared beta, or `fallback` when the file has none.
-// A file is taken for an error model when a '#' line comes before its first number, or when its first data line has
-// five or more fields and starts with the row number 0 (no list can start with 0: every shape is positive).
-// Returns false with *err = "PATH line N: what is wrong" on a wrong count, a row out of order, a field that is no
-// number and a shape that is not positive and finite; betas is then unspecified.
-inline bool parse_shapefactors(const std::string &path, int D, float fallback, float *betas, std::string *err) {
-    auto bad = [&](long line, const std::string &what) {
-        *err = path + " line " + std::to_string(line) + ": " + what;
-        return false;
-    };
-    FILE *fp = fopen(path.c_str(), "r");
-    if (!fp) {
-        *err = "cannot read " + path;
-        return false;
-    }
-    std::vector<std::string> lines;
-    {
-        std::string cur;
-        int c;
-        while ((c = fgetc(fp)) != EOF) {
-            if (c == '\n') {
-                lines.push_back(cur);
-                cur.clear();
-            } else {
-                cur.push_back((char)c);
-            }
-        }
-        if (!cur.empty()) lines.push_back(cur);
-        fclose(fp);
-    }
-    auto fields = [](const std::string &l) {
-        std::vector<std::string> f;
-        size_t i = 0;
-        while (i < l.size()) {
-            while (i < l.size() && isspace((unsigned char)l[i])) i++;
-            size_t j = i;
-            while (j < l.size() && !isspace((unsigned char)l[j])) j++;
-            if (j > i) f.push_back(l.substr(i, j - i));
-            i = j;
-        }
-        return f;
-    };
-    auto number = [](const std::string &t, double *v) {
-        char *end = nullptr;
-        *v = strtod(t.c_str(), &end);
-        return end != t.c_str() && *end == 0;
-    };
-    auto shape_ok = [](double v) { return (float)v > 0.0f && std::isfinite((float)v); };
-    // which of the two formats
-    bool model = false;
-    for (const std::string &l : lines) {
-        const std::vector<std::string> f = fields(l);
-        if (f.empty()) continue;
-        if (f[0][0] == '#') model = true;
-        else if (f.size() >= 5 && f[0] == "0") model = true;
-        break;
-    }
-    const long last = (long)lines.size() > 0 ? (long)lines.size() : 1;
-    if (!model) {
-        int n = 0;
-        for (size_t li = 0; li < lines.size(); li++) {
-            const std::vector<std::string> f = fields(lines[li]);
-            if (!f.empty() && f[0][0] == '#') continue;
-            for (const std::string &t : f) {
-                double v;
-                if (!number(t, &v)) return bad((long)li + 1, "'" + t + "' is not a number");
-                if (n == D) return bad((long)li + 1, "more than the " + std::to_string(D) + " shapes of the output layer");
-                if (!shape_ok(v)) return bad((long)li + 1, "shape " + t + " of bin " + std::to_string(n) + " is not positive and finite");
-                betas[n++] = (float)v;
-            }
-        }
-        if (n != D) return bad(last, std::to_string(n) + " shapes, the output layer has " + std::to_string(D));
-        return true;
-    }
-    double shared = std::nan("");
-    std::vector<int> unfit;
-    int row = 0;
-    for (size_t li = 0; li < lines.size(); li++) {
-        const std::vector<std::string> f = fields(lines[li]);
-        if (f.empty()) continue;
-        if (f[0][0] == '#') {
-            const size_t k = f[0] == "#" ? 1 : 0;  // "# shared_beta X" or "#shared_beta X"
-            if (f.size() > k + 1 && (f[k] == "shared_beta" || f[k] == "#shared_beta")) {
-                double v;
-                if (!number(f[k + 1], &v)) return bad((long)li + 1, "shared_beta '" + f[k + 1] + "' is not a number");
-                if (std::isfinite(v)) {
-                    if (!shape_ok(v)) return bad((long)li + 1, "shared_beta " + f[k + 1] + " is not positive and finite");
-                    shared = v;
-                }
-            }
-            continue;
-        }
-        if (row == D) return bad((long)li + 1, "more than the " + std::to_string(D) + " rows of the output layer");
-        if (f.size() < 5) return bad((long)li + 1, "a row has the fields d mean var kurt best_beta ..., this one has " + std::to_string(f.size()));
-        double v[5];
-        for (int k = 0; k < 5; k++)
-            if (!number(f[k], &v[k])) return bad((long)li + 1, "field " + std::to_string(k + 1) + " '" + f[k] + "' is not a number");
-        if (v[0] != (double)row) return bad((long)li + 1, "row " + f[0] + " where row " + std::to_string(row) + " belongs");
-        if (std::isnan(v[4])) {
-            unfit.push_back(row);
-        } else {
-            if (!shape_ok(v[4])) return bad((long)li + 1, "best_beta " + f[4] + " of bin " + std::to_string(row) + " is not positive and finite");
-            betas[row] = (float)v[4];
-        }
-        row++;
-    }
-    if (row != D) return bad(last, std::to_string(row) + " rows, the output layer has " + std::to_string(D));
-    for (int d : unfit) betas[d] = std::isnan(shared) ? fallback : (float)shared;
-    return true;
 }
 
 }  // namespace mlggd_host

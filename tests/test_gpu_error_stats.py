@@ -1,4 +1,4 @@
-"""GPU: the error statistics of a CV chunk (BPGpu.error_stats / error_stats_frames, csrc/errstats.hip.h).
+"""GPU: the error statistics of a CV chunk (BPGpu.error_stats / error_stats_frames, csrc/colstats.hip.h).
 
 The pin: out = eng.forward(inp), e = out - targ in float32, the four moment terms in float64 from that e, the power
 terms from oracle/pyoracle.pow_det (cross-checked once against the device's own pow_det) widened to float64, every sum

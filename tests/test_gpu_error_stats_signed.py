@@ -1,5 +1,5 @@
 """GPU: the signed error statistics of a CV chunk (BPGpu.error_stats_signed / error_stats_signed_frames,
-k_err_stats_signed in csrc/errstats.hip.h): per bin and grid shape P+ = sum_{e>0} e^beta and P- = sum_{e<0} (-e)^beta.
+k_err_stats_signed in csrc/colstats.hip.h): per bin and grid shape P+ = sum_{e>0} e^beta and P- = sum_{e<0} (-e)^beta.
 
 The pin is that of tests/test_gpu_error_stats.py: out = eng.forward(inp), e = out - targ in float32, the power terms
 from oracle/pyoracle.pow_det widened to float64 and sent to the side of e's sign, every sum by math.fsum; a double sum

@@ -1,4 +1,4 @@
-"""GPU: the output statistics of a CV chunk (BPGpu.output_stats / output_stats_frames, csrc/outstats.hip.h).
+"""GPU: the output statistics of a CV chunk (BPGpu.output_stats / output_stats_frames, csrc/colstats.hip.h).
 
 The pin: out = eng.forward(inp), the four terms y, y*y, t, t*t in float64 from the fp32 values, every sum by
 math.fsum.  A double sum of n terms in ANY order is within 2 n 2^-53 sum|term| of that, and nothing else separates the

@@ -1,4 +1,4 @@
-"""CPU: pkg.read_gv (mlggd_read_gv, host/gvfile.h) -- the reader of the decoders' gv=FILE: a plain list of D factors or
+"""CPU: pkg.read_gv (mlggd_read_gv, host/binfile.h) -- the reader of the decoders' gv=FILE: a plain list of D factors or
 the file an epoch with MLGGD_GVFILE writes (written here by tests/gv64.write_gv_file in its documented format), the
 shared factor, bins without a fit, and every malformed file with its path and line in the message."""
 import numpy as np

@@ -10,7 +10,11 @@
 Writes profiles/gv_bench.json and prints it as one JSON line.
 
     python tools/gv_bench.py [--samples 7920] [--utts 16] [--seconds 4] [--reps 9] [--gpu 0] [--out FILE]
-                             [--bench-parent FILE] [--bench-this FILE]
+                             [--bench-parent FILE] [--bench-this FILE] [--only-a] [--pkg-root DIR]
+
+--only-a stops after (a); --pkg-root DIR times another build with the same file (DIR holds its package, e.g. a built
+checkout of the parent commit), for an A/B of two builds in processes of their own; its result is printed and, unless --out names a file,
+not written.
 
 Every arm is a host clock around a call that ends in a stream synchronise; each is warmed up once, then the arms
 alternate inside every repetition and the MEDIAN over the repetitions is reported (with the fastest and slowest beside
@@ -25,7 +29,6 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 PKG = "speech-enhancement-based-on-a-maximum-likelihood-criterion_amd"
 DIM, CTX, TOFF, B = 257, 11, 5, 128
 
@@ -52,10 +55,15 @@ def main():
     ap.add_argument("--seconds", type=float, default=4.0)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--gpu", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gv_bench.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--bench-parent", default=None, help="file with the JSON lines of `python bench.py` on the parent commit")
     ap.add_argument("--bench-this", default=None, help="file with the JSON lines of `python bench.py` on this commit")
+    ap.add_argument("--only-a", action="store_true")
+    ap.add_argument("--pkg-root", default=ROOT)
     a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.pkg_root))
+    if a.out is None:  # the committed profile is this tree's: another build's figures go to it only when asked
+        a.out = os.path.join(ROOT, "profiles", "gv_bench.json") if os.path.samefile(a.pkg_root, ROOT) else os.devnull
     pkg = importlib.import_module(PKG)
     rng = np.random.default_rng(0)
     ls = [CTX * DIM, 2048, 2048, 2048, DIM]
@@ -94,6 +102,13 @@ def main():
         sa[k] = stats(v)
     sa["output_stats_over_cv_all"] = round(sa["output_stats_frames_s"]["median"] / sa["cv_all_frames_device_reduce_s"]["median"], 3)
     res["a_output_stats"] = sa
+    if a.only_a:
+        eng.close()
+        line = json.dumps(res)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        print(line)
+        return
 
     # (b) the decoders with and without factors
     mean = rng.normal(10, 2, DIM).astype(np.float32)

@@ -19,6 +19,14 @@ edge of the kernels:
 Per case: 3 training steps, then weights, biases, both momentum sets and scalefactor.  On the two single-device paths
 also, over 200 frames (one full bunch and a trailing partial one): cv_all under the device reduce and in host order,
 error_stats, error_stats_signed and output_stats -- the emulated worlds refuse the statistics by design.
+
+Statistics cases (STATS) -- the column statistics alone, on a 24-H-D net fed 3-frame windows of 8-wide frames, each
+through the chunk entries AND the _frames entries (error_stats, error_stats_signed, output_stats; the slab count of
+the output layer is dumped beside them):
+  D       5 (fewer bins than the 8 of a workgroup) and 13 (not a multiple of 8);
+  n, B    a chunk of 1, 33 and 2 B + 7 samples at B = 32 and B = 128;
+  K       a grid of 1 shape, of 3, and of MLGGD_MAX_BETAS = 32 (0.5 + k / 16: 1.0 and 2.0, the self-cases, are in it);
+  H       16 (one output slab), 64 (two) and 256 (eight).
 Needs a GPU: there is no CPU path."""
 import argparse
 import importlib
@@ -37,6 +45,10 @@ PATHS = ([(p, D, B) for p in ("fused", "unfused", "allreduce") for D, B in SHAPE
 MODELS = ("scalar", "shapes", "skew", "shapes+skew")
 GRID = (0.8, 1.0, 2.0)          # the statistics' own shape grid
 CV_FRAMES = 200
+# (D, H, B, n, K): see the docstring
+STATS = [(5, 64, 32, 1, 1), (5, 64, 32, 33, 32), (5, 64, 32, 71, 3), (13, 64, 128, 1, 32), (13, 64, 128, 33, 1),
+         (13, 64, 128, 263, 3), (13, 256, 32, 71, 32), (13, 256, 128, 263, 32), (5, 16, 128, 263, 1)]
+STATS_DIM, STATS_CTX, STATS_TOFF = 8, 3, 1
 
 
 def vectors(D):
@@ -91,6 +103,30 @@ def run_case(pkg, synth, gpu, path, D, B, model, out):
         os.environ.pop("MLGGD_LOSS_FUSE", None)
 
 
+def run_stats_case(pkg, synth, gpu, D, H, B, n, K, out):
+    ls = [STATS_CTX * STATS_DIM, H, D]
+    ws, bs = synth.make_weights(ls, seed=500 + D + H)
+    rng = np.random.default_rng(900 + D + H + B + n)
+    feat = rng.standard_normal((n + STATS_CTX - 1, STATS_DIM), dtype=np.float32)
+    targ = rng.standard_normal((n + STATS_CTX - 1, D), dtype=np.float32)
+    first = rng.permutation(n).astype(np.int32)           # a window per sample, in scattered order
+    rows = np.stack([feat[f:f + STATS_CTX].reshape(-1) for f in first])
+    grid = np.array([0.5 + k / 16.0 for k in range(K)], np.float32)
+    eng = pkg.BPGpu(1, gpu, ls, B, *HP, ws, bs, BETA, 1)
+    try:
+        key = "stats/D%d/H%d/B%d/n%d/K%d/" % (D, H, B, n, K)
+        out[key + "out_slabs"] = np.array(eng.out_slabs(), np.int32)
+        out[key + "error_stats"] = eng.error_stats(rows, targ[first + STATS_TOFF], grid)
+        out[key + "error_stats_signed"] = eng.error_stats_signed(rows, targ[first + STATS_TOFF], grid)
+        out[key + "output_stats"] = eng.output_stats(rows, targ[first + STATS_TOFF])
+        fr = (feat, targ, first, STATS_CTX, STATS_TOFF)
+        out[key + "error_stats_frames"] = eng.error_stats_frames(*fr, grid)
+        out[key + "error_stats_signed_frames"] = eng.error_stats_signed_frames(*fr, grid)
+        out[key + "output_stats_frames"] = eng.output_stats_frames(*fr)
+    finally:
+        eng.close()
+
+
 def compare(pa, pb):
     a, b = np.load(pa), np.load(pb)
     if sorted(a.files) != sorted(b.files):
@@ -131,10 +167,12 @@ def main():
     for path, D, B in PATHS:
         for model in MODELS:
             run_case(pkg, synth, a.gpu, path, D, B, model, out)
+    for case in STATS:
+        run_stats_case(pkg, synth, a.gpu, *case, out)
     for k, v in out.items():
         assert np.isfinite(np.asarray(v, np.float64)).all(), k
     np.savez(a.out, **out)
-    print("%d cases, %d arrays -> %s (package of %s)" % (len(PATHS) * len(MODELS), len(out), a.out, os.path.abspath(a.pkg_root)))
+    print("%d cases, %d arrays -> %s (package of %s)" % (len(PATHS) * len(MODELS) + len(STATS), len(out), a.out, os.path.abspath(a.pkg_root)))
     return 0
 
 
