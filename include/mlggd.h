@@ -706,6 +706,38 @@ int mlggd_debug_math(mlggd_handle h, const char *fn, const float *x, float y, fl
 int mlggd_debug_stamp_select(mlggd_handle h, const char *kernel_class, int layer);
 int mlggd_debug_stamp_read(mlggd_handle h, long long *out /* [cap_blocks][8] */, int cap_blocks, int *blocks);
 
+/* ---- pre-training (no counterpart in the reference, whose finetune.pl starts from ./pretraining_weights/...): one
+ * restricted Boltzmann machine on hidden layer `layer` (1 .. numlayers - 2) of a sigmoid engine, trained by one-step
+ * contrastive divergence as csrc/rbm_rule.h states it.  The session updates the engine's own W and bias of that layer in
+ * place; the visible bias and the momentum of W, bias and visible bias are the session's (0 at open), the engine's
+ * fine-tuning momentum is not touched.  visible: MLGGD_RBM_GAUSSIAN (unit variance, linear reconstruction: layer 1 on
+ * z-normalised input) or MLGGD_RBM_BERNOULLI.  Layers below `layer` are run by the engine's ordinary forward pass.
+ * Dropout flags are IGNORED by pre-training: nothing is omitted and no weight is scaled, whatever mlggd_config says.
+ * MLGGD_TILE64 applies to the forward launches below `layer`; the RBM's own products always take the 32 x 32-tile kernels.
+ * Refused before any device call: layer or visible out of range (MLGGD_ERR_ARG); a rectified-linear engine, a NAT
+ * engine, an engine with a communicator or an emulated world, a second open session on the engine (MLGGD_ERR_STATE);
+ * mlggd_destroy while a session is open (MLGGD_ERR_STATE).  Between two session calls every other entry works and sees W
+ * and bias as pre-training left them.  Not built: CD-k for k > 1, persistent chains, sampled visibles, learnt variances. */
+enum { MLGGD_RBM_GAUSSIAN = 0, MLGGD_RBM_BERNOULLI = 1 };
+typedef struct mlggd_rbm *mlggd_rbm_handle;
+int mlggd_rbm_open(mlggd_handle h, int layer, int visible, float lrate, float momentum, float weightcost, uint32_t seed,
+                   mlggd_rbm_handle *out);
+int mlggd_rbm_set_rates(mlggd_rbm_handle r, float lrate, float momentum); /* momentum ramp between epochs */
+/* One CD-1 step on every FULL bunch of the chunk (a trailing partial bunch is skipped, as in mlggd_train_chunk);
+ * *bunches: steps run; *recon_sqerr: sum over those steps of sum (v0 - v1)^2, float64 on the device, the same bits for
+ * the same input.  _frames: the chunk as a frame stream and the first frame of every sample (mlggd_load_frames).
+ * mlggd_last_train_ms then gives the device time and the step count of the call's steps (upload excluded). */
+int mlggd_rbm_train_chunk(mlggd_rbm_handle r, int n_frames, const float *in, int *bunches, double *recon_sqerr);
+int mlggd_rbm_train_frames(mlggd_rbm_handle r, int n_frames, int fea_context, const float *feat, int n_samples,
+                           const int32_t *first_frame, int *bunches, double *recon_sqerr);
+int mlggd_rbm_visible_bias(mlggd_rbm_handle r, float *c /* [K] */);
+/* Test hook: a tensor of the last step, row-major and un-padded.  "v0", "v1" [B][K]; "h0p", "h0s", "h1p" [B][N];
+ * "delta_w" [K][N]; "delta_b" [N]; "delta_c", "vbias" [K]  (K, N: units of layer - 1 and layer, B: bunchsize). */
+int mlggd_rbm_debug_tensor(mlggd_rbm_handle r, const char *name, float *dst, size_t count);
+int mlggd_rbm_close(mlggd_rbm_handle r); /* gives the session's device bytes back */
+/* r [B][N] of step `step` of a session opened with `seed` (rbm_rule.h); host only */
+int mlggd_rbm_draws(uint32_t seed, uint32_t step, int B, int N, float *r);
+
 #ifdef __cplusplus
 }
 #endif

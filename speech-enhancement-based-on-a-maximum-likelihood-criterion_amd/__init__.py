@@ -85,6 +85,8 @@ EXPORTS = [
     "mlggd_set_mask", "mlggd_get_mask", "mlggd_get_mask_bins", "mlggd_mask_targets", "mlggd_mask_select",
     "mlggd_set_asymmetry", "mlggd_get_asymmetry", "mlggd_error_stats_signed", "mlggd_error_stats_signed_frames",
     "mlggd_asym_fit", "mlggd_read_asymmetry",
+    "mlggd_rbm_open", "mlggd_rbm_set_rates", "mlggd_rbm_train_chunk", "mlggd_rbm_train_frames", "mlggd_rbm_visible_bias",
+    "mlggd_rbm_debug_tensor", "mlggd_rbm_close", "mlggd_rbm_draws",
 ]
 MAX_BETAS = 32
 
@@ -95,7 +97,7 @@ def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "colstats.hip.h", "gv_rule.h", "mask_rule.h", "mask.hip.h", "mix.hip.h",
-                                             "mix_rule.h", "nat_rule.h", "asym_rule.h", "devbuf.h", "devbuf_rule.h")]
+                                             "mix_rule.h", "nat_rule.h", "rbm_rule.h", "rbm.hip.h", "asym_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     srcs.append(os.path.join(_HERE, "host", "gvfile.h"))
@@ -229,6 +231,14 @@ def load():
     L.mlggd_get_mask_bins.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.mlggd_mask_targets.argtypes = [C.c_int, C.c_int, C.c_int64, _fp, _fp, C.c_float, _fp]
     L.mlggd_mask_select.argtypes = [C.c_int, C.c_int64, _fp, _fp, _fp, C.c_float, C.c_float, _fp]
+    L.mlggd_rbm_open.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.mlggd_rbm_set_rates.argtypes = [C.c_void_p, C.c_float, C.c_float]
+    L.mlggd_rbm_train_chunk.argtypes = [C.c_void_p, C.c_int, _fp, C.POINTER(C.c_int), _dp]
+    L.mlggd_rbm_train_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, C.c_int, _ip, C.POINTER(C.c_int), _dp]
+    L.mlggd_rbm_visible_bias.argtypes = [C.c_void_p, _fp]
+    L.mlggd_rbm_debug_tensor.argtypes = [C.c_void_p, C.c_char_p, _fp, C.c_size_t]
+    L.mlggd_rbm_close.argtypes = [C.c_void_p]
+    L.mlggd_rbm_draws.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int, _fp]
     _lib = L
     return L
 
@@ -760,6 +770,93 @@ def mask_select(noisy_lps, lps, mask, lo, hi):
     return out
 
 
+RBM_VISIBLE = ("gaussian", "bernoulli")  # MLGGD_RBM_GAUSSIAN = 0, MLGGD_RBM_BERNOULLI = 1 (include/mlggd.h)
+
+
+def rbm_draws(seed, step, B, N):
+    """r [B][N] in [0, 1): the uniform draws of step `step` of an RBM session opened with `seed`, h0s = (r < h0p)
+    (csrc/rbm_rule.h).  A host call: needs no device (mlggd_rbm_draws)."""
+    out = np.empty((int(B), int(N)), np.float32)
+    _check(load().mlggd_rbm_draws(int(seed) & 0xFFFFFFFF, int(step) & 0xFFFFFFFF, int(B), int(N), _p(out)))
+    return out
+
+
+class Rbm:
+    """CD-1 pre-training of one hidden layer of a sigmoid engine (csrc/rbm_rule.h, mlggd_rbm_*): made by BPGpu.rbm().
+    It trains the engine's own weights and bias of that layer in place; the visible bias and the momentum are its own."""
+
+    def __init__(self, eng, layer, visible, lrate, momentum, weightcost, seed):
+        self._h = None
+        self._eng = eng
+        self.layer = int(layer)
+        if isinstance(visible, str):
+            if visible not in RBM_VISIBLE:
+                raise ValueError("visible %r: must be one of %s" % (visible, " / ".join(map(repr, RBM_VISIBLE))))
+            visible = RBM_VISIBLE.index(visible)
+        h = C.c_void_p()
+        _check(load().mlggd_rbm_open(eng._h, self.layer, int(visible), float(lrate), float(momentum), float(weightcost),
+                                     int(seed) & 0xFFFFFFFF, C.byref(h)))
+        self._h = h
+        self.K, self.N = eng.layersizes[self.layer - 1], eng.layersizes[self.layer]
+        eng._rbms.append(self)
+
+    def set_rates(self, lrate, momentum):
+        _check(load().mlggd_rbm_set_rates(self._h, float(lrate), float(momentum)))
+
+    def train(self, inp):
+        """One CD-1 step on every full bunch of inp [n][layersizes[0]]: (bunches, recon_sqerr)."""
+        inp = _f32(inp)
+        if inp.ndim != 2 or inp.shape[1] != self._eng.K0:
+            raise ValueError("in must be [n][%d]" % self._eng.K0)
+        steps, sq = C.c_int(0), C.c_double(0.0)
+        _check(load().mlggd_rbm_train_chunk(self._h, inp.shape[0], _p(inp), C.byref(steps), C.byref(sq)))
+        return steps.value, sq.value
+
+    def train_frames(self, feat, first_frame, fea_context):
+        """The same on a frame stream [n_frames][layersizes[0] / fea_context] and the first frame of every sample."""
+        feat, _, first = self._eng._frames_args(feat, None, first_frame, fea_context)
+        steps, sq = C.c_int(0), C.c_double(0.0)
+        _check(load().mlggd_rbm_train_frames(self._h, feat.shape[0], int(fea_context), _p(feat), first.size,
+                                             first.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(steps), C.byref(sq)))
+        return steps.value, sq.value
+
+    def visible_bias(self):
+        out = np.empty(self.K, np.float32)
+        _check(load().mlggd_rbm_visible_bias(self._h, _p(out)))
+        return out
+
+    def tensor(self, name):
+        """A tensor of the last step: "v0", "v1" [B][K]; "h0p", "h0s", "h1p" [B][N]; "delta_w" [K][N]; "delta_b" [N];
+        "delta_c", "vbias" [K]."""
+        B = self._eng.bunchsize
+        shape = {"v0": (B, self.K), "v1": (B, self.K), "h0p": (B, self.N), "h0s": (B, self.N), "h1p": (B, self.N),
+                 "delta_w": (self.K, self.N), "delta_b": (self.N,), "delta_c": (self.K,), "vbias": (self.K,)}.get(name)
+        if shape is None:
+            raise ValueError("unknown RBM tensor %r" % (name,))
+        out = np.empty(shape, np.float32)
+        _check(load().mlggd_rbm_debug_tensor(self._h, name.encode(), _p(out), out.size))
+        return out
+
+    def close(self):
+        if self._h:
+            load().mlggd_rbm_close(self._h)
+            self._h = None
+            if self in self._eng._rbms:
+                self._eng._rbms.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 def comm_unique_id():
     buf = (C.c_char * UNIQUE_ID_BYTES)()
     _check(load().mlggd_comm_unique_id(buf))
@@ -775,6 +872,7 @@ class BPGpu:
         self._h = None
         act = activation_code(activation)  # hidden units: "sigmoid" (the reference's BPtrain_Sigmoid) or "relu"
         self._lives = []
+        self._rbms = []
         self._n_noise = 0
         self._nat = int(nat_frames) > 0
         self.layersizes = [int(x) for x in layersizes]
@@ -851,6 +949,8 @@ class BPGpu:
         if self._h:
             for g in list(self._lives):  # an engine with an open live group cannot be destroyed
                 g.close()
+            for r in list(self._rbms):  # ... nor one with an open RBM session
+                r.close()
             load().mlggd_destroy(self._h)
             self._h = None
 
@@ -1198,6 +1298,12 @@ class BPGpu:
         """A live group of n_sessions sessions on this engine (mlggd_live_open): push(blocks, end=None,
         return_f32=False), received(), close(); BPGpu.close() closes it too.  fea_context None: layersizes[0] / bins."""
         return LiveGroup(self, mean, inv_std, n_sessions, fs_khz, fea_context)
+
+    def rbm(self, layer, visible="gaussian", lrate=0.001, momentum=0.5, weightcost=0.0002, seed=1):
+        """Open a CD-1 pre-training session (Rbm, a context manager) on hidden layer `layer` = 1 .. numlayers - 2:
+        "gaussian" visibles for layer 1 on z-normalised input, "bernoulli" above.  The default rates are a choice of this
+        project, not a measured optimum.  One session per engine at a time; dropout flags are ignored."""
+        return Rbm(self, layer, visible, lrate, momentum, weightcost, seed)
 
     def last_train_ms(self):
         ms, steps = C.c_float(0), C.c_int(0)

@@ -37,6 +37,7 @@
 #include "mix.hip.h"
 #include "mix_rule.h"
 #include "nat_rule.h"
+#include "rbm_rule.h"
 #include "devbuf.h"
 
 // ------------------------------------------------------------------ errors
@@ -382,6 +383,7 @@ struct mlggd_engine {
     int mask_bins = 0;
     int mask_mode = mask_rule::kSelect;
     float mask_lo = mask_rule::kLo, mask_hi = mask_rule::kHi, mask_scale = mask_rule::kScale;
+    int rbm_open = 0;  // open pre-training sessions (mlggd_rbm_open, at most one): mlggd_destroy refuses while there is one
 };
 
 // buffer for the selected launch, nullptr otherwise; one-shot
@@ -684,7 +686,7 @@ static int exchange_y(mlggd_engine *e, int l, const float *src, hipStream_t st);
 enum { GATHER_INPUT = 1, GATHER_HIDDEN = 2, GATHER_HIDDEN_EACH = 4 };  // data-parallel factor exchange issued from inside the forward pass
 
 static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool training, bool prestaged = false,
-                       int gather_flags = 0) {
+                       int gather_flags = 0, int l_end = 0) {  // l_end > 0: layers 1 .. l_end - 1 only (rbm.hip.h)
     e->stop_ev_next = nullptr;  // an event armed by a launch sequence that bailed out early must not ride on an unrelated launch
     e->stop_ev_attached = false;
     if (prestaged) {
@@ -707,7 +709,7 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
     const bool cvscale = !training && e->cfg.dropoutflag == 1;
     const bool relu = e->cfg.activation == MLGGD_ACT_RELU;  // the hidden layers' epilogue: a host-side choice of instantiation
     if (drop) CHK(run_dropout(e, 0, in_rows));
-    for (int l = 1; l < e->L; l++) {
+    for (int l = 1; l < (l_end > 0 ? l_end : e->L); l++) {
         const int Kp = e->lsp[l - 1], Np = e->lsp[l], n_tiles = Np / 32;
         CHK(wait_weight_gathers(e, l, l));  // sharded data parallel: W_l of the previous step may still be arriving
         if (cvscale) {  // DevWeightMultiP before the GEMM, BP_GPU.cu:484-489
@@ -1955,6 +1957,7 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->live_groups > 0)
         return fail(MLGGD_ERR_STATE, "%d live group(s) of this engine are open: mlggd_live_close them first",
                     e->live_groups);
+    if (e->rbm_open > 0) return fail(MLGGD_ERR_STATE, "an RBM session of this engine is open: mlggd_rbm_close it first");
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->comm_stream) hipStreamSynchronize(e->comm_stream);
@@ -4935,3 +4938,4 @@ int mlggd_train_waves(mlggd_handle e, int fs_khz, int fea_context, const float *
 
 // the mask engine's kernels (declared in spectral.hip.h and mix.hip.h)
 #include "mask.hip.h"
+#include "rbm.hip.h"

@@ -265,6 +265,8 @@ __device__ __forceinline__ float pow_det(float xf, float yf) {
 // ---------------------------------------------------------------------------------------
 enum { FWD_SIGMOID = 0, FWD_SLAB = 1, FWD_RELU = 2 };
 enum { ACT_SIGMOID = 0, ACT_RELU = 1 };  // the dX kernels' switch; the values of MLGGD_ACT_* (include/mlggd.h)
+// dx_body's other epilogues: the product is an RBM's reconstruction (rbm.hip.h), DxArgs.Yt_prev the visible bias c [Kp]
+enum { ACT_VIS_LINEAR = 2, ACT_VIS_SIGMOID = 3 };
 
 struct FwdArgs {
     const float *W, *Yt_in, *bias;
@@ -731,7 +733,10 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
     static_assert(1024 % NT_ == 0, "every thread owns EPT_ whole output elements");
     float y_pre[EPT_];
     float4 y_pre4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // 4-wave epilogue: 4 consecutive frames of one unit
-    if constexpr (NW == 4) {
+    if constexpr (ACT == ACT_VIS_LINEAR || ACT == ACT_VIS_SIGMOID) {
+        static_assert(NW == 4, "the RBM down-pass has the 4-wave epilogue only");
+        y_pre4.x = Yt_prev[k0 + (tid >> 3)];  // the visible bias c [Kp] of this thread's unit (rbm.hip.h)
+    } else if constexpr (NW == 4) {
         y_pre4 = *reinterpret_cast<const float4 *>(&Yt_prev[(size_t)(k0 + (tid >> 3)) * Bp + b0 + (tid & 7) * 4]);
     } else {
 #pragma unroll
@@ -992,7 +997,17 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
             d4.w += p4.w;
         }
         float4 g4;  // kernDsigmoid, DevFunc.cu:67-68
-        if constexpr (ACT == ACT_RELU) {
+        if constexpr (ACT == ACT_VIS_LINEAR) {  // an RBM's reconstruction (rbm_rule.h): v1 = h0s W^T + c
+            g4.x = d4.x + y_pre4.x;
+            g4.y = d4.y + y_pre4.x;
+            g4.z = d4.z + y_pre4.x;
+            g4.w = d4.w + y_pre4.x;
+        } else if constexpr (ACT == ACT_VIS_SIGMOID) {  // ... and sigma of it for Bernoulli visibles
+            g4.x = sigmoid_det(d4.x + y_pre4.x);
+            g4.y = sigmoid_det(d4.y + y_pre4.x);
+            g4.z = sigmoid_det(d4.z + y_pre4.x);
+            g4.w = sigmoid_det(d4.w + y_pre4.x);
+        } else if constexpr (ACT == ACT_RELU) {
             g4.x = drelu(y_pre4.x, d4.x);
             g4.y = drelu(y_pre4.y, d4.y);
             g4.z = drelu(y_pre4.z, d4.z);
