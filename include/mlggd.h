@@ -506,6 +506,40 @@ int mlggd_asym_fit(int D, int64_t n, int n_betas, const float *betas, const doub
  * mlggd_read_shapefactors: MLGGD_ERR_ARG with "PATH line N: ..." as the message. */
 int mlggd_read_asymmetry(const char *path, int D, float fallback, float *kappas /* [D] */);
 
+/* ---- a learned scale per output bin (the paper's second optimisation of the ML-GGD objective; the reference ships
+ * the alternating one only).  MLGGD_SCALE_ALTERNATING, the default, re-solves alpha_d in closed form from every
+ * minibatch: the launches of an engine that never heard of this.  MLGGD_SCALE_LEARNED keeps a state (alpha_d, v_d) per
+ * bin across minibatches and moves ln alpha_d by gradient descent with momentum beside the weights (csrc/scale_rule.h
+ * states the rule): v' = momentum v - lrate (1 - beta S / alpha^beta), clamped to [-vmax, vmax], alpha' = alpha
+ * exp(v'); the weight gradient of a step divides by alpha^beta of the alpha BEFORE that step's update.  A bin whose
+ * alpha is 0 takes the closed form of its first minibatch (the alternating engine's bits) and v = 0.  lrate = momentum
+ * = 0 trains under a fixed scale vector.  It composes with mlggd_set_shapefactors and mlggd_set_asymmetry, runs on every
+ * loss path (one launch, MLGGD_LOSS_FUSE=0, a communicator: every rank applies the rule to the same all-reduced sums,
+ * so replicas stay identical without a new exchange), and the CV log-likelihood and mlggd_get_scalefactor read alpha
+ * as before.  The defaults (lrate 0.05, momentum 0.5, vmax 1) are a choice of this project, not a measured optimum.
+ *
+ * Entering the learned mode takes alpha from the current scalefactor (all zero on a fresh engine) and sets v = 0;
+ * calling it again in learned mode only changes the parameters.  mlggd_set_scalefactor in learned mode sets alpha and
+ * leaves v.  Going back to alternating leaves scalefactor as it is; the next step overwrites it as before.
+ * Refused before any device call, the engine unchanged: MLflag != 1 (MLGGD_ERR_STATE, whichever mode is asked
+ * for: a beta-norm has no scale); another mode, a lrate, momentum or vmax that is not finite, lrate < 0,
+ * momentum outside [0, 1), vmax <= 0 (MLGGD_ERR_ARG).  mlggd_get_scale_state / mlggd_set_scale_state need the learned
+ * mode (MLGGD_ERR_STATE); an alpha that is negative or not finite, or a velocity that is not finite, is MLGGD_ERR_ARG
+ * naming the bin.  velocity NULL: zeros (set), not returned (get). */
+enum { MLGGD_SCALE_ALTERNATING = 0, MLGGD_SCALE_LEARNED = 1 };
+int mlggd_set_scale_mode(mlggd_handle h, int mode, float lrate, float momentum, float vmax);
+int mlggd_get_scale_mode(mlggd_handle h, int *mode, float *lrate, float *momentum, float *vmax, int64_t *steps);
+int mlggd_get_scale_state(mlggd_handle h, float *alpha /* [D] */, float *velocity /* [D] or NULL */);
+int mlggd_set_scale_state(mlggd_handle h, const float *alpha /* [D] */, const float *velocity /* [D] or NULL: zeros */);
+/* Host only, no device.  The state as a text file: '#' header lines with D, the mode's parameters and the step count,
+ * then the rows `d alpha velocity`, every number in %.9g so that a round trip keeps every bit.  The reader skips '#'
+ * lines; a wrong row count, a row out of order, a field that is no number, an alpha that is negative or not finite, a
+ * velocity that is not finite and a file that cannot be read are MLGGD_ERR_ARG with "PATH line N: ..." as the message;
+ * so are a NULL path or alpha and D < 1. */
+int mlggd_read_scale_state(const char *path, int D, float *alpha /* [D] */, float *velocity /* [D] or NULL */);
+int mlggd_write_scale_state(const char *path, int D, const float *alpha /* [D] */, const float *velocity /* [D] or NULL: zeros */,
+                            float lrate, float momentum, float vmax, int64_t steps);
+
 /* ---- global variance equalisation (Xu, Du, Dai and Lee 2015; no counterpart in the reference).  A regression net
  * trained under MMSE or ML over-smooths: per bin the variance of its output is smaller than the clean target's.  The
  * post-filter is one factor per bin (or one for all bins) multiplied onto the NORMALISED network output before it is

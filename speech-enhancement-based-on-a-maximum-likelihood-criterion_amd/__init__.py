@@ -85,6 +85,8 @@ EXPORTS = [
     "mlggd_set_mask", "mlggd_get_mask", "mlggd_get_mask_bins", "mlggd_mask_targets", "mlggd_mask_select",
     "mlggd_set_asymmetry", "mlggd_get_asymmetry", "mlggd_error_stats_signed", "mlggd_error_stats_signed_frames",
     "mlggd_asym_fit", "mlggd_read_asymmetry",
+    "mlggd_set_scale_mode", "mlggd_get_scale_mode", "mlggd_get_scale_state", "mlggd_set_scale_state",
+    "mlggd_read_scale_state", "mlggd_write_scale_state",
     "mlggd_rbm_open", "mlggd_rbm_set_rates", "mlggd_rbm_train_chunk", "mlggd_rbm_train_frames", "mlggd_rbm_visible_bias",
     "mlggd_rbm_debug_tensor", "mlggd_rbm_close", "mlggd_rbm_draws",
 ]
@@ -97,11 +99,12 @@ def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "colstats.hip.h", "gv_rule.h", "mask_rule.h", "mask.hip.h", "mix.hip.h",
-                                             "mix_rule.h", "nat_rule.h", "rbm_rule.h", "rbm.hip.h", "asym_rule.h", "devbuf.h", "devbuf_rule.h")]
+                                             "mix_rule.h", "nat_rule.h", "rbm_rule.h", "rbm.hip.h", "asym_rule.h", "scale_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     srcs.append(os.path.join(_HERE, "host", "gvfile.h"))
     srcs.append(os.path.join(_HERE, "host", "asymfile.h"))
+    srcs.append(os.path.join(_HERE, "host", "scalefile.h"))
     srcs.append(os.path.join(_HERE, "host", "binfile.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -204,6 +207,12 @@ def load():
     L.mlggd_error_stats_signed_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, C.c_int, _fp, _dp]
     L.mlggd_asym_fit.argtypes = [C.c_int, C.c_int64, C.c_int, _fp, _dp, _dp, _dp, _dp, _ip, _dp, _ip]
     L.mlggd_read_asymmetry.argtypes = [C.c_char_p, C.c_int, C.c_float, _fp]
+    L.mlggd_set_scale_mode.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    L.mlggd_get_scale_mode.argtypes = [C.c_void_p, C.POINTER(C.c_int), _fp, _fp, _fp, C.POINTER(C.c_int64)]
+    L.mlggd_get_scale_state.argtypes = [C.c_void_p, _fp, _fp]
+    L.mlggd_set_scale_state.argtypes = [C.c_void_p, _fp, _fp]
+    L.mlggd_read_scale_state.argtypes = [C.c_char_p, C.c_int, _fp, _fp]
+    L.mlggd_write_scale_state.argtypes = [C.c_char_p, C.c_int, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_int64]
     L.mlggd_output_stats.argtypes = [C.c_void_p, C.c_int, _fp, _fp, _dp]
     L.mlggd_output_stats_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, _dp]
     L.mlggd_gv_fit.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _fp, _bp, _dp, _dp, _fp, _ip]
@@ -706,7 +715,34 @@ def read_asymmetry(path, D, fallback=1.0):
     return k
 
 
-GvFit = collections.namedtuple("GvFit", "gv_est gv_ref eta fitted gv_est_shared gv_ref_shared eta_shared fitted_shared")
+SCALE_MODES = ("alternating", "learned")  # MLGGD_SCALE_ALTERNATING = 0, MLGGD_SCALE_LEARNED = 1 (include/mlggd.h)
+ScaleMode = collections.namedtuple("ScaleMode", "mode lrate momentum vmax steps")
+
+
+def scale_mode_code(mode):
+    if mode not in SCALE_MODES:
+        raise ValueError("scale mode %r: must be one of %s" % (mode, ", ".join(SCALE_MODES)))
+    return SCALE_MODES.index(mode)
+
+
+def read_scale_state(path, D):
+    """(alpha, velocity), [D] float32 each, from the file write_scale_state or the trainer's MLGGD_SCALE_FILE writes.  A
+    host call: needs no device (mlggd_read_scale_state); a malformed file raises MlggdError naming the line."""
+    a, v = np.empty(int(D), np.float32), np.empty(int(D), np.float32)
+    _check(load().mlggd_read_scale_state(None if path is None else os.fsencode(path), int(D), _p(a), _p(v)))
+    return a, v
+
+
+def write_scale_state(path, alpha, velocity=None, lrate=0.05, momentum=0.5, vmax=1.0, steps=0):
+    """The learned scale's state as text, every number in %.9g: a round trip through read_scale_state keeps every bit.
+    velocity None: zeros.  A host call: needs no device (mlggd_write_scale_state)."""
+    a = np.ascontiguousarray(alpha, dtype=np.float32).ravel()
+    v = None if velocity is None else _f32(velocity, (a.size,))
+    _check(load().mlggd_write_scale_state(None if path is None else os.fsencode(path), a.size, _p(a), None if v is None else _p(v),
+                                          float(lrate), float(momentum), float(vmax), int(steps)))
+
+
+GvFit = collections.namedtuple("GvFit","gv_est gv_ref eta fitted gv_est_shared gv_ref_shared eta_shared fitted_shared")
 
 
 def gv_fit(n, sums):
@@ -1360,6 +1396,36 @@ class BPGpu:
     def set_scalefactor(self, alpha):
         a = _f32(alpha, (self.D,))
         _check(load().mlggd_set_scalefactor(self._h, _p(a)))
+
+    def set_scale_mode(self, mode="learned", lrate=0.05, momentum=0.5, vmax=1.0):
+        """How the GGD scale alpha_d is found (MLflag 1 only; csrc/scale_rule.h, mlggd_set_scale_mode).  "alternating",
+        the default of every engine: the closed form of each minibatch.  "learned": alpha_d is a state that lives across
+        minibatches and ln alpha_d moves by SGD with momentum beside the weights, v' = momentum v - lrate (1 - beta S /
+        alpha^beta) clamped to [-vmax, vmax], alpha' = alpha exp(v'); entering it takes alpha from the current
+        scalefactor (0: the bin seeds from its first minibatch) and v = 0.  lrate = momentum = 0 trains under a fixed
+        scale.  The default rates are a choice, not a measured optimum."""
+        _check(load().mlggd_set_scale_mode(self._h, scale_mode_code(mode), float(lrate), float(momentum), float(vmax)))
+
+    def scale_mode(self):
+        """ScaleMode(mode, lrate, momentum, vmax, steps) in effect (mlggd_get_scale_mode); steps counts the learned steps
+        since the mode was entered."""
+        m, st = C.c_int(0), C.c_int64(0)
+        lr, mo, vm = C.c_float(0), C.c_float(0), C.c_float(0)
+        _check(load().mlggd_get_scale_mode(self._h, C.byref(m), C.byref(lr), C.byref(mo), C.byref(vm), C.byref(st)))
+        return ScaleMode(SCALE_MODES[m.value], lr.value, mo.value, vm.value, st.value)
+
+    def scale_state(self):
+        """(alpha, velocity), [D] float32 each: the learned scale's state the next step reads (mlggd_get_scale_state)."""
+        a, v = np.empty(self.D, np.float32), np.empty(self.D, np.float32)
+        _check(load().mlggd_get_scale_state(self._h, _p(a), _p(v)))
+        return a, v
+
+    def set_scale_state(self, alpha, velocity=None):
+        """Set the learned scale's state; velocity None: zeros.  alpha must be finite and not negative, 0 meaning "seed
+        from the next minibatch" (mlggd_set_scale_state)."""
+        a = _f32(alpha, (self.D,))
+        v = None if velocity is None else _f32(velocity, (self.D,))
+        _check(load().mlggd_set_scale_state(self._h, _p(a), None if v is None else _p(v)))
 
     def shapefactors(self):
         """The D shapes in effect: the vector of set_shapefactors, else `shapefactor` D times."""

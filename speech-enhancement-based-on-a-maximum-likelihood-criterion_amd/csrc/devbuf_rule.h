@@ -21,6 +21,8 @@ inline size_t nat_floats(size_t n_nat, size_t fdim) { return (n_nat + 8) * fdim;
 inline size_t sample_slots(size_t n, size_t Bp) { return n + Bp + 32; }
 // rows of chunk_out for the outputs of n_frames frames
 inline size_t out_rows(size_t n_frames) { return n_frames + 32; }
+// floats of the learned scale's state (scale_rule.h): two copies of (alpha, v) per padded output unit
+inline size_t scale_state_floats(size_t Dp) { return 2 * 2 * Dp; }
 // bytes of a workspace buffer that has to hold `bytes`: an eighth of headroom, so that batches of slightly different
 // sizes settle after the first few
 inline size_t ws_bytes(size_t bytes) { return bytes + bytes / 8 + 256; }

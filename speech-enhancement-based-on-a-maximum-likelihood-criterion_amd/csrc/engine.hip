@@ -24,6 +24,7 @@
 #include "../host/errmodel.h"  // parse_shapefactors: one file format, one reader and one writer
 #include "../host/gvfile.h"    // parse_gv: the same for the global variance file
 #include "../host/asymfile.h"  // parse_asymmetry: the same for the asymmetric error model's file
+#include "../host/scalefile.h"  // parse_scale_state / write_scale_state: the learned scale's state file
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
@@ -222,6 +223,14 @@ struct mlggd_engine {
     bool asym = false;
     DevBuf<float> kappas_dev, asym_betas_dev;
     std::vector<float> kappas_host;
+    // mlggd_set_scale_mode: the scale as a learned parameter (scale_rule.h).  scale_state is [2 copies][alpha, v][Dp]
+    // (pads 0), allocated when the mode is first switched on; a step's loss launches read copy scale_cur and write the
+    // other one, and run_step swaps them once its last loss launch is enqueued.  scale_steps counts those swaps.
+    int scale_mode = MLGGD_SCALE_ALTERNATING;
+    float scale_lrate = scale_rule::kLrate, scale_momentum = scale_rule::kMomentum, scale_vmax = scale_rule::kVmax;
+    DevBuf<float> scale_state;
+    int scale_cur = 0;
+    long long scale_steps = 0;
     DevBuf<float> chunk_in, chunk_targ, chunk_out;
     // CV metrics: 0 = outputs copied back, host fp32 accumulation in the reference's order (default: it is what
     // the log lines are compared on); 1 = sums formed on the device (k_cv_reduce), nothing of size n x D leaves it
@@ -1256,14 +1265,25 @@ constexpr size_t LOSS_LDS_MAX = (size_t)(32 * (1152 + 1) + 32) * sizeof(float);
 // The error model in effect (ErrModel, kernels.hip.h) and the [Dp] device arrays its kernels read, nullptr where the
 // model has none: the one place that knows.  Both vectors are only ever set with MLflag == 1.  EM_ASYM's shapes are the
 // vector of mlggd_set_shapefactors, else cfg.shapefactor per unit.
+// learn: the scale is the engine's state (mlggd_set_scale_mode, scale_rule.h) and the _learn kernels take `scale`: the
+// copy this step reads, the copy it writes, the mode's parameters.  Only ever on with MLflag == 1.
 struct ErrModelInUse {
     ErrModel model;
     const float *betas, *kappas;
+    bool learn;
+    ScaleArgs scale;
 };
 static ErrModelInUse err_model(const mlggd_engine *e) {
-    if (e->asym) return {EM_ASYM, e->per_bin ? e->betas_dev : e->asym_betas_dev.p, e->kappas_dev.p};
-    if (e->per_bin) return {EM_BINS, e->betas_dev, nullptr};
-    return {EM_SHARED, nullptr, nullptr};
+    ErrModelInUse em = {EM_SHARED, nullptr, nullptr, false, {nullptr, nullptr, 0.0f, 0.0f, 0.0f}};
+    if (e->asym) em.model = EM_ASYM, em.betas = e->per_bin ? e->betas_dev : e->asym_betas_dev.p, em.kappas = e->kappas_dev.p;
+    else if (e->per_bin) em.model = EM_BINS, em.betas = e->betas_dev;
+    if (e->scale_mode == MLGGD_SCALE_LEARNED) {
+        const size_t copy = devbuf_rule::scale_state_floats((size_t)e->Dp) / 2;
+        em.learn = true;
+        em.scale = {e->scale_state.p + e->scale_cur * copy, e->scale_state.p + (1 - e->scale_cur) * copy, e->scale_lrate,
+                    e->scale_momentum, e->scale_vmax};
+    }
+    return em;
 }
 // One launch of a loss-family kernel: the dynamic-LDS attribute of the kernel actually launched (lds_attr 0: it needs
 // none), the launch on the engine's stream, its check.
@@ -1337,6 +1357,17 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
         const size_t lds_ml_max = (size_t)2 * LOSS_DT * (1152 + 1) * sizeof(float);
         const int n_ml = e->Dp / LOSS_DT;
         const dim3 grid(n_ml + (n_stage + 3) / 4), block(1024);
+        if (em.learn) switch (em.model) {
+            case EM_ASYM:
+                return launch_loss(e, "k_loss_ml_learn_asym", k_loss_ml_learn_asym, grid, block, lds_ml_max, lds_ml, la, em.scale,
+                                   em.betas, em.kappas, n_ml, sa, n_stage);
+            case EM_BINS:
+                return launch_loss(e, "k_loss_ml_learn_bins", k_loss_ml_learn_bins, grid, block, lds_ml_max, lds_ml, la, em.scale,
+                                   em.betas, n_ml, sa, n_stage);
+            default:
+                return launch_loss(e, "k_loss_ml_learn", k_loss_ml_learn, grid, block, lds_ml_max, lds_ml, la, em.scale, n_ml, sa,
+                                   n_stage);
+            }
         switch (em.model) {
         case EM_ASYM:
             return launch_loss(e, "k_loss_ml_asym", k_loss_ml_asym, grid, block, lds_ml_max, lds_ml, la, em.betas, em.kappas,
@@ -1381,6 +1412,20 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
     }
     if (cs == CS_ACCUMULATE) return MLGGD_OK;
     float *const dEdXt = e->dEdXt[L - 1], *const dEdX = e->dEdX[L - 1];
+    if (em.learn) switch (em.model) {
+        case EM_ASYM:
+            return launch_loss(e, "k_loss_grad_learn_asym", k_loss_grad_learn_asym, grid, block, LOSS_LDS_MAX, lds_grad, e->eT,
+                               e->pT, colsum_in, B, e->D, e->Dp, Bp, em.betas, em.kappas, nf, inv_n, e->scalefactor, dEdXt, dEdX,
+                               b_tiles, em.scale);
+        case EM_BINS:
+            return launch_loss(e, "k_loss_grad_learn_bins", k_loss_grad_learn_bins, grid, block, LOSS_LDS_MAX, lds_grad, e->eT,
+                               e->pT, colsum_in, B, e->D, e->Dp, Bp, em.betas, nf, inv_n, e->scalefactor, dEdXt, dEdX, b_tiles,
+                               em.scale);
+        default:
+            return launch_loss(e, "k_loss_grad_learn", k_loss_grad_learn, grid, block, LOSS_LDS_MAX, lds_grad, e->eT, e->pT,
+                               colsum_in, B, e->D, e->Dp, Bp, e->cfg.shapefactor, nf, inv_n, e->scalefactor, dEdXt, dEdX, b_tiles,
+                               em.scale);
+        }
     switch (em.model) {
     case EM_ASYM:
         return launch_loss(e, "k_loss_grad_asym", k_loss_grad_asym, grid, block, LOSS_LDS_MAX, lds_grad, e->eT, e->pT,
@@ -1597,6 +1642,9 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
     {
         RoctxRange r("loss (+ staging of the next minibatch)");
         CHK(run_loss(e, bn, nf, inv_n, !dp ? CS_LOCAL : e->fake_world ? CS_GIVEN : CS_ALLREDUCE, false, sa, n_stage));
+        // the learned scale: every loss launch of this step (one per emulated rank, the prepass included) has read copy
+        // scale_cur and written the other; the next step reads what they wrote
+        if (e->scale_mode == MLGGD_SCALE_LEARNED) e->scale_cur ^= 1, e->scale_steps++;
     }
     RoctxRange back_range("backward: dX, dW + update, exchange");
     if (gather && ML == 1 && L > 2) {
@@ -2030,11 +2078,109 @@ int mlggd_get_scalefactor(mlggd_handle e, float *alpha) {
     return MLGGD_OK;
 }
 
+// the learned scale's state: where alpha / v of the copy the NEXT step reads live
+static float *scale_alpha_cur(mlggd_engine *e) { return e->scale_state.p + scale_rule::alpha_at(e->scale_cur, (size_t)e->Dp, 0); }
+static float *scale_velocity_cur(mlggd_engine *e) { return e->scale_state.p + scale_rule::velocity_at(e->scale_cur, (size_t)e->Dp, 0); }
+static int scale_check_alpha(const mlggd_engine *e, const float *alpha) {
+    for (int d = 0; d < e->D; d++)
+        if (!scale_rule::valid_alpha(alpha[d]))
+            return fail(MLGGD_ERR_ARG, "alpha[%d] = %g: a scale must be finite and not negative (0: the bin seeds from its "
+                        "first minibatch)", d, (double)alpha[d]);
+    return MLGGD_OK;
+}
+
 int mlggd_set_scalefactor(mlggd_handle e, const float *alpha) {
     if (!e || !alpha) return fail(MLGGD_ERR_ARG, "NULL argument");
+    const bool learned = e->scale_mode == MLGGD_SCALE_LEARNED;  // alpha is then the state's: set it there too, v stays
+    if (learned) CHK(scale_check_alpha(e, alpha));
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->scalefactor, alpha, (size_t)e->D * 4, hipMemcpyHostToDevice, e->stream));
+    if (learned) HIPCHK(hipMemcpyAsync(scale_alpha_cur(e), alpha, (size_t)e->D * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+// ------------------------------------------------------------------ learned scale per output bin (scale_rule.h)
+int mlggd_set_scale_mode(mlggd_handle e, int mode, float lrate, float momentum, float vmax) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (e->cfg.MLflag != 1)
+        return fail(MLGGD_ERR_STATE, "a scale mode needs the ML-GGD loss (MLflag 1), this engine has MLflag %d: a beta-norm "
+                    "has no scale", e->cfg.MLflag);
+    if (mode != MLGGD_SCALE_ALTERNATING && mode != MLGGD_SCALE_LEARNED)
+        return fail(MLGGD_ERR_ARG, "scale mode %d: must be %d (alternating) or %d (learned)", mode, MLGGD_SCALE_ALTERNATING,
+                    MLGGD_SCALE_LEARNED);
+    if (!scale_rule::valid(mode, lrate, momentum, vmax))
+        return fail(MLGGD_ERR_ARG, "scale lrate %g, momentum %g, vmax %g: finite values with lrate >= 0, 0 <= momentum < 1 "
+                    "and vmax > 0 are required", (double)lrate, (double)momentum, (double)vmax);
+    if (mode == MLGGD_SCALE_LEARNED && e->scale_mode != MLGGD_SCALE_LEARNED) {
+        HIPCHK(hipSetDevice(e->device));
+        const size_t n = devbuf_rule::scale_state_floats((size_t)e->Dp);
+        HIPCHK(e->scale_state.grow(n, n, e->bufs, nullptr, nullptr));
+        // on the engine's stream: behind every step already enqueued, which may still write scalefactor
+        HIPCHK(hipMemsetAsync(e->scale_state.p, 0, n * sizeof(float), e->stream));
+        e->scale_cur = 0;
+        HIPCHK(hipMemcpyAsync(scale_alpha_cur(e), e->scalefactor, (size_t)e->D * 4, hipMemcpyDeviceToDevice, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->scale_steps = 0;
+    }
+    // kernel arguments of the launches to come: steps already enqueued chose their kernels when they were enqueued
+    e->scale_mode = mode, e->scale_lrate = lrate, e->scale_momentum = momentum, e->scale_vmax = vmax;
+    return MLGGD_OK;
+}
+
+int mlggd_get_scale_mode(mlggd_handle e, int *mode, float *lrate, float *momentum, float *vmax, int64_t *steps) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (mode) *mode = e->scale_mode;
+    if (lrate) *lrate = e->scale_lrate;
+    if (momentum) *momentum = e->scale_momentum;
+    if (vmax) *vmax = e->scale_vmax;
+    if (steps) *steps = (int64_t)e->scale_steps;
+    return MLGGD_OK;
+}
+
+int mlggd_get_scale_state(mlggd_handle e, float *alpha, float *velocity) {
+    if (!e || !alpha) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (e->scale_mode != MLGGD_SCALE_LEARNED) return fail(MLGGD_ERR_STATE, "mlggd_get_scale_state: the scale mode is not learned");
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(alpha, scale_alpha_cur(e), (size_t)e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    if (velocity) HIPCHK(hipMemcpyAsync(velocity, scale_velocity_cur(e), (size_t)e->D * 4, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_set_scale_state(mlggd_handle e, const float *alpha, const float *velocity) {
+    if (!e || !alpha) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (e->scale_mode != MLGGD_SCALE_LEARNED) return fail(MLGGD_ERR_STATE, "mlggd_set_scale_state: the scale mode is not learned");
+    CHK(scale_check_alpha(e, alpha));
+    if (velocity)
+        for (int d = 0; d < e->D; d++)
+            if (!std::isfinite(velocity[d]))
+                return fail(MLGGD_ERR_ARG, "velocity[%d] = %g: a velocity must be finite", d, (double)velocity[d]);
+    HIPCHK(hipSetDevice(e->device));
+    const std::vector<float> zeros(velocity ? 0 : e->D, 0.0f);
+    // on the engine's stream: behind every step already enqueued, which may still write this copy
+    HIPCHK(hipMemcpyAsync(scale_alpha_cur(e), alpha, (size_t)e->D * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(scale_velocity_cur(e), velocity ? velocity : zeros.data(), (size_t)e->D * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipMemcpyAsync(e->scalefactor, alpha, (size_t)e->D * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_read_scale_state(const char *path, int D, float *alpha, float *velocity) {
+    if (!path || !alpha) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    std::string err;
+    if (!mlggd_host::parse_scale_state(path, D, alpha, velocity, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    return MLGGD_OK;
+}
+
+int mlggd_write_scale_state(const char *path, int D, const float *alpha, const float *velocity, float lrate, float momentum,
+                            float vmax, int64_t steps) {
+    if (!path || !alpha) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (D < 1) return fail(MLGGD_ERR_ARG, "D %d < 1", D);
+    std::string err;
+    const mlggd_host::ScaleFileHeader h = {lrate, momentum, vmax, (long long)steps};
+    if (!mlggd_host::write_scale_state(path, D, alpha, velocity, h, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
     return MLGGD_OK;
 }
 

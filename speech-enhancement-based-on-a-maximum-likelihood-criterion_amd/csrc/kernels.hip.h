@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include "nat_rule.h"
 #include "asym_rule.h"
+#include "scale_rule.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -2220,14 +2221,47 @@ __global__ __launch_bounds__(256) void k_colsum(const float *__restrict__ pT, in
 // otherwise colsum_in is the GLOBAL minibatch sum (all-reduced).  nf = global minibatch size.
 // One workgroup per 8(d) x 32(b) tile; writes dEdXt and dEdX.  Dynamic LDS: 8*(Bp+1)+8 floats.
 // ---------------------------------------------------------------------------------------
-// beta and MLflag are read under EM_SHARED only: the other two models are ML by construction.
-template <int EM>
+// The learned scale (mlggd_set_scale_mode, scale_rule.h): the _learn kernels' extra argument.  in / out are the two copies
+// [alpha, v][Dp] of the engine's state: every launch of a step reads `in` and writes `out`, and the host swaps them once
+// per step, so that workgroups sharing a column (b_tiles of them in the two-kernel form) and launches sharing a step
+// (one per emulated rank) all see the same alpha, whichever of them has already written.
+struct ScaleArgs {
+    const float *in;
+    float *out;
+    float eta, mu, vmax;
+};
+// Column d < D with sum s: the rule's q, the denominator of this step's gradient; with write, (alpha', v') go to the
+// other copy and alpha' to scalefactor.  The text of the rule is scale_rule.h's; pow_or_self and exp_det are evaluated here.
+__device__ __forceinline__ float scale_learn_column(const ScaleArgs &S, int d, int Dp, float s, float nf, float beta,
+                                                    bool write, float *__restrict__ scalefactor) {
+    const float alpha = S.in[scale_rule::alpha_at(0, Dp, d)], v = S.in[scale_rule::velocity_at(0, Dp, d)];
+    const float v2 = scale_rule::beta_s(s, nf, beta);  // kernDivide, kernVecMulNum
+    float q, an, vn;
+    if (scale_rule::seeds(alpha)) {
+        an = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
+        vn = 0.0f;
+        q = pow_or_self(an, beta);
+    } else {
+        q = pow_or_self(alpha, beta);
+        vn = scale_rule::velocity(v2, q, v, S.eta, S.mu, S.vmax);
+        an = scale_rule::advance(alpha, exp_det(vn));
+    }
+    if (write) {
+        S.out[scale_rule::alpha_at(0, Dp, d)] = an;
+        S.out[scale_rule::velocity_at(0, Dp, d)] = vn;
+        scalefactor[d] = an;
+    }
+    return q;
+}
+// beta and MLflag are read under EM_SHARED only: the other two models are ML by construction.  LEARN: the scale is the
+// engine's state moved by scale_rule.h instead of the minibatch's closed form; every other statement is the same text.
+template <int EM, bool LEARN = false>
 __device__ __forceinline__ void loss_grad_body(const float *__restrict__ eT, const float *__restrict__ pT,
                                                const float *__restrict__ colsum_in, int B, int D, int Dp, int Bp,
                                                float beta_shared, const float *__restrict__ betas,
                                                const float *__restrict__ kappas, int MLflag, float nf, float inv_n,
                                                float *__restrict__ scalefactor, float *__restrict__ dEdXt,
-                                               float *__restrict__ dEdX, int b_tiles) {
+                                               float *__restrict__ dEdX, int b_tiles, const ScaleArgs &S = ScaleArgs()) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ float denom[LOSS_DT];
     const bool ml = EM != EM_SHARED || MLflag == 1;
@@ -2247,11 +2281,15 @@ __device__ __forceinline__ void loss_grad_body(const float *__restrict__ eT, con
             float q = 1.0f;
             if (d < D) {
                 const float beta = EM == EM_SHARED ? beta_shared : betas[d];
-                const float v1 = sums[tid] / nf;            // kernDivide
-                const float v2 = v1 * beta;                 // kernVecMulNum
-                const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
-                if (bt == 0) scalefactor[d] = alpha;
-                q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
+                if (LEARN) {
+                    q = scale_learn_column(S, d, Dp, sums[tid], nf, beta, bt == 0, scalefactor);
+                } else {
+                    const float v1 = sums[tid] / nf;            // kernDivide
+                    const float v2 = v1 * beta;                 // kernVecMulNum
+                    const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
+                    if (bt == 0) scalefactor[d] = alpha;
+                    q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
+                }
             }
             denom[tid] = q;
         }
@@ -2305,6 +2343,33 @@ __global__ __launch_bounds__(256) void k_loss_grad_asym(const float *__restrict_
                                                         float *__restrict__ dEdX, int b_tiles) {
     loss_grad_body<EM_ASYM>(eT, pT, colsum_in, B, D, Dp, Bp, 0.0f, betas, kappas, 1, nf, inv_n, scalefactor, dEdXt, dEdX,
                             b_tiles);
+}
+// The learned scale: ML only, so k_loss_grad_learn has no MLflag.
+__global__ __launch_bounds__(256) void k_loss_grad_learn(const float *__restrict__ eT, const float *__restrict__ pT,
+                                                         const float *__restrict__ colsum_in, int B, int D, int Dp,
+                                                         int Bp, float beta, float nf, float inv_n,
+                                                         float *__restrict__ scalefactor, float *__restrict__ dEdXt,
+                                                         float *__restrict__ dEdX, int b_tiles, ScaleArgs S) {
+    loss_grad_body<EM_SHARED, true>(eT, pT, colsum_in, B, D, Dp, Bp, beta, nullptr, nullptr, 1, nf, inv_n, scalefactor,
+                                    dEdXt, dEdX, b_tiles, S);
+}
+__global__ __launch_bounds__(256) void k_loss_grad_learn_bins(const float *__restrict__ eT, const float *__restrict__ pT,
+                                                              const float *__restrict__ colsum_in, int B, int D, int Dp,
+                                                              int Bp, const float *__restrict__ betas, float nf,
+                                                              float inv_n, float *__restrict__ scalefactor,
+                                                              float *__restrict__ dEdXt, float *__restrict__ dEdX,
+                                                              int b_tiles, ScaleArgs S) {
+    loss_grad_body<EM_BINS, true>(eT, pT, colsum_in, B, D, Dp, Bp, 0.0f, betas, nullptr, 1, nf, inv_n, scalefactor, dEdXt,
+                                  dEdX, b_tiles, S);
+}
+__global__ __launch_bounds__(256) void k_loss_grad_learn_asym(const float *__restrict__ eT, const float *__restrict__ pT,
+                                                              const float *__restrict__ colsum_in, int B, int D, int Dp,
+                                                              int Bp, const float *__restrict__ betas,
+                                                              const float *__restrict__ kappas, float nf, float inv_n,
+                                                              float *__restrict__ scalefactor, float *__restrict__ dEdXt,
+                                                              float *__restrict__ dEdX, int b_tiles, ScaleArgs S) {
+    loss_grad_body<EM_ASYM, true>(eT, pT, colsum_in, B, D, Dp, Bp, 0.0f, betas, kappas, 1, nf, inv_n, scalefactor, dEdXt,
+                                  dEdX, b_tiles, S);
 }
 
 // MLflag != 1 needs no statistic over the minibatch, so phases A and B collapse into one
@@ -2374,9 +2439,10 @@ struct LossMlArgs {
     int toff;
 };
 // wg: the loss workgroup, staging blocks not counted
-template <int EM>
+template <int EM, bool LEARN = false>
 __device__ __forceinline__ void loss_ml_body(const LossMlArgs &A, const float *__restrict__ betas,
-                                             const float *__restrict__ kappas, const int wg) {
+                                             const float *__restrict__ kappas, const int wg,
+                                             const ScaleArgs &S = ScaleArgs()) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ float denom[LOSS_DT];
     const float *__restrict__ slab = A.slab, *__restrict__ bias = A.bias, *__restrict__ targ = A.targ;
@@ -2419,11 +2485,15 @@ __device__ __forceinline__ void loss_ml_body(const LossMlArgs &A, const float *_
         float q = 1.0f;
         if (d0 + tid < D) {
             const float beta = EM == EM_SHARED ? A.beta : betas[d0 + tid];  // the column this thread sums, not the unit of its passes
-            const float v1 = s / A.nf;                  // kernDivide
-            const float v2 = v1 * beta;                 // kernVecMulNum
-            const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
-            A.scalefactor[d0 + tid] = alpha;
-            q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
+            if (LEARN) {
+                q = scale_learn_column(S, d0 + tid, Dp, s, A.nf, beta, true, A.scalefactor);
+            } else {
+                const float v1 = s / A.nf;                  // kernDivide
+                const float v2 = v1 * beta;                 // kernVecMulNum
+                const float alpha = pow_or_self(v2, 1.0f / beta);  // kernindex2 with ppp = 1.0f/shapefactor
+                A.scalefactor[d0 + tid] = alpha;
+                q = pow_or_self(alpha, beta);                 // pow(vec[j], alpha) in kernfunc2
+            }
         }
         denom[tid] = q;
     }
@@ -2484,6 +2554,34 @@ __global__ __launch_bounds__(1024) void k_loss_ml_asym(LossMlArgs A, const float
         return;
     }
     loss_ml_body<EM_ASYM>(A, betas, kappas, (int)blockIdx.x - n_stage);
+}
+__global__ __launch_bounds__(1024) void k_loss_ml_learn(LossMlArgs A, ScaleArgs S, int n_loss, StageArgs G,
+                                                        int n_stage_tiles) {
+    const int n_stage = (int)gridDim.x - n_loss;
+    if ((int)blockIdx.x < n_stage) {
+        transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
+        return;
+    }
+    loss_ml_body<EM_SHARED, true>(A, nullptr, nullptr, (int)blockIdx.x - n_stage, S);
+}
+__global__ __launch_bounds__(1024) void k_loss_ml_learn_bins(LossMlArgs A, ScaleArgs S, const float *__restrict__ betas,
+                                                             int n_loss, StageArgs G, int n_stage_tiles) {
+    const int n_stage = (int)gridDim.x - n_loss;
+    if ((int)blockIdx.x < n_stage) {
+        transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
+        return;
+    }
+    loss_ml_body<EM_BINS, true>(A, betas, nullptr, (int)blockIdx.x - n_stage, S);
+}
+__global__ __launch_bounds__(1024) void k_loss_ml_learn_asym(LossMlArgs A, ScaleArgs S, const float *__restrict__ betas,
+                                                             const float *__restrict__ kappas, int n_loss, StageArgs G,
+                                                             int n_stage_tiles) {
+    const int n_stage = (int)gridDim.x - n_loss;
+    if ((int)blockIdx.x < n_stage) {
+        transpose_in_body<4>(G, (int)blockIdx.x, n_stage_tiles);
+        return;
+    }
+    loss_ml_body<EM_ASYM, true>(A, betas, kappas, (int)blockIdx.x - n_stage, S);
 }
 
 // Forward-only output (cv_bunch_single, BP_GPU.cu:442-512): out[b][d] = bias + sum_s slab,

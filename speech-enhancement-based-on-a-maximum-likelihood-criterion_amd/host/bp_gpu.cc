@@ -133,6 +133,18 @@ void BP_GPU::OutputStats_frames(int n_frames, int fea_context, const float *feat
           "mlggd_output_stats_frames");
 }
 void BP_GPU::setShapefactors(const float *betas) { check(mlggd_set_shapefactors(h_, betas), "mlggd_set_shapefactors"); }
+void BP_GPU::setScaleLearned(float lrate, float momentum, float vmax) {
+    check(mlggd_set_scale_mode(h_, MLGGD_SCALE_LEARNED, lrate, momentum, vmax), "mlggd_set_scale_mode");
+}
+void BP_GPU::getScaleState(float *alpha, float *velocity) { check(mlggd_get_scale_state(h_, alpha, velocity), "mlggd_get_scale_state"); }
+void BP_GPU::setScaleState(const float *alpha, const float *velocity) {
+    check(mlggd_set_scale_state(h_, alpha, velocity), "mlggd_set_scale_state");
+}
+long long BP_GPU::scaleSteps() {
+    int64_t steps = 0;
+    check(mlggd_get_scale_mode(h_, nullptr, nullptr, nullptr, nullptr, &steps), "mlggd_get_scale_mode");
+    return (long long)steps;
+}
 void BP_GPU::returnWeights(float **weights, float **bias) {
     check(mlggd_get_weights(h_, weights, bias), "mlggd_get_weights");
 }

@@ -50,6 +50,12 @@ class BP_GPU {
     void ErrorStatsSigned(int n_frames, const float *in, const float *targ, int n_betas, const float *betas, double *sums);
     void ErrorStatsSigned_frames(int n_frames, int fea_context, const float *feat, const float *targ, int n_samples,
                                  const int *first_frame, int targ_offset, int n_betas, const float *betas, double *sums);
+    // the learned scale (not in the reference; MLflag 1 only): alpha per output bin as a state moved by SGD beside the
+    // weights (mlggd_set_scale_mode with MLGGD_SCALE_LEARNED), its state [D] + [D] and the steps it has taken
+    void setScaleLearned(float lrate, float momentum, float vmax);
+    void getScaleState(float *alpha, float *velocity);
+    void setScaleState(const float *alpha, const float *velocity);
+    long long scaleSteps();
     void returnWeights(float **weights, float **bias);
     float Gamma(float x) { return mlggd_gamma(x); }
     // data parallel (not in the reference): join an RCCL communicator of `world` ranks

@@ -42,6 +42,13 @@
 // names the file and the minimum, maximum and mean skew.  Needs MLflag=1.  One fit feeds
 // MLGGD_SHAPEFACTORS=fit.txt MLGGD_ASYMMETRY=fit.txt in the next epoch.
 //
+// Learned scale (new, opt-in; scalefile.h, csrc/scale_rule.h): with MLGGD_SCALE=learned every rank switches the engine
+// to the learned scale before the first chunk (mlggd_set_scale_mode; MLGGD_SCALE_LRATE, MLGGD_SCALE_MOMENTUM and
+// MLGGD_SCALE_VMAX are optional).  finetune.pl starts one process per epoch and a .wts file has no place for alpha, so
+// the state travels in a file: MLGGD_SCALE_FILE=PATH is read before the first chunk if it exists, and written by rank 0
+// after the epoch's CV pass.  One stderr line names the rates and the state's origin, one stdout line the file written.
+// Needs MLflag=1; the log file and the weights' format do not change.
+//
 // Data parallel (new): when WORLD_SIZE > 1 (torchrun-style env: RANK,
 // LOCAL_RANK, WORLD_SIZE; MLGGD_ID_FILE names a file on a shared filesystem used to hand the
 // RCCL unique id from rank 0 to the others) every rank reads the same chunks with the same
@@ -65,6 +72,8 @@
 #include "errmodel.h"
 #include "asymfile.h"
 #include "gvfile.h"
+#include "scalefile.h"
+#include "../csrc/scale_rule.h"
 #include "prefetch.h"
 #include "trainer_io.h"
 
@@ -208,6 +217,45 @@ int main(int argc, char *argv[]) {
             if (!mlggd_host::parse_asymmetry(asym_fn, (int)skews.size(), 1.0f, skews.data(), &why))
                 throw IoError("MLGGD_ASYMMETRY: " + why);
         }
+        // MLGGD_SCALE=learned: a bad value, a bad rate, a bad state file or a beta-norm run ends here, before anything is trained
+        const char *scale_env = getenv("MLGGD_SCALE");
+        if (scale_env && !*scale_env) scale_env = nullptr;
+        const char *scale_fn = getenv("MLGGD_SCALE_FILE");
+        if (scale_fn && !*scale_fn) scale_fn = nullptr;
+        const bool scale_learned = scale_env && std::string(scale_env) == "learned";
+        float scale_lrate = scale_rule::kLrate, scale_momentum = scale_rule::kMomentum, scale_vmax = scale_rule::kVmax;
+        std::vector<float> scale_alpha, scale_velocity;  // the state MLGGD_SCALE_FILE held, empty: none
+        long long scale_steps0 = 0;
+        if (scale_env && !scale_learned && std::string(scale_env) != "alternating")
+            throw IoError(std::string("MLGGD_SCALE=") + scale_env + ": must be learned or alternating");
+        if (scale_fn && !scale_learned) throw IoError(std::string("MLGGD_SCALE_FILE=") + scale_fn + ": needs MLGGD_SCALE=learned");
+        if (scale_learned) {
+            if (p->MLflag != 1)
+                throw IoError("MLGGD_SCALE=learned: a learned scale needs MLflag=1, this run has MLflag=" + std::to_string(p->MLflag));
+            auto rate = [](const char *name, float *v) {
+                const char *t = getenv(name);
+                if (!t || !*t) return;
+                char *end = nullptr;
+                *v = strtof(t, &end);
+                if (end == t || *end != 0) throw IoError(std::string(name) + "=" + t + ": not a number");
+            };
+            rate("MLGGD_SCALE_LRATE", &scale_lrate);
+            rate("MLGGD_SCALE_MOMENTUM", &scale_momentum);
+            rate("MLGGD_SCALE_VMAX", &scale_vmax);
+            if (!scale_rule::valid(scale_rule::kLearned, scale_lrate, scale_momentum, scale_vmax))
+                throw IoError("MLGGD_SCALE=learned: MLGGD_SCALE_LRATE must be finite and >= 0, MLGGD_SCALE_MOMENTUM in [0, 1), "
+                              "MLGGD_SCALE_VMAX finite and > 0");
+            FILE *have = scale_fn ? fopen(scale_fn, "r") : nullptr;  // no file yet: the first epoch seeds from its first minibatch
+            if (have) {
+                fclose(have);
+                const int Dout = p->layersizes[io->numlayers - 1];
+                scale_alpha.resize(Dout);
+                scale_velocity.resize(Dout);
+                std::string why;
+                if (!mlggd_host::parse_scale_state(scale_fn, Dout, scale_alpha.data(), scale_velocity.data(), &why, &scale_steps0))
+                    throw IoError("MLGGD_SCALE_FILE: " + why);
+            }
+        }
         // ---- train (BPtrain.cc:81-102).  The chunk plan and the fetch thread only touch host state, so the
         // first chunk is read while the engine initialises HIP and uploads the weights (the reference creates
         // BP_GPU first, BPtrain.cc:77-78, and reads the first chunk afterwards).
@@ -291,6 +339,14 @@ int main(int argc, char *argv[]) {
             }
             fprintf(stderr, "asymmetry: %s, %zu bins, kappa min %.9g max %.9g mean %.9g\n", asym_fn, skews.size(),
                     (double)lo, (double)hi, sum / (double)skews.size());
+        }
+        if (scale_learned) {
+            net->setScaleLearned(scale_lrate, scale_momentum, scale_vmax);
+            if (!scale_alpha.empty()) net->setScaleState(scale_alpha.data(), scale_velocity.data());
+            fprintf(stderr, "learned scale: lrate %.9g momentum %.9g vmax %.9g, %s%s%s\n", (double)scale_lrate,
+                    (double)scale_momentum, (double)scale_vmax, scale_alpha.empty() ? "every bin seeds from its first minibatch" : "state of ",
+                    scale_alpha.empty() ? "" : scale_fn,
+                    scale_alpha.empty() ? "" : (" after " + std::to_string(scale_steps0) + " steps").c_str());
         }
         phase("engine (HIP init, upload)", t_phase);
         const int K0 = p->layersizes[0], D = p->layersizes[io->numlayers - 1], B = p->bunchsize;
@@ -381,6 +437,17 @@ int main(int argc, char *argv[]) {
             }
             if (io->fp_log) fflush(io->fp_log);
             phase("cross validation", t_phase);
+
+            // ---- the learned scale's state, for the next epoch's process (every rank holds the same one)
+            if (scale_learned && scale_fn) {
+                std::vector<float> a(D), v(D);
+                net->getScaleState(a.data(), v.data());
+                const long long steps = scale_steps0 + net->scaleSteps();
+                const mlggd_host::ScaleFileHeader h = {scale_lrate, scale_momentum, scale_vmax, steps};
+                std::string why;
+                if (!mlggd_host::write_scale_state(scale_fn, D, a.data(), v.data(), h, &why)) throw IoError("MLGGD_SCALE_FILE: " + why);
+                printf("learned scale: %s written, %lld steps\n", scale_fn, steps);
+            }
 
             // ---- the per-bin models of the CV set: one more pass over the CV chunks each, nothing of it reaches the log.
             // `stats` folds the chunk Readchunk*_cv left in the buffers into part ([rows][D], both chunk forms), the
