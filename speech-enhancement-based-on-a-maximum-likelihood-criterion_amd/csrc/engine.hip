@@ -194,12 +194,6 @@ struct mlggd_engine {
     int B = 0, Bp = 0, D = 0, Dp = 0, K0 = 0;
     int device = 0;
     hipStream_t stream = nullptr, comm_stream = nullptr;
-    // weight-gradient/update kernels (HBM-bound) run on their own stream beside the MFMA-bound
-    // dX chain of the main stream; ev_dx[l] orders dw(l) after dX(l) (old-weights semantics),
-    // ev_upd orders the next step after the last update
-    hipStream_t dw_stream = nullptr;
-    hipEvent_t ev_dx[MLGGD_MAXLAYER] = {0}, ev_upd = nullptr;
-    int two_streams = 0;  // measured slower on MI355X (cross-stream event waits + contention): off
 
     float *W[MLGGD_MAXLAYER] = {0}, *dW[MLGGD_MAXLAYER] = {0};
     float *bias[MLGGD_MAXLAYER] = {0}, *dbias[MLGGD_MAXLAYER] = {0};
@@ -298,13 +292,10 @@ struct mlggd_engine {
     int fdim = 0, toff = 0, raw_frames = 0;
     unsigned step_counter = 0;
     // launch-plan knobs (defaults chosen from measurements; env overrides for A/B runs)
-    int fwd_pipe = 4, dx_pipe = 4;  // main loops software-pipelined inside the wave (forward: operands by LDS-DMA; 1: through staging registers; 0: the round-1 loops, for A/B)
-    // 4 waves per workgroup (one per SIMD) since the main loops are pipelined inside the wave: a wave no longer needs a
-    // partner on its SIMD to fill its chunk-boundary gaps, and four partial tiles reduce faster than eight
     // 64 x 64-tile forward / dX kernels (kernels64.hip.h): 1 = where the shape gives every CU such a tile (units and
     // frames multiples of 64, tiles >= CUs), 0 = never, 2 = wherever the shape divides (tests, A/B); MLGGD_TILE64
     int tile64 = 1, n_cus = 256;
-    int fwd_nw = 4, dx_nw = 4, dw_tile = 1, dw_persist = 1, dwp_per_cu = 2, dw_merge = 1, loss_fuse = 1, tile_map = 0, stage_ahead = 1;  // dw_tile 0 = auto
+    int dw_tile = 1, dw_persist = 1, dwp_per_cu = 2, dw_merge = 1, loss_fuse = 1, tile_map = 0, stage_ahead = 1;  // dw_tile 0 = auto
 
     // data parallel
     int world = 1, rank = 0;
@@ -388,7 +379,6 @@ struct mlggd_engine {
 
     // a mask engine (mlggd_config.mask_bins = M >= 1, mask_rule.h): D = 2 M outputs, LPS half first.  The scale is read
     // where targets are formed from waves and where a decoder post-filters; mode and thresholds by the decoders alone.
-    // Behind everything else: the members the training step reads keep their offsets.
     int mask_bins = 0;
     int mask_mode = mask_rule::kSelect;
     float mask_lo = mask_rule::kLo, mask_hi = mask_rule::kHi, mask_scale = mask_rule::kScale;
@@ -455,17 +445,16 @@ static int download_padded(float *dst, const float *src, int Np, int K, int N, h
 // classes are bracketed by events recorded on the stream before and after, which adds the cost of the bracket.
 struct ProfScope {
     mlggd_engine *e;
-    hipStream_t st;
     bool on, attach;
-    ProfScope(mlggd_engine *eng, int cls, int layer, hipStream_t s = nullptr)
-        : e(eng), st(s ? s : eng->stream), on(false), attach(cls == KC_DW || cls == KC_FWD || cls == KC_DX) {
+    ProfScope(mlggd_engine *eng, int cls, int layer)
+        : e(eng), on(false), attach(cls == KC_DW || cls == KC_FWD || cls == KC_DX) {
         if (e->prof_class == cls && (e->prof_layer == 0 || e->prof_layer == layer) &&
             e->step_counter % (unsigned)e->prof_stride == 0 && e->prof_used + 2 <= e->prof_cap) {
             on = true;
             if (attach) {
                 e->prof_attach = &e->prof_ev[e->prof_used];  // consumed by the launch itself
                 e->prof_attached = false;
-            } else if (hipEventRecord(e->prof_ev[e->prof_used], st) != hipSuccess) {
+            } else if (hipEventRecord(e->prof_ev[e->prof_used], e->stream) != hipSuccess) {
                 on = false;
             }
         }
@@ -475,7 +464,7 @@ struct ProfScope {
         if (attach) {
             e->prof_attach = nullptr;
             if (e->prof_attached) e->prof_used += 2;
-        } else if (hipEventRecord(e->prof_ev[e->prof_used + 1], st) == hipSuccess) {
+        } else if (hipEventRecord(e->prof_ev[e->prof_used + 1], e->stream) == hipSuccess) {
             e->prof_used += 2;
         }
     }
@@ -643,12 +632,16 @@ static bool tile64_ok(const mlggd_engine *e, int units_p) {
     return e->tile64 == 2 || (long)(units_p / 64) * (e->Bp / 64) >= e->n_cus;
 }
 static bool fwd64_used(const mlggd_engine *e, int l) {
-    if (e->fwd_pipe != 4 || e->fwd_nw != 4 || !tile64_ok(e, e->lsp[l])) return false;
+    if (!tile64_ok(e, e->lsp[l])) return false;
     return l != e->L - 1 || e->S_out == 1;  // an output layer only when it needs no split-K slabs (it is that wide)
 }
 static bool dx64_used(const mlggd_engine *e, int l) {
-    return l >= 2 && e->dx_pipe == 4 && e->dx_nw == 4 && tile64_ok(e, e->lsp[l - 1]);
+    return l >= 2 && tile64_ok(e, e->lsp[l - 1]);
 }
+// Which of k_dx's two forms a launch over Kp units takes.  Both are 4 waves with the main loop software-pipelined inside
+// the wave.  Operands by LDS-DMA (136 KB of LDS) where one workgroup per CU is all there is: <= 256 workgroups.  Through
+// staging registers (71 KB: two workgroups per CU) above that.  run_dx and the RBM's down-pass (rbm.hip.h) both ask here.
+static bool dx_dma(const mlggd_engine *e, int Kp) { return (Kp / 32) * (e->Bp / 32) <= 256; }
 
 static int run_transpose(mlggd_engine *e, const Bunch &bn, int frames) {
     ProfScope ps(e, KC_TRANSPOSE, 0);
@@ -693,6 +686,21 @@ static int gather_begin_armed(mlggd_engine *e);
 static int gather_one(mlggd_engine *e, const float *src, float *dst, size_t count, hipStream_t st);
 static int exchange_y(mlggd_engine *e, int l, const float *src, hipStream_t st);
 enum { GATHER_INPUT = 1, GATHER_HIDDEN = 2, GATHER_HIDDEN_EACH = 4 };  // data-parallel factor exchange issued from inside the forward pass
+
+// A hidden layer's 32 x 32-tile forward launch.  k_fwd has one form: 4 waves, the main loop software-pipelined inside the
+// wave, operands by LDS-DMA.  The stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd).
+template <int MODE>
+static int launch_fwd(mlggd_engine *e, int nwg, const FwdArgs &fa, long long *st) {
+    const size_t lds = fwd_lds_floats<4, 4>() * sizeof(float);
+    if (st) {
+        CHK(ensure_lds(e, k_fwd<MODE, 4, 4, true>, lds));
+        launch_timed(e, k_fwd<MODE, 4, 4, true>, dim3(nwg), dim3(256), lds, e->stream, fa, st);
+    } else {
+        CHK(ensure_lds(e, k_fwd<MODE, 4, 4, false>, lds));
+        launch_timed(e, k_fwd<MODE, 4, 4, false>, dim3(nwg), dim3(256), lds, e->stream, fa, st);
+    }
+    return MLGGD_OK;
+}
 
 static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool training, bool prestaged = false,
                        int gather_flags = 0, int l_end = 0) {  // l_end > 0: layers 1 .. l_end - 1 only (rbm.hip.h)
@@ -748,42 +756,13 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
                 }
             } else if (l != e->L - 1) {
                 long long *st = stamps_for(e, KC_FWD, l, n_tiles * b_tiles);
-#define LAUNCH_FWD(NW, PIPE)                                                                                \
-    {                                                                                                       \
-        const size_t lds = fwd_lds_floats<NW, PIPE>() * sizeof(float);                                      \
-        if (relu && st) LAUNCH_FWD_(FWD_RELU, NW, PIPE, true)                                               \
-        else if (relu) LAUNCH_FWD_(FWD_RELU, NW, PIPE, false)                                               \
-        else if (st) LAUNCH_FWD_(FWD_SIGMOID, NW, PIPE, true)                                               \
-        else LAUNCH_FWD_(FWD_SIGMOID, NW, PIPE, false)                                                      \
-    }
-    // the stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd)
-#define LAUNCH_FWD_(MODE, NW, PIPE, STAMPED)                                                                \
-    {                                                                                                       \
-        CHK(ensure_lds(e, k_fwd<MODE, NW, PIPE, STAMPED>, lds));                                            \
-        launch_timed(e, k_fwd<MODE, NW, PIPE, STAMPED>, dim3(n_tiles * b_tiles), dim3(64 * NW), lds, e->stream, fa, st); \
-    }
-                // PIPE 4 (default): main loop software-pipelined inside the wave, operands by LDS-DMA; 1: the same
-                // pipeline through staging registers (MLGGD_FWD_PIPE=1); 0: the round-1 loop (MLGGD_FWD_PIPE=0, and the
-                // 16-wave form, whose 128-VGPR budget and 160 KB of LDS the pipelined loops do not fit)
-                if (e->fwd_nw == 16) LAUNCH_FWD(16, 0)
-                else if (e->fwd_nw == 8 && e->fwd_pipe == 4) LAUNCH_FWD(8, 4)
-                else if (e->fwd_nw == 8 && e->fwd_pipe) LAUNCH_FWD(8, 1)
-                else if (e->fwd_nw == 8) LAUNCH_FWD(8, 0)
-                else if (e->fwd_pipe == 4) LAUNCH_FWD(4, 4)
-                else if (e->fwd_pipe) LAUNCH_FWD(4, 1)
-                else LAUNCH_FWD(4, 0)
-#undef LAUNCH_FWD
-#undef LAUNCH_FWD_
+                if (relu) CHK(launch_fwd<FWD_RELU>(e, n_tiles * b_tiles, fa, st));
+                else CHK(launch_fwd<FWD_SIGMOID>(e, n_tiles * b_tiles, fa, st));
             } else {
                 const int nwg = n_tiles * b_tiles * e->S_out;
-                if (e->fwd_pipe == 4) {
-                    const size_t lds = fwd_lds_floats<4, 4>() * sizeof(float);
-                    CHK(ensure_lds(e, k_fwd<FWD_SLAB, 4, 4>, lds));
-                    launch_timed(e, k_fwd<FWD_SLAB, 4, 4>, dim3(nwg), dim3(256), lds, e->stream, fa, (long long *)nullptr);
-                } else {
-                    const size_t lds = fwd_lds_floats<4, 1>() * sizeof(float);
-                    launch_timed(e, k_fwd<FWD_SLAB, 4, 1>, dim3(nwg), dim3(256), lds, e->stream, fa, (long long *)nullptr);
-                }
+                const size_t lds = fwd_lds_floats<4, 4>() * sizeof(float);
+                CHK(ensure_lds(e, k_fwd<FWD_SLAB, 4, 4>, lds));
+                launch_timed(e, k_fwd<FWD_SLAB, 4, 4>, dim3(nwg), dim3(256), lds, e->stream, fa, (long long *)nullptr);
             }
         }
         CHK(launch_check("k_fwd"));
@@ -807,7 +786,7 @@ static int run_forward(mlggd_engine *e, const Bunch &bn, int frames, bool traini
 }
 
 template <int T>
-static int launch_dw(mlggd_engine *e, int l, const float *in_rows, bool fused, float nf, hipStream_t st) {
+static int launch_dw(mlggd_engine *e, int l, const float *in_rows, bool fused, float nf) {
     const int Kp = e->lsp[l - 1], Np = e->lsp[l];
     const int k_wg = (Kp + 64 * T - 1) / (64 * T), n_wg = (Np + 64 * T - 1) / (64 * T);
     const float *A = (l == 1) ? in_rows : e->Y[l - 1];
@@ -816,12 +795,12 @@ static int launch_dw(mlggd_engine *e, int l, const float *in_rows, bool fused, f
     if (fused) CHK(ensure_lds(e, k_dw<T, true>, lds));
     else CHK(ensure_lds(e, k_dw<T, false>, lds));
     if (fused)
-        launch_timed(e, k_dw<T, true>, dim3(k_wg * n_wg), dim3(256), lds, st, A, ldA, (const float *)e->dEdX[l], e->W[l],
+        launch_timed(e, k_dw<T, true>, dim3(k_wg * n_wg), dim3(256), lds, e->stream, A, ldA, (const float *)e->dEdX[l], e->W[l],
                      e->dW[l], (float *)nullptr, e->bias[l], e->dbias[l], (float *)nullptr, e->ls[l - 1], e->ls[l], Np,
                      e->B, e->Bp, n_wg, nf, e->cfg.momentum, e->cfg.lrate, e->cfg.weightcost,
                      stamps_for(e, KC_DW, l, k_wg * n_wg));
     else
-        launch_timed(e, k_dw<T, false>, dim3(k_wg * n_wg), dim3(256), lds, st, A, ldA, (const float *)e->dEdX[l], e->W[l],
+        launch_timed(e, k_dw<T, false>, dim3(k_wg * n_wg), dim3(256), lds, e->stream, A, ldA, (const float *)e->dEdX[l], e->W[l],
                      e->dW[l], e->G[l], e->bias[l], e->dbias[l], e->gb[l], e->ls[l - 1], e->ls[l], Np, e->B, e->Bp, n_wg,
                      nf, e->cfg.momentum, e->cfg.lrate, e->cfg.weightcost, (long long *)nullptr);
     return launch_check("k_dw");
@@ -937,7 +916,7 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
 }
 
 template <int H>
-static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream_t st, int stamp_layer) {
+static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, int stamp_layer) {
     const size_t lds = dwp_lds_floats() * sizeof(float);
     const int grid = dwp_grid(e, J.total);
     if (J.total < 1) return MLGGD_OK;
@@ -960,10 +939,10 @@ static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream
         memcpy(&nb, &C.nf, sizeof(nb));
         if ((nb & 0x007FFFFFu) == 0u && C.nf >= 1.0f) {
             CHK(ensure_lds(e, k_dwp_bias<H, true>, lds));
-            hipLaunchKernelGGL((k_dwp_bias<H, true>), dim3(grid), dim3(256), lds, st, table, J.total, C, (long long *)nullptr);
+            hipLaunchKernelGGL((k_dwp_bias<H, true>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, (long long *)nullptr);
         } else {
             CHK(ensure_lds(e, k_dwp_bias<H, false>, lds));
-            hipLaunchKernelGGL((k_dwp_bias<H, false>), dim3(grid), dim3(256), lds, st, table, J.total, C, (long long *)nullptr);
+            hipLaunchKernelGGL((k_dwp_bias<H, false>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, (long long *)nullptr);
         }
         return launch_check("k_dwp_bias");
     }
@@ -974,7 +953,7 @@ static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream
             long long *sp = stamps_for(e, KC_DW, -1, 2 * grid);
             if (sp) {
                 CHK(ensure_lds(e, k_dwp_phases<H>, lds));
-                hipLaunchKernelGGL((k_dwp_phases<H>), dim3(grid), dim3(256), lds, st, table, J.total, C, sp);
+                hipLaunchKernelGGL((k_dwp_phases<H>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, sp);
                 return launch_check("k_dwp_phases");
             }
         }
@@ -985,7 +964,7 @@ static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream
 #define DWP_ABL(A_)                                                                                       \
     case A_:                                                                                              \
         CHK(ensure_lds(e, k_dwp_ablate<H, A_>, lds));                                                     \
-        launch_timed(e, k_dwp_ablate<H, A_>, dim3(grid), dim3(256), lds, st, table, J.total, C, (long long *)nullptr); \
+        launch_timed(e, k_dwp_ablate<H, A_>, dim3(grid), dim3(256), lds, e->stream, table, J.total, C, (long long *)nullptr); \
         return launch_check("k_dwp_ablate");
             switch (abl) {
                 DWP_ABL(1) DWP_ABL(2) DWP_ABL(3) DWP_ABL(4) DWP_ABL(7) DWP_ABL(15) DWP_ABL(31) DWP_ABL(63) DWP_ABL(16) DWP_ABL(48) DWP_ABL(256) DWP_ABL(1024) DWP_ABL(2048) DWP_ABL(512) DWP_ABL(576)
@@ -1004,10 +983,10 @@ static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream
     {                                                                                                     \
         if (stamps) {                                                                                     \
             CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_, true>, lds));                                       \
-            launch_timed(e, k_dwp<H, FUSED_, POW2_, true>, dim3(grid), dim3(256), lds, st, table, J.total, C, stamps); \
+            launch_timed(e, k_dwp<H, FUSED_, POW2_, true>, dim3(grid), dim3(256), lds, e->stream, table, J.total, C, stamps); \
         } else {                                                                                          \
             CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_>, lds));                                             \
-            launch_timed(e, k_dwp<H, FUSED_, POW2_>, dim3(grid), dim3(256), lds, st, table, J.total, C, stamps); \
+            launch_timed(e, k_dwp<H, FUSED_, POW2_>, dim3(grid), dim3(256), lds, e->stream, table, J.total, C, stamps); \
         }                                                                                                 \
     }
     if (fused && pow2) DWP_LAUNCH(true, true)
@@ -1022,13 +1001,13 @@ static bool dwp_usable(const mlggd_engine *e) {
     return e->dw_persist && e->Bp % 64 == 0 && (Hh == 1 || Hh == 2 || Hh == 4 || Hh == 8);
 }
 // units: 64-frame units per tile = (frames the jobs' operands hold) / 64
-static int launch_dwp(mlggd_engine *e, const DwpJobs &J, bool fused, hipStream_t st, int stamp_layer, int units = 0) {
+static int launch_dwp(mlggd_engine *e, const DwpJobs &J, bool fused, int stamp_layer, int units = 0) {
     switch (units > 0 ? units : e->Bp / 64) {
-    case 1: return launch_dwp_t<1>(e, J, fused, st, stamp_layer);
-    case 2: return launch_dwp_t<2>(e, J, fused, st, stamp_layer);
-    case 4: return launch_dwp_t<4>(e, J, fused, st, stamp_layer);
-    case 8: return launch_dwp_t<8>(e, J, fused, st, stamp_layer);
-    case 16: return launch_dwp_t<16>(e, J, fused, st, stamp_layer);
+    case 1: return launch_dwp_t<1>(e, J, fused, stamp_layer);
+    case 2: return launch_dwp_t<2>(e, J, fused, stamp_layer);
+    case 4: return launch_dwp_t<4>(e, J, fused, stamp_layer);
+    case 8: return launch_dwp_t<8>(e, J, fused, stamp_layer);
+    case 16: return launch_dwp_t<16>(e, J, fused, stamp_layer);
     default: return fail(MLGGD_ERR_STATE, "no dW kernel for %d units per tile", units);
     }
 }
@@ -1439,6 +1418,20 @@ static int run_loss(mlggd_engine *e, const Bunch &bn, float nf, float inv_n, Col
     }
 }
 
+// a 32 x 32-tile dX launch in the form PIPE (dx_dma); the stamped instantiation only when the launch was picked for stamps
+template <int PIPE, int ACT>
+static int launch_dx(mlggd_engine *e, int nwg, const DxArgs &xa, long long *st) {
+    const size_t lds = dx_lds_floats<4, PIPE>() * sizeof(float);
+    if (st) {
+        CHK(ensure_lds(e, k_dx<4, PIPE, ACT, true>, lds));
+        launch_timed(e, k_dx<4, PIPE, ACT, true>, dim3(nwg), dim3(256), lds, e->stream, xa, st);
+    } else {
+        CHK(ensure_lds(e, k_dx<4, PIPE, ACT, false>, lds));
+        launch_timed(e, k_dx<4, PIPE, ACT, false>, dim3(nwg), dim3(256), lds, e->stream, xa, st);
+    }
+    return MLGGD_OK;
+}
+
 // dEdX_{l-1} from dEdX_l and the OLD W_l (+ the derivative of layer l-1's activation): BP_GPU.cu:402,430
 static int run_dx(mlggd_engine *e, int l) {
     const int Kp = e->lsp[l - 1], b_tiles = e->Bp / 32;
@@ -1460,43 +1453,21 @@ static int run_dx(mlggd_engine *e, int l) {
         return launch_check("k_dx64");
     }
     long long *st = stamps_for(e, KC_DX, l, (Kp / 32) * b_tiles);  // k_dx64 carries no stamps: it leaves the selection alone
-#define LAUNCH_DX(NW, PIPE)                                                                                  \
-    {                                                                                                        \
-        const size_t lds = dx_lds_floats<NW, PIPE>() * sizeof(float);                                        \
-        if (relu && st) LAUNCH_DX_(NW, PIPE, ACT_RELU, true)                                                 \
-        else if (relu) LAUNCH_DX_(NW, PIPE, ACT_RELU, false)                                                 \
-        else if (st) LAUNCH_DX_(NW, PIPE, ACT_SIGMOID, true)                                                 \
-        else LAUNCH_DX_(NW, PIPE, ACT_SIGMOID, false)                                                        \
-    }
-    // the stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd)
-#define LAUNCH_DX_(NW, PIPE, ACT, STAMPED)                                                                   \
-    {                                                                                                        \
-        CHK(ensure_lds(e, k_dx<NW, PIPE, ACT, STAMPED>, lds));                                               \
-        launch_timed(e, k_dx<NW, PIPE, ACT, STAMPED>, dim3((Kp / 32) * b_tiles), dim3(64 * NW), lds, e->stream, xa, st); \
-    }
-    // PIPE 4 (default where one workgroup per CU is all there is: <= 256 workgroups): main loop software-pipelined
-    // inside the wave, operands by LDS-DMA (136 KB of LDS); 1: the same pipeline through staging registers (71 KB: two
-    // workgroups per CU for larger minibatches; MLGGD_DX_PIPE=1); 0: the round-1 loop (MLGGD_DX_PIPE=0, A/B)
-    const bool dma = e->dx_pipe == 4 && (Kp / 32) * b_tiles <= 256;
-    if (e->dx_nw == 8 && e->dx_pipe) LAUNCH_DX(8, 1)
-    else if (e->dx_nw == 8) LAUNCH_DX(8, 0)
-    else if (dma) LAUNCH_DX(4, 4)
-    else if (e->dx_pipe) LAUNCH_DX(4, 1)
-    else LAUNCH_DX(4, 0)
-#undef LAUNCH_DX
-#undef LAUNCH_DX_
+    const int nwg = (Kp / 32) * b_tiles;
+    if (dx_dma(e, Kp)) CHK((relu ? launch_dx<4, ACT_RELU>(e, nwg, xa, st) : launch_dx<4, ACT_SIGMOID>(e, nwg, xa, st)));
+    else CHK((relu ? launch_dx<1, ACT_RELU>(e, nwg, xa, st) : launch_dx<1, ACT_SIGMOID>(e, nwg, xa, st)));
     return launch_check("k_dx");
 }
 
 // the weight-gradient kernel of ONE layer (fused: with the update as its epilogue; else G_l, gb_l are written)
-static int launch_dw_layer(mlggd_engine *e, int l, const float *in_rows, bool fused, float nf, hipStream_t st) {
+static int launch_dw_layer(mlggd_engine *e, int l, const float *in_rows, bool fused, float nf) {
     const int Kp = e->lsp[l - 1], Np = e->lsp[l];
     const long tiles128 = (long)((Kp + 127) / 128) * ((Np + 127) / 128);
     const bool big = e->dw_tile == 0 ? tiles128 >= 192 : e->dw_tile == 2;
-    ProfScope ps(e, KC_DW, l, st);
-    if (dwp_usable(e)) return launch_dwp(e, dwp_jobs(e, l, l, in_rows, nf), fused, st, l);
-    if (big) return launch_dw<2>(e, l, in_rows, fused, nf, st);
-    return launch_dw<1>(e, l, in_rows, fused, nf, st);
+    ProfScope ps(e, KC_DW, l);
+    if (dwp_usable(e)) return launch_dwp(e, dwp_jobs(e, l, l, in_rows, nf), fused, l);
+    if (big) return launch_dw<2>(e, l, in_rows, fused, nf);
+    return launch_dw<1>(e, l, in_rows, fused, nf);
 }
 
 static int launch_accum(float *dst, const float *a, const float *b, size_t n, hipStream_t st) {
@@ -1586,7 +1557,7 @@ static int fake_world_prepass(mlggd_engine *e, int sample0, float nf, float inv_
             for (int l = 1; l < L; l++) CHK(put(e->dEdX[l], e->dEdXall[l], (size_t)Bp * e->lsp[l]));
         } else {
             for (int l = L - 1; l >= 1; l--) {
-                CHK(launch_dw_layer(e, l, in_rows, false, nf, e->stream));
+                CHK(launch_dw_layer(e, l, in_rows, false, nf));
                 CHK(launch_accum(e->Gpre[l], r == 0 ? nullptr : e->Gpre[l], e->G[l], (size_t)e->lsp[l - 1] * e->lsp[l], e->stream));
             }
             CHK(launch_accum(e->gbpre, r == 0 ? nullptr : e->gbpre, e->gb_all, e->gb_all_count, e->stream));
@@ -1652,12 +1623,10 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
         for (int g = 1; g < L - 1; g++) CHK(exchange_y(e, g, e->Y[g], nullptr));
         CHK(gather_end(e));
     }
-    const bool two = e->two_streams != 0;
-    hipStream_t dws = two ? e->dw_stream : e->stream;
     // single GPU: every dW(l) only needs dEdX_l and Y_{l-1}, so one persistent launch walks the
     // tiles of all layers after the last dX (the data-parallel path keeps one launch per layer so
     // that the all-reduce of layer l overlaps the rest of the backward pass)
-    const bool merged = (!dp && !two && e->dw_merge && dwp_usable(e)) || gather;
+    const bool merged = (!dp && e->dw_merge && dwp_usable(e)) || gather;
     int pending_hi = L - 1;  // gather mode: dEdX_l for l in [l .. pending_hi] are final and not yet sent
     bool mainline_done = false;  // the last factor group went out on the main stream: the dW launch needs no further event
     for (int l = L - 1; l >= 1; l--) {
@@ -1668,7 +1637,7 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
             CHK(gather_end(e));
             HIPCHK(hipEventRecord(e->ev_layer[l], e->comm_stream));
         } else if (gather && l <= 2) {  // two groups: everything down to dEdX_2 beside dX_2, dEdX_1 at the end
-            if (l == 1 && e->dp_mainline && !two) {
+            if (l == 1 && e->dp_mainline) {
                 // dEdX_1 is the one factor nothing can hide: the dW launch waits for it.  On the MAIN stream it costs
                 // its own time; by way of the communication stream it cost two event hand-offs more (30 us between
                 // dX_2 and k_dwp in the 1-rank rehearsal).  The earlier groups are awaited here, where they have
@@ -1689,19 +1658,13 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
         }
         // dX_l produces dEdX_{l-1}; if the next iteration sends it (or a group ending with it) on the communication
         // stream, the event that stream waits for rides on this launch
-        if (l != 1 && gather && !two &&
-            (fine || l - 1 == 2 || (l - 1 == 1 && !(e->dp_mainline))))
-            gather_arm(e);
+        if (l != 1 && gather && (fine || l - 1 == 2 || (l - 1 == 1 && !e->dp_mainline))) gather_arm(e);
         if (l != 1) CHK(run_dx(e, l));
-        if (two) {  // dw(l) after dX(l): dEdX_l is final and W_l has been read (old weights)
-            HIPCHK(hipEventRecord(e->ev_dx[l], e->stream));
-            HIPCHK(hipStreamWaitEvent(dws, e->ev_dx[l], 0));
-        }
         if (merged) continue;  // all layers' dW + update run as one launch after the last dX
-        if (dp && !gather && !two) arm_stop(e, e->ev_grad[l]);  // "G_l written" rides on the launch that writes it
-        CHK(launch_dw_layer(e, l, in_rows, !dp, nf, dws));
+        if (dp && !gather) arm_stop(e, e->ev_grad[l]);  // "G_l written" rides on the launch that writes it
+        CHK(launch_dw_layer(e, l, in_rows, !dp, nf));
         if (dp && !gather) {
-            if (!take_stop(e)) HIPCHK(hipEventRecord(e->ev_grad[l], dws));
+            if (!take_stop(e)) HIPCHK(hipEventRecord(e->ev_grad[l], e->stream));
             HIPCHK(hipStreamWaitEvent(e->comm_stream, e->ev_grad[l], 0));
             if (e->fake_world) {  // sum over the emulated ranks: what the all-reduce (or the union of the reduce-scatter blocks) delivers
                 if (e->world > 1) CHK(launch_accum(e->G[l], e->Gpre[l], e->G[l], (size_t)Kp * Np, e->comm_stream));
@@ -1719,7 +1682,7 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
     if (gather && e->dp_mode == 2) {
         if (!mainline_done) {
             HIPCHK(hipEventRecord(e->ev_gathered, e->comm_stream));
-            HIPCHK(hipStreamWaitEvent(dws, e->ev_gathered, 0));
+            HIPCHK(hipStreamWaitEvent(e->stream, e->ev_gathered, 0));
         }
         const int units = e->world * Bp / 64;
         if (e->fake_world) {
@@ -1734,37 +1697,36 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
                         for (int sr = 0; sr < e->world; sr++) {
                             const float *src = sr + 1 < e->world ? e->Ysrc[l][sr] : (l == 0 ? in_rows : e->Y[l]);
                             HIPCHK(hipMemcpyAsync(e->Yall[l] + (size_t)sr * cnt, src + (size_t)r * cnt, cnt * sizeof(float),
-                                                  hipMemcpyDeviceToDevice, dws));
+                                                  hipMemcpyDeviceToDevice, e->stream));
                         }
                     }
                 if (only || r == e->world - 1) {  // the bias update comes from the LAST rank's bias-only tiles
                     DwpJobs Jb = dwp_jobs_shard(e, nf, r, 1, false);
-                    if (Jb.total > 0) CHK(launch_dwp(e, Jb, true, dws, 1, units));
+                    if (Jb.total > 0) CHK(launch_dwp(e, Jb, true, 1, units));
                 }
                 DwpJobs J = dwp_jobs_shard(e, nf, r, 0, only ? true : e->world == 1);
-                ProfScope ps(e, KC_DW, 1, dws);
-                if (J.total > 0) CHK(launch_dwp(e, J, true, dws, 1, units));
+                ProfScope ps(e, KC_DW, 1);
+                if (J.total > 0) CHK(launch_dwp(e, J, true, 1, units));
             }
         } else {
             {
                 DwpJobs Jb = dwp_jobs_shard(e, nf, e->rank, 1, false);  // bias-only tiles: no W access, so they go first
-                if (Jb.total > 0) CHK(launch_dwp(e, Jb, true, dws, 1, units));
-                ProfScope ps(e, KC_DW, 1, dws);
+                if (Jb.total > 0) CHK(launch_dwp(e, Jb, true, 1, units));
+                ProfScope ps(e, KC_DW, 1);
                 DwpJobs J = dwp_jobs_shard(e, nf, e->rank, 0, true);
-                if (!two) arm_stop(e, e->ev_dw_done);  // the event the W gathers wait for rides on this launch
-                if (J.total > 0) CHK(launch_dwp(e, J, true, dws, 1, units));
+                arm_stop(e, e->ev_dw_done);  // the event the W gathers wait for rides on this launch
+                if (J.total > 0) CHK(launch_dwp(e, J, true, 1, units));
             }
             const bool dw_done_attached = take_stop(e);
             // W_1 is what the next forward pass waits for first: its all-gather goes on the MAIN stream, right behind
             // the update (no hand-off to the communication stream and back: 21 us between k_dwp and forward_1 in the
             // 1-rank rehearsal); the upper layers' blocks travel on the communication stream beside forward_1
-            const bool w1_main = e->dp_mainline && !two;
-            if (!dw_done_attached) HIPCHK(hipEventRecord(e->ev_dw_done, dws));
+            if (!dw_done_attached) HIPCHK(hipEventRecord(e->ev_dw_done, e->stream));
             HIPCHK(hipStreamWaitEvent(e->comm_stream, e->ev_dw_done, 0));
             e->comm_after_dw = true;
             for (int l = 1; l < L; l++) {  // layer 1 first: the next forward pass needs it first
                 const size_t count = (size_t)e->shard_rows[l] * 64 * e->lsp[l];
-                hipStream_t st = (l == 1 && w1_main) ? e->stream : e->comm_stream;
+                hipStream_t st = (l == 1 && e->dp_mainline) ? e->stream : e->comm_stream;
                 NCCLCHK(g_rccl.AllGather(e->W[l] + (size_t)e->rank * count, e->W[l], count, 7, e->comm, st));
                 if (st == e->comm_stream) {
                     HIPCHK(hipEventRecord(e->ev_W[l], e->comm_stream));
@@ -1777,23 +1739,23 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
         // the old W_2), layer 1 when dEdX_1 has
         const int units = e->world * Bp / 64;
         if (L - 1 >= 2) {
-            HIPCHK(hipStreamWaitEvent(dws, e->ev_layer[2], 0));
-            ProfScope ps(e, KC_DW, L - 1, dws);
-            CHK(launch_dwp(e, dwp_jobs_global(e, nf, L - 1, 2), true, dws, L - 1, units));
+            HIPCHK(hipStreamWaitEvent(e->stream, e->ev_layer[2], 0));
+            ProfScope ps(e, KC_DW, L - 1);
+            CHK(launch_dwp(e, dwp_jobs_global(e, nf, L - 1, 2), true, L - 1, units));
         }
-        HIPCHK(hipStreamWaitEvent(dws, e->ev_layer[1], 0));
-        ProfScope ps(e, KC_DW, 1, dws);
-        CHK(launch_dwp(e, dwp_jobs_global(e, nf, 1, 1), true, dws, 1, units));
+        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_layer[1], 0));
+        ProfScope ps(e, KC_DW, 1);
+        CHK(launch_dwp(e, dwp_jobs_global(e, nf, 1, 1), true, 1, units));
     } else if (gather) {
         if (!mainline_done) {
             HIPCHK(hipEventRecord(e->ev_gathered, e->comm_stream));
-            HIPCHK(hipStreamWaitEvent(dws, e->ev_gathered, 0));
+            HIPCHK(hipStreamWaitEvent(e->stream, e->ev_gathered, 0));
         }
-        ProfScope ps(e, KC_DW, 1, dws);
-        CHK(launch_dwp(e, dwp_jobs_global(e, nf, L - 1, 1), true, dws, 1, e->world * Bp / 64));
+        ProfScope ps(e, KC_DW, 1);
+        CHK(launch_dwp(e, dwp_jobs_global(e, nf, L - 1, 1), true, 1, e->world * Bp / 64));
     } else if (merged) {
-        ProfScope ps(e, KC_DW, 1, dws);
-        CHK(launch_dwp(e, dwp_jobs(e, L - 1, 1, in_rows, nf), true, dws, 1));
+        ProfScope ps(e, KC_DW, 1);
+        CHK(launch_dwp(e, dwp_jobs(e, L - 1, 1, in_rows, nf), true, 1));
     }
     if (dp && !gather) {
         // bias gradients were written by the dw kernels; ev_grad[1] is the last of them
@@ -1805,8 +1767,8 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
         }
         HIPCHK(hipEventRecord(e->ev_bias_red, e->comm_stream));
         for (int l = L - 1; l >= 1; l--) {
-            HIPCHK(hipStreamWaitEvent(dws, e->ev_red[l], 0));
-            ProfScope ps(e, KC_UPDATE, l, dws);
+            HIPCHK(hipStreamWaitEvent(e->stream, e->ev_red[l], 0));
+            ProfScope ps(e, KC_UPDATE, l);
             const int Kp = e->lsp[l - 1], Np = e->lsp[l];
             // kernUpdatedelta + kernAccSum (DevFunc.cu:490-507,427-443) on the rows [row0, row0 + rows) of W_l: the
             // whole matrix (MLGGD_DP_AR_SHARD=0), or the block of weight rows this rank received the summed gradient
@@ -1822,27 +1784,26 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
                 if (row1 <= row0) continue;  // a block that lies entirely in the pad rows
                 const size_t off = (size_t)row0 * Np, n4 = (size_t)(row1 - row0) * Np / 4;
                 const size_t blocks = (n4 + 255) / 256;
-                hipLaunchKernelGGL(k_apply_update, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, dws,
+                hipLaunchKernelGGL(k_apply_update, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, e->stream,
                                    e->W[l] + off, e->dW[l] + off, e->G[l] + off, n4, nf, e->cfg.momentum, e->cfg.lrate,
                                    e->cfg.weightcost);
                 CHK(launch_check("k_apply_update"));
             }
         }
-        HIPCHK(hipStreamWaitEvent(dws, e->ev_bias_red, 0));
+        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_bias_red, 0));
         BiasJobs jobs = make_bias_jobs(e);
-        hipLaunchKernelGGL(k_bias_apply, dim3((jobs.total + 255) / 256), dim3(256), 0, dws, jobs, nf,
+        hipLaunchKernelGGL(k_bias_apply, dim3((jobs.total + 255) / 256), dim3(256), 0, e->stream, jobs, nf,
                            e->cfg.momentum, e->cfg.lrate);
         CHK(launch_check("k_bias_apply"));
         if (e->ar_shard && !e->fake_world) {
             // the updated W blocks travel back: all-gather in place, layer 1 first and -- like the sharded factor
             // mode -- on the MAIN stream (the next forward pass waits for it first; no hand-off to the communication
             // stream and back), the upper layers on the communication stream beside forward_1, each with its event
-            const bool w1_main = e->dp_mainline && !two;
-            HIPCHK(hipEventRecord(e->ev_dw_done, dws));
+            HIPCHK(hipEventRecord(e->ev_dw_done, e->stream));
             HIPCHK(hipStreamWaitEvent(e->comm_stream, e->ev_dw_done, 0));
             for (int l = 1; l < L; l++) {
                 const size_t count = (size_t)e->shard_rows[l] * 64 * e->lsp[l];
-                hipStream_t st = (l == 1 && w1_main) ? e->stream : e->comm_stream;
+                hipStream_t st = (l == 1 && e->dp_mainline) ? e->stream : e->comm_stream;
                 NCCLCHK(g_rccl.AllGather(e->W[l] + (size_t)e->rank * count, e->W[l], count, 7, e->comm, st));
                 if (st == e->comm_stream) {
                     HIPCHK(hipEventRecord(e->ev_W[l], e->comm_stream));
@@ -1850,10 +1811,6 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
                 }
             }
         }
-    }
-    if (two) {  // the next forward pass (and any host read-back on the main stream) waits for the updates
-        HIPCHK(hipEventRecord(e->ev_upd, dws));
-        HIPCHK(hipStreamWaitEvent(e->stream, e->ev_upd, 0));
     }
     e->step_counter++;
     return MLGGD_OK;
@@ -1921,13 +1878,8 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
     e->Dp = e->lsp[e->L - 1];
     e->nat_frames = cfg->nat_frames;
     e->mask_bins = cfg->mask_bins;
-    if (const char *v = getenv("MLGGD_FWD_NW")) e->fwd_nw = atoi(v);
     if (const char *v = getenv("MLGGD_WAVES_LOOKUP")) e->ww.lookup_table = !strcmp(v, "table");
-    if (const char *v = getenv("MLGGD_DX_NW")) e->dx_nw = atoi(v);
-    if (const char *v = getenv("MLGGD_FWD_PIPE")) e->fwd_pipe = atoi(v);
-    if (const char *v = getenv("MLGGD_DX_PIPE")) e->dx_pipe = atoi(v);
     if (const char *v = getenv("MLGGD_DW_TILE")) e->dw_tile = atoi(v);
-    if (const char *v = getenv("MLGGD_TWO_STREAMS")) e->two_streams = atoi(v);
     if (const char *v = getenv("MLGGD_DW_PERSIST")) e->dw_persist = atoi(v);
     if (const char *v = getenv("MLGGD_DWP_PER_CU")) e->dwp_per_cu = atoi(v);
     if (const char *v = getenv("MLGGD_DW_MERGE")) e->dw_merge = atoi(v);
@@ -1945,13 +1897,10 @@ int mlggd_create(const mlggd_config *cfg, const float *const *weights, const flo
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus > 0) e->n_cus = cus;
     }
     HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    // (the second compute stream only exists when MLGGD_TWO_STREAMS asks for it: every HIP stream takes one of the
-    // process's few hardware queues, and two streams of one engine that land on the SAME queue serialise -- round 3:
-    // the first communicator engine created after other engines had come and gone ran its step in 251 instead of
-    // 173 us because its communication stream shared a queue with its main stream)
-    if (e->two_streams) HIPCHK(hipStreamCreateWithFlags(&e->dw_stream, hipStreamNonBlocking));
-    for (int l = 0; l < e->L; l++) HIPCHK(hipEventCreateWithFlags(&e->ev_dx[l], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&e->ev_upd, hipEventDisableTiming));
+    // (one compute stream: every HIP stream takes one of the process's few hardware queues, and two streams of one engine
+    // that land on the SAME queue serialise -- round 3: the first communicator engine created after other engines had
+    // come and gone ran its step in 251 instead of 173 us because its communication stream shared a queue with its main
+    // stream)
     HIPCHK(hipEventCreate(&e->ev_t0));
     HIPCHK(hipEventCreate(&e->ev_t1));
 
@@ -2009,7 +1958,6 @@ int mlggd_destroy(mlggd_handle e) {
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->comm_stream) hipStreamSynchronize(e->comm_stream);
-    if (e->dw_stream) hipStreamSynchronize(e->dw_stream);
     if (e->stat_comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->stat_comm);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
     for (void *p : e->allocs) hipFree(p);
@@ -2034,10 +1982,6 @@ int mlggd_destroy(mlggd_handle e) {
     if (e->ev_t0) hipEventDestroy(e->ev_t0);
     if (e->ev_t1) hipEventDestroy(e->ev_t1);
     if (e->comm_stream) hipStreamDestroy(e->comm_stream);
-    for (int l = 0; l < MLGGD_MAXLAYER; l++)
-        if (e->ev_dx[l]) hipEventDestroy(e->ev_dx[l]);
-    if (e->ev_upd) hipEventDestroy(e->ev_upd);
-    if (e->dw_stream) hipStreamDestroy(e->dw_stream);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;  // every DevBuf frees itself here: all streams have been synchronised above
     return MLGGD_OK;
@@ -2615,7 +2559,6 @@ int mlggd_sync(mlggd_handle e) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (e->dw_stream) HIPCHK(hipStreamSynchronize(e->dw_stream));
     if (e->comm_stream) HIPCHK(hipStreamSynchronize(e->comm_stream));
     return MLGGD_OK;
 }
@@ -3458,8 +3401,8 @@ int mlggd_debug_buffers(mlggd_handle e, int64_t *allocations, int64_t *bytes) {
 int mlggd_debug_gemm_plan(mlggd_handle e, int layer, int *fwd_waves, int *dx_waves) {
     if (!e || !fwd_waves || !dx_waves) return fail(MLGGD_ERR_ARG, "NULL argument");
     if (layer < 1 || layer >= e->L) return fail(MLGGD_ERR_ARG, "layer %d not in 1..%d", layer, e->L - 1);
-    *fwd_waves = fwd64_used(e, layer) ? 1 : e->fwd_nw;  // (the output layer's 4 waves x out_slabs otherwise)
-    *dx_waves = dx64_used(e, layer) ? 1 : e->dx_nw;
+    *fwd_waves = fwd64_used(e, layer) ? 1 : 4;  // (the output layer's 4 waves x out_slabs otherwise)
+    *dx_waves = dx64_used(e, layer) ? 1 : 4;
     return MLGGD_OK;
 }
 int mlggd_debug_out_slabs(mlggd_handle e, int *slabs) {
@@ -3614,7 +3557,7 @@ int mlggd_profile_overhead(mlggd_handle e, float *usec) {
 int mlggd_dw_launches_per_step(mlggd_handle e, int *launches) {
     if (!e || !launches) return fail(MLGGD_ERR_ARG, "NULL argument");
     const bool dp = e->comm != nullptr || e->fake_world;
-    const bool merged = (!dp && !e->two_streams && e->dw_merge && dwp_usable(e)) || (dp && e->dp_mode >= 1);
+    const bool merged = (!dp && e->dw_merge && dwp_usable(e)) || (dp && e->dp_mode >= 1);
     const bool fine = dp && e->dp_mode == 1 && e->dp_fine != 0 && e->L - 1 >= 2;
     *launches = fine ? 2 : merged ? 1 : e->L - 1;
     return MLGGD_OK;

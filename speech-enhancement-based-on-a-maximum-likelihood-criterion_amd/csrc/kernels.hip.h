@@ -286,18 +286,23 @@ __device__ __forceinline__ size_t y_blocked_base(int u0, int yblk, int Bp) {
     const int blk = (int)((unsigned)u0 / (unsigned)yblk);
     return (size_t)blk * Bp * yblk + (u0 - blk * yblk);
 }
-// LDS floats needed by fwd_body<.,NW>: staging/reduction tiles + the 32x33 transposition tile
-// staging / reduction tiles (two 8 KB tiles per wave in the LDS-DMA form, PIPE 4; one otherwise) + the 32x36 transposition tile
-template <int NW, int PIPE> constexpr int fwd_lds_floats() { return NW * (PIPE == 4 ? 4096 : 2048) + 32 * 36; }
+// LDS floats needed by fwd_body: staging / reduction tiles (two 8 KB tiles per wave) + the 32x36 transposition tile.
+// One form is left -- 4 waves, main loop pipelined inside the wave with operands by LDS-DMA (PIPE 4) -- and the
+// parameter lists are kept as they were, so that the kernels keep their names.
+template <int NW, int PIPE> constexpr int fwd_lds_floats() {
+    static_assert(NW == 4 && PIPE == 4, "the forward kernels have one form");
+    return NW * 4096 + 32 * 36;
+}
 
 template <int MODE, int NW, int PIPE = 1>
 __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float *smem, long long *stamps) {
+    static_assert(NW == 4 && PIPE == 4, "the forward kernels have one form");
     const float *__restrict__ W = A.W, *__restrict__ Yt_in = A.Yt_in, *__restrict__ bias = A.bias;
     float *__restrict__ Yt_out = A.Yt_out, *__restrict__ Y_out = A.Y_out, *__restrict__ slab = A.slab;
     const int Kp = A.Kp, Np = A.Np, Bp = A.Bp, N = A.N, n_tiles = A.n_tiles, b_tiles = A.b_tiles, S = A.S;
-    // per wave: [32 k rows][32] of W then [32 k rows][32] of Yt (8 KB); the cross-wave
+    // per wave: two tiles of [32 k rows][32] of W then [32 k rows][32] of Yt (8 KB each); the cross-wave
     // reduction buffer red[NW][1024] aliases the same storage after the main loop
-    float(*tileT)[36] = reinterpret_cast<float(*)[36]>(smem + NW * (PIPE == 4 ? 4096 : 2048));
+    float(*tileT)[36] = reinterpret_cast<float(*)[36]>(smem + NW * 4096);
     stamp(stamps, 0, bid);
     stamp_clk(stamps, 4, bid);
     const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
@@ -333,9 +338,6 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
     const rsrc_t rW = make_rsrc(W, (size_t)Kp * Np * 4), rY = make_rsrc(Yt_in, (size_t)Kp * Bp * 4);
     const int r8 = lane >> 3, c4 = lane & 7;
     const int voW = (r8 * Np + n0 + 4 * c4) * 4, voY = (r8 * Bp + b0 + 4 * c4) * 4;
-    float *stg = smem + wave * 2048;
-    float *wdst = stg + r8 * 32 + 4 * c4;
-    const float *ard = stg + h * 32 + i, *brd = stg + 1024 + h * 32 + i;
 
     f32x16 acc;
 #pragma unroll
@@ -347,15 +349,17 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
     // reduction).  The empty asm with a "memory" clobber is a compiler-level fence the loads cannot be sunk across;
     // it does not use their values, so nothing waits for them until the epilogue does.  (A/B in one process: dX -0.2 ..
     // -0.3 us per launch, forward within noise: the loads hit L2.)
+    // (bias_pre fed the epilogue of the 8- and 16-wave forms and nothing reads it since they went.  The statements
+    // stayed so that retiring those forms moved no instruction: without them the compiler numbers two address registers
+    // of every k_fwd the other way round, profiles/retired_arms_isa.txt.  A change that moves k_fwd's text anyway
+    // can drop them.)
     constexpr int NT_ = 64 * NW, EPT_ = 1024 / NT_ > 0 ? 1024 / NT_ : 1;
-    static_assert(1024 % NT_ == 0, "every thread owns EPT_ whole output elements");
     float bias_pre[EPT_];
 #pragma unroll
     for (int q = 0; q < EPT_; q++) bias_pre[q] = MODE != FWD_SLAB ? bias[n0 + ((tid + NT_ * q) >> 5)] : 0.0f;
-    const float bias_row = (MODE != FWD_SLAB && NW == 4) ? bias[n0 + (tid >> 3)] : 0.0f;  // 4-wave epilogue
+    const float bias_row = MODE != FWD_SLAB ? bias[n0 + (tid >> 3)] : 0.0f;  // a thread owns 4 frames of one unit
     asm volatile("" ::: "memory");
 
-    if constexpr (PIPE == 4) {
     // LDS-DMA form of the pipelined loop: a chunk goes global -> LDS directly (buffer_load ... lds, one wave-load = 8
     // rows of 128 B = 1 KB of the row-major tile), no staging registers, no ds_write.  Two tiles per wave: while the
     // MFMAs of chunk c run on registers, chunk c+2 is requested into the tile chunk c was read from (groups 0..3) and
@@ -431,149 +435,6 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
 #undef FWD_RD4
 #undef FWD_BODYD
 #undef FWD_DRAIND
-    } else
-    if constexpr (PIPE == 0) {
-    float4 wa[4], ya[4], wb[4], yb[4];
-    // rows past Kp are range-checked zeros; rows past this wave's range are only ever
-    // multiplied under the npairs guard of the drain
-#define FWD_LOAD(WR, YR, C)                                                        \
-    {                                                                              \
-        const int row0 = 2 * (p0 + 16 * (C));                                      \
-        _Pragma("unroll") for (int q = 0; q < 4; q++) {                            \
-            WR[q] = bload4(rW, voW, (row0 + 8 * q) * Np * 4);                      \
-            YR[q] = bload4(rY, voY, (row0 + 8 * q) * Bp * 4);                      \
-        }                                                                          \
-    }
-#define FWD_WRITE(WR, YR)                                                          \
-    {                                                                              \
-        _Pragma("unroll") for (int q = 0; q < 4; q++) {                            \
-            *reinterpret_cast<float4 *>(wdst + q * 256) = WR[q];                   \
-            *reinterpret_cast<float4 *>(wdst + 1024 + q * 256) = YR[q];            \
-        }                                                                          \
-        __builtin_amdgcn_wave_barrier();                                           \
-    }
-#define FWD_COMPUTE(CNT)                                                           \
-    {                                                                              \
-        _Pragma("unroll") for (int u = 0; u < 16; u++) {                           \
-            if (u < (CNT)) acc = mfma32(ard[u * 64], brd[u * 64], acc);            \
-        }                                                                          \
-        __builtin_amdgcn_wave_barrier();                                           \
-    }
-    if (nch > 0) {
-        FWD_LOAD(wa, ya, 0);
-        FWD_LOAD(wb, yb, 1);
-        int c = 0;
-        for (; c + 2 < nch; c += 2) {  // steady state: chunks c, c+1 are full; loads unconditional
-            FWD_WRITE(wa, ya);
-            FWD_LOAD(wa, ya, c + 2);
-            FWD_COMPUTE(16);
-            FWD_WRITE(wb, yb);
-            FWD_LOAD(wb, yb, c + 3);
-            FWD_COMPUTE(16);
-        }
-        FWD_WRITE(wa, ya);
-        FWD_COMPUTE(npairs - 16 * c);
-        if (c + 1 < nch) {
-            FWD_WRITE(wb, yb);
-            FWD_COMPUTE(npairs - 16 * (c + 1));
-        }
-    }
-#undef FWD_LOAD
-#undef FWD_WRITE
-#undef FWD_COMPUTE
-    } else {
-    // Main loop, software-pipelined INSIDE the wave (round 2; before, a wave went global -> registers -> LDS ->
-    // fragments -> 16 MFMAs chunk after chunk and issued no MFMA for ~500 cycles at every chunk boundary; the SIMD's
-    // other wave filled those gaps only until the older wave of the pair had finished -- the arbiter prefers it --
-    // and then ran alone at two thirds of the pipe: per-wave stamps showed wave 0 done at 8.4 us and waves 4..7
-    // at 11.7 us of a launch whose MFMA time is 8.0 us).  Now the 16 MFMAs of chunk c run on fragments that are
-    // already in registers, and in their shadow the wave stores chunk c+1 (registers, loaded 1.5 chunks earlier)
-    // to its LDS tile, reads ALL of its fragments back, and refills those registers with chunk c+3: two MFMAs
-    // per group, the other instructions pinned to their group by sched_barrier.  LDS operations of one wave
-    // complete in order, the tile is wave-private: no barrier, no wait between the stores and the reads.
-    // Same MFMA order as before: same bits.
-    float4 wa[4], ya[4], wb[4], yb[4];
-    float fa[16], fb[16], ga[16], gb[16];
-    // rows past Kp are range-checked zeros; rows past this wave's range are only ever
-    // multiplied under the npairs guard of the drain
-    // A chunk past this wave's last one is "loaded" from the end of the buffer: out of range for the resource, so it
-    // returns zeros without a memory request (the pipelined body prefetches three chunks ahead unconditionally --
-    // a branch would split its basic block -- and those three would otherwise be the NEXT wave's rows: +37 % traffic)
-    const int endW = Kp * Np * 4, endY = Kp * Bp * 4;
-#define FWD_LOAD1(WR, YR, C, Q)                                                    \
-    {                                                                              \
-        const int row0 = 2 * (p0 + 16 * (C));                                      \
-        const bool live = (C) < nch;                                               \
-        WR[Q] = bload4(rW, voW, live ? (row0 + 8 * (Q)) * Np * 4 : endW);          \
-        YR[Q] = bload4(rY, voY, live ? (row0 + 8 * (Q)) * Bp * 4 : endY);          \
-    }
-#define FWD_WRITE1(WR, YR, Q)                                                      \
-    {                                                                              \
-        *reinterpret_cast<float4 *>(wdst + (Q) * 256) = WR[Q];                     \
-        *reinterpret_cast<float4 *>(wdst + 1024 + (Q) * 256) = YR[Q];              \
-    }
-#define FWD_READ4(NA, NB, Q)                                                       \
-    {                                                                              \
-        _Pragma("unroll") for (int u = 4 * (Q); u < 4 * (Q) + 4; u++) {            \
-            NA[u] = ard[u * 64];                                                   \
-            NB[u] = brd[u * 64];                                                   \
-        }                                                                          \
-    }
-    // chunk C on fragments (FA, FB); chunk C+1 sits in registers (WR, YR) -> LDS -> fragments (NA, NB); (WR, YR)
-    // are then refilled with chunk C+3
-#define FWD_BODY(FA, FB, NA, NB, WR, YR, C)                                        \
-    {                                                                              \
-        _Pragma("unroll") for (int g = 0; g < 4; g++) {                            \
-            acc = mfma32(FA[2 * g], FB[2 * g], acc);                               \
-            acc = mfma32(FA[2 * g + 1], FB[2 * g + 1], acc);                       \
-            FWD_WRITE1(WR, YR, g);                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                     \
-        }                                                                          \
-        _Pragma("unroll") for (int g = 4; g < 8; g++) {                            \
-            acc = mfma32(FA[2 * g], FB[2 * g], acc);                               \
-            acc = mfma32(FA[2 * g + 1], FB[2 * g + 1], acc);                       \
-            FWD_READ4(NA, NB, g - 4);                                              \
-            FWD_LOAD1(WR, YR, (C) + 3, g - 4);                                     \
-            __builtin_amdgcn_sched_barrier(0);                                     \
-        }                                                                          \
-    }
-#define FWD_DRAIN(FA, FB, CNT)                                                     \
-    {                                                                              \
-        _Pragma("unroll") for (int u = 0; u < 16; u++) {                           \
-            if (u < (CNT)) acc = mfma32(FA[u], FB[u], acc);                        \
-        }                                                                          \
-    }
-    if (nch > 0) {
-        const int nfull = npairs >> 4, rem = npairs & 15;
-#pragma unroll
-        for (int q = 0; q < 4; q++) FWD_LOAD1(wa, ya, 0, q);
-#pragma unroll
-        for (int q = 0; q < 4; q++) FWD_LOAD1(wb, yb, 1, q);
-#pragma unroll
-        for (int q = 0; q < 4; q++) FWD_WRITE1(wa, ya, q);
-#pragma unroll
-        for (int q = 0; q < 4; q++) FWD_READ4(fa, fb, q);
-#pragma unroll
-        for (int q = 0; q < 4; q++) FWD_LOAD1(wa, ya, 2, q);
-        __builtin_amdgcn_sched_barrier(0);
-        int c = 0;
-        for (; c + 1 < nfull; c += 2) {
-            FWD_BODY(fa, fb, ga, gb, wb, yb, c);
-            FWD_BODY(ga, gb, fa, fb, wa, ya, c + 1);
-        }
-        if (c < nfull) {
-            FWD_BODY(fa, fb, ga, gb, wb, yb, c);
-            FWD_DRAIN(ga, gb, rem);
-        } else {
-            FWD_DRAIN(fa, fb, rem);
-        }
-    }
-#undef FWD_LOAD1
-#undef FWD_WRITE1
-#undef FWD_READ4
-#undef FWD_BODY
-#undef FWD_DRAIN
-    }
 
     stamp(stamps, 1, bid);
     // cross-wave reduction through LDS (aliases the staging tiles: wait for every wave)
@@ -583,79 +444,34 @@ __device__ __forceinline__ void fwd_body(const FwdArgs &A, const int bid, float 
     for (int r = 0; r < 16; r++) red[wave][acc_row(r, lane) * 32 + i] = acc[r];
     __syncthreads();
     stamp(stamps, 2, bid);
-    if constexpr (NW == 4) {
-        // 256 threads: a thread owns 4 consecutive frames of one unit.  The four partial tiles come in with one
-        // ds_read_b128 each (added in wave order, as below), both output layouts leave as 16-byte stores
-        // (11 LDS / memory instructions per thread instead of 32)
-        const int row = tid >> 3, col4 = (tid & 7) * 4;
-        float4 v4 = *reinterpret_cast<const float4 *>(&red[0][row * 32 + col4]);
+    // 256 threads: a thread owns 4 consecutive frames of one unit.  The four partial tiles come in with one
+    // ds_read_b128 each (added in wave order: deterministic), both output layouts leave as 16-byte stores
+    // (11 LDS / memory instructions per thread instead of 32)
+    const int row = tid >> 3, col4 = (tid & 7) * 4;
+    float4 v4 = *reinterpret_cast<const float4 *>(&red[0][row * 32 + col4]);
 #pragma unroll
-        for (int w = 1; w < NW; w++) {
-            const float4 p4 = *reinterpret_cast<const float4 *>(&red[w][row * 32 + col4]);
-            v4.x += p4.x;
-            v4.y += p4.y;
-            v4.z += p4.z;
-            v4.w += p4.w;
-        }
-        if (MODE == FWD_SLAB) {
-            *reinterpret_cast<float4 *>(&slab[((size_t)s * Np + n0 + row) * Bp + b0 + col4]) = v4;
-        } else {
-            const int n = n0 + row;
-            const float4 y4 = MODE == FWD_RELU ? relu4(v4, bias_row, n < N) : sigmoid_det4(v4, bias_row, n < N);  // kernSigmoid, DevFunc.cu:48
-            *reinterpret_cast<float4 *>(&Yt_out[(size_t)n * Bp + b0 + col4]) = y4;
-            tileT[col4][row] = y4.x;
-            tileT[col4 + 1][row] = y4.y;
-            tileT[col4 + 2][row] = y4.z;
-            tileT[col4 + 3][row] = y4.w;
-            __syncthreads();
-            // thread -> frame row, 4 consecutive units
-            const size_t yo = A.yblk ? y_blocked_base(n0, A.yblk, Bp) + (size_t)(b0 + row) * A.yblk + col4
-                                     : (size_t)(b0 + row) * Np + n0 + col4;
-            *reinterpret_cast<float4 *>(&Y_out[yo]) = *reinterpret_cast<const float4 *>(&tileT[row][col4]);
-        }
-        stamp(stamps, 3, bid);
-        stamp_clk(stamps, 6, bid);
-        return;
-    }
-    // 1024 tile elements over 64*NW threads; partial sums added in wave order (deterministic)
-    constexpr int NT = 64 * NW, EPT = 1024 / NT > 0 ? 1024 / NT : 1;
-    float v[EPT];
-#pragma unroll
-    for (int q = 0; q < EPT; q++) {
-        const int e = tid + NT * q;
-        float sum = 0.0f;
-        if (e < 1024) {
-            sum = red[0][e];
-#pragma unroll
-            for (int w = 1; w < NW; w++) sum += red[w][e];
-        }
-        v[q] = sum;
+    for (int w = 1; w < NW; w++) {
+        const float4 p4 = *reinterpret_cast<const float4 *>(&red[w][row * 32 + col4]);
+        v4.x += p4.x;
+        v4.y += p4.y;
+        v4.z += p4.z;
+        v4.w += p4.w;
     }
     if (MODE == FWD_SLAB) {
-#pragma unroll
-        for (int q = 0; q < EPT; q++) {
-            const int e = tid + NT * q, row = e >> 5, col = e & 31;
-            if (e < 1024) slab[((size_t)s * Np + n0 + row) * Bp + b0 + col] = v[q];
-        }
+        *reinterpret_cast<float4 *>(&slab[((size_t)s * Np + n0 + row) * Bp + b0 + col4]) = v4;
     } else {
-#pragma unroll
-        for (int q = 0; q < EPT; q++) {
-            const int e = tid + NT * q, row = e >> 5, col = e & 31;
-            if (e < 1024) {
-                const int n = n0 + row;
-                const float x = v[q] + bias_pre[q];
-                const float y = (n < N) ? (MODE == FWD_RELU ? relu_det(x) : sigmoid_det(x)) : 0.0f;  // kernSigmoid, DevFunc.cu:48
-                Yt_out[(size_t)n * Bp + b0 + col] = y;
-                tileT[col][row] = y;
-            }
-        }
+        const int n = n0 + row;
+        const float4 y4 = MODE == FWD_RELU ? relu4(v4, bias_row, n < N) : sigmoid_det4(v4, bias_row, n < N);  // kernSigmoid, DevFunc.cu:48
+        *reinterpret_cast<float4 *>(&Yt_out[(size_t)n * Bp + b0 + col4]) = y4;
+        tileT[col4][row] = y4.x;
+        tileT[col4 + 1][row] = y4.y;
+        tileT[col4 + 2][row] = y4.z;
+        tileT[col4 + 3][row] = y4.w;
         __syncthreads();
-#pragma unroll
-        for (int q = 0; q < EPT; q++) {
-            const int e = tid + NT * q, bl = e >> 5, nl = e & 31;
-            if (e < 1024)
-                Y_out[A.yblk ? y_blocked_base(n0, A.yblk, Bp) + (size_t)(b0 + bl) * A.yblk + nl : (size_t)(b0 + bl) * Np + n0 + nl] = tileT[bl][nl];
-        }
+        // thread -> frame row, 4 consecutive units
+        const size_t yo = A.yblk ? y_blocked_base(n0, A.yblk, Bp) + (size_t)(b0 + row) * A.yblk + col4
+                                 : (size_t)(b0 + row) * Np + n0 + col4;
+        *reinterpret_cast<float4 *>(&Y_out[yo]) = *reinterpret_cast<const float4 *>(&tileT[row][col4]);
     }
     stamp(stamps, 3, bid);
     stamp_clk(stamps, 6, bid);
@@ -678,11 +494,18 @@ struct DxArgs {
     float *dEdXt_prev, *dEdX_prev;
     int Kp, Np, Bp, k_tiles, b_tiles, map, b_shift;
 };
-// per wave: W piece [32][66] + dEdXt piece [64][32]; LDS-DMA form (PIPE 4): two sets of two unpadded 8 KB tiles
-template <int NW, int PIPE> constexpr int dx_lds_floats() { return NW * (PIPE == 4 ? 8192 : 32 * DX_LDW + 2048) + 32 * 36; }
+// per wave: W piece [32][66] + dEdXt piece [64][32]; LDS-DMA form (PIPE 4): two sets of two unpadded 8 KB tiles.
+// Two forms are left, both 4 waves with the main loop pipelined inside the wave: operands by LDS-DMA (PIPE 4) or through
+// staging registers (PIPE 1); the host picks one from the shape (engine.hip dx_dma).  The parameter lists are kept as
+// they were, so that the kernels keep their names.
+template <int NW, int PIPE> constexpr int dx_lds_floats() {
+    static_assert(NW == 4 && (PIPE == 4 || PIPE == 1), "the dX kernels have two forms");
+    return NW * (PIPE == 4 ? 8192 : 32 * DX_LDW + 2048) + 32 * 36;
+}
 
 template <int NW, int PIPE = 1, int ACT = ACT_SIGMOID>
 __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *smem, long long *stamps) {
+    static_assert(NW == 4 && (PIPE == 4 || PIPE == 1), "the dX kernels have two forms");
     const float *__restrict__ W = A.W, *__restrict__ dEdXt = A.dEdXt, *__restrict__ Yt_prev = A.Yt_prev;
     float *__restrict__ dEdXt_prev = A.dEdXt_prev, *__restrict__ dEdX_prev = A.dEdX_prev;
     const int Kp = A.Kp, Np = A.Np, Bp = A.Bp, k_tiles = A.k_tiles, b_tiles = A.b_tiles;
@@ -730,21 +553,11 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
 
     // the epilogue's global operand (y of this thread's output elements, for the sigmoid derivative) is fetched now,
     // above a compiler-level fence, not behind the last barrier (see fwd_body)
-    constexpr int NT_ = 64 * NW, EPT_ = 1024 / NT_ > 0 ? 1024 / NT_ : 1;
-    static_assert(1024 % NT_ == 0, "every thread owns EPT_ whole output elements");
-    float y_pre[EPT_];
-    float4 y_pre4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // 4-wave epilogue: 4 consecutive frames of one unit
+    float4 y_pre4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // a thread owns 4 consecutive frames of one unit
     if constexpr (ACT == ACT_VIS_LINEAR || ACT == ACT_VIS_SIGMOID) {
-        static_assert(NW == 4, "the RBM down-pass has the 4-wave epilogue only");
         y_pre4.x = Yt_prev[k0 + (tid >> 3)];  // the visible bias c [Kp] of this thread's unit (rbm.hip.h)
-    } else if constexpr (NW == 4) {
-        y_pre4 = *reinterpret_cast<const float4 *>(&Yt_prev[(size_t)(k0 + (tid >> 3)) * Bp + b0 + (tid & 7) * 4]);
     } else {
-#pragma unroll
-        for (int q = 0; q < EPT_; q++) {
-            const int e_ = tid + NT_ * q;
-            y_pre[q] = Yt_prev[(size_t)(k0 + (e_ >> 5)) * Bp + b0 + (e_ & 31)];
-        }
+        y_pre4 = *reinterpret_cast<const float4 *>(&Yt_prev[(size_t)(k0 + (tid >> 3)) * Bp + b0 + (tid & 7) * 4]);
     }
     asm volatile("" ::: "memory");
 
@@ -838,62 +651,6 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
 #undef DX_RD1
 #undef DX_BODYD
 #undef DX_DRAIND
-    } else
-    if constexpr (PIPE == 0) {
-    float4 wa[8], da[8], wv[8], dv[8];
-    // Quads past this wave's range read valid or range-checked-zero data and are only ever
-    // multiplied under the count guard of the drain.
-#define DX_LOAD(WR, DR, C)                                                                 \
-    {                                                                                      \
-        const int quad0 = q0 + (C)*16;                                                     \
-        _Pragma("unroll") for (int it = 0; it < 8; it++) {                                 \
-            WR[it] = bload4(rW, voW, quad0 * 16 + it * (16 * Np));                         \
-            DR[it] = bload4(rD, voD, (4 * quad0 + 8 * it) * Bp * 4);                       \
-        }                                                                                  \
-    }
-#define DX_WRITE(WR, DR)                                                                   \
-    {                                                                                      \
-        _Pragma("unroll") for (int it = 0; it < 8; it++) {                                 \
-            float *dst = wdst + (4 * it) * DX_LDW;                                         \
-            *reinterpret_cast<float2 *>(dst + wsw) = make_float2(WR[it].x, WR[it].y);      \
-            *reinterpret_cast<float2 *>(dst + (2 - wsw)) = make_float2(WR[it].z, WR[it].w); \
-            *reinterpret_cast<float4 *>(ddst + it * 256) = DR[it];                         \
-        }                                                                                  \
-        __builtin_amdgcn_wave_barrier();                                                   \
-    }
-#define DX_COMPUTE(CNT)                                                                    \
-    {                                                                                      \
-        _Pragma("unroll") for (int j = 0; j < 16; j++) {                                   \
-            if (j < (CNT)) {                                                               \
-                const float2 av = *reinterpret_cast<const float2 *>((j < 8 ? ard : ard_hi) + 4 * j); \
-                acc = mfma32(av.x, brd[(4 * j) * 32], acc);                                \
-                acc = mfma32(av.y, brd[(4 * j + 2) * 32], acc);                            \
-            }                                                                              \
-        }                                                                                  \
-        __builtin_amdgcn_wave_barrier();                                                   \
-    }
-    if (nch > 0) {
-        DX_LOAD(wa, da, 0);
-        DX_LOAD(wv, dv, 1);
-        int c = 0;
-        for (; c + 2 < nch; c += 2) {  // steady state: full chunks, unconditional loads
-            DX_WRITE(wa, da);
-            DX_LOAD(wa, da, c + 2);
-            DX_COMPUTE(16);
-            DX_WRITE(wv, dv);
-            DX_LOAD(wv, dv, c + 3);
-            DX_COMPUTE(16);
-        }
-        DX_WRITE(wa, da);
-        DX_COMPUTE(myq - 16 * c);
-        if (c + 1 < nch) {
-            DX_WRITE(wv, dv);
-            DX_COMPUTE(myq - 16 * (c + 1));
-        }
-    }
-#undef DX_LOAD
-#undef DX_WRITE
-#undef DX_COMPUTE
     } else {
     // Software-pipelined inside the wave like fwd_body's loop: the 32 MFMAs of chunk c (16 quads = 64 n) run on
     // fragments already in registers; in their shadow chunk c+1 goes registers -> LDS (groups 0..7) -> fragments
@@ -986,71 +743,47 @@ __device__ __forceinline__ void dx_body(const DxArgs &A, const int bid, float *s
     for (int r = 0; r < 16; r++) red[wave][acc_row(r, lane) * 32 + i] = acc[r];
     __syncthreads();
     stamp(stamps, 2, bid);
-    if constexpr (NW == 4) {  // see fwd_body: ds_read_b128 of the partial tiles, 16-byte stores of both layouts
-        const int row = tid >> 3, col4 = (tid & 7) * 4;
-        float4 d4 = *reinterpret_cast<const float4 *>(&red[0][row * 32 + col4]);
+    // see fwd_body: ds_read_b128 of the partial tiles, 16-byte stores of both layouts
+    const int row = tid >> 3, col4 = (tid & 7) * 4;
+    float4 d4 = *reinterpret_cast<const float4 *>(&red[0][row * 32 + col4]);
 #pragma unroll
-        for (int w = 1; w < NW; w++) {
-            const float4 p4 = *reinterpret_cast<const float4 *>(&red[w][row * 32 + col4]);
-            d4.x += p4.x;
-            d4.y += p4.y;
-            d4.z += p4.z;
-            d4.w += p4.w;
-        }
-        float4 g4;  // kernDsigmoid, DevFunc.cu:67-68
-        if constexpr (ACT == ACT_VIS_LINEAR) {  // an RBM's reconstruction (rbm_rule.h): v1 = h0s W^T + c
-            g4.x = d4.x + y_pre4.x;
-            g4.y = d4.y + y_pre4.x;
-            g4.z = d4.z + y_pre4.x;
-            g4.w = d4.w + y_pre4.x;
-        } else if constexpr (ACT == ACT_VIS_SIGMOID) {  // ... and sigma of it for Bernoulli visibles
-            g4.x = sigmoid_det(d4.x + y_pre4.x);
-            g4.y = sigmoid_det(d4.y + y_pre4.x);
-            g4.z = sigmoid_det(d4.z + y_pre4.x);
-            g4.w = sigmoid_det(d4.w + y_pre4.x);
-        } else if constexpr (ACT == ACT_RELU) {
-            g4.x = drelu(y_pre4.x, d4.x);
-            g4.y = drelu(y_pre4.y, d4.y);
-            g4.z = drelu(y_pre4.z, d4.z);
-            g4.w = drelu(y_pre4.w, d4.w);
-        } else {
-            g4.x = (1.0f - y_pre4.x) * y_pre4.x * d4.x;
-            g4.y = (1.0f - y_pre4.y) * y_pre4.y * d4.y;
-            g4.z = (1.0f - y_pre4.z) * y_pre4.z * d4.z;
-            g4.w = (1.0f - y_pre4.w) * y_pre4.w * d4.w;
-        }
-        *reinterpret_cast<float4 *>(&dEdXt_prev[(size_t)(k0 + row) * Bp + b0 + col4]) = g4;
-        tileT[col4][row] = g4.x;
-        tileT[col4 + 1][row] = g4.y;
-        tileT[col4 + 2][row] = g4.z;
-        tileT[col4 + 3][row] = g4.w;
-        __syncthreads();
-        *reinterpret_cast<float4 *>(&dEdX_prev[(size_t)(b0 + row) * Kp + k0 + col4]) =
-            *reinterpret_cast<const float4 *>(&tileT[row][col4]);
-        stamp(stamps, 3, bid);
-        return;
+    for (int w = 1; w < NW; w++) {
+        const float4 p4 = *reinterpret_cast<const float4 *>(&red[w][row * 32 + col4]);
+        d4.x += p4.x;
+        d4.y += p4.y;
+        d4.z += p4.z;
+        d4.w += p4.w;
     }
-    constexpr int NT = 64 * NW, EPT = 1024 / NT > 0 ? 1024 / NT : 1;
-#pragma unroll
-    for (int q = 0; q < EPT; q++) {
-        const int e = tid + NT * q, row = e >> 5, col = e & 31;
-        if (e < 1024) {
-            float dedy = red[0][e];
-#pragma unroll
-            for (int w = 1; w < NW; w++) dedy += red[w][e];
-            const size_t o = (size_t)(k0 + row) * Bp + b0 + col;
-            const float y = y_pre[q];
-            const float g = ACT == ACT_RELU ? drelu(y, dedy) : (1.0f - y) * y * dedy;  // kernDsigmoid, DevFunc.cu:67-68
-            dEdXt_prev[o] = g;
-            tileT[col][row] = g;
-        }
+    float4 g4;  // kernDsigmoid, DevFunc.cu:67-68
+    if constexpr (ACT == ACT_VIS_LINEAR) {  // an RBM's reconstruction (rbm_rule.h): v1 = h0s W^T + c
+        g4.x = d4.x + y_pre4.x;
+        g4.y = d4.y + y_pre4.x;
+        g4.z = d4.z + y_pre4.x;
+        g4.w = d4.w + y_pre4.x;
+    } else if constexpr (ACT == ACT_VIS_SIGMOID) {  // ... and sigma of it for Bernoulli visibles
+        g4.x = sigmoid_det(d4.x + y_pre4.x);
+        g4.y = sigmoid_det(d4.y + y_pre4.x);
+        g4.z = sigmoid_det(d4.z + y_pre4.x);
+        g4.w = sigmoid_det(d4.w + y_pre4.x);
+    } else if constexpr (ACT == ACT_RELU) {
+        g4.x = drelu(y_pre4.x, d4.x);
+        g4.y = drelu(y_pre4.y, d4.y);
+        g4.z = drelu(y_pre4.z, d4.z);
+        g4.w = drelu(y_pre4.w, d4.w);
+    } else {
+        g4.x = (1.0f - y_pre4.x) * y_pre4.x * d4.x;
+        g4.y = (1.0f - y_pre4.y) * y_pre4.y * d4.y;
+        g4.z = (1.0f - y_pre4.z) * y_pre4.z * d4.z;
+        g4.w = (1.0f - y_pre4.w) * y_pre4.w * d4.w;
     }
+    *reinterpret_cast<float4 *>(&dEdXt_prev[(size_t)(k0 + row) * Bp + b0 + col4]) = g4;
+    tileT[col4][row] = g4.x;
+    tileT[col4 + 1][row] = g4.y;
+    tileT[col4 + 2][row] = g4.z;
+    tileT[col4 + 3][row] = g4.w;
     __syncthreads();
-#pragma unroll
-    for (int q = 0; q < EPT; q++) {
-        const int e = tid + NT * q, bl = e >> 5, kl = e & 31;
-        if (e < 1024) dEdX_prev[(size_t)(b0 + bl) * Kp + k0 + kl] = tileT[bl][kl];
-    }
+    *reinterpret_cast<float4 *>(&dEdX_prev[(size_t)(b0 + row) * Kp + k0 + col4]) =
+        *reinterpret_cast<const float4 *>(&tileT[row][col4]);
     stamp(stamps, 3, bid);
 }
 

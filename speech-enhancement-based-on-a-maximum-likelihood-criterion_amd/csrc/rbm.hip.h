@@ -5,11 +5,11 @@
 // One step is six kernels (l = 1) on the engine's stream:
 //   k_transpose_in            v0 rows straight into the stacked visible factor Vs[0 .. B) and v0^T into Yt[0]
 //                             (l > 1: the engine's forward launches of layers 1 .. l - 1, then one device copy of Y[l-1])
-//   k_fwd<FWD_SIGMOID, 4, P>  h0p = sigma(v0 W + b): the hidden forward's own kernel, unchanged
+//   k_fwd<FWD_SIGMOID, 4, 4>  h0p = sigma(v0 W + b): the hidden forward's own kernel, unchanged
 //   k_rbm_sample              h0s^T (the down-pass' operand) and -h0p into the stacked hidden factor Hs[0 .. B)
 //   k_dx<4, P, ACT_VIS_*>     v1 = h0s W^T + c (or sigma of it): dx_body with the reconstruction epilogue; v1^T for the
-//                             next up-pass and v1 rows into Vs[B .. 2 B)
-//   k_fwd<FWD_SIGMOID, 4, P>  h1p = sigma(v1 W + b), rows into Hs[B .. 2 B)
+//                             next up-pass and v1 rows into Vs[B .. 2 B).  P = 4 or 1: engine.hip dx_dma, as in run_dx
+//   k_fwd<FWD_SIGMOID, 4, 4>  h1p = sigma(v1 W + b), rows into Hs[B .. 2 B)
 //   k_rbm_vbias               dc, c and the step's float64 reconstruction partials (one per 32 visible units, fixed order)
 //   k_dw<1, true>             g = Vs^T Hs at depth 2 B with dW, W, db and b updated in its epilogue: W and dW are read and
 //                             written once per step
@@ -143,15 +143,9 @@ static int rbm_up(mlggd_rbm *r, const float *Yt_in, float *rows_out) {
     fa.s_shift = 0;
     fa.yblk = 0;
     const dim3 grid(fa.n_tiles * fa.b_tiles);
-    if (e->fwd_pipe == 4) {
-        const size_t lds = fwd_lds_floats<4, 4>() * sizeof(float);
-        CHK(ensure_lds(e, k_fwd<FWD_SIGMOID, 4, 4, false>, lds));
-        hipLaunchKernelGGL((k_fwd<FWD_SIGMOID, 4, 4, false>), grid, dim3(256), lds, e->stream, fa, (long long *)nullptr);
-    } else {
-        const size_t lds = fwd_lds_floats<4, 1>() * sizeof(float);
-        CHK(ensure_lds(e, k_fwd<FWD_SIGMOID, 4, 1, false>, lds));
-        hipLaunchKernelGGL((k_fwd<FWD_SIGMOID, 4, 1, false>), grid, dim3(256), lds, e->stream, fa, (long long *)nullptr);
-    }
+    const size_t lds = fwd_lds_floats<4, 4>() * sizeof(float);
+    CHK(ensure_lds(e, k_fwd<FWD_SIGMOID, 4, 4, false>, lds));
+    hipLaunchKernelGGL((k_fwd<FWD_SIGMOID, 4, 4, false>), grid, dim3(256), lds, e->stream, fa, (long long *)nullptr);
     return launch_check("k_fwd (RBM up-pass)");
 }
 
@@ -165,7 +159,7 @@ static int rbm_down_t(mlggd_rbm *r) {
     xa.dEdXt_prev = r->VT.p;
     xa.dEdX_prev = r->Vs.p + (size_t)e->B * Kp;
     const dim3 grid((Kp / 32) * b_tiles);
-    if (e->dx_pipe == 4 && (Kp / 32) * b_tiles <= 256) {  // run_dx's choice between the two pipelined forms
+    if (dx_dma(e, Kp)) {  // run_dx's choice between the two forms
         const size_t lds = dx_lds_floats<4, 4>() * sizeof(float);
         CHK(ensure_lds(e, k_dx<4, 4, ACT, false>, lds));
         hipLaunchKernelGGL((k_dx<4, 4, ACT, false>), grid, dim3(256), lds, e->stream, xa, (long long *)nullptr);

@@ -22,9 +22,8 @@ import shapes64 as s6
 pytestmark = pytest.mark.gpu
 
 HP = (0.1, 0.9, 1e-5)
-KNOBS = ("MLGGD_TILE64", "MLGGD_S_OUT", "MLGGD_LOSS_FUSE", "MLGGD_DW_MERGE", "MLGGD_STAGE_AHEAD", "MLGGD_FWD_NW",
-         "MLGGD_DX_NW", "MLGGD_FWD_PIPE", "MLGGD_DX_PIPE", "MLGGD_TWO_STREAMS", "MLGGD_CV_DEVICE", "MLGGD_DW_TILE",
-         "MLGGD_DW_PERSIST", "MLGGD_DWP_PER_CU", "MLGGD_TILE_MAP")
+KNOBS = ("MLGGD_TILE64", "MLGGD_S_OUT", "MLGGD_LOSS_FUSE", "MLGGD_DW_MERGE", "MLGGD_STAGE_AHEAD", "MLGGD_CV_DEVICE",
+         "MLGGD_DW_TILE", "MLGGD_DW_PERSIST", "MLGGD_DWP_PER_CU", "MLGGD_TILE_MAP")
 SHAPES = [(19, 32), (19, 160), (257, 32), (257, 160)]
 SINGLE = [(m, D, B) for m in ("fused", "unfused") for D, B in SHAPES]
 WORLDS = [("gather", D, 32) for D in (19, 257)] + [("allreduce", D, B) for D, B in SHAPES]

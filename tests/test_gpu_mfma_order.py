@@ -76,11 +76,16 @@ def test_forward_and_dw_of_a_one_layer_net_equal_the_twin_bitwise(pkg, pyoracle,
     assert differs
 
 
-@pytest.mark.parametrize("H,D,B", [(96, 257, 128), (160, 2048, 128), (64, 1000, 64)])
+@pytest.mark.parametrize("H,D,B", [(96, 257, 128), (160, 2048, 128), (64, 1000, 64), (531, 257, 512)])
 def test_dx_equals_the_twin_bitwise(pkg, pyoracle, H, D, B):
     """dX with the reduction over D output units (quads, 4 waves, pad columns): a first layer with zero weights and biases
-    has activations of exactly 0.5 on both sides, so dEdX_1 = 0.25 * (dEdX_2 . W_2^T) compares bit for bit."""
+    has activations of exactly 0.5 on both sides, so dEdX_1 = 0.25 * (dEdX_2 . W_2^T) compares bit for bit.  Up to 256
+    workgroups k_dx takes its operands by LDS-DMA, above that through staging registers: 531 units at B = 512 are
+    17 x 16 = 272 workgroups, the only case here of the second form (544 % 64 != 0: no 64 x 64 tiles; 8 units of 64
+    frames: k_dwp forms the gradients)."""
     K0 = 64
+    workgroups = -(-H // 32) * -(-B // 32)      # on the host: the grid of the dX launch, 32 x 32 tiles over units x frames
+    assert (workgroups > 256) == (H == 531) and (H != 531 or (workgroups == 272 and -(-H // 32) * 32 % 64 and B // 64 == 8))
     rng = np.random.default_rng(H + D)
     W1, b1 = np.zeros((K0, H), np.float32), np.zeros(H, np.float32)
     W2 = rng.normal(0, 0.05, (H, D)).astype(np.float32)

@@ -270,9 +270,8 @@ def test_the_64_tile_kernels_and_a_bunch_of_128(pkg, synth, monkeypatch, B):
 
 
 NON_DEFAULT = {"MLGGD_TILE64": "2", "MLGGD_S_OUT": "3", "MLGGD_LOSS_FUSE": "0", "MLGGD_DW_MERGE": "0",
-               "MLGGD_STAGE_AHEAD": "0", "MLGGD_FWD_NW": "8", "MLGGD_DX_NW": "8", "MLGGD_FWD_PIPE": "1",
-               "MLGGD_DX_PIPE": "1", "MLGGD_TWO_STREAMS": "1", "MLGGD_CV_DEVICE": "1", "MLGGD_DW_TILE": "2",
-               "MLGGD_DW_PERSIST": "0", "MLGGD_DWP_PER_CU": "1", "MLGGD_TILE_MAP": "1"}
+               "MLGGD_STAGE_AHEAD": "0", "MLGGD_CV_DEVICE": "1", "MLGGD_DW_TILE": "2", "MLGGD_DW_PERSIST": "0",
+               "MLGGD_DWP_PER_CU": "1", "MLGGD_TILE_MAP": "1"}
 assert set(NON_DEFAULT) == set(KNOBS)
 
 

@@ -15,8 +15,7 @@ import rbm64
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("MLGGD_TILE64", "MLGGD_FWD_NW", "MLGGD_DX_NW", "MLGGD_FWD_PIPE", "MLGGD_DX_PIPE", "MLGGD_DW_TILE", "MLGGD_DW_PERSIST",
-         "MLGGD_TILE_MAP", "MLGGD_STAGE_AHEAD", "MLGGD_LOSS_FUSE")
+KNOBS = ("MLGGD_TILE64", "MLGGD_DW_TILE", "MLGGD_DW_PERSIST", "MLGGD_TILE_MAP", "MLGGD_STAGE_AHEAD", "MLGGD_LOSS_FUSE")
 HP = (0.1, 0.9, 1e-5)         # the engine's fine-tuning rates: pre-training must not read them
 R = rbm64.RATES
 VIS = {1: "gaussian", 2: "bernoulli"}

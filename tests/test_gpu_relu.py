@@ -1,7 +1,7 @@
 """GPU: rectified-linear hidden units (BPGpu(..., activation="relu")) through every layer of the engine.
 
 Beside the bit-for-bit runs against the oracle's twin (tests/test_gpu_twin_relu_bins.py: 4-wave and 64 x 64 kernels), the
-ReLU kernels -- every loop variant included -- are held to the float64 model of tests/relu64.py: every kernel of a
+ReLU kernels are held to the float64 model of tests/relu64.py: every kernel of a
 training step against its own fp32 inputs with derived per-element bounds (tests/test_relu_model.py shows on the CPU
 that the bounds pass the rules and refuse the slips they are meant for), one step on exactly representable data with no
 bound at all, the special values of the rule itself, and then the features built on run_forward / the dX launcher --
@@ -86,61 +86,6 @@ def test_every_kernel_of_three_steps_within_its_bound(pkg, monkeypatch, B, ml, b
     finally:
         eng.close()
     assert not bad, case + "\n" + "\n".join(bad)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# 2. every loop variant
-VAR_LS, VAR_B = [1210, 1060, 70, 262, 40], 96
-FWD_VARIANTS = [(4, 0), (4, 1), (4, 4), (8, 0), (8, 1), (8, 4), (16, 0)]
-DX_VARIANTS = [(4, 0), (4, 1), (4, 4), (8, 0), (8, 1), (8, 4)]
-_variant_runs = {}
-
-
-def variant_run(pkg, monkeypatch, env):
-    """one ML step at VAR_LS under `env`, every kernel checked against its bound; cached per environment"""
-    key = tuple(sorted(env.items()))
-    if key not in _variant_runs:
-        L = len(VAR_LS)
-        W, b = b6.make_net(VAR_LS, 31)
-        x, t = b6.make_data(VAR_LS, VAR_B, 32)
-        eng = new_engine(pkg, monkeypatch, VAR_LS, VAR_B, r6.CASE_HP, 1.2, 1, W, b, env)
-        try:
-            s = one_step(eng, x, t, r6.CASE_HP, 1.2, 1, L)
-        finally:
-            eng.close()
-        reps = r6.check_step_relu(s)
-        record("variant " + " ".join("%s=%s" % (k[6:], v) for k, v in key), reps)
-        _variant_runs[key] = (s, fail_lines(reps))
-    return _variant_runs[key]
-
-
-def same_step_bits(a, b):
-    for l in a.y:
-        assert a.y[l].tobytes() == b.y[l].tobytes(), "y %d" % l
-    for l in a.dedx:
-        assert a.dedx[l].tobytes() == b.dedx[l].tobytes(), "dedx %d" % l
-    assert a.out.tobytes() == b.out.tobytes()
-
-
-@pytest.mark.parametrize("nw,pipe", FWD_VARIANTS)
-def test_forward_loop_variants(pkg, monkeypatch, nw, pipe):
-    """MLGGD_FWD_NW x MLGGD_FWD_PIPE on a ReLU engine, at the shape of test_forward_and_dx_loop_variants (a wave's K
-    range of several chunks plus a partial one, a single partial chunk, nothing at all).  What holds between the
-    sigmoid variants holds here: the loops of ONE wave count issue the same MFMAs in the same order and are
-    bit-identical to each other (asserted against that wave count's MLGGD_FWD_PIPE=0 loop, for y, out and every dedx);
-    another wave count is another K split, equal to rounding only -- so every variant is also held to the per-kernel
-    bounds on its own."""
-    s, bad = variant_run(pkg, monkeypatch, {"MLGGD_FWD_NW": str(nw), "MLGGD_FWD_PIPE": str(pipe)})
-    assert not bad, "\n".join(bad)
-    same_step_bits(s, variant_run(pkg, monkeypatch, {"MLGGD_FWD_NW": str(nw), "MLGGD_FWD_PIPE": "0"})[0])
-
-
-@pytest.mark.parametrize("nw,pipe", DX_VARIANTS)
-def test_dx_loop_variants(pkg, monkeypatch, nw, pipe):
-    """MLGGD_DX_NW x MLGGD_DX_PIPE likewise (8 waves with pipe 4 selects the staged loop, as on a sigmoid engine)"""
-    s, bad = variant_run(pkg, monkeypatch, {"MLGGD_DX_NW": str(nw), "MLGGD_DX_PIPE": str(pipe)})
-    assert not bad, "\n".join(bad)
-    same_step_bits(s, variant_run(pkg, monkeypatch, {"MLGGD_DX_NW": str(nw), "MLGGD_DX_PIPE": "0"})[0])
 
 
 def test_the_64x64_kernels(pkg, monkeypatch):

@@ -138,11 +138,22 @@ def test_a_whole_relu_run_equals_the_twin(pkg, pyoracle, monkeypatch, ls, B, ste
     whole_run(pkg, pyoracle, monkeypatch, ls, B, steps, seed, ml, beta)
 
 
-@pytest.mark.parametrize("ls,B,steps,seed,ml,beta", tc.SINGLE_RUNS, ids=["real_widths", "dwp4", "dwp8"])
+@pytest.mark.parametrize("ls,B,steps,seed,ml,beta", tc.SINGLE_RUNS, ids=["real_widths", "dwp4", "dwp8", "dx_both_forms"])
 def test_relu_runs_at_the_real_widths_and_behind_the_wide_dw_kernels(pkg, pyoracle, monkeypatch, ls, B, steps, seed, ml, beta):
     """2827-2048^3-257 at B = 128, 8 ML-GGD steps with beta = 1: only there does the persistent k_dwp walk many tiles per
-    workgroup after ReLU-sparse activations.  [300, 96, 40] at B = 256 and 512: k_dwp<4> / k_dwp<8> behind a ReLU layer."""
-    whole_run(pkg, pyoracle, monkeypatch, ls, B, steps, seed, ml, beta)
+    workgroup after ReLU-sparse activations.  [300, 96, 40] at B = 256 and 512: k_dwp<4> / k_dwp<8> behind a ReLU layer.
+    [40, 531, 64, 19] at B = 512: the dX launch over the 531 units has 17 x 16 = 272 workgroups, more than 256, and takes
+    its operands through staging registers; the one over the 64 units has 2 x 16 and takes them by LDS-DMA -- both
+    forms of k_dx<.., ACT_RELU> in one run (544 is no multiple of 64 and 2 x 8 tiles of 64 x 64 are fewer than the CUs, so
+    the plan must say 4 waves for both; 8 units of 64 frames, so k_dwp<8> forms the gradients)."""
+    check = None
+    if ls == tc.DX_BOTH_LS:
+        assert tc.dx_workgroups(ls, B) == {2: 17 * 16, 3: 2 * 16} and 2 * 16 <= 256 < 17 * 16 and B % 64 == 0 and B // 64 == 8
+
+        def check(got):
+            assert got[1][1] == 4 and got[2][1] == 4, got
+
+    whole_run(pkg, pyoracle, monkeypatch, ls, B, steps, seed, ml, beta, plan_check=check)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -17,9 +17,8 @@ pytestmark = pytest.mark.gpu
 SHIPPED = (0.1, 0.9, 1e-5)
 NO_MOM = (0.05, 0.0, 0.0)
 DECAY = (0.3, 0.5, 1e-2)      # lr wc W of the order of the gradient term
-KNOBS = ("MLGGD_TILE64", "MLGGD_S_OUT", "MLGGD_LOSS_FUSE", "MLGGD_DW_MERGE", "MLGGD_STAGE_AHEAD", "MLGGD_FWD_NW",
-         "MLGGD_DX_NW", "MLGGD_FWD_PIPE", "MLGGD_DX_PIPE", "MLGGD_TWO_STREAMS", "MLGGD_CV_DEVICE", "MLGGD_DW_TILE",
-         "MLGGD_DW_PERSIST", "MLGGD_DWP_PER_CU", "MLGGD_TILE_MAP")
+KNOBS = ("MLGGD_TILE64", "MLGGD_S_OUT", "MLGGD_LOSS_FUSE", "MLGGD_DW_MERGE", "MLGGD_STAGE_AHEAD", "MLGGD_CV_DEVICE",
+         "MLGGD_DW_TILE", "MLGGD_DW_PERSIST", "MLGGD_DWP_PER_CU", "MLGGD_TILE_MAP")
 TABLE = {}
 
 

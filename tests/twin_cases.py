@@ -14,16 +14,19 @@ import shapes64 as s6
 HP = r6.CASE_HP                         # lrate 0.01, momentum 0.9, weightcost 1e-5
 LOSSES = [(0, 2.0), (0, 1.0), (1, 1.0), (1, 1.2), (1, 0.9)]
 REAL_LS = [2827, 2048, 2048, 2048, 257]
-VAR_LS = [1210, 1060, 70, 262, 40]      # tests/test_gpu_relu.py VAR_LS: a wave's K range of several chunks plus a partial one,
-                                        # a single partial chunk, an empty one
+VAR_LS = [1210, 1060, 70, 262, 40]      # a wave's K range of several chunks plus a partial one, a single partial chunk,
+                                        # an empty one
+DX_BOTH_LS = [40, 531, 64, 19]          # at B = 512 one dX launch in each form of k_dx (dx_workgroups below)
 DROP_LS = [257 * 3, 256, 192, 257]      # the shape of test_dropout_runs_equal_the_twin_bit_for_bit
 DROP_KW = dict(dropoutflag=1, visible_omit=0.2, hid_omit=0.5)
 DROP_SEED = 77
 
 # a. whole ReLU runs: (layersizes, B, steps, seed) x LOSSES ...
 RUNS = [(r6.CASE_LS, 24, 6, 3), (r6.CASE_LS, 128, 6, 3), (VAR_LS, 96, 3, 31)]
-# ... and single cases (layersizes, B, steps, seed, ml, beta): the real widths; k_dwp<4> / <8> behind a ReLU layer
-SINGLE_RUNS = [(REAL_LS, 128, 8, 51, 1, 1.0), ([300, 96, 40], 256, 3, 52, 1, 1.2), ([300, 96, 40], 512, 3, 52, 1, 1.2)]
+# ... and single cases (layersizes, B, steps, seed, ml, beta): the real widths; k_dwp<4> / <8> behind a ReLU layer; both
+# forms of k_dx in one run
+SINGLE_RUNS = [(REAL_LS, 128, 8, 51, 1, 1.0), ([300, 96, 40], 256, 3, 52, 1, 1.2), ([300, 96, 40], 512, 3, 52, 1, 1.2),
+               (DX_BOTH_LS, 512, 3, 53, 1, 1.2)]
 # b. the 64 x 64 kernels (MLGGD_TILE64=2): (layersizes, B, steps, seed, the plan the CPU check runs: hidden forwards
 # and dX launches in the 64 x 64 form, which the GPU test requires of the engine's own plan)
 TILE64 = [([96, 128, 128, 40], 64, 3, 41, [(1, 4), (1, 1), (4, 1)]),
@@ -54,6 +57,12 @@ def data(ls, n, seed):
     x.setflags(write=False)
     t.setflags(write=False)
     return x, t
+
+
+def dx_workgroups(ls, B):
+    """{l: workgroups of the 32 x 32-tile dX launch of layer l, l = 2 .. L - 1}: unit tiles of layer l - 1 x frame tiles.
+    Up to 256 of them k_dx takes its operands by LDS-DMA, above that through staging registers (engine.hip dx_dma)."""
+    return {l: -(-ls[l - 1] // 32) * -(-B // 32) for l in range(2, len(ls))}
 
 
 def distinct_betas(D, seed=5):

@@ -9,8 +9,8 @@ pkg = importlib.import_module(PKG); synth = importlib.import_module(PKG + ".synt
 ls = synth.baseline_layersizes(); B = 128
 ws, bs = synth.make_weights(ls); NB = 32
 inp, targ = synth.make_frames(NB * B, 257, 11)
-configs = [dict(zip(("MLGGD_FWD_NW", "MLGGD_DX_NW", "MLGGD_DW_TILE"), c)) for c in
-           [("4", "4", "2"), ("8", "4", "2"), ("16", "4", "2"), ("8", "8", "2"), ("8", "8", "1"), ("16", "8", "1")]]
+configs = [dict(zip(("MLGGD_DW_PERSIST", "MLGGD_DW_MERGE", "MLGGD_DW_TILE"), c)) for c in
+           [("1", "1", "1"), ("1", "0", "1"), ("0", "0", "1"), ("0", "0", "2")]]
 if len(sys.argv) > 1:
     configs = [dict(kv.split("=") for kv in a.split(",")) for a in sys.argv[1:]]
 ref = None
