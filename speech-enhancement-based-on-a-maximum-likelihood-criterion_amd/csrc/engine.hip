@@ -18,6 +18,7 @@
 #include <functional>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mlggd.h"
@@ -545,9 +546,9 @@ static DxArgs dx_args(mlggd_engine *e, int l) {
     return a;
 }
 
-static DwpArgs dwp_args(mlggd_engine *e, int l, const float *in_rows, const float *Yrow_prev, float nf) {
+static DwpArgs dwp_args(mlggd_engine *e, int l, const float *in_rows, const float *Yrow_prev) {
     DwpArgs a;
-    memset(&a, 0, sizeof(a));  // every byte, tail padding included: dwp_table compares plans with memcmp
+    memset(&a, 0, sizeof(a));
     const int Kp = e->lsp[l - 1], Np = e->lsp[l];
     a.Yrow = (l == 1) ? in_rows : Yrow_prev;
     a.dEdX = e->dEdX[l];
@@ -562,17 +563,23 @@ static DwpArgs dwp_args(mlggd_engine *e, int l, const float *in_rows, const floa
     a.N = e->ls[l];
     a.Kp = Kp;
     a.Np = Np;
-    a.B = e->B;
     a.n_wg = (Np + 63) / 64;
     a.ntiles = ((Kp + 63) / 64) * a.n_wg;
-    a.nf = nf;
-    a.mom = e->cfg.momentum;
-    a.lr = e->cfg.lrate;
-    a.wc = e->cfg.weightcost;
     a.k_first = 0;
     a.wd_off = 0;
     a.do_bias = 1;
     return a;
+}
+// what every tile of a launch shares.  frames: rows of the minibatch the jobs' operands hold (e->B on one device,
+// world * Bp over gathered factors)
+static DwpConst dwp_const(const mlggd_engine *e, float nf, int frames) {
+    DwpConst C;
+    C.B = frames;
+    C.nf = nf;
+    C.mom = e->cfg.momentum;
+    C.lr = e->cfg.lrate;
+    C.wc = e->cfg.weightcost;
+    return C;
 }
 
 // one minibatch of the resident chunk: expanded rows, or raw streams + per-row first frame
@@ -813,12 +820,12 @@ static int dwp_grid(mlggd_engine *e, int ntiles) {
 }
 // jobs for layers lhi, lhi-1, ..., llo in one launch
 static_assert(DWP_MAXJOBS >= MLGGD_MAXLAYER, "job table too small");
-static DwpJobs dwp_jobs(mlggd_engine *e, int lhi, int llo, const float *in_rows, float nf) {
+static DwpJobs dwp_jobs(mlggd_engine *e, int lhi, int llo, const float *in_rows) {
     DwpJobs J;
     memset(&J, 0, sizeof(J));
     int nj = 0, end = 0;
     for (int l = lhi; l >= llo; l--) {
-        J.job[nj] = dwp_args(e, l, in_rows, e->Y[l - 1], nf);
+        J.job[nj] = dwp_args(e, l, in_rows, e->Y[l - 1]);
         end += J.job[nj].ntiles;
         J.tile_end[nj++] = end;
     }
@@ -829,25 +836,13 @@ static DwpJobs dwp_jobs(mlggd_engine *e, int lhi, int llo, const float *in_rows,
 // The per-tile records the persistent dW kernel walks (kernels.hip.h DwpDesc), built once per launch plan and
 // kept on the device: the plan is the job list (which layers / row blocks / operands) and the grid.  A training
 // run uses two plans (the layer-1 operand alternates between the two staged-row buffers), a data-parallel run
-// a few more.  Hyper-parameters are not part of the plan: they travel in DwpConst with every launch.
+// a few more.  Hyper-parameters and the frame count are not part of the plan: they travel in DwpConst with every launch.
+// The cache is keyed on the job list with memcmp: a value comparison as long as this holds (every builder starts from
+// zeroed storage, so the unused job slots are equal too).
+static_assert(std::has_unique_object_representations_v<DwpJobs>, "padding or a float in DwpJobs: memcmp is no comparison");
 static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, const DwpDesc **out) {
-    // The key is rebuilt field by field into zeroed storage, so padding bytes (DwpArgs has 4 at its tail) and the
-    // unused job slots never take part in the memcmp.  Hyper-parameters and the frame count are not part of a plan.
-    DwpJobs key;
-    memset(&key, 0, sizeof(key));
-    for (int j = 0; j < J.njobs && j < DWP_MAXJOBS; j++) {
-        const DwpArgs &s = J.job[j];
-        DwpArgs &a = key.job[j];
-        a.Yrow = s.Yrow; a.dEdX = s.dEdX; a.Wt = s.Wt; a.delta = s.delta; a.G = s.G;
-        a.bias = s.bias; a.dbias = s.dbias; a.gb = s.gb;
-        a.ldA = s.ldA; a.K = s.K; a.N = s.N; a.Kp = s.Kp; a.Np = s.Np; a.n_wg = s.n_wg; a.ntiles = s.ntiles;
-        a.k_first = s.k_first; a.wd_off = s.wd_off; a.do_bias = s.do_bias; a.k_base = s.k_base;
-        key.tile_end[j] = J.tile_end[j];
-    }
-    key.njobs = J.njobs;
-    key.total = J.total;
     for (const auto &t : e->dwp_tables)
-        if (t.fused == fused && t.grid == grid && memcmp(&t.key, &key, sizeof(key)) == 0) {
+        if (t.fused == fused && t.grid == grid && memcmp(&t.key, &J, sizeof(J)) == 0) {
             *out = t.dev.p;
             return MLGGD_OK;
         }
@@ -904,7 +899,7 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
         d.szW = 0;
     }
     mlggd_engine::DwpTable t;
-    t.key = key;
+    t.key = J;
     t.fused = fused;
     t.grid = grid;
     HIPCHK(t.dev.grow(recs.size(), recs.size(), e->bufs, nullptr, nullptr));
@@ -915,99 +910,85 @@ static int dwp_table(mlggd_engine *e, const DwpJobs &J, bool fused, int grid, co
     return MLGGD_OK;
 }
 
-template <int H>
-static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, bool fused, int stamp_layer) {
+// G / n is a multiply when n, the frame count as the kernels get it, is a power of two >= 1 (bit-identical, see
+// kernels.hip.h POW2)
+static bool pow2_frames(float nf) {
+    unsigned bits;
+    memcpy(&bits, &nf, sizeof(bits));
+    return (bits & 0x007FFFFFu) == 0u && nf >= 1.0f;
+}
+// one launch of k_dwp<H, FUSED, POW2>: the stamped instantiation only when the launch was picked for stamps
+// (kernels.hip.h k_fwd).  bias_only (FUSED plans only): k_dwp_bias<H, POW2> in its place, by a plain launch -- the
+// profiler's event pair and an armed stop event belong to the launch of the weight tiles that follows it.
+template <int H, bool FUSED, bool POW2>
+static int launch_dwp_k(mlggd_engine *e, int grid, const DwpDesc *table, int total, const DwpConst &C, bool bias_only,
+                        long long *stamps) {
     const size_t lds = dwp_lds_floats() * sizeof(float);
+    if constexpr (FUSED) {
+        if (bias_only) {
+            CHK(ensure_lds(e, k_dwp_bias<H, POW2>, lds));
+            hipLaunchKernelGGL((k_dwp_bias<H, POW2>), dim3(grid), dim3(256), lds, e->stream, table, total, C, (long long *)nullptr);
+            return launch_check("k_dwp_bias");
+        }
+    }
+    if (stamps) {
+        CHK(ensure_lds(e, k_dwp<H, FUSED, POW2, true>, lds));
+        launch_timed(e, k_dwp<H, FUSED, POW2, true>, dim3(grid), dim3(256), lds, e->stream, table, total, C, stamps);
+    } else {
+        CHK(ensure_lds(e, k_dwp<H, FUSED, POW2, false>, lds));
+        launch_timed(e, k_dwp<H, FUSED, POW2, false>, dim3(grid), dim3(256), lds, e->stream, table, total, C, stamps);
+    }
+    return launch_check("k_dwp");
+}
+template <int H>
+static int launch_dwp_t(mlggd_engine *e, const DwpJobs &J, const DwpConst &C, bool fused, int stamp_layer) {
     const int grid = dwp_grid(e, J.total);
     if (J.total < 1) return MLGGD_OK;
     const DwpDesc *table = nullptr;
-    DwpConst C;
-    C.B = J.job[0].B;
-    C.nf = J.job[0].nf;
-    C.mom = J.job[0].mom;
-    C.lr = J.job[0].lr;
-    C.wc = J.job[0].wc;
     bool bias_only = J.njobs > 0, any_bias_only = false;  // only the sharded data-parallel plans hold bias-only jobs
     for (int j = 0; j < J.njobs; j++) {
         bias_only = bias_only && J.job[j].wd_off != 0;
         any_bias_only = any_bias_only || J.job[j].wd_off != 0;
     }
-    if (any_bias_only) {
-        if (!bias_only || !fused) return fail(MLGGD_ERR_STATE, "bias-only jobs need a launch of their own on the fused path");
-        CHK(dwp_table(e, J, fused, grid, &table));
-        unsigned nb;
-        memcpy(&nb, &C.nf, sizeof(nb));
-        if ((nb & 0x007FFFFFu) == 0u && C.nf >= 1.0f) {
-            CHK(ensure_lds(e, k_dwp_bias<H, true>, lds));
-            hipLaunchKernelGGL((k_dwp_bias<H, true>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, (long long *)nullptr);
-        } else {
-            CHK(ensure_lds(e, k_dwp_bias<H, false>, lds));
-            hipLaunchKernelGGL((k_dwp_bias<H, false>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, (long long *)nullptr);
-        }
-        return launch_check("k_dwp_bias");
-    }
+    if (any_bias_only && (!bias_only || !fused))
+        return fail(MLGGD_ERR_STATE, "bias-only jobs need a launch of their own on the fused path");
+    // (from here on bias_only == any_bias_only)
     CHK(dwp_table(e, J, fused, grid, &table));
-    if constexpr (H == 2 || H == 8) {
-        if (e->stamp_class == KC_DW && e->stamp_layer == -1 && e->stamp_buf.p && fused && C.nf == 128.0f) {
-            // diagnostic: the twin kernel with per-phase cycle sums (rows grid .. 2*grid-1 of the stamp buffer)
-            long long *sp = stamps_for(e, KC_DW, -1, 2 * grid);
-            if (sp) {
-                CHK(ensure_lds(e, k_dwp_phases<H>, lds));
-                hipLaunchKernelGGL((k_dwp_phases<H>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, sp);
-                return launch_check("k_dwp_phases");
+    const bool pow2 = pow2_frames(C.nf);
+    long long *stamps = nullptr;
+    if (!bias_only) {
+        if constexpr (H == 2 || H == 8) {
+            if (e->stamp_class == KC_DW && e->stamp_layer == -1 && e->stamp_buf.p && fused && C.nf == 128.0f) {
+                // diagnostic: the twin kernel with per-phase cycle sums (rows grid .. 2*grid-1 of the stamp buffer)
+                long long *sp = stamps_for(e, KC_DW, -1, 2 * grid);
+                if (sp) {
+                    const size_t lds = dwp_lds_floats() * sizeof(float);
+                    CHK(ensure_lds(e, k_dwp_phases<H>, lds));
+                    hipLaunchKernelGGL((k_dwp_phases<H>), dim3(grid), dim3(256), lds, e->stream, table, J.total, C, sp);
+                    return launch_check("k_dwp_phases");
+                }
             }
         }
+        stamps = stamps_for(e, KC_DW, stamp_layer, grid);
     }
-    if constexpr (H == 2) {
-        static const int abl = getenv("MLGGD_DWP_ABLATE") ? atoi(getenv("MLGGD_DWP_ABLATE")) : 0;
-        if (abl && fused) {  // timing-only diagnostics: results are wrong by construction
-#define DWP_ABL(A_)                                                                                       \
-    case A_:                                                                                              \
-        CHK(ensure_lds(e, k_dwp_ablate<H, A_>, lds));                                                     \
-        launch_timed(e, k_dwp_ablate<H, A_>, dim3(grid), dim3(256), lds, e->stream, table, J.total, C, (long long *)nullptr); \
-        return launch_check("k_dwp_ablate");
-            switch (abl) {
-                DWP_ABL(1) DWP_ABL(2) DWP_ABL(3) DWP_ABL(4) DWP_ABL(7) DWP_ABL(15) DWP_ABL(31) DWP_ABL(63) DWP_ABL(16) DWP_ABL(48) DWP_ABL(256) DWP_ABL(1024) DWP_ABL(2048) DWP_ABL(512) DWP_ABL(576)
-            default: return fail(MLGGD_ERR_ARG, "MLGGD_DWP_ABLATE=%d is not built", abl);
-            }
-#undef DWP_ABL
-        }
-    }
-    long long *stamps = stamps_for(e, KC_DW, stamp_layer, grid);  // (the ablation twins carry none: they are timed against k_dwp)
-    // G / n is a multiply when n is a power of two (bit-identical, see kernels.hip.h POW2)
-    unsigned nfbits;
-    memcpy(&nfbits, &C.nf, sizeof(nfbits));
-    const bool pow2 = (nfbits & 0x007FFFFFu) == 0u && C.nf >= 1.0f;
-    // the stamped instantiation only when this launch was picked for stamps (kernels.hip.h k_fwd)
-#define DWP_LAUNCH(FUSED_, POW2_)                                                                         \
-    {                                                                                                     \
-        if (stamps) {                                                                                     \
-            CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_, true>, lds));                                       \
-            launch_timed(e, k_dwp<H, FUSED_, POW2_, true>, dim3(grid), dim3(256), lds, e->stream, table, J.total, C, stamps); \
-        } else {                                                                                          \
-            CHK(ensure_lds(e, k_dwp<H, FUSED_, POW2_>, lds));                                             \
-            launch_timed(e, k_dwp<H, FUSED_, POW2_>, dim3(grid), dim3(256), lds, e->stream, table, J.total, C, stamps); \
-        }                                                                                                 \
-    }
-    if (fused && pow2) DWP_LAUNCH(true, true)
-    else if (fused) DWP_LAUNCH(true, false)
-    else if (pow2) DWP_LAUNCH(false, true)
-    else DWP_LAUNCH(false, false)
-#undef DWP_LAUNCH
-    return launch_check("k_dwp");
+    if (fused)
+        return pow2 ? launch_dwp_k<H, true, true>(e, grid, table, J.total, C, bias_only, stamps)
+                    : launch_dwp_k<H, true, false>(e, grid, table, J.total, C, bias_only, stamps);
+    return pow2 ? launch_dwp_k<H, false, true>(e, grid, table, J.total, C, false, stamps)
+                : launch_dwp_k<H, false, false>(e, grid, table, J.total, C, false, stamps);
 }
 static bool dwp_usable(const mlggd_engine *e) {
     const int Hh = e->Bp / 64;
     return e->dw_persist && e->Bp % 64 == 0 && (Hh == 1 || Hh == 2 || Hh == 4 || Hh == 8);
 }
 // units: 64-frame units per tile = (frames the jobs' operands hold) / 64
-static int launch_dwp(mlggd_engine *e, const DwpJobs &J, bool fused, int stamp_layer, int units = 0) {
+static int launch_dwp(mlggd_engine *e, const DwpJobs &J, const DwpConst &C, bool fused, int stamp_layer, int units = 0) {
     switch (units > 0 ? units : e->Bp / 64) {
-    case 1: return launch_dwp_t<1>(e, J, fused, stamp_layer);
-    case 2: return launch_dwp_t<2>(e, J, fused, stamp_layer);
-    case 4: return launch_dwp_t<4>(e, J, fused, stamp_layer);
-    case 8: return launch_dwp_t<8>(e, J, fused, stamp_layer);
-    case 16: return launch_dwp_t<16>(e, J, fused, stamp_layer);
+    case 1: return launch_dwp_t<1>(e, J, C, fused, stamp_layer);
+    case 2: return launch_dwp_t<2>(e, J, C, fused, stamp_layer);
+    case 4: return launch_dwp_t<4>(e, J, C, fused, stamp_layer);
+    case 8: return launch_dwp_t<8>(e, J, C, fused, stamp_layer);
+    case 16: return launch_dwp_t<16>(e, J, C, fused, stamp_layer);
     default: return fail(MLGGD_ERR_STATE, "no dW kernel for %d units per tile", units);
     }
 }
@@ -1159,18 +1140,16 @@ static int shard_alloc(mlggd_engine *e) {
 // jobs of (virtual) rank r.  pass 0: its row blocks of every layer (own_bias: whether its own row-block-0 job
 // applies the bias update); pass 1: the bias-only jobs of the layers whose row block 0 it does not own -- a
 // separate launch of the bias-only kernel (k_dwp_bias)
-static DwpJobs dwp_jobs_shard(mlggd_engine *e, float nf, int r, int pass, bool own_bias) {
-    DwpJobs G = dwp_jobs(e, e->L - 1, 1, e->Yall[0], nf), J;
+static DwpJobs dwp_jobs_shard(mlggd_engine *e, int r, int pass, bool own_bias) {
+    DwpJobs G = dwp_jobs(e, e->L - 1, 1, e->Yall[0]), J;
     memset(&J, 0, sizeof(J));
     int nj = 0, end = 0;
     {
-        const bool with_bias_only = true;
         for (int j = 0; j < G.njobs; j++) {
             const int l = e->L - 1 - j;
             DwpArgs a = G.job[j];
             a.Yrow = e->Yall[l - 1];
             a.dEdX = e->dEdXall[l];
-            a.B = e->world * e->Bp;
             const int k_wg = a.ntiles / a.n_wg;
             const int kf = r * e->shard_rows[l];
             if (e->dp_a2a) {  // Yall[l-1] holds the units of this rank's block only: [world x Bp][block width]
@@ -1182,7 +1161,7 @@ static DwpJobs dwp_jobs_shard(mlggd_engine *e, float nf, int r, int pass, bool o
                 a.k_first = kf;
                 a.ntiles = (kl - kf) * a.n_wg;
                 a.do_bias = (kf == 0 && own_bias) ? 1 : 0;
-            } else if (pass == 1 && kf != 0 && with_bias_only) {
+            } else if (pass == 1 && kf != 0) {
                 a.k_first = 0;
                 a.ntiles = a.n_wg;
                 a.wd_off = 1;
@@ -1199,13 +1178,12 @@ static DwpJobs dwp_jobs_shard(mlggd_engine *e, float nf, int r, int pass, bool o
     J.total = end;
     return J;
 }
-static DwpJobs dwp_jobs_global(mlggd_engine *e, float nf, int lhi, int llo) {
-    DwpJobs J = dwp_jobs(e, lhi, llo, e->Yall[0], nf);
+static DwpJobs dwp_jobs_global(mlggd_engine *e, int lhi, int llo) {
+    DwpJobs J = dwp_jobs(e, lhi, llo, e->Yall[0]);
     for (int j = 0; j < J.njobs; j++) {
         const int l = lhi - j;
         J.job[j].Yrow = e->Yall[l - 1];
         J.job[j].dEdX = e->dEdXall[l];
-        J.job[j].B = e->world * e->Bp;
     }
     return J;
 }
@@ -1465,7 +1443,7 @@ static int launch_dw_layer(mlggd_engine *e, int l, const float *in_rows, bool fu
     const long tiles128 = (long)((Kp + 127) / 128) * ((Np + 127) / 128);
     const bool big = e->dw_tile == 0 ? tiles128 >= 192 : e->dw_tile == 2;
     ProfScope ps(e, KC_DW, l);
-    if (dwp_usable(e)) return launch_dwp(e, dwp_jobs(e, l, l, in_rows, nf), fused, l);
+    if (dwp_usable(e)) return launch_dwp(e, dwp_jobs(e, l, l, in_rows), dwp_const(e, nf, e->B), fused, l);
     if (big) return launch_dw<2>(e, l, in_rows, fused, nf);
     return launch_dw<1>(e, l, in_rows, fused, nf);
 }
@@ -1685,6 +1663,7 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
             HIPCHK(hipStreamWaitEvent(e->stream, e->ev_gathered, 0));
         }
         const int units = e->world * Bp / 64;
+        const DwpConst C = dwp_const(e, nf, e->world * Bp);
         if (e->fake_world) {
             // all virtual ranks in turn on this GPU: their row blocks are disjoint, so the union is the whole
             // update; the bias update is taken from the LAST rank's bias-only jobs so that path is exercised
@@ -1701,21 +1680,21 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
                         }
                     }
                 if (only || r == e->world - 1) {  // the bias update comes from the LAST rank's bias-only tiles
-                    DwpJobs Jb = dwp_jobs_shard(e, nf, r, 1, false);
-                    if (Jb.total > 0) CHK(launch_dwp(e, Jb, true, 1, units));
+                    DwpJobs Jb = dwp_jobs_shard(e, r, 1, false);
+                    if (Jb.total > 0) CHK(launch_dwp(e, Jb, C, true, 1, units));
                 }
-                DwpJobs J = dwp_jobs_shard(e, nf, r, 0, only ? true : e->world == 1);
+                DwpJobs J = dwp_jobs_shard(e, r, 0, only ? true : e->world == 1);
                 ProfScope ps(e, KC_DW, 1);
-                if (J.total > 0) CHK(launch_dwp(e, J, true, 1, units));
+                if (J.total > 0) CHK(launch_dwp(e, J, C, true, 1, units));
             }
         } else {
             {
-                DwpJobs Jb = dwp_jobs_shard(e, nf, e->rank, 1, false);  // bias-only tiles: no W access, so they go first
-                if (Jb.total > 0) CHK(launch_dwp(e, Jb, true, 1, units));
+                DwpJobs Jb = dwp_jobs_shard(e, e->rank, 1, false);  // bias-only tiles: no W access, so they go first
+                if (Jb.total > 0) CHK(launch_dwp(e, Jb, C, true, 1, units));
                 ProfScope ps(e, KC_DW, 1);
-                DwpJobs J = dwp_jobs_shard(e, nf, e->rank, 0, true);
+                DwpJobs J = dwp_jobs_shard(e, e->rank, 0, true);
                 arm_stop(e, e->ev_dw_done);  // the event the W gathers wait for rides on this launch
-                if (J.total > 0) CHK(launch_dwp(e, J, true, 1, units));
+                if (J.total > 0) CHK(launch_dwp(e, J, C, true, 1, units));
             }
             const bool dw_done_attached = take_stop(e);
             // W_1 is what the next forward pass waits for first: its all-gather goes on the MAIN stream, right behind
@@ -1738,24 +1717,25 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
         // two launches: layers L-1..2 as soon as dEdX_2 has arrived (after dX_2 in stream order, which still reads
         // the old W_2), layer 1 when dEdX_1 has
         const int units = e->world * Bp / 64;
+        const DwpConst C = dwp_const(e, nf, e->world * Bp);
         if (L - 1 >= 2) {
             HIPCHK(hipStreamWaitEvent(e->stream, e->ev_layer[2], 0));
             ProfScope ps(e, KC_DW, L - 1);
-            CHK(launch_dwp(e, dwp_jobs_global(e, nf, L - 1, 2), true, L - 1, units));
+            CHK(launch_dwp(e, dwp_jobs_global(e, L - 1, 2), C, true, L - 1, units));
         }
         HIPCHK(hipStreamWaitEvent(e->stream, e->ev_layer[1], 0));
         ProfScope ps(e, KC_DW, 1);
-        CHK(launch_dwp(e, dwp_jobs_global(e, nf, 1, 1), true, 1, units));
+        CHK(launch_dwp(e, dwp_jobs_global(e, 1, 1), C, true, 1, units));
     } else if (gather) {
         if (!mainline_done) {
             HIPCHK(hipEventRecord(e->ev_gathered, e->comm_stream));
             HIPCHK(hipStreamWaitEvent(e->stream, e->ev_gathered, 0));
         }
         ProfScope ps(e, KC_DW, 1);
-        CHK(launch_dwp(e, dwp_jobs_global(e, nf, L - 1, 1), true, 1, e->world * Bp / 64));
+        CHK(launch_dwp(e, dwp_jobs_global(e, L - 1, 1), dwp_const(e, nf, e->world * Bp), true, 1, e->world * Bp / 64));
     } else if (merged) {
         ProfScope ps(e, KC_DW, 1);
-        CHK(launch_dwp(e, dwp_jobs(e, L - 1, 1, in_rows, nf), true, 1));
+        CHK(launch_dwp(e, dwp_jobs(e, L - 1, 1, in_rows), dwp_const(e, nf, e->B), true, 1));
     }
     if (dp && !gather) {
         // bias gradients were written by the dw kernels; ev_grad[1] is the last of them

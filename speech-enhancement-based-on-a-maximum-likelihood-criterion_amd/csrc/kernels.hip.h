@@ -991,18 +991,19 @@ __global__ __launch_bounds__(256) void k_dw(const float *__restrict__ Yrow, int 
 // Persistent, software-pipelined form of k_dw (same math, same outputs) for Bp = 64*H:
 // 64x64 tiles, <= 2 workgroups per CU, each walking tiles t = blockIdx.x, += gridDim.x.
 // A "unit" is one 64-frame slice of a tile's two operand tiles (32 KB of LDS, two buffers).
-// While unit u runs on the MFMA pipe, the 16-byte loads of unit u+1 (to registers) and 1/H
-// of the NEXT tile's W/delta tiles (to a second register set) are in flight, so memory streams
-// continuously instead of in per-workgroup bursts (the stage -> MFMA -> store lock-step of k_dw).
+// While unit u runs on the MFMA pipe, the 16-byte loads of unit u+1 (straight into the other LDS
+// buffer, by LDS-DMA) and 1/H of the NEXT tile's W/delta tiles (to one of two register sets) are in
+// flight, so memory streams continuously instead of in per-workgroup bursts (the stage -> MFMA ->
+// store lock-step of k_dw).
 // What bounds it (profiles/r01_sq_counters.txt, r01_vmem_rate.txt): its memory-
 // pipeline time (118 MB of stores at 27 ns per dwordx4 store and CU, 351 MB of loads at 7 ns) and its
 // MFMA time add up instead of overlapping; the per-unit loads are therefore interleaved with the
-// MFMAs in the instruction stream (DWP_INTERLEAVE), the only placement that overlaps on this chip
-// (tools/overlap_probe.hip).  Every global access is an UNCONDITIONAL buffer
+// MFMAs in the instruction stream (the groups of DWP_UNIT), the only placement that overlaps on this
+// chip (tools/overlap_probe.hip).  Every global access is an UNCONDITIONAL buffer
 // load/store whose out-of-range cases (pad rows k >= K, no next tile) are expressed through the
 // offset / an empty descriptor and dropped by the hardware range check: with no branch
-// around any memory instruction the compiler's s_waitcnt vmcnt(N) before the LDS write
-// leaves exactly the younger prefetch loads in flight.
+// around any memory instruction the s_waitcnt vmcnt(N) before a unit's hand-off barrier
+// leaves exactly the younger stores and W/delta prefetch loads in flight.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void bstore1(float v, rsrc_t r, int voff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, 0, 0);
@@ -1011,17 +1012,19 @@ __device__ __forceinline__ void bstore4(float4 v, rsrc_t r, int voff) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), r, voff, 0, 0);
 }
 
+// One layer's share of a launch, as the host describes it (engine.hip dwp_args); the kernel walks the tile records
+// made of it (DwpDesc below).  Hyper-parameters and the frame count travel in DwpConst.
 struct DwpArgs {
     const float *Yrow, *dEdX;
     float *Wt, *delta, *G, *bias, *dbias, *gb;
-    int ldA, K, N, Kp, Np, B, n_wg, ntiles;
-    float nf, mom, lr, wc;
+    int ldA, K, N, Kp, Np, n_wg, ntiles;
     // sharded data parallel: the job covers tile rows k_first .. of the layer;
     // wd_off = 1 makes it a bias-only job (W/delta are neither read nor written: the tiles of weight
     // row block 0 run on every rank so that every rank applies the same bias update); do_bias = 0
     // suppresses the bias update of a job that does own row block 0
     int k_first, wd_off, do_bias;
     int k_base;  // first unit that Yrow's columns hold (0: all of them; all-to-all form: the rank's block starts here)
+    int pad_;    // always 0: no padding bytes, so two job lists are equal exactly when their bytes are (engine.hip dwp_table)
 };
 // One launch may walk the tiles of several layers (every dW(l) only needs dEdX_l and Y_{l-1}, both
 // final once the last dX has run): job j owns the global tile numbers [tile_end[j-1], tile_end[j]).
@@ -1100,12 +1103,10 @@ struct DwpConst {
 // PHASES: diagnostic twin only (mlggd_debug_stamp_select("dw", -1)): wave 0 sums the shader-clock cycles of
 // [0] units 0..H-2 up to the last MFMA issue, [1] their hand-off (vmcnt wait, LDS write, barrier), [2] the last
 // unit, [3] unused, [4] the last hand-off, over all its tiles -> row nblocks + bid of the stamp buffer.
-// ABL: timing-only ablations of the diagnostic twins (wrong results by construction; MLGGD_DWP_ABLATE):
-// 1 no epilogue update / stores, 2 no W / delta loads, 4 no MFMAs, 8 no fragment reads and no MFMAs, 16 no operand
-// loads, 32 no operand LDS writes; and two A/B switches with correct results: 64 operand LDS writes after the block
-// instead of inside it, 256 / 1024 / 2048 the form of the update (scalar, packed, the compiler's mixture; see UPD).
-constexpr int DWP_UPDATE_FORM = 2048;
-template <int H, bool FUSED, bool POW2, bool PHASES = false, int ABL = 0>
+// BIAS_ONLY: the tiles of k_dwp_bias (no weight rows: only the operand staging and the bias gradient / update are
+// needed): compiles out the fragment reads, the MFMAs, the pending epilogue's update and stores inside the unit
+// blocks, and the W / delta loads of the next tile.
+template <int H, bool FUSED, bool POW2, bool PHASES = false, bool BIAS_ONLY = false>
 __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, const int total, const DwpConst C, const int bid,
                                          const int nblocks, float *lds, long long *stamps) {
     stamp_clk(stamps, 0, bid);  // diagnostic (nullptr in every normal launch): wall + shader clock at start / end
@@ -1122,7 +1123,9 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
     f32x16 acc, accp;  // this tile's accumulators; the previous tile's, whose epilogue is pending
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[r] = accp[r] = 0.0f;
-    float4 ra[4], rb[4];  // operands of the next unit on their way global -> LDS
+    // the first unit's operands on their way global -> LDS: only the prologue uses these and DWP_WRITE_UNIT, but
+    // declared inside the prologue's block they reorder the instructions of every FUSED kernel
+    float4 ra[4], rb[4];
     // W / delta of tiles k (set k & 1): set 1 is consumed by the (empty) pending epilogue of the first tile
     float4 pw0[4], pd0[4], pw1[4], pd1[4];
 #pragma unroll
@@ -1153,14 +1156,10 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
 #define DWP_DIVN(x) (POW2 ? (x) * inv_nf : (x) / nf)
 #define DWP_DIVN2(x) (POW2 ? (x) * inv2 : (x) / nf2)
     f32x2 mom2 = {mom, mom}, lr2 = {lr, lr}, wc2 = {wc, wc}, inv2 = {inv_nf, inv_nf}, nf2 = {nf, nf}, one2 = {1.0f, 1.0f};
-    // Form of the update (all three evaluate the same IEEE operations per element, -ffp-contract=off: same bits):
-    // 256 scalar instructions; 1024 packed pairs with the constants pinned in VGPR pairs (14 instructions per float4;
-    // the empty asm hides from the compiler that they are wave-uniform); 2048 the packed source as the compiler
-    // lowers it by itself -- a mixture: it scalarises the multiplies by the SGPR-held constants.  An ABL bit picks
-    // one for the A/B twins (tools/dwp_ablate.py); otherwise DWP_UPDATE_FORM.  None of the three measured faster than
-    // the others (profiles/prologue_diet_update_forms.txt), so the default stays the form the kernel always had.
-    constexpr int UPD = (ABL & (256 | 1024 | 2048)) ? (ABL & (256 | 1024 | 2048)) : DWP_UPDATE_FORM;
-    if (UPD == 1024) asm volatile("" : "+v"(mom2), "+v"(lr2), "+v"(wc2), "+v"(inv2), "+v"(nf2), "+v"(one2));
+    // Form of the update: the packed source (DWP_EPI_UPDATE) as the compiler lowers it by itself -- a mixture: it
+    // scalarises the multiplies by the SGPR-held constants.  A scalar source and packed pairs with the constants
+    // pinned in VGPR pairs evaluate the same IEEE operations per element (-ffp-contract=off: same bits) and measured
+    // no faster (profiles/prologue_diet_update_forms.txt), so the form the kernel always had is the one that stays.
     // voffset of this lane's float4 number 0 of the wave tile of T, formed once per tile; OOB for the columns that do
     // not exist (a property of the lane).  Rows that do not exist need no test: the record's szW ends with the tile's
     // last real row (engine.hip dwp_table), so the hardware range check drops their stores and zeroes their loads.
@@ -1245,16 +1244,7 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
     {                                                                                           \
         const float4 gv_ = gq[IT];                                                              \
         const int off = DWP_OFF(offp_, tp, IT);                                                 \
-        if (FUSED && UPD == 256) { /* scalar form of the same expressions */                    \
-            const float4 w = PW[IT];                                                            \
-            float4 d = PD[IT];                                                                  \
-            d.x = mom * d.x - lr * (DWP_DIVN(gv_.x) + wc * w.x);                                \
-            d.y = mom * d.y - lr * (DWP_DIVN(gv_.y) + wc * w.y);                                \
-            d.z = mom * d.z - lr * (DWP_DIVN(gv_.z) + wc * w.z);                                \
-            d.w = mom * d.w - lr * (DWP_DIVN(gv_.w) + wc * w.w);                                \
-            bstore4(d, rDp, off);                                                               \
-            bstore4(make_float4(d.x + 1.0f * w.x, d.y + 1.0f * w.y, d.z + 1.0f * w.z, d.w + 1.0f * w.w), rWp, off); \
-        } else if (FUSED) { /* kernUpdatedelta (DevFunc.cu:502) then kernAccSum (DevFunc.cu:440) */ \
+        if (FUSED) { /* kernUpdatedelta (DevFunc.cu:502) then kernAccSum (DevFunc.cu:440) */ \
             const f32x2 w0 = {PW[IT].x, PW[IT].y}, w1 = {PW[IT].z, PW[IT].w};                   \
             f32x2 d0 = {PD[IT].x, PD[IT].y}, d1 = {PD[IT].z, PD[IT].w};                         \
             const f32x2 g0 = {gv_.x, gv_.y}, g1 = {gv_.z, gv_.w};                               \
@@ -1301,35 +1291,34 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
         const float *bp = lds + (BUF)*8192 + 4096 + h5 * 64 + 32 * wn + i;                      \
         float fa[32], fb[32]; /* static indices only: registers */                              \
         float4 gq[4];                                                                           \
+        /* (BIAS_ONLY: constants nobody reads; leaving fa / fb unset instead reorders k_dwp_bias's instructions) */ \
         _Pragma("unroll") for (int p = 0; p < 4; p++) {                                         \
-            fa[p] = (ABL & 8) ? 1.0f : ap[p * 128];                                             \
-            fb[p] = (ABL & 8) ? 1.0f : bp[p * 128];                                             \
+            fa[p] = BIAS_ONLY ? 1.0f : ap[p * 128];                                             \
+            fb[p] = BIAS_ONLY ? 1.0f : bp[p * 128];                                             \
         }                                                                                       \
         if (FIRSTU) tnn_raw = DWP_FETCH(t + 2 * nblocks);                                       \
         __builtin_amdgcn_sched_barrier(0);                                                      \
         _Pragma("unroll") for (int g = 0; g < 16; g++) {                                        \
-            if (!(ABL & 12)) {                                                                  \
+            if (!BIAS_ONLY) {                                                                   \
                 acc = mfma32(fa[2 * g], fb[2 * g], acc);                                        \
                 acc = mfma32(fa[2 * g + 1], fb[2 * g + 1], acc);                                \
-            } else if (!(ABL & 8)) {                                                            \
-                asm volatile("" ::"v"(fa[2 * g]), "v"(fb[2 * g]), "v"(fa[2 * g + 1]), "v"(fb[2 * g + 1])); \
             }                                                                                   \
-            if (g < 14 && !(ABL & 8)) {                                                         \
+            if (g < 14 && !BIAS_ONLY) {                                                         \
                 _Pragma("unroll") for (int p = 2 * g + 4; p < 2 * g + 6; p++) {                 \
                     fa[p] = ap[p * 128];                                                        \
                     fb[p] = bp[p * 128];                                                        \
                 }                                                                               \
             }                                                                                   \
-            /* operands of the next unit: one 16-byte load per group -- two per group in the unit that carries the     \
-               pending epilogue, so that all of them are OLDER than its stores (groups 4..10): s_waitcnt vmcnt counts  \
-               in issue order, and the hand-off below must not have to wait for a store to be acknowledged */          \
-            /* operands of the next unit straight into LDS by LDS-DMA (buffer_load ... lds): no staging registers  \
-               (-28 VGPRs), no ds_write_b128, -2.4 % launch time (ABL & 512 restores the register path for A/B).   \
+            /* operands of the next unit straight into LDS by LDS-DMA (buffer_load ... lds), one 16-byte load per  \
+               lane and instruction: no staging registers (-28 VGPRs) and no ds_write_b128, -2.4 % launch time      \
+               against loading into registers and writing LDS in groups 12..15.  All of them are OLDER than the     \
+               pending epilogue's last stores (group 10): s_waitcnt vmcnt counts in issue order, and the hand-off   \
+               below must not have to wait for a store to be acknowledged.                      \
                Wave w's 64 lanes fill rows 4w..4w+3 (+16q) of the A / B halves, 1 KB contiguous per instruction,   \
                which is exactly the row-major layout the fragment reads expect.  In the unit that carries a         \
                pending epilogue the A rows are its scratch, so they are filled only after the scratch has been      \
                read back (groups 6..9); the B rows go first (groups 0..3). */                    \
-            if (!(ABL & 512) && !(ABL & 16)) {                                                  \
+            {                                                                                   \
                 const int qa = FIRSTU ? g - 6 : g, qb = FIRSTU ? g : g - 4;                     \
                 if (qa >= 0 && qa < 4) {                                                        \
                     float *dst = lds + ((BUF) ^ 1) * 8192 + (4 * wave + 16 * qa) * 64;          \
@@ -1342,12 +1331,6 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
                                                              voB_, (row0_ + 16 * qb) * ldB_ * 4, 0, 0);  \
                 }                                                                               \
             }                                                                                   \
-            if ((ABL & 512) && !(ABL & 16) && (FIRSTU ? g < 4 : g < 8)) {                        \
-                const bool two_ = FIRSTU;                                                       \
-                const int q = two_ ? g : g >> 1, row = row0_ + srow + 16 * q;                    \
-                if (two_ || (g & 1) == 0) ra[q] = bload4(rA_, (row * ldA_ + 4 * scol) * 4, 0);   \
-                if (two_ || (g & 1) == 1) rb[q] = bload4(rB_, (row * ldB_ + 4 * scol) * 4, 0);   \
-            }                                                                                   \
             /* epilogue of the previous tile: accumulators -> scratch (groups 0, 1), read back (float4 IT in group    \
                2 + IT), update + stores (group 4 + 2 IT: every read is at least two groups old when it is used) */ \
             if (FIRSTU) {                                                                       \
@@ -1357,12 +1340,12 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
                     __builtin_amdgcn_wave_barrier();                                            \
                 }                                                                               \
                 if (g >= 2 && g <= 5) DWP_EPI_SCRATCH_READ((BUF) ^ 1, g - 2)                    \
-                if (g >= 4 && g <= 10 && (g & 1) == 0 && !(ABL & 1)) DWP_EPI_UPDATE(PW, PD, (g - 4) >> 1) \
+                if (g >= 4 && g <= 10 && (g & 1) == 0 && !BIAS_ONLY) DWP_EPI_UPDATE(PW, PD, (g - 4) >> 1) \
             }                                                                                   \
             /* W / delta of the NEXT tile, consumed by its epilogue a whole tile later: into the set the pending       \
                epilogue has just used (groups 12..15 when this unit is both first and last, else one load per group    \
                8..15) */                                                                        \
-            if (FUSED && LASTU && !(ABL & 2)) {                                                 \
+            if (FUSED && LASTU && !BIAS_ONLY) {                                                 \
                 if (FIRSTU) {                                                                   \
                     if (g >= 12) {                                                              \
                         PW[g - 12] = bload4(rWn, DWP_OFF(offn_, tn, g - 12), 0);                \
@@ -1373,30 +1356,19 @@ __device__ __forceinline__ void dwp_body(const DwpDesc *__restrict__ table, cons
                     else PD[g - 12] = bload4(rDn, DWP_OFF(offn_, tn, g - 12), 0);               \
                 }                                                                               \
             }                                                                                   \
-            /* register path only (ABL & 512): the next unit's operands go to LDS inside the block (groups 12..15:  \
-               their loads are 8+ groups old; the scratch of a pending epilogue in the same rows was read back in     \
-               groups 2..5), -3 % launch time against writing them after the last MFMA (ABL & 64) */ \
-            if ((ABL & 512) && !(ABL & (32 | 64)) && g >= 12) {                                 \
-                float *as_ = lds + ((BUF) ^ 1) * 8192, *bs_ = as_ + 4096;                       \
-                *reinterpret_cast<float4 *>(as_ + (srow + 16 * (g - 12)) * 64 + 4 * scol) = ra[g - 12]; \
-                *reinterpret_cast<float4 *>(bs_ + (srow + 16 * (g - 12)) * 64 + 4 * scol) = rb[g - 12]; \
-            }                                                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                  \
         }                                                                                       \
         DWP_PHASE(LASTU ? 2 : 0)                                                                \
-        if ((ABL & 64) && !(ABL & 32)) DWP_WRITE_UNIT((BUF) ^ 1)                                \
-        if (!(ABL & 512)) {                                                                     \
+        {                                                                                       \
             /* every wave's own DMA has to have landed before the barrier lets the others read its rows: wait for   \
                all vector-memory operations but the ones issued after the last DMA of this unit (vmcnt counts in     \
-               issue order): first unit: 2 stores of group 10 (+ 8 W / delta loads of groups 12..15 when it is also \
-               the last); other last units: 8 W / delta loads; otherwise none */                 \
-            constexpr int lo_ = 0;                                                              \
+               issue order): first unit: the stores of group 10 (2 FUSED, else 1; + 8 W / delta loads of groups     \
+               12..15 when it is also the last); other last units: 8 W / delta loads; otherwise none */ \
             const int younger = FIRSTU ? ((FUSED ? 2 : 1) + ((LASTU && FUSED) ? 8 : 0)) : ((LASTU && FUSED) ? 8 : 0); \
-            if (younger == 0) __builtin_amdgcn_s_waitcnt(0x0F70 | lo_);                         \
+            if (younger == 0) __builtin_amdgcn_s_waitcnt(0x0F70);                               \
             else if (younger == 1) __builtin_amdgcn_s_waitcnt(0x0F71);                          \
             else if (younger == 2) __builtin_amdgcn_s_waitcnt(0x0F72);                          \
             else if (younger == 8) __builtin_amdgcn_s_waitcnt(0x0F78);                          \
-            else if (younger == 9) __builtin_amdgcn_s_waitcnt(0x0F79);                          \
             else __builtin_amdgcn_s_waitcnt(0x0F7A);                                            \
         }                                                                                       \
         __syncthreads();                                                                        \
@@ -1525,12 +1497,7 @@ __global__ __launch_bounds__(256) void k_dwp(const DwpDesc *__restrict__ table, 
 // the unit blocks and undoes the interleave for every tile (what slowed the round-1 kernel down).
 template <int H, bool POW2>
 __global__ __launch_bounds__(256) void k_dwp_bias(const DwpDesc *__restrict__ table, int total, DwpConst C, long long *stamps) {
-    dwp_body<H, true, POW2, false, 15>(table, total, C, (int)blockIdx.x, (int)gridDim.x, g_dyn_lds, nullptr);
-}
-// timing-only ablation twins (never launched unless MLGGD_DWP_ABLATE asks for one)
-template <int H, int ABL>
-__global__ __launch_bounds__(256) void k_dwp_ablate(const DwpDesc *__restrict__ table, int total, DwpConst C, long long *stamps) {
-    dwp_body<H, true, true, false, ABL>(table, total, C, (int)blockIdx.x, (int)gridDim.x, g_dyn_lds, nullptr);
+    dwp_body<H, true, POW2, false, true>(table, total, C, (int)blockIdx.x, (int)gridDim.x, g_dyn_lds, nullptr);
 }
 // diagnostic twin of k_dwp<H, true, true> with the per-phase cycle sums (never launched unless asked for)
 template <int H>

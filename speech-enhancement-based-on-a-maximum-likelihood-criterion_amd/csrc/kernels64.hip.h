@@ -30,22 +30,17 @@ static_assert(4 * T64_SCR <= T64_NB * T64_CH, "the epilogue scratch aliases the 
 #define T64_LDSP(p) ((__attribute__((address_space(3))) void *)(p))
 
 // ---------------------------------------------------------------------------------------
-// The main loop of the forward kernel (the weight-gradient experiments of round 4 ran on it too): C[64 x 64] += A^T B over `nch` chunks of 32 reduction
+// The main loop of the forward kernel: C[64 x 64] += A^T B over `nch` chunks of 32 reduction
 // rows, both operands row-major with the reduction index as the ROW ([32][64] pieces: forward: W[k][n], Yt[k][b];
 // dW: Y[b][k], dEdX[b][n]).  4 waves as 2 x 2 (wm: half of A's columns, wn: half of B's); ring of 4 chunks, DMA three
 // chunks ahead, one barrier per chunk in the middle of its MFMA block.
-// after_prologue(): called once between the DMAs of chunks 0..2 and the first wait; it may issue EXTRA (template) more
-// vector-memory loads per lane (used by the dW experiments of round 4, profiles/r04_dw64_ab.txt; the forward kernel passes
-// 0): vmcnt counts in issue order, so bodies 0 and 1 -- whose awaited chunks 1, 2 are OLDER than those loads -- leave
-// them in flight, and from body 2 on they have arrived.
 // endA / endB: a byte offset at or past the end of the resource's range -- where the chunks past the last one are
 // "loaded" from (out of range for every lane: no memory request).
 // ---------------------------------------------------------------------------------------
-template <int EXTRA, class F>
 __device__ __forceinline__ void t64_rowmajor_loop(const rsrc_t rA, const rsrc_t rB, const int voA, const int voB,
                                                   const int rowA_bytes, const int rowB_bytes, const int endA, const int endB,
                                                   const int nch, float *smem, const int wave, const int wm, const int wn,
-                                                  const int fo, f32x16 &acc, F after_prologue) {
+                                                  const int fo, f32x16 &acc) {
     float fa[16], fb[16], ga[16], gb[16];
     // instruction Q (0..3) of this wave's share of chunk C: rows 4t..4t+3 of A (Q < 2) or of B (Q >= 2), t = 2 wave + (Q & 1)
 #define T64_DMA(C, BUF, Q)                                                                         \
@@ -71,7 +66,7 @@ __device__ __forceinline__ void t64_rowmajor_loop(const rsrc_t rA, const rsrc_t 
     // chunk C on (FA, FB), read from buffer CUR one body ago; chunk C+1 is in (or landing in) buffer CUR+1; chunk C+3
     // goes to buffer CUR+3 = CUR-1, whose chunk C-1 every wave has finished reading (it passed the barrier of body C-1
     // after the lgkmcnt wait at the top of that body).  VM: vector-memory operations that may still be in flight at the
-    // wait: the 8 DMAs of chunks C+2, C+3 (+ EXTRA in bodies 0 and 1).
+    // wait: the 8 DMAs of chunks C+2, C+3.
 #define T64_BODY(FA, FB, NA, NB, CUR, C, VM)                                                       \
     {                                                                                              \
         __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0): the fragments of chunk C have arrived */ \
@@ -96,16 +91,15 @@ __device__ __forceinline__ void t64_rowmajor_loop(const rsrc_t rA, const rsrc_t 
     for (int q = 0; q < 4; q++) T64_DMA(1, 1, q);
 #pragma unroll
     for (int q = 0; q < 4; q++) T64_DMA(2, 2, q);
-    after_prologue();
-    __builtin_amdgcn_s_waitcnt(0x0F70 | ((8 + EXTRA) & 15) | (((8 + EXTRA) >> 4) << 14));
+    __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8): this wave's part of chunk 0 has landed
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int q = 0; q < 4; q++) T64_RD4(0, fa, fb, q);
     __builtin_amdgcn_sched_barrier(0);
     // (wave-uniform branches BETWEEN bodies only: a body is one basic block)
-    T64_BODY(fa, fb, ga, gb, 0, 0, 8 + EXTRA);
+    T64_BODY(fa, fb, ga, gb, 0, 0, 8);
     if (nch > 1) {
-        T64_BODY(ga, gb, fa, fb, 1, 1, 8 + EXTRA);
+        T64_BODY(ga, gb, fa, fb, 1, 1, 8);
         if (nch > 2) {
             T64_BODY(fa, fb, ga, gb, 2, 2, 8);
             if (nch > 3) {
@@ -170,7 +164,7 @@ __device__ __forceinline__ void fwd64_body(const FwdArgs &A, const int bid, floa
     for (int q = 0; q < 4; q++) bias_pre[q] = MODE != FWD_SLAB ? bias[n0 + 32 * wm + er + 8 * q] : 0.0f;
     asm volatile("" ::: "memory");
 
-    t64_rowmajor_loop<0>(rW, rY, voW, voY, Np * 4, Bp * 4, endW, endY, nch, smem, wave, wm, wn, fo, acc, [] {});
+    t64_rowmajor_loop(rW, rY, voW, voY, Np * 4, Bp * 4, endW, endY, nch, smem, wave, wm, wn, fo, acc);
     __syncthreads();                     // every wave is done with the operand ring: the scratch below aliases it
 
     // epilogue, wave-private: accumulators -> S[n][b] -> bias + sigmoid, 16-byte stores of Yt [unit][frame]; the same

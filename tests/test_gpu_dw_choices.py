@@ -22,7 +22,7 @@ pytestmark = pytest.mark.gpu
 
 HP = (0.1, 0.9, 1e-5)                      # lrate, momentum, weightcost
 DP_KNOBS = ("MLGGD_DP_MODE", "MLGGD_DP_FINE", "MLGGD_DP_STOPEV", "MLGGD_DP_MAINLINE", "MLGGD_DP_AR_SHARD",
-            "MLGGD_DP_STAT_COMM", "MLGGD_DWP_ABLATE", "MLGGD_FAKE_ONLY_RANK")
+            "MLGGD_DP_STAT_COMM", "MLGGD_FAKE_ONLY_RANK")
 R = [531, 97, 33, 1, 257]                  # no dimension a multiple of 32, 64 or 128; a one-unit layer; 257 -> Np = 288: the
 #                                            last 128-tile is 32 columns wide; 531 -> Kp = 544: 32 rows in the last 128-tile row
 M = [531, 300, 130, 257]

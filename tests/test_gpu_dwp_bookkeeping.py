@@ -116,6 +116,39 @@ def test_constants_that_fold_change_no_bit(pkg, pyoracle, hp):
     assert ragged_run(pkg, pyoracle, hp) == 0
 
 
+def test_a_new_learning_rate_reuses_the_plans_and_equals_a_fresh_engine(pkg):
+    """531-97-33-1-257 at B = 64, momentum 0 (so the weights are the whole state): two minibatches, set_lrate, two more.
+    Hyper-parameters are no part of a launch plan (csrc/engine.hip dwp_table), so the second call builds none; and they
+    reach the kernel with every launch, so its result is that of a fresh engine created with the new rate on the weights
+    the first call left, bit for bit."""
+    ls, B = [531, 97, 33, 1, 257], 64
+    ws, bs = random_net(ls, 21)
+    x, t = random_frames(4 * B, ls, 22)
+    eng = pkg.BPGpu(1, 0, ls, B, 0.1, 0.0, 1e-5, ws, bs, 2.0, 0)
+    try:
+        assert eng.train(x[:2 * B], t[:2 * B]) == 2
+        w1, b1 = eng.returnWeights()
+        plans = eng.plan_count()
+        assert plans >= 1
+        eng.set_lrate(0.025)
+        assert eng.train(x[2 * B:], t[2 * B:]) == 2
+        assert eng.plan_count() == plans
+        wa, ba = eng.returnWeights()
+    finally:
+        eng.close()
+    fresh = pkg.BPGpu(1, 0, ls, B, 0.025, 0.0, 1e-5, w1, b1, 2.0, 0)
+    try:
+        assert fresh.train(x[2 * B:], t[2 * B:]) == 2
+        wf, bf = fresh.returnWeights()
+    finally:
+        fresh.close()
+    bad = 0
+    for l in range(len(wa)):
+        bad += differing("W_%d" % (l + 1), wa[l], wf[l]) + differing("b_%d" % (l + 1), ba[l], bf[l])
+        assert not np.array_equal(wa[l], w1[l])                   # the second call trained the layer
+    assert bad == 0
+
+
 def test_the_next_forward_sees_no_leaked_store(pkg, pyoracle):
     """After the three steps, the forward of a fresh batch (a whole minibatch and a ragged rest) equals the twin's: a
     store that had leaked into a pad row or pad column of W would be summed by the next layer's GEMM."""

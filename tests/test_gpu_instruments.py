@@ -20,7 +20,7 @@ from test_gpu_vs_float64 import DECAY, KNOBS, SHIPPED, data, fail_lines, read_st
 pytestmark = pytest.mark.gpu
 
 DP_KNOBS = ("MLGGD_DP_MODE", "MLGGD_DP_FINE", "MLGGD_DP_STOPEV", "MLGGD_DP_MAINLINE", "MLGGD_DP_AR_SHARD",
-            "MLGGD_DP_STAT_COMM", "MLGGD_DW_PERSIST", "MLGGD_DWP_ABLATE", "MLGGD_FAKE_ONLY_RANK")
+            "MLGGD_DP_STAT_COMM", "MLGGD_DW_PERSIST", "MLGGD_FAKE_ONLY_RANK")
 CLASSES = ("transpose", "fwd", "loss", "dx", "dw", "update")
 NET, RAGGED, NET64 = [531, 300, 130, 257], [531, 97, 33, 1, 257], [192, 128, 64, 257]
 NO_MOM = (0.05, 0.0, 1e-2)      # momentum 0: the step forgets the old delta, weight decay still reads every W
