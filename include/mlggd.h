@@ -540,6 +540,53 @@ int mlggd_read_scale_state(const char *path, int D, float *alpha /* [D] */, floa
 int mlggd_write_scale_state(const char *path, int D, const float *alpha /* [D] */, const float *velocity /* [D] or NULL: zeros */,
                             float lrate, float momentum, float vmax, int64_t steps);
 
+/* ---- Adam beside SGD with momentum (Kingma and Ba 2015; the reference ships the SGD rule only).  MLGGD_OPT_SGD, the
+ * default, is the engine every other entry describes: the launches and allocations of an engine that never heard of
+ * this.  MLGGD_OPT_ADAM keeps two moments (m, v) per weight and per bias on the device (csrc/adam_rule.h states the
+ * rule): g = G / n + weightcost w (the SGD rule's gradient expression; no weightcost on a bias), m' = beta1 m +
+ * (1 - beta1) g, v' = beta2 v + (1 - beta2) g g, w' = w - a_t m' / (sqrt(v') + eps), with the bias correction folded
+ * into the step size a_t = lrate sqrt(1 - beta2^t) / (1 - beta1^t), formed on the host in double from running products.
+ * A step forms the gradient with the unfused dW launches of the all-reduce exchange -- same kernels, same plan
+ * (mlggd_debug_gemm_plan) -- and applies the rule in ONE more launch over all layers; nothing else in a step changes,
+ * so every training entry, loss configuration, activation, dropout, mask and NAT engine works unchanged.  lrate and
+ * mlggd_set_lrate are the Adam rate, momentum is ignored in the mode, weightcost stays the L2 term inside g.  RBM
+ * sessions keep their own rule.  Not built: decoupled decay (AdamW), AMSGrad, a rate per layer, the data-parallel
+ * exchanges.  No default here has been evaluated on speech.
+ *
+ * mlggd_set_optimizer: entering Adam -- also from Adam -- zeroes m and v and sets steps = 0, behind every step already
+ * enqueued; the SGD momentum buffers are left alone in both directions, so going back to SGD continues from the deltas
+ * it had.  Refused before any device call, the engine unchanged: a kind other than the two, beta1 or beta2 outside
+ * [0, 1), an eps that is not finite or <= 0 (MLGGD_ERR_ARG, whichever kind is asked for); Adam on an engine that has
+ * joined a communicator or an emulated world (MLGGD_ERR_STATE), as are mlggd_comm_init / mlggd_debug_fake_world on an
+ * engine in the mode.  mlggd_get_optimizer: any pointer may be NULL; steps counts the updates since the mode was entered
+ * or the state set.  mlggd_get_optimizer_state / mlggd_set_optimizer_state move the moments unpadded, in the shapes and
+ * with the slot-0-unused pointer arrays of mlggd_get_weights; they need the mode (MLGGD_ERR_STATE); negative steps, a
+ * moment that is not finite and a negative second moment are MLGGD_ERR_ARG. */
+enum { MLGGD_OPT_SGD = 0, MLGGD_OPT_ADAM = 1 };
+int mlggd_set_optimizer(mlggd_handle h, int kind, float beta1, float beta2, float eps);
+int mlggd_get_optimizer(mlggd_handle h, int *kind, float *beta1, float *beta2, float *eps, int64_t *steps);
+int mlggd_get_optimizer_state(mlggd_handle h, float *const *m_w, float *const *v_w, float *const *m_b, float *const *v_b);
+int mlggd_set_optimizer_state(mlggd_handle h, const float *const *m_w, const float *const *v_w, const float *const *m_b,
+                              const float *const *v_b, int64_t steps);
+/* Host only, no device: the rule of csrc/adam_rule.h, compiled for the host, on n values in place -- update number
+ * steps_before + 1 of a run.  G is the summed gradient, nf the minibatch size.  MLGGD_ERR_ARG: n or steps_before < 0, a
+ * NULL array with n > 0, betas or eps mlggd_set_optimizer would refuse. */
+int mlggd_adam_apply(float *w, float *m, float *v, const float *G, int64_t n, float nf, float weightcost, float lrate, float beta1,
+                     float beta2, float eps, int64_t steps_before);
+/* Host only, no device.  The state as a binary little-endian file (host/optfile.h states the format): a magic word, a
+ * version, the layer sizes, the betas, eps and steps, then m and v per layer, unpadded.  The pointer arrays have slot 0
+ * unused.  mlggd_read_optimizer_header returns the sizes (layersizes: room for MLGGD_MAXLAYER) so that a caller can
+ * allocate; mlggd_read_optimizer_state is told the sizes it expects and refuses a file for another net naming both.
+ * A file that ends early, bytes behind the last array, another magic or version and a file that cannot be read or
+ * written are MLGGD_ERR_ARG with "PATH: ..." as the message. */
+int mlggd_write_optimizer_state(const char *path, int numlayers, const int32_t *layersizes, const float *const *m_w,
+                                const float *const *v_w, const float *const *m_b, const float *const *v_b, float beta1, float beta2,
+                                float eps, int64_t steps);
+int mlggd_read_optimizer_header(const char *path, int32_t *numlayers, int32_t *layersizes, float *beta1, float *beta2, float *eps,
+                                int64_t *steps);
+int mlggd_read_optimizer_state(const char *path, int numlayers, const int32_t *layersizes, float *const *m_w, float *const *v_w,
+                               float *const *m_b, float *const *v_b, float *beta1, float *beta2, float *eps, int64_t *steps);
+
 /* ---- global variance equalisation (Xu, Du, Dai and Lee 2015; no counterpart in the reference).  A regression net
  * trained under MMSE or ML over-smooths: per bin the variance of its output is smaller than the clean target's.  The
  * post-filter is one factor per bin (or one for all bins) multiplied onto the NORMALISED network output before it is

@@ -87,6 +87,8 @@ EXPORTS = [
     "mlggd_asym_fit", "mlggd_read_asymmetry",
     "mlggd_set_scale_mode", "mlggd_get_scale_mode", "mlggd_get_scale_state", "mlggd_set_scale_state",
     "mlggd_read_scale_state", "mlggd_write_scale_state",
+    "mlggd_set_optimizer", "mlggd_get_optimizer", "mlggd_get_optimizer_state", "mlggd_set_optimizer_state", "mlggd_adam_apply",
+    "mlggd_write_optimizer_state", "mlggd_read_optimizer_header", "mlggd_read_optimizer_state",
     "mlggd_rbm_open", "mlggd_rbm_set_rates", "mlggd_rbm_train_chunk", "mlggd_rbm_train_frames", "mlggd_rbm_visible_bias",
     "mlggd_rbm_debug_tensor", "mlggd_rbm_close", "mlggd_rbm_draws",
 ]
@@ -99,12 +101,13 @@ def build(force=False):
     """Compile libmlggd.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(_CSRC, f) for f in ("engine.hip", "kernels.hip.h", "kernels64.hip.h", "spectral.hip.h", "score.hip.h", "live.hip.h",
                                              "live_rule.h", "stoi.hip.h", "stoi_rule.h", "colstats.hip.h", "gv_rule.h", "mask_rule.h", "mask.hip.h", "mix.hip.h",
-                                             "mix_rule.h", "nat_rule.h", "rbm_rule.h", "rbm.hip.h", "asym_rule.h", "scale_rule.h", "devbuf.h", "devbuf_rule.h")]
+                                             "mix_rule.h", "nat_rule.h", "rbm_rule.h", "rbm.hip.h", "asym_rule.h", "scale_rule.h", "adam_rule.h", "devbuf.h", "devbuf_rule.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "mlggd.h"))
     srcs.append(os.path.join(_HERE, "host", "errmodel.h"))
     srcs.append(os.path.join(_HERE, "host", "gvfile.h"))
     srcs.append(os.path.join(_HERE, "host", "asymfile.h"))
     srcs.append(os.path.join(_HERE, "host", "scalefile.h"))
+    srcs.append(os.path.join(_HERE, "host", "optfile.h"))
     srcs.append(os.path.join(_HERE, "host", "binfile.h"))
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(LIB_PATH) < os.path.getmtime(s) for s in srcs)
@@ -213,6 +216,15 @@ def load():
     L.mlggd_set_scale_state.argtypes = [C.c_void_p, _fp, _fp]
     L.mlggd_read_scale_state.argtypes = [C.c_char_p, C.c_int, _fp, _fp]
     L.mlggd_write_scale_state.argtypes = [C.c_char_p, C.c_int, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_int64]
+    _i64p = C.POINTER(C.c_int64)
+    L.mlggd_set_optimizer.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float]
+    L.mlggd_get_optimizer.argtypes = [C.c_void_p, C.POINTER(C.c_int), _fp, _fp, _fp, _i64p]
+    L.mlggd_get_optimizer_state.argtypes = [C.c_void_p, _fpp, _fpp, _fpp, _fpp]
+    L.mlggd_set_optimizer_state.argtypes = [C.c_void_p, _fpp, _fpp, _fpp, _fpp, C.c_int64]
+    L.mlggd_adam_apply.argtypes = [_fp, _fp, _fp, _fp, C.c_int64] + [C.c_float] * 6 + [C.c_int64]
+    L.mlggd_write_optimizer_state.argtypes = [C.c_char_p, C.c_int, _ip, _fpp, _fpp, _fpp, _fpp, C.c_float, C.c_float, C.c_float, C.c_int64]
+    L.mlggd_read_optimizer_header.argtypes = [C.c_char_p, _ip, _ip, _fp, _fp, _fp, _i64p]
+    L.mlggd_read_optimizer_state.argtypes = [C.c_char_p, C.c_int, _ip, _fpp, _fpp, _fpp, _fpp, _fp, _fp, _fp, _i64p]
     L.mlggd_output_stats.argtypes = [C.c_void_p, C.c_int, _fp, _fp, _dp]
     L.mlggd_output_stats_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, _fp, _fp, C.c_int, _ip, C.c_int, _dp]
     L.mlggd_gv_fit.argtypes = [C.c_int, C.c_int64, _dp, _dp, _dp, _fp, _bp, _dp, _dp, _fp, _ip]
@@ -740,6 +752,67 @@ def write_scale_state(path, alpha, velocity=None, lrate=0.05, momentum=0.5, vmax
     v = None if velocity is None else _f32(velocity, (a.size,))
     _check(load().mlggd_write_scale_state(None if path is None else os.fsencode(path), a.size, _p(a), None if v is None else _p(v),
                                           float(lrate), float(momentum), float(vmax), int(steps)))
+
+
+OPTIMIZERS = ("sgd", "adam")  # MLGGD_OPT_SGD = 0, MLGGD_OPT_ADAM = 1 (include/mlggd.h)
+Optimizer = collections.namedtuple("Optimizer", "name beta1 beta2 eps steps")
+OptimizerState = collections.namedtuple("OptimizerState", "m_w v_w m_b v_b steps")
+OptimizerFile = collections.namedtuple("OptimizerFile", "layersizes beta1 beta2 eps steps m_w v_w m_b v_b")
+
+
+def optimizer_code(name):
+    if name not in OPTIMIZERS:
+        raise ValueError("optimizer %r: must be one of %s" % (name, ", ".join(OPTIMIZERS)))
+    return OPTIMIZERS.index(name)
+
+
+def adam_apply(w, m, v, G, nf, weightcost, lrate, beta1=0.9, beta2=0.999, eps=1e-8, steps=0):
+    """One Adam update of the arrays (w, m, v) from the summed gradient G of a minibatch of nf frames, `steps` updates
+    having been taken before: the rule of csrc/adam_rule.h compiled for the host (mlggd_adam_apply), the statements the
+    device launch runs.  Returns new (w, m, v), float32 in w's shape; the inputs are not written.  Needs no device."""
+    w, m, v, G = (np.array(a, dtype=np.float32, order="C") for a in (w, m, v, G))
+    if not (w.shape == m.shape == v.shape == G.shape):
+        raise ValueError("w, m, v and G must have one shape")
+    _check(load().mlggd_adam_apply(_p(w), _p(m), _p(v), _p(G), w.size, float(nf), float(weightcost), float(lrate), float(beta1),
+                                   float(beta2), float(eps), int(steps)))
+    return w, m, v
+
+
+def _moment_arrays(layersizes):
+    L = len(layersizes)
+    return ([np.empty((layersizes[l], layersizes[l + 1]), np.float32) for l in range(L - 1)],
+            [np.empty(layersizes[l + 1], np.float32) for l in range(L - 1)])
+
+
+def write_optimizer_state(path, layersizes, m_w, v_w, m_b, v_b, beta1=0.9, beta2=0.999, eps=1e-8, steps=0):
+    """The Adam state as the binary file the trainer's MLGGD_OPT_FILE holds (host/optfile.h): the moments of every layer,
+    unpadded, in returnWeights' shapes, behind a header with the layer sizes, the betas, eps and steps.  A host call:
+    needs no device (mlggd_write_optimizer_state)."""
+    ls = [int(x) for x in layersizes]
+    L = len(ls)
+    arrs = []
+    for name, group, wide in (("m_w", m_w, True), ("v_w", v_w, True), ("m_b", m_b, False), ("v_b", v_b, False)):
+        if len(group) != max(L - 1, 0):
+            raise ValueError("%s: %d arrays for %d layers" % (name, len(group), L))
+        arrs.append([_f32(a, (ls[l], ls[l + 1]) if wide else (ls[l + 1],)) for l, a in enumerate(group)])
+    lsa = (C.c_int32 * max(L, 1))(*ls)
+    _check(load().mlggd_write_optimizer_state(None if path is None else os.fsencode(path), L, lsa, *[_ptr_array(a) for a in arrs],
+                                              float(beta1), float(beta2), float(eps), int(steps)))
+
+
+def read_optimizer_state(path):
+    """OptimizerFile(layersizes, beta1, beta2, eps, steps, m_w, v_w, m_b, v_b) from the file write_optimizer_state or
+    the trainer's MLGGD_OPT_FILE writes.  A host call: needs no device; a file that is cut, of another version or not
+    such a file raises MlggdError naming what is wrong."""
+    fn = None if path is None else os.fsencode(path)
+    n, lsa = C.c_int32(0), (C.c_int32 * MAXLAYER)()
+    _check(load().mlggd_read_optimizer_header(fn, C.byref(n), lsa, None, None, None, None))
+    ls = [int(lsa[i]) for i in range(n.value)]
+    (m_w, m_b), (v_w, v_b) = _moment_arrays(ls), _moment_arrays(ls)
+    b1, b2, eps, st = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int64(0)
+    _check(load().mlggd_read_optimizer_state(fn, len(ls), lsa, _ptr_array(m_w), _ptr_array(v_w), _ptr_array(m_b), _ptr_array(v_b),
+                                             C.byref(b1), C.byref(b2), C.byref(eps), C.byref(st)))
+    return OptimizerFile(ls, b1.value, b2.value, eps.value, st.value, m_w, v_w, m_b, v_b)
 
 
 GvFit = collections.namedtuple("GvFit","gv_est gv_ref eta fitted gv_est_shared gv_ref_shared eta_shared fitted_shared")
@@ -1427,6 +1500,41 @@ class BPGpu:
         v = None if velocity is None else _f32(velocity, (self.D,))
         _check(load().mlggd_set_scale_state(self._h, _p(a), None if v is None else _p(v)))
 
+    def set_optimizer(self, name="adam", beta1=0.9, beta2=0.999, eps=1e-8):
+        """The weight rule of the steps to come (csrc/adam_rule.h, mlggd_set_optimizer).  "sgd", the default of every
+        engine: the reference's SGD with momentum and L2.  "adam": two moments per weight and bias on the device, g = G / n
+        + weightcost w, m' = beta1 m + (1 - beta1) g, v' = beta2 v + (1 - beta2) g g, w' = w - a_t m' / (sqrt(v') + eps)
+        with the bias correction in a_t; lrate (and set_lrate) is the Adam rate, momentum is ignored.  Entering "adam"
+        -- also from "adam" -- zeroes the moments and the step count; the SGD momentum buffers are left alone, so "sgd"
+        continues from the deltas it had.  Single device only.  No default here has been evaluated on speech."""
+        _check(load().mlggd_set_optimizer(self._h, optimizer_code(name), float(beta1), float(beta2), float(eps)))
+
+    def optimizer(self):
+        """Optimizer(name, beta1, beta2, eps, steps) in effect (mlggd_get_optimizer); steps counts the Adam updates."""
+        k, st = C.c_int(0), C.c_int64(0)
+        b1, b2, ep = C.c_float(0), C.c_float(0), C.c_float(0)
+        _check(load().mlggd_get_optimizer(self._h, C.byref(k), C.byref(b1), C.byref(b2), C.byref(ep), C.byref(st)))
+        return Optimizer(OPTIMIZERS[k.value], b1.value, b2.value, ep.value, st.value)
+
+    def optimizer_state(self):
+        """OptimizerState(m_w, v_w, m_b, v_b, steps): the Adam moments of every layer, unpadded, in returnWeights' shapes
+        (mlggd_get_optimizer_state)."""
+        ls = self.layersizes[:self.numlayers]
+        (m_w, m_b), (v_w, v_b) = _moment_arrays(ls), _moment_arrays(ls)
+        _check(load().mlggd_get_optimizer_state(self._h, _ptr_array(m_w), _ptr_array(v_w), _ptr_array(m_b), _ptr_array(v_b)))
+        return OptimizerState(m_w, v_w, m_b, v_b, self.optimizer().steps)
+
+    def set_optimizer_state(self, m_w, v_w, m_b, v_b, steps):
+        """Set the Adam moments and the number of updates they stand for (mlggd_set_optimizer_state): with the weights,
+        what a run needs to continue as if it had not been interrupted."""
+        n = self.numlayers - 1
+        ws = lambda g: [_f32(a, (self.layersizes[l], self.layersizes[l + 1])) for l, a in enumerate(g)]
+        bs = lambda g: [_f32(a, (self.layersizes[l + 1],)) for l, a in enumerate(g)]
+        if not (len(m_w) == len(v_w) == len(m_b) == len(v_b) == n):
+            raise ValueError("expected %d arrays of each kind" % n)
+        mw, vw, mb, vb = ws(m_w), ws(v_w), bs(m_b), bs(v_b)
+        _check(load().mlggd_set_optimizer_state(self._h, _ptr_array(mw), _ptr_array(vw), _ptr_array(mb), _ptr_array(vb), int(steps)))
+
     def shapefactors(self):
         """The D shapes in effect: the vector of set_shapefactors, else `shapefactor` D times."""
         b = np.empty(self.D, np.float32)
@@ -1470,8 +1578,10 @@ class BPGpu:
             shape = (self.bunchsize, self.layersizes[layer])
         elif name in ("weights", "delta_w", "grad_w"):
             shape = (self.layersizes[layer - 1], self.layersizes[layer])
-        elif name in ("bias", "delta_b"):
+        elif name in ("bias", "delta_b", "grad_b"):
             shape = (self.layersizes[layer],)
+        elif name == "adam_pads":  # counts of pad entries that are not zero: W, m_w, v_w, bias, m_b, v_b
+            shape = (6,)
         else:
             raise KeyError(name)
         a = np.empty(shape, np.float32)

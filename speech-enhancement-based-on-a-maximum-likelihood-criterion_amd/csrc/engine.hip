@@ -26,6 +26,7 @@
 #include "../host/gvfile.h"    // parse_gv: the same for the global variance file
 #include "../host/asymfile.h"  // parse_asymmetry: the same for the asymmetric error model's file
 #include "../host/scalefile.h"  // parse_scale_state / write_scale_state: the learned scale's state file
+#include "../host/optfile.h"    // read_opt_state / write_opt_state: the optimizer's state file
 #include "kernels.hip.h"
 #include "spectral.hip.h"
 #include "score.hip.h"
@@ -226,6 +227,17 @@ struct mlggd_engine {
     DevBuf<float> scale_state;
     int scale_cur = 0;
     long long scale_steps = 0;
+    // mlggd_set_optimizer: Adam beside SGD with momentum (adam_rule.h).  Entering the mode allocates, per layer, the two
+    // moments of the padded weight matrix and of the bias (zero pads that stay zero) and the gradient buffers G_l / gb_l
+    // the unfused dW launches write (the all-reduce exchange's own, which a single-device engine does not have); a step
+    // then ends with one k_adam_apply launch over all of them.  adam_steps counts the updates, adam_prod holds
+    // beta1^steps and beta2^steps as running products in double.  Nothing here exists on an engine that never entered it.
+    int opt_kind = MLGGD_OPT_SGD;
+    float adam_b1 = adam_rule::kBeta1, adam_b2 = adam_rule::kBeta2, adam_eps = adam_rule::kEps;
+    long long adam_steps = 0;
+    adam_rule::Products adam_prod;
+    DevBuf<float> adam_mw[MLGGD_MAXLAYER], adam_vw[MLGGD_MAXLAYER], adam_mb[MLGGD_MAXLAYER], adam_vb[MLGGD_MAXLAYER];
+    DevBuf<float> adam_G[MLGGD_MAXLAYER], adam_gb;
     DevBuf<float> chunk_in, chunk_targ, chunk_out;
     // CV metrics: 0 = outputs copied back, host fp32 accumulation in the reference's order (default: it is what
     // the log lines are compared on); 1 = sums formed on the device (k_cv_reduce), nothing of size n x D leaves it
@@ -1208,6 +1220,44 @@ static BiasJobs make_bias_jobs(mlggd_engine *e) {
     return jobs;
 }
 
+// The Adam update of one step (mlggd_set_optimizer, adam_rule.h): every layer's padded weight matrix, then every
+// bias vector, in one launch.  The counters move when the launch is enqueued: a_t is the launch's argument.
+static_assert(ADAM_MAXJOBS >= 2 * (MLGGD_MAXLAYER - 1), "job table too small");
+static AdamJobs make_adam_jobs(mlggd_engine *e) {
+    AdamJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    int nj = 0;
+    unsigned first = 0;
+    auto add = [&](float *w, float *m, float *v, const float *G, size_t n, float wc) {
+        AdamJob &j = jobs.job[nj++];
+        j.w = w, j.m = m, j.v = v, j.G = G;
+        j.n4 = (unsigned)(n / 4);  // n is a multiple of 32: the padded widths are
+        j.first = first;
+        j.wc = wc;
+        first += (j.n4 + 255u) / 256u;
+    };
+    for (int l = e->L - 1; l >= 1; l--)
+        add(e->W[l], e->adam_mw[l].p, e->adam_vw[l].p, e->G[l], (size_t)e->lsp[l - 1] * e->lsp[l], e->cfg.weightcost);
+    for (int l = e->L - 1; l >= 1; l--) add(e->bias[l], e->adam_mb[l].p, e->adam_vb[l].p, e->gb[l], (size_t)e->lsp[l], 0.0f);
+    jobs.njobs = nj;
+    jobs.chunks = first;
+    return jobs;
+}
+static int run_adam_apply(mlggd_engine *e, float nf) {
+    adam_rule::Products after = e->adam_prod;
+    adam_rule::advance(&after, e->adam_b1, e->adam_b2);
+    const adam_rule::Consts c = adam_rule::consts(nf, e->cfg.lrate, e->adam_b1, e->adam_b2, e->adam_eps, after);
+    const AdamJobs jobs = make_adam_jobs(e);
+    {
+        ProfScope ps(e, KC_UPDATE, 1);
+        hipLaunchKernelGGL(k_adam_apply, dim3(jobs.chunks > 2048u ? 2048u : jobs.chunks), dim3(256), 0, e->stream, jobs, c);
+    }
+    CHK(launch_check("k_adam_apply"));
+    e->adam_prod = after;
+    e->adam_steps++;
+    return MLGGD_OK;
+}
+
 // ---- pieces of one step ----------------------------------------------------------------------------
 // Where the per-dimension sum of |e|^beta of the ML loss (BP_GPU.cu:416) comes from:
 enum ColsumSource {
@@ -1604,7 +1654,10 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
     // single GPU: every dW(l) only needs dEdX_l and Y_{l-1}, so one persistent launch walks the
     // tiles of all layers after the last dX (the data-parallel path keeps one launch per layer so
     // that the all-reduce of layer l overlaps the rest of the backward pass)
-    const bool merged = (!dp && e->dw_merge && dwp_usable(e)) || gather;
+    // Adam (single device only): the dW launches of the all-reduce exchange, unfused and one per layer, write G_l / gb_l
+    // and k_adam_apply ends the step
+    const bool adam = e->opt_kind == MLGGD_OPT_ADAM;
+    const bool merged = (!dp && !adam && e->dw_merge && dwp_usable(e)) || gather;
     int pending_hi = L - 1;  // gather mode: dEdX_l for l in [l .. pending_hi] are final and not yet sent
     bool mainline_done = false;  // the last factor group went out on the main stream: the dW launch needs no further event
     for (int l = L - 1; l >= 1; l--) {
@@ -1640,7 +1693,7 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
         if (l != 1) CHK(run_dx(e, l));
         if (merged) continue;  // all layers' dW + update run as one launch after the last dX
         if (dp && !gather) arm_stop(e, e->ev_grad[l]);  // "G_l written" rides on the launch that writes it
-        CHK(launch_dw_layer(e, l, in_rows, !dp, nf));
+        CHK(launch_dw_layer(e, l, in_rows, !dp && !adam, nf));
         if (dp && !gather) {
             if (!take_stop(e)) HIPCHK(hipEventRecord(e->ev_grad[l], e->stream));
             HIPCHK(hipStreamWaitEvent(e->comm_stream, e->ev_grad[l], 0));
@@ -1792,6 +1845,7 @@ static int run_step(mlggd_engine *e, int sample0, bool prestaged = false, const 
             }
         }
     }
+    if (adam) CHK(run_adam_apply(e, nf));
     e->step_counter++;
     return MLGGD_OK;
 }
@@ -2105,6 +2159,190 @@ int mlggd_write_scale_state(const char *path, int D, const float *alpha, const f
     std::string err;
     const mlggd_host::ScaleFileHeader h = {lrate, momentum, vmax, (long long)steps};
     if (!mlggd_host::write_scale_state(path, D, alpha, velocity, h, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    return MLGGD_OK;
+}
+
+// ------------------------------------------------------------------ Adam beside SGD with momentum (adam_rule.h)
+// the mode's buffers, allocated on first entry; the moments zeroed on the engine's stream, behind every step enqueued
+static int adam_enter(mlggd_engine *e) {
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->adam_gb.p) {
+        size_t gbn = 0;
+        for (int l = 1; l < e->L; l++) gbn += e->lsp[l];
+        HIPCHK(e->adam_gb.grow(gbn, gbn, e->bufs, &e->stream, nullptr));
+        e->gb_all = e->adam_gb.p;
+        e->gb_all_count = gbn;
+        size_t off = 0;
+        for (int l = e->L - 1; l >= 1; l--) {
+            e->gb[l] = e->gb_all + off;
+            off += e->lsp[l];
+        }
+    }
+    for (int l = 1; l < e->L; l++) {
+        const size_t n = (size_t)e->lsp[l - 1] * e->lsp[l], nb = (size_t)e->lsp[l];
+        if (!e->adam_G[l].p) {  // pads are zero from here on: the dW launches write the real rows and columns only
+            HIPCHK(e->adam_G[l].grow(n, n, e->bufs, &e->stream, nullptr));
+            e->G[l] = e->adam_G[l].p;
+        }
+        HIPCHK(e->adam_mw[l].grow(n, n, e->bufs, nullptr, nullptr));
+        HIPCHK(e->adam_vw[l].grow(n, n, e->bufs, nullptr, nullptr));
+        HIPCHK(e->adam_mb[l].grow(nb, nb, e->bufs, nullptr, nullptr));
+        HIPCHK(e->adam_vb[l].grow(nb, nb, e->bufs, nullptr, nullptr));
+        HIPCHK(hipMemsetAsync(e->adam_mw[l].p, 0, n * sizeof(float), e->stream));
+        HIPCHK(hipMemsetAsync(e->adam_vw[l].p, 0, n * sizeof(float), e->stream));
+        HIPCHK(hipMemsetAsync(e->adam_mb[l].p, 0, nb * sizeof(float), e->stream));
+        HIPCHK(hipMemsetAsync(e->adam_vb[l].p, 0, nb * sizeof(float), e->stream));
+    }
+    return MLGGD_OK;
+}
+
+int mlggd_set_optimizer(mlggd_handle e, int kind, float beta1, float beta2, float eps) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (!adam_rule::valid_kind(kind))
+        return fail(MLGGD_ERR_ARG, "optimizer %d: must be %d (SGD with momentum) or %d (Adam)", kind, MLGGD_OPT_SGD, MLGGD_OPT_ADAM);
+    if (!adam_rule::valid(beta1, beta2, eps))
+        return fail(MLGGD_ERR_ARG, "beta1 %g, beta2 %g, eps %g: betas in [0, 1) and a finite eps > 0 are required", (double)beta1,
+                    (double)beta2, (double)eps);
+    if (kind == MLGGD_OPT_ADAM) {
+        if (e->comm || e->fake_world)
+            return fail(MLGGD_ERR_STATE, "mlggd_set_optimizer: Adam runs on a single-device engine, this one has joined a "
+                        "communicator or an emulated world");
+        CHK(adam_enter(e));
+        e->adam_b1 = beta1, e->adam_b2 = beta2, e->adam_eps = eps;
+        e->adam_steps = 0;
+        e->adam_prod = adam_rule::Products();
+    }
+    // the launches to come: steps already enqueued chose their kernels when they were enqueued.  The SGD momentum
+    // buffers are touched in neither direction.
+    e->opt_kind = kind;
+    return MLGGD_OK;
+}
+
+int mlggd_get_optimizer(mlggd_handle e, int *kind, float *beta1, float *beta2, float *eps, int64_t *steps) {
+    if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
+    if (kind) *kind = e->opt_kind;
+    if (beta1) *beta1 = e->adam_b1;
+    if (beta2) *beta2 = e->adam_b2;
+    if (eps) *eps = e->adam_eps;
+    if (steps) *steps = (int64_t)e->adam_steps;
+    return MLGGD_OK;
+}
+
+int mlggd_get_optimizer_state(mlggd_handle e, float *const *m_w, float *const *v_w, float *const *m_b, float *const *v_b) {
+    if (!e || !m_w || !v_w || !m_b || !v_b) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (e->opt_kind != MLGGD_OPT_ADAM) return fail(MLGGD_ERR_STATE, "mlggd_get_optimizer_state: the optimizer is not Adam");
+    for (int l = 1; l < e->L; l++)
+        if (!m_w[l] || !v_w[l] || !m_b[l] || !v_b[l]) return fail(MLGGD_ERR_ARG, "a moment array of layer %d is NULL", l);
+    HIPCHK(hipSetDevice(e->device));
+    for (int l = 1; l < e->L; l++) {
+        CHK(download_padded(m_w[l], e->adam_mw[l].p, e->lsp[l], e->ls[l - 1], e->ls[l], e->stream));
+        CHK(download_padded(v_w[l], e->adam_vw[l].p, e->lsp[l], e->ls[l - 1], e->ls[l], e->stream));
+        HIPCHK(hipMemcpyAsync(m_b[l], e->adam_mb[l].p, (size_t)e->ls[l] * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(v_b[l], e->adam_vb[l].p, (size_t)e->ls[l] * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return MLGGD_OK;
+}
+
+int mlggd_set_optimizer_state(mlggd_handle e, const float *const *m_w, const float *const *v_w, const float *const *m_b,
+                              const float *const *v_b, int64_t steps) {
+    if (!e || !m_w || !v_w || !m_b || !v_b) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (e->opt_kind != MLGGD_OPT_ADAM) return fail(MLGGD_ERR_STATE, "mlggd_set_optimizer_state: the optimizer is not Adam");
+    if (steps < 0) return fail(MLGGD_ERR_ARG, "steps %lld < 0", (long long)steps);
+    for (int l = 1; l < e->L; l++) {
+        if (!m_w[l] || !v_w[l] || !m_b[l] || !v_b[l]) return fail(MLGGD_ERR_ARG, "a moment array of layer %d is NULL", l);
+        const size_t n = (size_t)e->ls[l - 1] * e->ls[l], nb = (size_t)e->ls[l];
+        for (size_t i = 0; i < n + nb; i++) {
+            const float m = i < n ? m_w[l][i] : m_b[l][i - n], v = i < n ? v_w[l][i] : v_b[l][i - n];
+            if (!std::isfinite(m) || !std::isfinite(v) || v < 0.0f)
+                return fail(MLGGD_ERR_ARG, "layer %d, %s %zu: m = %g, v = %g -- a first moment must be finite, a second moment "
+                            "finite and not negative", l, i < n ? "weight" : "bias", i < n ? i : i - n, (double)m, (double)v);
+        }
+    }
+    HIPCHK(hipSetDevice(e->device));
+    // on the engine's stream: behind every step already enqueued.  The pads of the device arrays are not touched.
+    for (int l = 1; l < e->L; l++) {
+        CHK(upload_padded(e->adam_mw[l].p, e->lsp[l], m_w[l], e->ls[l - 1], e->ls[l], e->stream));
+        CHK(upload_padded(e->adam_vw[l].p, e->lsp[l], v_w[l], e->ls[l - 1], e->ls[l], e->stream));
+        HIPCHK(hipMemcpyAsync(e->adam_mb[l].p, m_b[l], (size_t)e->ls[l] * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->adam_vb[l].p, v_b[l], (size_t)e->ls[l] * 4, hipMemcpyHostToDevice, e->stream));
+    }
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->adam_steps = (long long)steps;
+    e->adam_prod = adam_rule::products(e->adam_b1, e->adam_b2, steps);
+    return MLGGD_OK;
+}
+
+int mlggd_adam_apply(float *w, float *m, float *v, const float *G, int64_t n, float nf, float weightcost, float lrate, float beta1,
+                     float beta2, float eps, int64_t steps_before) {
+    if (n < 0 || steps_before < 0) return fail(MLGGD_ERR_ARG, "n %lld or steps_before %lld < 0", (long long)n, (long long)steps_before);
+    if (n > 0 && (!w || !m || !v || !G)) return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (!adam_rule::valid(beta1, beta2, eps))
+        return fail(MLGGD_ERR_ARG, "beta1 %g, beta2 %g, eps %g: betas in [0, 1) and a finite eps > 0 are required", (double)beta1,
+                    (double)beta2, (double)eps);
+    const int64_t t = steps_before == INT64_MAX ? INT64_MAX : steps_before + 1;  // the products are spent long before
+    const adam_rule::Consts c = adam_rule::consts(nf, lrate, beta1, beta2, eps, adam_rule::products(beta1, beta2, t));
+    for (int64_t i = 0; i < n; i++) {
+        const adam_rule::Moments r = adam_rule::step(w[i], m[i], v[i], G[i], weightcost, c);
+        w[i] = r.w, m[i] = r.m, v[i] = r.v;
+    }
+    return MLGGD_OK;
+}
+
+int mlggd_write_optimizer_state(const char *path, int numlayers, const int32_t *layersizes, const float *const *m_w,
+                                const float *const *v_w, const float *const *m_b, const float *const *v_b, float beta1, float beta2,
+                                float eps, int64_t steps) {
+    if (!path || (numlayers > 0 && !layersizes) || (numlayers > 1 && (!m_w || !v_w || !m_b || !v_b)))
+        return fail(MLGGD_ERR_ARG, "NULL argument");
+    if (!adam_rule::valid(beta1, beta2, eps))
+        return fail(MLGGD_ERR_ARG, "beta1 %g, beta2 %g, eps %g: betas in [0, 1) and a finite eps > 0 are required", (double)beta1,
+                    (double)beta2, (double)eps);
+    for (int l = 1; l < numlayers; l++)
+        if (!m_w[l] || !v_w[l] || !m_b[l] || !v_b[l]) return fail(MLGGD_ERR_ARG, "a moment array of layer %d is NULL", l);
+    std::string err;
+    const std::vector<int> ls(layersizes, layersizes + (numlayers > 0 ? numlayers : 0));
+    if (!mlggd_host::write_opt_state(path, numlayers, ls.data(), beta1, beta2, eps, (long long)steps, m_w, v_w, m_b, v_b, &err))
+        return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    return MLGGD_OK;
+}
+
+int mlggd_read_optimizer_header(const char *path, int32_t *numlayers, int32_t *layersizes, float *beta1, float *beta2, float *eps,
+                                int64_t *steps) {
+    if (!path || !numlayers || !layersizes) return fail(MLGGD_ERR_ARG, "NULL argument");
+    mlggd_host::OptState s;
+    std::string err;
+    if (!mlggd_host::read_opt_header(path, &s, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    if (s.layersizes.size() > (size_t)MLGGD_MAXLAYER)
+        return fail(MLGGD_ERR_ARG, "%s: %zu layers, an engine has at most %d", path, s.layersizes.size(), MLGGD_MAXLAYER);
+    *numlayers = (int32_t)s.layersizes.size();
+    for (size_t l = 0; l < s.layersizes.size(); l++) layersizes[l] = s.layersizes[l];
+    if (beta1) *beta1 = s.beta1;
+    if (beta2) *beta2 = s.beta2;
+    if (eps) *eps = s.eps;
+    if (steps) *steps = (int64_t)s.steps;
+    return MLGGD_OK;
+}
+
+int mlggd_read_optimizer_state(const char *path, int numlayers, const int32_t *layersizes, float *const *m_w, float *const *v_w,
+                               float *const *m_b, float *const *v_b, float *beta1, float *beta2, float *eps, int64_t *steps) {
+    if (!path || numlayers < 0 || (numlayers > 0 && !layersizes) || (numlayers > 1 && (!m_w || !v_w || !m_b || !v_b)))
+        return fail(MLGGD_ERR_ARG, "NULL argument");
+    for (int l = 1; l < numlayers; l++)
+        if (!m_w[l] || !v_w[l] || !m_b[l] || !v_b[l]) return fail(MLGGD_ERR_ARG, "a moment array of layer %d is NULL", l);
+    mlggd_host::OptState s;
+    std::string err;
+    const std::vector<int> ls(layersizes, layersizes + numlayers);
+    if (!mlggd_host::read_opt_state(path, ls.data(), numlayers, &s, &err)) return fail(MLGGD_ERR_ARG, "%s", err.c_str());
+    for (int l = 1; l < numlayers; l++) {
+        memcpy(m_w[l], s.m_w[l - 1].data(), s.m_w[l - 1].size() * sizeof(float));
+        memcpy(v_w[l], s.v_w[l - 1].data(), s.v_w[l - 1].size() * sizeof(float));
+        memcpy(m_b[l], s.m_b[l - 1].data(), s.m_b[l - 1].size() * sizeof(float));
+        memcpy(v_b[l], s.v_b[l - 1].data(), s.v_b[l - 1].size() * sizeof(float));
+    }
+    if (beta1) *beta1 = s.beta1;
+    if (beta2) *beta2 = s.beta2;
+    if (eps) *eps = s.eps;
+    if (steps) *steps = (int64_t)s.steps;
     return MLGGD_OK;
 }
 
@@ -3127,6 +3365,35 @@ int mlggd_debug_tensor(mlggd_handle e, const char *name, int layer, float *dst, 
         HIPCHK(hipStreamSynchronize(e->stream));
         return MLGGD_OK;
     }
+    if (nm == "grad_b") {
+        if (!e->gb[layer]) return fail(MLGGD_ERR_STATE, "tensor %s does not exist on this path", name);
+        CHK(need(N));
+        HIPCHK(hipMemcpyAsync(dst, e->gb[layer], (size_t)N * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        return MLGGD_OK;
+    }
+    if (nm == "adam_pads") {  // how many pad entries of W, m_w, v_w, bias, m_b, v_b of the layer are not (+-)0: [6]
+        if (e->opt_kind != MLGGD_OPT_ADAM) return fail(MLGGD_ERR_STATE, "tensor %s does not exist on this path", name);
+        CHK(need(6));
+        const int Kp = e->lsp[layer - 1];
+        const float *mats[3] = {e->W[layer], e->adam_mw[layer].p, e->adam_vw[layer].p};
+        const float *vecs[3] = {e->bias[layer], e->adam_mb[layer].p, e->adam_vb[layer].p};
+        std::vector<float> t((size_t)Kp * Np);
+        for (int a = 0; a < 3; a++) {
+            HIPCHK(hipMemcpyAsync(t.data(), mats[a], t.size() * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            size_t bad = 0;
+            for (int k = 0; k < Kp; k++)
+                for (int n = 0; n < Np; n++) bad += (k >= K || n >= N) && t[(size_t)k * Np + n] != 0.0f;
+            dst[a] = (float)bad;
+            HIPCHK(hipMemcpyAsync(t.data(), vecs[a], (size_t)Np * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipStreamSynchronize(e->stream));
+            bad = 0;
+            for (int n = N; n < Np; n++) bad += t[n] != 0.0f;
+            dst[3 + a] = (float)bad;
+        }
+        return MLGGD_OK;
+    }
     if (nm == "bias" || nm == "delta_b") {
         CHK(need(N));
         HIPCHK(hipMemcpyAsync(dst, nm == "bias" ? e->bias[layer] : e->dbias[layer], (size_t)N * 4,
@@ -3265,6 +3532,7 @@ int mlggd_comm_init(mlggd_handle e, const void *id, int world_size, int rank) {
         return fail(MLGGD_ERR_ARG, "rank %d / world_size %d invalid", rank, world_size);
     if (e->comm) return fail(MLGGD_ERR_STATE, "communicator already initialised");
     if (e->nat_frames > 0) return fail(MLGGD_ERR_STATE, "mlggd_comm_init: an engine with nat_frames = %d runs on a single device", e->nat_frames);
+    if (e->opt_kind == MLGGD_OPT_ADAM) return fail(MLGGD_ERR_STATE, "mlggd_comm_init: an engine whose optimizer is Adam runs on a single device");
     if (e->cfg.dropoutflag == 1 && world_size > 1)
         return fail(MLGGD_ERR_ARG, "dropout is not supported on the data-parallel path");
     // the exchange mode first: a request the shape rules out must fail BEFORE a communicator exists (every rank takes
@@ -3320,6 +3588,7 @@ int mlggd_debug_fake_world(mlggd_handle e, int world_size, int mode) {
     if (!e) return fail(MLGGD_ERR_ARG, "NULL handle");
     if (e->comm || e->fake_world) return fail(MLGGD_ERR_STATE, "communicator already initialised");
     if (e->nat_frames > 0) return fail(MLGGD_ERR_STATE, "mlggd_debug_fake_world: an engine with nat_frames = %d runs on a single device", e->nat_frames);
+    if (e->opt_kind == MLGGD_OPT_ADAM) return fail(MLGGD_ERR_STATE, "mlggd_debug_fake_world: an engine whose optimizer is Adam runs on a single device");
     if (mode < 0 || mode > 3) return fail(MLGGD_ERR_ARG, "mode %d not in 0..3", mode);
     if (world_size < 1 || (mode != 2 && !gather_usable(e, world_size)))
         return fail(MLGGD_ERR_ARG, "fake world of %d ranks: needs bunchsize %% 32 == 0 and world*bunchsize in {64,...,1024}", world_size);
@@ -3537,7 +3806,7 @@ int mlggd_profile_overhead(mlggd_handle e, float *usec) {
 int mlggd_dw_launches_per_step(mlggd_handle e, int *launches) {
     if (!e || !launches) return fail(MLGGD_ERR_ARG, "NULL argument");
     const bool dp = e->comm != nullptr || e->fake_world;
-    const bool merged = (!dp && e->dw_merge && dwp_usable(e)) || (dp && e->dp_mode >= 1);
+    const bool merged = (!dp && e->opt_kind != MLGGD_OPT_ADAM && e->dw_merge && dwp_usable(e)) || (dp && e->dp_mode >= 1);
     const bool fine = dp && e->dp_mode == 1 && e->dp_fine != 0 && e->L - 1 >= 2;
     *launches = fine ? 2 : merged ? 1 : e->L - 1;
     return MLGGD_OK;

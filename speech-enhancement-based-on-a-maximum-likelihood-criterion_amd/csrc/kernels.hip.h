@@ -19,6 +19,7 @@
 #include "nat_rule.h"
 #include "asym_rule.h"
 #include "scale_rule.h"
+#include "adam_rule.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -1592,6 +1593,50 @@ __global__ __launch_bounds__(256) void k_bias_apply(BiasJobs jobs, float nf, flo
     const float d = mom * jb.dbias[n] - lr * (jb.gb[n] / nf + 0.0f * bv);
     jb.dbias[n] = d;
     jb.bias[n] = d + 1.0f * bv;
+}
+
+// ---------------------------------------------------------------------------------------
+// The Adam rule (adam_rule.h, mlggd_set_optimizer) on every layer's padded weight matrix and every bias vector in one
+// launch, from the gradients the unfused dW launches wrote: reads G, W, m, v, writes W, m, v, 16 bytes per lane and
+// array.  A job is one array of n4 float4 (a whole padded [Kp][Np] matrix, or the Np entries of a bias: pads hold
+// G = w = m = v = 0 and stay 0); the jobs' chunks of 256 float4 are numbered through, `first` being a job's first chunk,
+// so a workgroup's chunk belongs to one job and the look-up is scalar.  Grid-stride over the chunks under a capped grid.
+// ---------------------------------------------------------------------------------------
+#define ADAM_MAXJOBS 18  // 2 (MLGGD_MAXLAYER - 1): weights and bias of every layer
+struct AdamJob {
+    float *w, *m, *v;
+    const float *G;
+    unsigned n4;     // float4 of the array
+    unsigned first;  // chunks of 256 float4 in front of this job
+    float wc;        // weightcost; 0 for a bias
+    int pad_;
+};
+struct AdamJobs {
+    AdamJob job[ADAM_MAXJOBS];
+    int njobs;
+    unsigned chunks;  // of all jobs
+};
+
+__global__ __launch_bounds__(256) void k_adam_apply(AdamJobs jobs, adam_rule::Consts c) {
+    for (unsigned ch = blockIdx.x; ch < jobs.chunks; ch += gridDim.x) {
+        int j = 0;
+        for (int q = 1; q < jobs.njobs; q++)
+            if (ch >= jobs.job[q].first) j = q;
+        const AdamJob jb = jobs.job[j];
+        const unsigned idx = (ch - jb.first) * 256u + threadIdx.x;
+        if (idx >= jb.n4) continue;
+        const float4 g = reinterpret_cast<const float4 *>(jb.G)[idx];
+        float4 w = reinterpret_cast<float4 *>(jb.w)[idx];
+        float4 m = reinterpret_cast<float4 *>(jb.m)[idx];
+        float4 v = reinterpret_cast<float4 *>(jb.v)[idx];
+        const adam_rule::Moments x = adam_rule::step(w.x, m.x, v.x, g.x, jb.wc, c);
+        const adam_rule::Moments y = adam_rule::step(w.y, m.y, v.y, g.y, jb.wc, c);
+        const adam_rule::Moments z = adam_rule::step(w.z, m.z, v.z, g.z, jb.wc, c);
+        const adam_rule::Moments u = adam_rule::step(w.w, m.w, v.w, g.w, jb.wc, c);
+        reinterpret_cast<float4 *>(jb.w)[idx] = make_float4(x.w, y.w, z.w, u.w);
+        reinterpret_cast<float4 *>(jb.m)[idx] = make_float4(x.m, y.m, z.m, u.m);
+        reinterpret_cast<float4 *>(jb.v)[idx] = make_float4(x.v, y.v, z.v, u.v);
+    }
 }
 
 // ---------------------------------------------------------------------------------------

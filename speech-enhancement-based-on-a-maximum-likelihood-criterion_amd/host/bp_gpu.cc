@@ -145,6 +145,20 @@ long long BP_GPU::scaleSteps() {
     check(mlggd_get_scale_mode(h_, nullptr, nullptr, nullptr, nullptr, &steps), "mlggd_get_scale_mode");
     return (long long)steps;
 }
+void BP_GPU::setOptimizerAdam(float beta1, float beta2, float eps) {
+    check(mlggd_set_optimizer(h_, MLGGD_OPT_ADAM, beta1, beta2, eps), "mlggd_set_optimizer");
+}
+void BP_GPU::getOptimizerState(float **m_w, float **v_w, float **m_b, float **v_b) {
+    check(mlggd_get_optimizer_state(h_, m_w, v_w, m_b, v_b), "mlggd_get_optimizer_state");
+}
+void BP_GPU::setOptimizerState(float **m_w, float **v_w, float **m_b, float **v_b, long long steps) {
+    check(mlggd_set_optimizer_state(h_, m_w, v_w, m_b, v_b, (int64_t)steps), "mlggd_set_optimizer_state");
+}
+long long BP_GPU::optimizerSteps() {
+    int64_t steps = 0;
+    check(mlggd_get_optimizer(h_, nullptr, nullptr, nullptr, nullptr, &steps), "mlggd_get_optimizer");
+    return (long long)steps;
+}
 void BP_GPU::returnWeights(float **weights, float **bias) {
     check(mlggd_get_weights(h_, weights, bias), "mlggd_get_weights");
 }

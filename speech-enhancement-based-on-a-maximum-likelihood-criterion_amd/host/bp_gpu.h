@@ -56,6 +56,12 @@ class BP_GPU {
     void getScaleState(float *alpha, float *velocity);
     void setScaleState(const float *alpha, const float *velocity);
     long long scaleSteps();
+    // (new, opt-in; not in the reference) Adam beside SGD with momentum (mlggd_set_optimizer with MLGGD_OPT_ADAM): the
+    // moments in returnWeights' shapes and pointer arrays (slot 0 unused), and the updates taken
+    void setOptimizerAdam(float beta1, float beta2, float eps);
+    void getOptimizerState(float **m_w, float **v_w, float **m_b, float **v_b);
+    void setOptimizerState(float **m_w, float **v_w, float **m_b, float **v_b, long long steps);
+    long long optimizerSteps();
     void returnWeights(float **weights, float **bias);
     float Gamma(float x) { return mlggd_gamma(x); }
     // data parallel (not in the reference): join an RCCL communicator of `world` ranks

@@ -49,6 +49,14 @@
 // after the epoch's CV pass.  One stderr line names the rates and the state's origin, one stdout line the file written.
 // Needs MLflag=1; the log file and the weights' format do not change.
 //
+// Adam (new, opt-in; optfile.h, csrc/adam_rule.h): with MLGGD_OPTIMIZER=adam the engine is switched to Adam before the
+// first chunk (mlggd_set_optimizer; MLGGD_ADAM_BETA1, MLGGD_ADAM_BETA2 and MLGGD_ADAM_EPS are optional); lrate is then the
+// Adam rate and momentum is ignored.  An optimizer with a state is useless across one-process-per-epoch runs unless the
+// state travels too: MLGGD_OPT_FILE=PATH (binary, optfile.h) is read before the first chunk if it exists -- a file for
+// another net ends the run -- and written after the epoch's weights file.  One stderr line names the parameters and the
+// state's origin, one stdout line the file written.  A single rank only: WORLD_SIZE > 1 is refused naming the variable.
+// The log file and the weights' format do not change.
+//
 // Data parallel (new): when WORLD_SIZE > 1 (torchrun-style env: RANK,
 // LOCAL_RANK, WORLD_SIZE; MLGGD_ID_FILE names a file on a shared filesystem used to hand the
 // RCCL unique id from rank 0 to the others) every rank reads the same chunks with the same
@@ -74,6 +82,8 @@
 #include "gvfile.h"
 #include "scalefile.h"
 #include "../csrc/scale_rule.h"
+#include "optfile.h"
+#include "../csrc/adam_rule.h"
 #include "prefetch.h"
 #include "trainer_io.h"
 
@@ -256,6 +266,43 @@ int main(int argc, char *argv[]) {
                     throw IoError("MLGGD_SCALE_FILE: " + why);
             }
         }
+        // MLGGD_OPTIMIZER=adam: a bad value, a bad parameter, several ranks or a bad state file ends the run here, before
+        // anything is trained
+        const char *opt_env = getenv("MLGGD_OPTIMIZER");
+        if (opt_env && !*opt_env) opt_env = nullptr;
+        const char *opt_fn = getenv("MLGGD_OPT_FILE");
+        if (opt_fn && !*opt_fn) opt_fn = nullptr;
+        const bool adam = opt_env && std::string(opt_env) == "adam";
+        float adam_b1 = adam_rule::kBeta1, adam_b2 = adam_rule::kBeta2, adam_eps = adam_rule::kEps;
+        mlggd_host::OptState opt_state;  // what MLGGD_OPT_FILE held
+        bool opt_restored = false;
+        if (opt_env && !adam && std::string(opt_env) != "sgd") throw IoError(std::string("MLGGD_OPTIMIZER=") + opt_env + ": must be adam or sgd");
+        if (opt_fn && !adam) throw IoError(std::string("MLGGD_OPT_FILE=") + opt_fn + ": needs MLGGD_OPTIMIZER=adam");
+        if (adam) {
+            if (world > 1)
+                throw IoError("MLGGD_OPTIMIZER=adam: Adam runs on a single rank, this run has WORLD_SIZE=" + std::to_string(world));
+            auto number = [](const char *name, float *v) {
+                const char *t = getenv(name);
+                if (!t || !*t) return;
+                char *end = nullptr;
+                *v = strtof(t, &end);
+                if (end == t || *end != 0) throw IoError(std::string(name) + "=" + t + ": not a number");
+            };
+            number("MLGGD_ADAM_BETA1", &adam_b1);
+            number("MLGGD_ADAM_BETA2", &adam_b2);
+            number("MLGGD_ADAM_EPS", &adam_eps);
+            if (!adam_rule::valid(adam_b1, adam_b2, adam_eps))
+                throw IoError("MLGGD_OPTIMIZER=adam: MLGGD_ADAM_BETA1 and MLGGD_ADAM_BETA2 must lie in [0, 1), MLGGD_ADAM_EPS must be "
+                              "finite and > 0");
+            FILE *have = opt_fn ? fopen(opt_fn, "rb") : nullptr;  // no file yet: the first epoch starts from zero moments
+            if (have) {
+                fclose(have);
+                std::string why;
+                if (!mlggd_host::read_opt_state(opt_fn, p->layersizes, io->numlayers, &opt_state, &why))
+                    throw IoError("MLGGD_OPT_FILE: " + why);
+                opt_restored = true;
+            }
+        }
         // ---- train (BPtrain.cc:81-102).  The chunk plan and the fetch thread only touch host state, so the
         // first chunk is read while the engine initialises HIP and uploads the weights (the reference creates
         // BP_GPU first, BPtrain.cc:77-78, and reads the first chunk afterwards).
@@ -348,6 +395,24 @@ int main(int argc, char *argv[]) {
                     scale_alpha.empty() ? "" : scale_fn,
                     scale_alpha.empty() ? "" : (" after " + std::to_string(scale_steps0) + " steps").c_str());
         }
+        // [L] pointer arrays with slot 0 unused over a state's vectors, as mlggd_get_weights takes them
+        auto moment_ptrs = [&](std::vector<std::vector<float>> &g) {
+            std::vector<float *> q((size_t)io->numlayers, nullptr);
+            for (int l = 1; l < io->numlayers; l++) q[l] = g[l - 1].data();
+            return q;
+        };
+        if (adam) {
+            net->setOptimizerAdam(adam_b1, adam_b2, adam_eps);
+            if (opt_restored) {
+                // the file's own betas and eps describe the run that wrote it; this run's are the ones in effect
+                std::vector<float *> mw = moment_ptrs(opt_state.m_w), vw = moment_ptrs(opt_state.v_w), mb = moment_ptrs(opt_state.m_b),
+                                     vb = moment_ptrs(opt_state.v_b);
+                net->setOptimizerState(mw.data(), vw.data(), mb.data(), vb.data(), opt_state.steps);
+            }
+            fprintf(stderr, "adam: beta1 %.9g beta2 %.9g eps %.9g, %s%s%s\n", (double)adam_b1, (double)adam_b2, (double)adam_eps,
+                    opt_restored ? "state of " : "moments start from zero", opt_restored ? opt_fn : "",
+                    opt_restored ? (" after " + std::to_string(opt_state.steps) + " steps").c_str() : "");
+        }
         phase("engine (HIP init, upload)", t_phase);
         const int K0 = p->layersizes[0], D = p->layersizes[io->numlayers - 1], B = p->bunchsize;
         std::vector<float> loc_in, loc_targ;
@@ -402,6 +467,22 @@ int main(int argc, char *argv[]) {
             net->returnWeights(p->weights, p->bias);
             io->Writeweights();
             printf("finish to write weights\n\n");
+            // ---- the optimizer's state, for the next epoch's process
+            if (adam && opt_fn) {
+                mlggd_host::OptState st;
+                st.layersizes.assign(p->layersizes, p->layersizes + io->numlayers);
+                st.beta1 = adam_b1, st.beta2 = adam_b2, st.eps = adam_eps;
+                for (int l = 1; l < io->numlayers; l++) {
+                    const size_t kn = (size_t)p->layersizes[l - 1] * p->layersizes[l], n = (size_t)p->layersizes[l];
+                    st.m_w.emplace_back(kn), st.v_w.emplace_back(kn), st.m_b.emplace_back(n), st.v_b.emplace_back(n);
+                }
+                std::vector<float *> mw = moment_ptrs(st.m_w), vw = moment_ptrs(st.v_w), mb = moment_ptrs(st.m_b), vb = moment_ptrs(st.v_b);
+                net->getOptimizerState(mw.data(), vw.data(), mb.data(), vb.data());
+                st.steps = net->optimizerSteps();
+                std::string why;
+                if (!mlggd_host::write_opt_state(opt_fn, st, &why)) throw IoError("MLGGD_OPT_FILE: " + why);
+                printf("adam: %s written, %lld steps\n", opt_fn, st.steps);
+            }
             phase("download + write weights", t_phase);
 
             // ---- CV (BPtrain.cc:112-140)
