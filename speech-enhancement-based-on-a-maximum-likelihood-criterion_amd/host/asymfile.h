@@ -1,4 +1,4 @@
-// asymfile.h -- the trainer's opt-in fit of the asymmetric GGD error model (MLGGD_ASYMMODEL=FILE, bptrain_main.cc): the
+// asymfile.h -- the trainer's opt-in fit of the asymmetric GGD error model (MLGGD_ASYMMODEL=FILE, read in train_options.cc): the
 // text file written from the CV set's signed error statistics (mlggd_error_stats_signed over every CV chunk, added,
 // then mlggd_asym_fit over the grid of MLGGD_ERRMODEL_BETAS).  The reader of that file for MLGGD_ASYMMETRY=FILE,
 // parse_asymmetry (also behind mlggd_read_asymmetry), is in binfile.h with its two siblings.  Not in the reference: the

@@ -1,4 +1,4 @@
-// errmodel.h -- the trainer's opt-in error-model report (MLGGD_ERRMODEL=FILE, bptrain_main.cc): the shape grid of
+// errmodel.h -- the trainer's opt-in error-model report (MLGGD_ERRMODEL=FILE, read in train_options.cc): the shape grid of
 // MLGGD_ERRMODEL_BETAS and the text file written from the CV set's error statistics (mlggd_error_stats over every CV
 // chunk, added, then mlggd_ggd_fit).  The reader of that file for MLGGD_SHAPEFACTORS=FILE, parse_shapefactors (also
 // behind mlggd_read_shapefactors), is in binfile.h with its two siblings.  Not in the reference: the 28-key command

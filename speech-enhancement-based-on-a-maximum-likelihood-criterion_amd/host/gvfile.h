@@ -1,4 +1,4 @@
-// gvfile.h -- the trainer's opt-in global variance report (MLGGD_GVFILE=FILE, bptrain_main.cc): the text file written
+// gvfile.h -- the trainer's opt-in global variance report (MLGGD_GVFILE=FILE, read in train_options.cc): the text file written
 // from the CV set's output statistics (mlggd_output_stats over every CV chunk, added, then mlggd_gv_fit).  The reader of
 // that file for the decoders' gv=FILE, parse_gv (also behind mlggd_read_gv), is in binfile.h with its two siblings.  Not
 // in the reference: the 28-key command line, the weights file and the log file do not change.

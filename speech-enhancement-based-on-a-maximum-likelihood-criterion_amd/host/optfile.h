@@ -1,5 +1,5 @@
 // optfile.h -- the state of the Adam optimizer (mlggd_set_optimizer, csrc/adam_rule.h) as a binary file, so that the
-// trainer can carry it from one epoch's process to the next (MLGGD_OPT_FILE=PATH, bptrain_main.cc): a .wts file holds
+// trainer can carry it from one epoch's process to the next (MLGGD_OPT_FILE=PATH, read in train_options.cc): a .wts file holds
 // weights only.  Also behind mlggd_read_optimizer_header / mlggd_read_optimizer_state / mlggd_write_optimizer_state.
 // Not in the reference: the 28-key command line, the log file and the weights' format (binfile.h) do not change.  No
 // dependency on mlggd.h.

@@ -1,5 +1,5 @@
 // scalefile.h -- the state of the learned scale (mlggd_set_scale_mode, csrc/scale_rule.h) as a text file, so that the
-// trainer can carry it from one epoch's process to the next (MLGGD_SCALE_FILE=PATH, bptrain_main.cc): a .wts file has
+// trainer can carry it from one epoch's process to the next (MLGGD_SCALE_FILE=PATH, read in train_options.cc): a .wts file has
 // no place for alpha.  Also behind mlggd_read_scale_state / mlggd_write_scale_state.  Not in the reference: the 28-key
 // command line and the log file do not change.  No dependency on mlggd.h.
 //

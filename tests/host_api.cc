@@ -1,12 +1,14 @@
 // host_api.cc -- C entry points over trainer_io for the CPU test-suite (ctypes): lets
 // tests/ drive the real host code (CLI parse, pfile reader, chunk planner, chunk reader,
-// .wts writer) without a GPU and compare it with an independent NumPy restatement.
+// .wts writer, and the reader of the trainer's environment, train_options) without a GPU and compare it with an
+// independent NumPy restatement.
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "dp_launch.h"
+#include "train_options.h"
 #include "trainer_io.h"
 
 using namespace mlggd_host;
@@ -145,6 +147,58 @@ int mlggd_host_para(void *h, const char *key, char *out, int cap) {
             v += buf;
         }
     } else return -1;
+    snprintf(out, cap, "%s", v.c_str());
+    return (int)v.size();
+}
+
+// The trainer's options (host/train_options.h) as read_train_options gives them for the opened command line and an
+// environment of the n strings vars[i] = "NAME=VALUE" and nothing else, as text: one "name value" line per scalar (ints
+// "%d", floats "%.9g", a string as it is, nothing behind the name for an unset one), "name N v0 .. vN-1" per vector;
+// of each restored moment array, "name N first last".  Returns the text's length -- written whole if it is < cap --
+// or -1 for a refusal, with the trainer's message in mlggd_host_last_error.
+int mlggd_host_train_options(void *h, const char *const *vars, int n, char *out, int cap) {
+    Interface *io = (Interface *)h;
+    auto env = [&](const char *name) -> const char * {
+        const size_t len = strlen(name);
+        for (int i = 0; i < n; i++)
+            if (!strncmp(vars[i], name, len) && vars[i][len] == '=') return vars[i] + len + 1;
+        return nullptr;
+    };
+    std::string v;
+    char buf[64];
+    auto I = [&](const char *name, long long x) { v += name + std::string(" ") + std::to_string(x) + "\n"; };
+    auto F = [&](const char *name, float x) { snprintf(buf, sizeof(buf), " %.9g\n", (double)x); v += name + std::string(buf); };
+    auto S = [&](const char *name, const std::string &x) { v += name + std::string(" ") + x + "\n"; };
+    auto V = [&](const std::string &name, const std::vector<float> &x, bool ends_only) {
+        v += name + " " + std::to_string(x.size());
+        for (size_t i = 0; i < x.size(); i += ends_only && x.size() > 1 ? x.size() - 1 : 1) {
+            snprintf(buf, sizeof(buf), " %.9g", (double)x[i]);
+            v += buf;
+        }
+        v += "\n";
+    };
+    try {
+        const TrainOptions o = read_train_options(*io->para, io->numlayers, env);
+        I("world", o.world), I("rank", o.rank), I("local_rank", o.local_rank), I("timing", o.timing);
+        I("frames", o.frames), I("pinned", o.pinned), I("watchdog_s", o.watchdog_s);
+        S("id_file", o.id_file), I("rendezvous_timeout", o.rendezvous_timeout);
+        S("errmodel_fn", o.errmodel_fn), S("asymmodel_fn", o.asymmodel_fn), S("gv_fn", o.gv_fn), V("model_betas", o.model_betas, false);
+        S("shapes_fn", o.shapes_fn), V("shapes", o.shapes, false), S("asym_fn", o.asym_fn), V("skews", o.skews, false);
+        I("scale_learned", o.scale_learned), S("scale_fn", o.scale_fn);
+        F("scale_lrate", o.scale_lrate), F("scale_momentum", o.scale_momentum), F("scale_vmax", o.scale_vmax);
+        V("scale_alpha", o.scale_alpha, false), V("scale_velocity", o.scale_velocity, false), I("scale_steps0", o.scale_steps0);
+        I("adam", o.adam), S("opt_fn", o.opt_fn);
+        F("adam_beta1", o.adam_beta1), F("adam_beta2", o.adam_beta2), F("adam_eps", o.adam_eps);
+        I("opt_restored", o.opt_restored), I("opt_steps", o.opt_state.steps);
+        for (size_t l = 0; l < o.opt_state.m_w.size(); l++) {
+            const std::string layer = std::to_string(l + 1);
+            V("opt_m_w" + layer, o.opt_state.m_w[l], true), V("opt_v_w" + layer, o.opt_state.v_w[l], true);
+            V("opt_m_b" + layer, o.opt_state.m_b[l], true), V("opt_v_b" + layer, o.opt_state.v_b[l], true);
+        }
+    } catch (const std::exception &e) {
+        g_err = e.what();
+        return -1;
+    }
     snprintf(out, cap, "%s", v.c_str());
     return (int)v.size();
 }

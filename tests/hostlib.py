@@ -64,6 +64,7 @@ def lib():
                                                    C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.mlggd_host_shuffle.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int]
         L.mlggd_host_para.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int]
+        L.mlggd_host_train_options.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_char_p, C.c_int]
         L.mlggd_host_weights.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.mlggd_host_write_pfile.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.mlggd_host_rank_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
@@ -149,6 +150,22 @@ class HostIO:
         if lib().mlggd_host_para(self.h, key.encode(), buf, len(buf)) < 0:
             raise KeyError(key)
         return buf.value.decode()
+
+    def train_options_text(self, env):
+        """the trainer's options (host/train_options.h) for this command line and the environment `env`, a dict that
+        stands for the whole of it, as the hook prints them; a refusal raises HostError with the trainer's message"""
+        vars_ = [("%s=%s" % kv).encode() for kv in env.items()]
+        arr = (C.c_char_p * max(len(vars_), 1))(*vars_)
+        buf = C.create_string_buffer(1 << 16)
+        n = lib().mlggd_host_train_options(self.h, arr, len(vars_), buf, len(buf))
+        if n < 0:
+            raise HostError(lib().mlggd_host_last_error().decode())
+        assert n < len(buf)
+        return buf.value.decode()
+
+    def train_options(self, env):
+        """train_options_text as a dict: field name -> the list of words behind it"""
+        return {l.split()[0]: l.split()[1:] for l in self.train_options_text(env).splitlines()}
 
     def shuffle(self, n):
         v = (C.c_int * n)(*range(n))
